@@ -40,9 +40,12 @@ def _newer(src_list, target):
 
 
 def build(force=False, verbose=False, extra_hip_flags=(), out=None, tag=""):
-    """extra_hip_flags/out/tag build an experimental variant next to the default library."""
+    """extra_hip_flags/out/tag build an experimental variant next to the default library.  When everything is up to date this
+    writes nothing (no lock either): a process without write access to the tree loads the library as it was built."""
     global OUT
     out = out or OUT
+    if not force and not _stale(_jobs(extra_hip_flags, tag), out):
+        return out
     os.makedirs(OBJ, exist_ok=True)
     # one builder at a time (the ranks of a multi-process launch all come through here): the others wait on the lock and then
     # find everything up to date; the library is linked under a temporary name and renamed into place, so a process that is
@@ -56,11 +59,14 @@ def build(force=False, verbose=False, extra_hip_flags=(), out=None, tag=""):
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(force, verbose, extra_hip_flags, out, tag):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+def _headers():
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h", ".inc"))]
-    headers += [os.path.join(HERE, "..", "include", f) for f in ("admm_hip.h", "admm_kinds.h")]
-    jobs = [
+    return headers + [os.path.join(HERE, "..", "include", f) for f in ("admm_hip.h", "admm_kinds.h")]
+
+
+def _jobs(extra_hip_flags, tag):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    return [
         (["g++"] + HOST_FLAGS + ["-mavx2", "-mfma"], "dense.cpp", "dense.o"),
         (["g++"] + HOST_FLAGS, "factor.cpp", "factor.o"),
         ([hipcc] + HIPHOST_FLAGS, "host_setup.cpp", "host_setup.o"),
@@ -68,6 +74,18 @@ def _build_locked(force, verbose, extra_hip_flags, out, tag):
         ([hipcc] + HIPHOST_FLAGS, "comm.cpp", "comm.o"),
         ([hipcc] + HIP_FLAGS + list(extra_hip_flags), "admm_hip.hip", "admm_hip%s.o" % tag),
     ]
+
+
+def _stale(jobs, out):
+    """what _build_locked would do: rebuild an object older than its source or a header, link when one was rebuilt or out is missing"""
+    headers = _headers()
+    return not os.path.exists(out) or any(_newer([os.path.join(CSRC, src)] + headers, os.path.join(OBJ, obj)) for _, src, obj in jobs)
+
+
+def _build_locked(force, verbose, extra_hip_flags, out, tag):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    headers = _headers()
+    jobs = _jobs(extra_hip_flags, tag)
     objs = []
     rebuilt = False
     for cmd, src, obj in jobs:

@@ -53,6 +53,7 @@ LOCAL_BYTES_PER_TET = 472.0
 LOCAL_BYTES_PER_TET_MIN = 400.0
 RHS_BYTES_PER_TET = 96.0
 ADMM_ITERS = 20
+DUMP_MAX_BYTES = 64 * 1000 * 1000      # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -70,7 +71,46 @@ def parse():
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-extras", action="store_true", help="skip the class-API frame cost and the other BASELINE configs (N = 1 only)")
     p.add_argument("--cpu-dims", type=int, nargs=3, default=[16, 16, 65], help="bounded CPU-baseline sample (cubes)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed -- positions x and velocities v, float64, one row per node -- "
+                        "as DIR/<name>.npy (rank 0; above %d MB in all, a fixed seeded sample of the nodes, their indices in node_index.npy)" % (DUMP_MAX_BYTES // 1000000))
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_outputs(out_dir, x, v):
+    """The arrays a caller of System::step receives after the last timed step (m_x, m_v), node-major, as <name>.npy. If they exceed
+    DUMP_MAX_BYTES together, the same fixed seeded sample of nodes is written from both, with the node indices beside them."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    v = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+    arrays = {"x": x, "v": v}
+    n = x.shape[0]
+    if x.nbytes + v.nbytes > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 8 * 1024) // (2 * 3 * 8 + 8)      # x and v rows + the index, 8 KB kept for the headers
+        idx = np.sort(np.random.default_rng(20241015).choice(n, size=keep, replace=False))
+        arrays = {"x": x[idx], "v": v[idx], "node_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
+    return {"dir": out_dir, "nodes": n, "sampled": "node_index" in arrays, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
+def use_built_library(pkg):
+    """bench.py times the library build() produced and never compiles: it may run without write access to the tree, and a compile
+    is no part of a measurement.  The package's lib() brings a stale library up to date on load; here the rebuild step it calls is
+    replaced by a check, so that a missing library, or one older than a source, is an error naming build()."""
+    pkg_dir = os.path.dirname(os.path.abspath(pkg.__file__))
+    so = os.path.join(pkg_dir, "libadmm_hip.so")
+    srcs = [os.path.join(pkg_dir, "csrc", f) for f in os.listdir(os.path.join(pkg_dir, "csrc"))]
+    srcs += [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
+
+    def built_only(force=False, verbose=False):
+        if force or not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
+            raise SystemExit("bench.py: %s is missing or older than its sources; run __graft_entry__.build() first" % so)
+        return so
+    pkg.build = built_only      # what lib() calls before it loads the library
 
 
 def cpu_baseline(dims):
@@ -400,6 +440,7 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
     from __graft_entry__ import load_package
     pkg = load_package()
+    use_built_library(pkg)
 
     nx, ny, nz = a.dims
     # the solver runs on torch's CURRENT stream (the fallback all-reduce through torch.distributed is ordered on it); made a
@@ -517,6 +558,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     xs = s.m_x
+    dumped = None
+    if a.dump_outputs and rank == 0:      # the last timed step's result, read before anything below steps the system again
+        dumped = dump_outputs(a.dump_outputs, xs, s.m_v)
     if not os.environ.get("BENCH_TIMING_EXPERIMENT"):   # (kernel-timing experiments with deliberately wrong arithmetic set this)
         assert np.isfinite(xs).all(), "non-finite positions"
 
@@ -680,6 +724,8 @@ def main():
                    "x_checksum": float(np.abs(xs).sum())},
         "roofline": roof,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if world > 1 or fake_dist or fake_world > 1:
         # the exchange, as the library accounts for it (admm_hip_info.comm_doubles_*): ONE collective per ADMM iteration (subtree shards: the
         # packed top rows; contiguous: the whole right-hand side) + under subtree shards one more per frame (the full x before the velocity update)

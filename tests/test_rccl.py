@@ -186,7 +186,7 @@ def _bench_fake(tmp_path, shard, graph_comm, dims, port, extra_env=None):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shard", ["subtree", "contiguous"])
-def test_bench_fake_world_over_the_library_communicator(tmp_path, shard):
+def test_bench_fake_world_over_the_library_communicator(pkg, tmp_path, shard):
     """bench.py as a fresh torch.distributed.run child (started before anything touches the GPU): 1-rank NCCL process group,
     the ncclUniqueId through it, admm_hip_rccl_init, then rank 0's share of an 8-rank partition stepping over ncclAllReduce.
     Eager and captured iterations give the same frames (x_checksum is a sum of |x|: equal only if the frames are)."""
@@ -205,7 +205,7 @@ def test_bench_fake_world_over_the_library_communicator(tmp_path, shard):
 
 
 @pytest.mark.gpu
-def test_bench_fake_world_full_size_eager(tmp_path):
+def test_bench_fake_world_full_size_eager(pkg, tmp_path):
     """The driver's 8-GPU command at the headline size, one rank of it: 1 001 472 tets, subtree shards, eager launches with
     ncclAllReduce between the kernels (no graph above 100k nodes) -- what every rank of the first real 8-GPU run executes."""
     from test_sharding import _free_port

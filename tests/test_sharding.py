@@ -704,7 +704,7 @@ def test_two_shards_on_one_gpu(pkg):
 
 
 @pytest.mark.gpu
-def test_bench_two_ranks_end_to_end(tmp_path):
+def test_bench_two_ranks_end_to_end(pkg, tmp_path):
     """bench.py exactly as the driver launches it for N = 2 (torch.distributed.run, one process per rank, all-reduce hook
     inside the C step loop, barrier + MAX-over-ranks timing, one JSON line from rank 0) -- on a 1-GPU box both ranks share
     cuda:0 and gloo stands in for RCCL (test hooks of bench.py).  Same final positions as the single-rank run."""
@@ -779,14 +779,16 @@ def _bench_one_rank_line():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [4, 8])
-def test_bench_n_ranks_end_to_end(n):
-    """`python bench.py --gpus 4` / `--gpus 8` exactly as typed -- what the driver's first multi-GPU commands are: bench.py starts its N ranks
+@pytest.mark.parametrize("n", [4])
+def test_bench_n_ranks_end_to_end(pkg, n):
+    """`python bench.py --gpus 4` exactly as typed -- what the driver's first multi-GPU commands are: bench.py starts its N ranks
     itself (fresh torch.distributed.run child), every rank a REAL process with its own context; on this one-GPU box they share cuda:0 and gloo
     stands in for RCCL (bench.py's test hooks).  N processes through the consensus bootstrap, the rank-local factorization (initialize is a
     collective: the subtree roots' update matrices meet in one all-reduce), the subtree partition with a replicated top of several levels,
     the N-way per_rank gather: rc 0, ONE JSON line, a head count of N through the very all-reduce path the iterations use, every per_rank
-    list N long, the ranks' elements a partition, every rank factored only its share, the final positions those of the one-rank run."""
+    list N long, the ranks' elements a partition, every rank factored only its share, the final positions those of the one-rank run.
+    (N = 8 would put nine processes on the one GPU, more than a shared node allows; the 8-way partition is covered in one process by
+    test_sharded_step_matches_single_rank and test_distributed_top_vs_replicated_top.)"""
     import json
     one = _bench_one_rank_line()
     env = dict(os.environ, ADMM_BENCH_SHARE_GPU="1", ADMM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", ADMM_HIP_DIST_TOP="1")      # (the distributed top: by default only from 300k nodes on)
@@ -813,15 +815,15 @@ def test_bench_n_ranks_end_to_end(n):
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_a_hung_collective_exits_nonzero():
-    """Eight real processes, rank 5 stops reaching the collective in a timed frame: every watchdog ends its rank within the per-frame limit, the
-    launcher relays a non-zero code, no JSON line."""
+def test_bench_four_ranks_a_hung_collective_exits_nonzero(pkg):
+    """Four real processes (the most a shared one-GPU node takes besides this one), rank 3 stops reaching the collective in a timed frame:
+    every watchdog ends its rank within the per-frame limit, the launcher relays a non-zero code, no JSON line."""
     import time
     env = dict(os.environ, ADMM_BENCH_SHARE_GPU="1", ADMM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", ADMM_BENCH_FRAME_TIMEOUT_MIN="5", ADMM_BENCH_FRAME_TIMEOUT_MAX="10",
-               ADMM_BENCH_TEST_HANG_RANK="5", ADMM_BENCH_TEST_HANG_AFTER="13")      # the 14th collective of the timed region: the 7th iteration of timed frame 0 (two per iteration under the distributed top)
+               ADMM_BENCH_TEST_HANG_RANK="3", ADMM_BENCH_TEST_HANG_AFTER="13")      # the 14th collective of the timed region: the 7th iteration of timed frame 0 (two per iteration under the distributed top)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     t = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"] + _BENCH_NRANK_ARGS, capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"] + _BENCH_NRANK_ARGS, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert "no progress for" in r.stderr and "timed frame" in r.stderr and "exiting with code 3" in r.stderr
@@ -876,7 +878,7 @@ def test_bench_watchdog_ends_a_stalled_process():
 
 
 @pytest.mark.gpu
-def test_bench_two_ranks_a_hung_collective_exits_nonzero():
+def test_bench_two_ranks_a_hung_collective_exits_nonzero(pkg):
     """One rank of a 2-rank run never reaches the collective of a timed frame (test hook in bench.py's all-reduce hook): the watchdogs
     end the ranks within the per-frame limit, bench.py relays a non-zero code, no JSON line, and stderr says which rank stalled where."""
     import time
