@@ -100,11 +100,24 @@ int upload_factor(admm_hip_ctx *ctx) {
             }
             if (ctx->xcd_min_supernodes > 0) { xcd_order(sm, ADMM_FWD_SMALL_WAVES, ctx->xcd_min_supernodes); xcd_order(bg, 1, ctx->xcd_min_supernodes); xcd_order(bw, 1, ctx->xcd_min_supernodes); }
             L.n_small = (int)sm.size(); L.n_big = (int)bg.size(); L.n_bwd = (int)bw.size();
-            {
-                int kmax = 0;
-                for (const admm_dev::SweepItem &q : bg) kmax = std::max(kmax, q.k);
-                // few tiles (all resident at once even with 16 waves each): the more waves share a tile's columns the shorter its chain
-                L.big_nw = (int)bg.size() <= ctx->fwd_nw16_max_tiles ? 16 : (kmax <= ctx->fwd_nw4_kmax ? 4 : (kmax <= ctx->fwd_nw8_kmax ? 8 : 16));
+            int kmax = 0;
+            for (const admm_dev::SweepItem &q : bg) kmax = std::max(kmax, q.k);
+            // few tiles (all resident at once even with 16 waves each): the more waves share a tile's columns the shorter its chain
+            L.big_nw = (int)bg.size() <= ctx->fwd_nw16_max_tiles ? 16 : (kmax <= ctx->fwd_nw4_kmax ? 4 : (kmax <= ctx->fwd_nw8_kmax ? 8 : 16));
+            if (getenv("ADMM_HIP_VERBOSE")) {
+                // the sweep plan of this level (tests/test_wide_supernodes.py asserts from it which kernel paths a scene reaches): column
+                // chunks of the widest block item, row chunks of the tallest front in the backward kernel, and per root its product's chunks
+                using namespace admm_dev;
+                const char *pass = ps.want < 0 ? "top" : "own";
+                const int kchunk = L.big_nw == 16 ? FwdBig<16>::KCHUNK : (L.big_nw == 8 ? FwdBig<8>::KCHUNK : FwdBig<4>::KCHUNK);
+                int fmax = 0;
+                for (const SweepItem &q : bw) fmax = std::max(fmax, q.k + q.r);
+                fprintf(stderr, "admm_hip: plan %s level %zu: fwd wave %d block %d big_nw %d kmax %d chunks %d | bwd cw %d nw %d items %d fmax %d rchunks %d | cg4 %d\n",
+                        pass, l, L.n_small, L.n_big, L.big_nw, kmax, (kmax + kchunk - 1) / kchunk, L.bwd_cw, L.bwd_nw, L.n_bwd, fmax, (fmax + BWD_RCHUNK - 1) / BWD_RCHUNK,
+                        F.cg4.empty() ? 0 : 1);
+                for (const LevelDev::Root &R : L.roots)
+                    fprintf(stderr, "admm_hip: plan %s level %zu: root k %d %s chunks %d\n", pass, l, R.k, R.k <= ctx->root_fuse_k ? "fused" : "gather",
+                            (R.k + ROOT_KCHUNK - 1) / ROOT_KCHUNK);
             }
 #ifdef ADMM_SWEEP_PROFILE
             {
@@ -122,6 +135,9 @@ int upload_factor(admm_hip_ctx *ctx) {
             TRY(upload(ctx, &L.d_small, sm)); TRY(upload(ctx, &L.d_big, bg)); TRY(upload(ctx, &L.d_bwd, bw));
         }
     }
+    if (subtree && ctx->dist_top && getenv("ADMM_HIP_VERBOSE"))      // (the top's per-level lines above are not run: the root's rows are this rank's product)
+        fprintf(stderr, "admm_hip: plan dist-top rank %d: root k %d rows %d..%d nrows %d chunks %d\n", ctx->rank, ctx->root_k, ctx->root_r0, ctx->root_r1,
+                ctx->root_r1 - ctx->root_r0, (ctx->root_k + admm_dev::ROOT_KCHUNK - 1) / admm_dev::ROOT_KCHUNK);
 #ifdef ADMM_SWEEP_PROFILE
     {
         unsigned long long *p = nullptr;

@@ -528,3 +528,87 @@ def extreme_matrices(rng, n):
     while len(M) < n:
         M.append(rng.normal(size=(3, 3)) * 10.0 ** rng.integers(-3, 4))
     return np.array(M[:n]).reshape(n, 9)
+
+
+class SparseReference:
+    """An independent, extended-precision solve of the global system A = M + dt^2 D^T W^2 D, assembled as a scipy.sparse matrix from the
+    ORACLE's selector D (D_triplets), its weight diagonal and the masses -- not from the library's assembly (apply_A).  splu (SuperLU)
+    factors it once; every solution is refined with residuals evaluated in np.longdouble until the correction is below 1e-16 of the
+    solution.  kappa1 estimates the 1-norm condition number: onenormest of A times onenormest of A^-1 applied through the LU.
+
+    with_weights(w) rebuilds the reference for new per-force weights (System::recompute_weights with edited Force::weight members): the
+    rows of force i are [global_idx_i, global_idx_i + rows of its kind) of W, the layout the constructor checks against the oracle's W."""
+
+    def __init__(self, oracle, m3, dt):
+        import scipy.sparse as sp
+        self.dt, self.m3 = float(dt), np.asarray(m3, dtype=np.float64).ravel()
+        rr, cc, vv = oracle.D_triplets()
+        self.n, self.rows = self.m3.size, oracle.rows
+        self.D = sp.csr_matrix((vv, (rr, cc)), shape=(self.rows, self.n))
+        self.kinds = np.array([oracle.force(i).kind for i in range(oracle.n_forces)])
+        self.gidx = oracle.global_idx()
+        self.w0 = oracle.weights()
+        W = oracle.wdiag
+        assert np.array_equal(self._wdiag(self.w0), W), "per-force rows of W do not match the oracle's weight diagonal"
+        self._factor(W)
+
+    def _wdiag(self, w):
+        nrows = np.array(KIND_ROWS)[self.kinds]
+        W = np.zeros(self.rows)
+        W[np.repeat(self.gidx, nrows) + (np.arange(nrows.sum()) - np.repeat(np.cumsum(nrows) - nrows, nrows))] = np.repeat(w, nrows)
+        return W
+
+    def _factor(self, W):
+        import scipy.sparse as sp
+        import scipy.sparse.linalg as sla
+        A = (sp.diags(self.m3) + (self.dt * self.dt) * (self.D.T @ sp.diags(W * W) @ self.D)).tocsr()
+        A.sum_duplicates(); A.sort_indices()
+        self.A = A
+        self.norm_inf = float(np.abs(A).sum(axis=1).max())
+        self._Al = A.data.astype(np.longdouble)
+        # A is symmetric positive definite: a symmetric fill-reducing order and diagonal pivots
+        self.lu = sla.splu(A.tocsc(), permc_spec="MMD_AT_PLUS_A", diag_pivot_thresh=0.0, options=dict(SymmetricMode=True))
+        inv = sla.LinearOperator(A.shape, matvec=self.lu.solve, rmatvec=self.lu.solve, dtype=np.float64)
+        self.kappa1 = float(sla.onenormest(A) * sla.onenormest(inv))
+
+    def with_weights(self, w):
+        ref = SparseReference.__new__(SparseReference)
+        ref.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("A", "norm_inf", "_Al", "lu", "kappa1")})
+        ref._factor(ref._wdiag(np.asarray(w, dtype=np.float64)))
+        return ref
+
+    def residual(self, x, b):
+        """b - A x in np.longdouble"""
+        A = self.A
+        prod = self._Al * np.asarray(x, dtype=np.longdouble)[A.indices]
+        return np.asarray(b, dtype=np.longdouble) - np.add.reduceat(prod, A.indptr[:-1])
+
+    def backward_error(self, x, b):
+        """normwise backward error |b - A x|_inf / (|A|_inf |x|_inf + |b|_inf), the residual in longdouble"""
+        return float(np.abs(self.residual(x, b)).max()) / (self.norm_inf * float(np.abs(x).max()) + float(np.abs(b).max()))
+
+    def solve(self, b, max_steps=10):
+        """-> (x_ref, the longdouble residual of x_ref, the refinement steps taken)"""
+        x = self.lu.solve(np.asarray(b, dtype=np.float64)).astype(np.longdouble)
+        for step in range(1, max_steps + 1):
+            r = self.residual(x, b)
+            dx = self.lu.solve(r.astype(np.float64))
+            x = x + dx
+            if np.abs(dx).max() <= 1e-16 * float(np.abs(x).max()):
+                break
+        else:
+            raise AssertionError("iterative refinement did not converge in %d steps" % max_steps)
+        xr = x.astype(np.float64)
+        return xr, self.residual(xr, b), step
+
+
+def bar_reference(mg, dims, mu=1e5, lam=1e5, max_iter=5, density=1000.0, dt=0.04):
+    """SparseReference of the bar that make_bar_system builds (Neo-Hookean tets + anchors on the k = 0 face), through the oracle"""
+    x, t = mg.bar(*dims)
+    m3 = np.repeat(mg.lumped_tet_mass(x, t, density), 3)
+    o = Oracle(); o.settings(dt, 1)
+    o.add_nodes(x.ravel(), m3)
+    o.add_forces(KIND["TET_NH"], t, [mu, lam, max_iter])
+    o.add_forces(KIND["ANCHOR"], mg.bar_anchor_nodes(dims[0], dims[1]), [-1.0, 1.0])
+    assert o.initialize()
+    return SparseReference(o, m3, dt), x, m3
