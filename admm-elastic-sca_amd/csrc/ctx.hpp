@@ -194,6 +194,11 @@ struct admm_hip_ctx {
     int xcd_min_supernodes = 16;                  // levels with at least this many supernodes get the XCD-aware item order (0 = off; ADMM_HIP_XCD)
     int bwd_nw_min_cols = 4096, fwd_nw16_max_tiles = 512;
     int fwd_nw4_kmax = 200, fwd_nw8_kmax = 400;   // forward sweep: levels whose widest supernode has at most this many columns run 4 / 8 waves per tile (ADMM_HIP_FWD_NW4 / _NW8)
+    // the bottom subtrees of the elimination tree (every supernode up to the cut level) swept by ONE launch per sweep, one workgroup per
+    // subtree, the hand-off between its levels in LDS (upload.inc fuse_subtrees; ADMM_HIP_SWEEP_FUSE=0: per-level launches only)
+    bool sweep_fuse = true;
+    int fuse_cut = -1, n_fuse = 0, fuse_lds = 0;  // cut level (-1: nothing fused), subtrees, dynamic LDS bytes of the fused launches
+    int *d_fuse_rec = nullptr; int64_t *d_fuse_off = nullptr;      // the subtrees' records (ints) and their offsets [n_fuse + 1]
     int64_t graph_launches = 0;               // hipGraphLaunch calls so far (admm_hip_debug_graph_state)
     bool graphs_stale = false;                // a captured iteration holds the communicator it was captured with: set when that changes (comm.cpp), honoured by the next admm_hip_step
     bool graph_comm = false;                  // ADMM_HIP_GRAPH_COMM=1: also capture the multi-GPU iteration (ncclAllReduce inside the graph)

@@ -467,6 +467,108 @@ __global__ __launch_bounds__(64 * ADMM_FWD_SMALL_WAVES) void solve_fwd_small_ker
     ADMM_SWEEP_STAMP(2);
 }
 
+// Forward sweep over the bottom subtrees of the tree (upload.inc fuse_subtrees): one workgroup per subtree walks its levels bottom-up;
+// a wave takes one (supernode, 64-row tile) at a time with the arithmetic, the column order and the child order of
+// solve_fwd_small_kernel<true> -- bitwise the same w and root contributions.  The subtree's record (items, front maps) is copied to LDS
+// once; the members' contributions stay in LDS, so past that copy the only global loads are y and the panels, neither of which depends
+// on a value computed here, and the levels are separated by barriers that wait for LDS alone.  Only the root's contribution goes to C.
+// Record (ints): [0] levels, [1] first item, [2] contribution area, [3] staged vectors (both in doubles from the start of LDS),
+// [4..5] the root's first contribution slot; from SUB_HDR the level pointers; items of SUB_ITEM ints: k, r, first, tile, front map
+// (int offset in the record, -1 = no children), destination of the contribution (double offset in the contribution area, -1 = C),
+// panel offset (two ints).  A front map holds four ints per front row: double offsets of the children's rows in the contribution area.
+constexpr int SUB_HDR = 8, SUB_ITEM = 8;
+#ifndef ADMM_SUBTREE_WAVES
+#define ADMM_SUBTREE_WAVES 8      // waves per subtree workgroup
+#endif
+#ifndef ADMM_SUBTREE_DEPTH
+#define ADMM_SUBTREE_DEPTH ADMM_FWD_SMALL_DEPTH      // panel columns per load group in the subtree kernel
+#endif
+constexpr int SUB_WAVES = ADMM_SUBTREE_WAVES;
+__device__ __forceinline__ int sub_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__global__ __launch_bounds__(64 * SUB_WAVES) void solve_fwd_subtree_kernel(const int *__restrict__ recs, const int64_t *__restrict__ rec_off, const double *__restrict__ panels,
+                                                                           const double *__restrict__ y, double *__restrict__ W, double *__restrict__ C) {
+    extern __shared__ double sub_lds[];
+    int *meta = reinterpret_cast<int *>(sub_lds);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    {
+        const int64_t o0 = rec_off[blockIdx.x], o1 = rec_off[blockIdx.x + 1];
+        const int4 *src = reinterpret_cast<const int4 *>(recs + o0);
+        int4 *dst = reinterpret_cast<int4 *>(meta);
+        const int n4 = (int)((o1 - o0) >> 2);
+        for (int q = threadIdx.x; q < n4; q += 64 * SUB_WAVES) dst[q] = src[q];
+    }
+    __syncthreads();
+    const int n_lv = meta[0], item0 = meta[1];
+    double *cb = sub_lds + meta[2];
+    double *ts = sub_lds + meta[3] + 3 * 64 * wave;
+    const int64_t root_soff = (int64_t)(((uint64_t)(uint32_t)meta[5] << 32) | (uint32_t)meta[4]);
+    constexpr int DS = ADMM_SUBTREE_DEPTH;
+    for (int lv = 0; lv < n_lv; ++lv) {
+        const int e = meta[SUB_HDR + lv + 1];
+        for (int itm = meta[SUB_HDR + lv] + wave; itm < e; itm += SUB_WAVES) {
+            const int *I = meta + item0 + SUB_ITEM * itm;
+            const int k = sub_uniform(I[0]), r = sub_uniform(I[1]), first = sub_uniform(I[2]), tile = sub_uniform(I[3]);
+            const int moff = sub_uniform(I[4]), cdst = sub_uniform(I[5]);
+            const int64_t poff = (int64_t)(((uint64_t)(uint32_t)sub_uniform(I[7]) << 32) | (uint32_t)sub_uniform(I[6]));
+            const int f = k + r;
+            const int i = tile * 64 + lane;
+            const bool row_ok = i < f;
+            const double *P = panels + poff + (row_ok ? i : 0);
+            const int jend = row_ok ? ((i < k) ? i + 1 : k) : 0;
+            const bool pass = row_ok && i >= k, stage = lane < k;
+            const double *src = y + 3 * (size_t)(first + (stage ? lane : 0));
+            const double y0 = src[0], y1 = src[1], y2 = src[2];
+            double cur[DS], nxt[DS];
+            {
+                const int jl = max(jend - 1, 0);
+#pragma unroll
+                for (int q = 0; q < DS; ++q) cur[q] = P[(size_t)f * min(q, jl)];
+            }
+            int4 ab_c = make_int4(-1, -1, -1, -1), ab_t = make_int4(-1, -1, -1, -1);
+            if (moff >= 0) {
+                const int4 *M = reinterpret_cast<const int4 *>(meta + moff);
+                if (pass) ab_c = M[i];
+                if (stage) ab_t = M[lane];
+            }
+            // the staging of solve_fwd_small_kernel<true>, with the contributions read from LDS
+            double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+            const double *cxp = cb + max(ab_c.x, 0), *cyp = cb + max(ab_c.y, 0);
+            const double *txp = cb + max(ab_t.x, 0), *typ = cb + max(ab_t.y, 0);
+            const double cx0 = cxp[0], cx1 = cxp[1], cx2 = cxp[2], cy0 = cyp[0], cy1 = cyp[1], cy2 = cyp[2];
+            const double tx0 = txp[0], tx1 = txp[1], tx2 = txp[2], ty0 = typ[0], ty1 = typ[1], ty2 = typ[2];
+            c0 += ab_c.x >= 0 ? cx0 : 0.0; c1 += ab_c.x >= 0 ? cx1 : 0.0; c2 += ab_c.x >= 0 ? cx2 : 0.0;
+            c0 += ab_c.y >= 0 ? cy0 : 0.0; c1 += ab_c.y >= 0 ? cy1 : 0.0; c2 += ab_c.y >= 0 ? cy2 : 0.0;
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+            s0 += ab_t.x >= 0 ? tx0 : 0.0; s1 += ab_t.x >= 0 ? tx1 : 0.0; s2 += ab_t.x >= 0 ? tx2 : 0.0;
+            s0 += ab_t.y >= 0 ? ty0 : 0.0; s1 += ab_t.y >= 0 ? ty1 : 0.0; s2 += ab_t.y >= 0 ? ty2 : 0.0;
+            if (ab_c.z >= 0) { const double *c = cb + ab_c.z; c0 += c[0]; c1 += c[1]; c2 += c[2]; }
+            if (ab_c.w >= 0) { const double *c = cb + ab_c.w; c0 += c[0]; c1 += c[1]; c2 += c[2]; }
+            if (ab_t.z >= 0) { const double *c = cb + ab_t.z; s0 += c[0]; s1 += c[1]; s2 += c[2]; }
+            if (ab_t.w >= 0) { const double *c = cb + ab_t.w; s0 += c[0]; s1 += c[1]; s2 += c[2]; }
+            if (stage) { ts[3 * lane] = y0 - s0; ts[3 * lane + 1] = y1 - s1; ts[3 * lane + 2] = y2 - s2; }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (ts is private to the wave)
+#pragma unroll
+            for (int q = 0; q < DS; ++q) cur[q] = (q < jend) ? cur[q] : 0.0;
+            if (row_ok) {
+                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+                for (int j = 0; j < jend; j += DS) {
+#pragma unroll
+                    for (int q = 0; q < DS; ++q) nxt[q] = (j + DS + q < jend) ? P[(size_t)f * (j + DS + q)] : 0.0;
+                    const double *t = &ts[3 * j];
+#pragma unroll
+                    for (int q = 0; q < DS; ++q) if (j + q < jend) { a0 += cur[q] * t[3 * q]; a1 += cur[q] * t[3 * q + 1]; a2 += cur[q] * t[3 * q + 2]; }
+#pragma unroll
+                    for (int q = 0; q < DS; ++q) cur[q] = nxt[q];
+                }
+                if (i < k) { double *dst = W + 3 * (size_t)(first + i); dst[0] = a0; dst[1] = a1; dst[2] = a2; }
+                else if (cdst >= 0) { double *dst = cb + cdst + 3 * (i - k); dst[0] = a0 + c0; dst[1] = a1 + c1; dst[2] = a2 + c2; }
+                else { double *dst = C + 3 * (size_t)(root_soff + (i - k)); dst[0] = a0 + c0; dst[1] = a1 + c1; dst[2] = a2 + c2; }
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // this level's contributions are in LDS
+    }
+}
+
 // Forward sweep, supernodes with k > 64: one block of NW waves = one
 // (supernode, 64-row tile); the waves split the columns, partial sums are
 // combined through LDS in wave order.  NW = 16 for the wide supernodes at the top of the tree; levels of narrower ones run

@@ -209,6 +209,9 @@ int launch_solve(admm_hip_ctx *ctx, hipEvent_t mid, hipEvent_t ex0 = nullptr, hi
             bad_pair = true;
         }
     };
+    if (ctx->n_fuse)      // the bottom subtrees first, one workgroup each (then the levels above the cut)
+        hipLaunchKernelGGL(solve_fwd_subtree_kernel, dim3(ctx->n_fuse), dim3(64 * SUB_WAVES), ctx->fuse_lds, ctx->stream, (const int *)ctx->d_fuse_rec,
+                           (const int64_t *)ctx->d_fuse_off, (const double *)ctx->d_panels, (const double *)ctx->d_y, ctx->d_w, ctx->d_c);
     forward(ctx->levels, ctx->stream);
     if (!ctx->levels_top.empty()) {
         // subtree sharding: own subtrees are done; ONE small all-reduce carries the top nodes' partial right-hand sides and the

@@ -13,6 +13,122 @@ template <class T> std::vector<T> permute_nodes(const std::vector<T> &h, const s
 // of the LAST iteration stay); meta: (tag, level, workgroups, KB, list, first slot) per launch
 unsigned long long *g_swp_base; size_t g_swp_wgs; std::vector<int> g_swp_meta;
 #endif
+// ---- the bottom subtrees, one workgroup each (solve_fwd_subtree_kernel / solve_bwd_subtree_kernel) --------------------------------
+// Cut level c: the highest level such that every supernode at or below it has at most 64 columns (the wave-per-tile forward and the
+// 4-column backward shape) and the subtrees below it -- supernodes up to level c whose parent lies above c -- still number at least two
+// per CU.  Each such subtree becomes one record, loaded into LDS once by its workgroup (admm_dev::SUB_* for the layout): the items of
+// every level, bottom-up; per supernode with children its front map (for every front row the LDS offsets of the children's
+// contribution rows landing on it, in the child order of Factor::cg4); the LDS offsets of the members' contributions.  Only the
+// subtree's root writes its contribution to C.  A subtree whose LDS does not leave two workgroups per CU, the subtree of a whole tree
+// (a root of the elimination tree at or below the cut) and trees whose front rows receive more than four contributions (no cg4) stay on
+// the per-level path.  fused[s] = 1 for the supernodes the fused launch sweeps.
+int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std::vector<char> &fused) {
+    using namespace admm_dev;
+    const Factor &F = ctx->F;
+    const int ns = (int)F.sn.size();
+    fused.assign(ns, 0);
+    ctx->fuse_cut = -1; ctx->n_fuse = 0; ctx->fuse_lds = 0;
+    if (!ctx->sweep_fuse || F.cg4.empty() || F.levels.empty()) return ADMM_OK;
+    auto mine = [&](int s) { return !own || (*own)[s] == want; };
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, ctx->device_id));
+    const int cus = std::max(prop.multiProcessorCount, 1);
+    const int lds_cap = (int)std::min<size_t>(prop.sharedMemPerBlock, prop.maxSharedMemoryPerMultiProcessor / 2);
+    const int kcap = std::min(std::min(ctx->fwd_small_k, ctx->bwd_small_k), FWD_SMALL_KMAX);
+    int cut = -1;
+    for (int l = 0; l < (int)F.levels.size(); ++l) {
+        bool narrow = true;
+        for (int s : F.levels[l]) if (mine(s) && F.sn[s].ncols > kcap) narrow = false;
+        if (!narrow) break;
+        int roots = 0;
+        for (int s = 0; s < ns; ++s) {
+            const int p = F.sn[s].parent;
+            if (mine(s) && F.sn[s].level <= l && p >= 0 && F.sn[p].level > l) ++roots;
+        }
+        if (roots >= 2 * cus) cut = l;
+    }
+    if (cut < 0) return ADMM_OK;
+    std::vector<std::vector<int> > children(ns);
+    for (int s = 0; s < ns; ++s) if (F.sn[s].parent >= 0) children[F.sn[s].parent].push_back(s);
+    std::vector<int> local_slot(F.n_slots, -1);      // member's contribution slot -> LDS offset (doubles, from the contribution area)
+    struct Rec { std::vector<int> v; double bytes; std::vector<int> members; };
+    std::vector<Rec> recs;
+    int lds_max = 0, left = 0;      // (left: subtrees that stay on the per-level path)
+    for (int t = 0; t < ns; ++t) {
+        const int p = F.sn[t].parent;
+        if (!mine(t) || F.sn[t].level > cut || p < 0 || F.sn[p].level <= cut) continue;
+        std::vector<int> mem, stack{t};      // the subtree, then per level
+        while (!stack.empty()) { const int s = stack.back(); stack.pop_back(); mem.push_back(s); for (int c : children[s]) stack.push_back(c); }
+        const int nlv = F.sn[t].level + 1;
+        std::vector<std::vector<int> > bylv(nlv);
+        for (int s : mem) bylv[F.sn[s].level].push_back(s);
+        for (auto &v : bylv) std::sort(v.begin(), v.end());
+        bool ok = true;
+        for (int s : mem) if (!mine(s) || F.sn[s].root_inv_off >= 0) ok = false;
+        // layout: header, level pointers, items, front maps; then (in LDS) the members' contributions and the waves' staged vectors
+        int cdoubles = 0;
+        for (int s : mem) if (s != t) { for (int q = 0; q < F.sn[s].nrows; ++q) local_slot[F.sn[s].slot_off + q] = cdoubles + 3 * q; cdoubles += 3 * F.sn[s].nrows; }
+        std::vector<int> lvp{0}, items, maps;
+        int n_items = 0;
+        for (int l = 0; l < nlv; ++l) {
+            if (bylv[l].empty()) continue;
+            for (int s : bylv[l]) {
+                const Supernode &S = F.sn[s];
+                const int f = S.ncols + S.nrows;
+                int moff = -1;
+                if (!children[s].empty()) {
+                    moff = (int)maps.size();
+                    for (int fr = 0; fr < f; ++fr) for (int e = 0; e < 4; ++e) {
+                        const int g = F.cg4[4 * (size_t)(S.front_off + fr) + e];
+                        const int o = g < 0 ? -1 : local_slot[g];
+                        if (g >= 0 && o < 0) ok = false;
+                        maps.push_back(o);
+                    }
+                }
+                const int cdst = s == t ? -1 : (S.nrows ? local_slot[S.slot_off] : 0);      // (-1: the root, to C)
+                const int64_t po = ctx->dev_panel_off[s];
+                for (int tile = 0; tile < (f + 63) / 64; ++tile) {
+                    items.insert(items.end(), {S.ncols, S.nrows, S.first, tile, moff, cdst, (int)(uint32_t)(po & 0xffffffff), (int)(po >> 32)});
+                    ++n_items;
+                }
+            }
+            lvp.push_back(n_items);
+        }
+        for (int s : mem) if (s != t) for (int q = 0; q < F.sn[s].nrows; ++q) local_slot[F.sn[s].slot_off + q] = -1;
+        if (!ok) { ++left; continue; }
+        const int nl = (int)lvp.size() - 1;
+        const int item0 = (SUB_HDR + nl + 1 + 3) & ~3, map0 = item0 + SUB_ITEM * n_items;
+        const int n_ints = (map0 + (int)maps.size() + 3) & ~3;
+        std::vector<int> v(n_ints, 0);
+        const int64_t rs = F.sn[t].slot_off;
+        const int cbuf = n_ints / 2;      // (doubles)
+        const int ts_off = cbuf + cdoubles;
+        v[0] = nl; v[1] = item0; v[2] = cbuf; v[3] = ts_off; v[4] = (int)(uint32_t)(rs & 0xffffffff); v[5] = (int)(rs >> 32);
+        for (int l = 0; l <= nl; ++l) v[SUB_HDR + l] = lvp[l];
+        for (size_t q = 0; q < items.size(); ++q) {
+            v[item0 + q] = items[q];
+            if (q % SUB_ITEM == 4 && items[q] >= 0) v[item0 + q] += map0;      // front map: offset in the record
+        }
+        std::copy(maps.begin(), maps.end(), v.begin() + map0);
+        const int lds = 8 * (ts_off + 3 * 64 * SUB_WAVES);
+        if (lds > lds_cap) { ++left; continue; }
+        double bytes = 0.0;
+        for (int s : mem) { const double k = F.sn[s].ncols, f = k + F.sn[s].nrows; bytes += 8.0 * (f * k - 0.5 * k * (k - 1)); }
+        lds_max = std::max(lds_max, lds);
+        recs.push_back({std::move(v), bytes, std::move(mem)});
+    }
+    if (getenv("ADMM_HIP_VERBOSE"))
+        fprintf(stderr, "admm_hip: plan fused cut %d subtrees %d left %d lds %d cap %d\n", cut, (int)recs.size(), left, lds_max, lds_cap);
+    if (recs.empty()) return ADMM_OK;
+    // the largest subtrees start first
+    std::stable_sort(recs.begin(), recs.end(), [](const Rec &a, const Rec &b) { return a.bytes > b.bytes; });
+    std::vector<int> all; std::vector<int64_t> off{0};
+    for (const Rec &r : recs) { all.insert(all.end(), r.v.begin(), r.v.end()); off.push_back((int64_t)all.size()); for (int s : r.members) fused[s] = 1; }
+    TRY(upload(ctx, &ctx->d_fuse_rec, all)); TRY(upload(ctx, &ctx->d_fuse_off, off));
+    ctx->fuse_cut = cut; ctx->n_fuse = (int)recs.size(); ctx->fuse_lds = lds_max;
+    return ADMM_OK;
+}
+
 int upload_factor(admm_hip_ctx *ctx) {
 #ifdef ADMM_SWEEP_PROFILE
     g_swp_wgs = 0; g_swp_meta.clear();
@@ -51,6 +167,8 @@ int upload_factor(admm_hip_ctx *ctx) {
     if (subtree) { passes.push_back({ctx->rank, &ctx->levels}); passes.push_back({-1, &ctx->levels_top}); }
     else passes.push_back({0, &ctx->levels});
     const std::vector<int> *own = subtree ? &ctx->sn_owner : nullptr;
+    std::vector<char> fused;      // supernodes of the fused bottom subtrees (this rank's own ones under subtree sharding): no per-level items
+    TRY(fuse_subtrees(ctx, own, subtree ? ctx->rank : 0, fused));
     // Subtree sharding: which top supernodes' x does a rank need?  The forward sweep over the top is complete on every rank (it sums
     // towards the root), but the backward sweep only has to reach the separators a rank touches: those that appear among the front rows
     // of its own subtrees, those its elements have a node in, and their ancestors.  Everybody evaluates the rule for EVERY rank (no
@@ -93,7 +211,8 @@ int upload_factor(admm_hip_ctx *ctx) {
                     L.roots.push_back({S.ncols, S.first, S.front_off, ctx->dev_root_inv_off[s]});
                     continue;
                 }
-                for (int t = 0; t < tiles; ++t) { it.part = t; if (fwd_small) sm.push_back(it); else bg.push_back(it); }
+                const bool in_fused = ps.want >= 0 && fused[s];
+                if (!in_fused) for (int t = 0; t < tiles; ++t) { it.part = t; if (fwd_small) sm.push_back(it); else bg.push_back(it); }
                 const int chunks = (S.ncols + L.bwd_nw * L.bwd_cw - 1) / (L.bwd_nw * L.bwd_cw);
                 if (subtree && ps.want < 0 && !top_needed[s]) continue;      // replicated top: no backward work for a separator this rank never reads
                 for (int c = 0; c < chunks; ++c) { it.part = c; bw.push_back(it); }
