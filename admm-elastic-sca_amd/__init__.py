@@ -25,7 +25,7 @@ KIND_NODES = [1, 2, 4, 4, 4, 4, 3, 4, 1, 3, 3]
 KIND_ROWS = [3, 3, 9, 9, 9, 9, 6, 9, 3, 6, 6]
 KIND_PARAMS = [2, 1, 1, 3, 3, 3, 4, 1, 1, 4, 3]
 KIND_STATE = [0, 0, 0, 0, 4, 4, 0, 0, 0, 0, 4]
-SHAPE = dict(FLOOR=0, SPHERE=1, CYLINDER=2)
+SHAPE = dict(FLOOR=0, SPHERE=1, CYLINDER=2, MESH=3)
 EXPLICIT = dict(CONST=0, WIND=1)
 
 _dp = C.POINTER(C.c_double)
@@ -144,6 +144,12 @@ def lib():
         L.admm_hip_keep_z.argtypes = [C.c_void_p, C.c_int]
         L.admm_hip_get_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         L.admm_hip_get_timing_previous.argtypes = [C.c_void_p, C.POINTER(Timing)]
+        L.admm_hip_mesh_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, _dp, C.c_int, _ip, C.c_char_p, C.c_int]
+        L.admm_hip_mesh_destroy.argtypes = [C.c_void_p]
+        L.admm_hip_mesh_destroy.restype = None
+        L.admm_hip_mesh_query.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, _dp]
+        L.admm_hip_mesh_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]
+        L.admm_hip_add_collision_mesh.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -154,6 +160,48 @@ def _d(a):
 
 def _i(a):
     return a.ctypes.data_as(_ip) if a is not None else None
+
+
+class Mesh:
+    """A closed triangle mesh prepared for collision queries (admm_hip_mesh_create): validated, pseudo-normals and BVH built.
+    verts [nv][3] float64, tris [nt][3] int32, counter-clockwise seen from outside.  Invalid input raises AdmmHipError."""
+
+    def __init__(self, verts, tris):
+        self.L = lib()
+        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        rc = self.L.admm_hip_mesh_create(C.byref(h), v.shape[0], _d(v), t.shape[0], _i(t), err, len(err))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_create error %d: %s" % (rc, err.value.decode()))
+        self.h = h
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.admm_hip_mesh_destroy(self.h)
+            self.h = None
+
+    def query(self, pts, t=(0.0, 0.0, 0.0)):
+        """-> (proj [n][3], sdist [n]) for the instance translated by t: proj = t + the closest point, sdist > 0 inside (host evaluation)"""
+        p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        tt = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        proj = np.empty_like(p); sd = np.empty(p.shape[0])
+        rc = self.L.admm_hip_mesh_query(self.h, _d(tt), p.shape[0], _d(p), _d(proj), _d(sd))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_query error %d" % rc)
+        return proj, sd
+
+    def info(self):
+        nt, nn, dep = C.c_int(), C.c_int(), C.c_int()
+        box = np.zeros(6)
+        self.L.admm_hip_mesh_info(self.h, C.byref(nt), C.byref(nn), C.byref(dep), _d(box))
+        return dict(n_tris=nt.value, n_nodes=nn.value, depth=dep.value, lo=box[:3].copy(), hi=box[3:].copy())
+
+
+def mesh_query(verts, tris, pts, t=(0.0, 0.0, 0.0)):
+    """closest points and signed distances of pts to the closed mesh (verts, tris) translated by t -> (proj, sdist), sdist > 0 inside"""
+    return Mesh(verts, tris).query(pts, t)
 
 
 class System:
@@ -299,6 +347,13 @@ class System:
         t = np.ascontiguousarray(types, dtype=np.int32)
         p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 4)
         self._chk(self.L.admm_hip_set_collision_shapes(self.h, t.size, _i(t), _d(p)))
+
+    def add_collision_mesh(self, verts, tris):
+        """registers a closed triangle mesh (before initialize) -> its mesh_id for SHAPE["MESH"] entries {tx, ty, tz, mesh_id}"""
+        m = verts if isinstance(verts, Mesh) else Mesh(verts, tris)
+        mid = C.c_int()
+        self._chk(self.L.admm_hip_add_collision_mesh(self.h, m.h, C.byref(mid)))
+        return mid.value
 
     def set_gravity(self, which, g):
         self._chk(self.L.admm_hip_set_gravity(self.h, which, float(g[0]), float(g[1]), float(g[2])))

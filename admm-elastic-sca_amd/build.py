@@ -3,6 +3,8 @@
   dense.cpp, factor.cpp                  : host-side ordering / multifrontal factorization, g++ -O3 -fopenmp
   host_setup.cpp, partition.cpp, comm.cpp : host-only parts of the library around the context (ctx.hpp): assembly + factor set-up,
                                            subtree sharding, RCCL / all-reduce hooks -- hipcc as a host compile (HIP runtime API only)
+  mesh.cpp                               : mesh obstacles on the host (validation, BVH, the host query of mesh_query.hpp), g++ -O3
+                                           -ffp-contract=off (the device's arithmetic)
   admm_hip.hip                           : the device translation unit: kernels (kernels_*.hpp, factor_dev.hpp), device factorization,
                                            upload, launches, step loop, C ABI; hipcc --offload-arch=gfx950, -ffp-contract=off
                                            (operation order = reference's)
@@ -72,6 +74,7 @@ def _jobs(extra_hip_flags, tag):
         ([hipcc] + HIPHOST_FLAGS, "host_setup.cpp", "host_setup.o"),
         ([hipcc] + HIPHOST_FLAGS, "partition.cpp", "partition.o"),
         ([hipcc] + HIPHOST_FLAGS, "comm.cpp", "comm.o"),
+        (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "mesh.cpp", "mesh.o"),
         ([hipcc] + HIP_FLAGS + list(extra_hip_flags), "admm_hip.hip", "admm_hip%s.o" % tag),
     ]
 

@@ -201,9 +201,15 @@ int admm_hip_set_gravity(admm_hip_ctx *ctx, int which, double gx, double gy, dou
 int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
     if (!ctx || n_shapes < 0 || (n_shapes && (!types || !params))) return ADMM_ERR_ARG;
     if (n_shapes > ADMM_MAX_SHAPES) return fail(ctx, ADMM_ERR_UNSUPPORTED, "at most %d collision shapes", ADMM_MAX_SHAPES);
+    for (int j = 0; j < n_shapes; ++j)      // (checked before the table changes: a refused list leaves the last good one in place)
+        if (types[j] == ADMM_SHAPE_MESH) {
+            const double id = params[4 * (size_t)j + 3];
+            if (!(id >= 0.0 && id < (double)ctx->meshes.size() && id == (double)(int)id))
+                return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh_id %g is not a registered mesh (have %d)", j, id, (int)ctx->meshes.size());
+        }
     ctx->shapes.n = n_shapes;
     for (int j = 0; j < n_shapes; ++j) {
-        if (types[j] < ADMM_SHAPE_FLOOR || types[j] > ADMM_SHAPE_CYLINDER) return fail(ctx, ADMM_ERR_UNSUPPORTED, "collision shape type %d", types[j]);
+        if (types[j] < ADMM_SHAPE_FLOOR || types[j] > ADMM_SHAPE_MESH) return fail(ctx, ADMM_ERR_UNSUPPORTED, "collision shape type %d", types[j]);
         ctx->shapes.type[j] = types[j];
         for (int q = 0; q < 4; ++q) ctx->shapes.par[j][q] = params[4 * (size_t)j + q];
     }
@@ -212,6 +218,15 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
         HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
+    return ADMM_OK;
+}
+
+// extension, no reference counterpart (include/admm_hip.h): the context keeps its own copy, uploaded at finalize
+int admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, int *mesh_id) {
+    if (!ctx || !mesh || mesh->nodes.empty()) return ADMM_ERR_ARG;
+    if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision meshes must be registered before finalize");
+    ctx->meshes.push_back(*mesh);
+    if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
     return ADMM_OK;
 }
 

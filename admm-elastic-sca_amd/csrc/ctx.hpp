@@ -20,6 +20,7 @@
 #include "../../include/admm_hip.h"
 #include "factor.hpp"
 #include "dev_types.hpp"
+#include "mesh_host.hpp"
 
 namespace admm_lib {
 
@@ -119,6 +120,9 @@ struct admm_hip_ctx {
     admm_dev::Gravity grav{};             // fast path: only constant all-node forces
     std::vector<Explicit> explicits; bool explicit_simple = true;
     admm_dev::ShapeTable shapes{}; admm_dev::ShapeTable *d_shapes = nullptr;
+    // closed triangle meshes named by ADMM_SHAPE_MESH entries (admm_hip_add_collision_mesh, before finalize): with at least one, the collision
+    // batches run project_collision_mesh_kernel instead of a segment of project_multi_kernel; their arrays are uploaded at finalize
+    std::vector<admm_hip_mesh> meshes; admm_mesh::MeshDev *d_meshes = nullptr;
     SymCSC A;
     Factor F;
     admm_hip_info info{};

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include "local_math.hpp"
 #include "dev_types.hpp"
+#include "mesh_query.hpp"
 #include "../../include/admm_kinds.h"
 
 namespace admm_dev {
@@ -388,6 +389,22 @@ void project_tet_kernel(BatchDev b, const double *__restrict__ x, BatchDev tail,
 // the point Dx+u is pushed out of every analytic shape it penetrates, in list
 // order (CollisionFloor.hpp:51-58, CollisionSphere.hpp:50-66, CollisionCylinder.hpp:48-66)
 // ---------------------------------------------------------------------------
+// one analytic shape of the list (floor, sphere, z-cylinder) pushes p out; shared by project_collision_block and project_collision_mesh_kernel
+__device__ __forceinline__ void collide_analytic(const ShapeTable *__restrict__ shapes, const int q, double p[3]) {
+    const double c0 = shapes->par[q][0], c1 = shapes->par[q][1], c2 = shapes->par[q][2], R = shapes->par[q][3];
+    const int ty = shapes->type[q];
+    if (ty == ADMM_SHAPE_FLOOR) {
+        if (c1 - p[1] > 0) p[1] = c1;
+    } else if (ty == ADMM_SHAPE_SPHERE) {
+        const double d0 = p[0] - c0, d1 = p[1] - c1, d2 = p[2] - c2;
+        const double nrm = sqrt(d0 * d0 + (d1 * d1 + d2 * d2));
+        if (R - nrm > 0) { p[0] = c0 + R * (d0 / nrm); p[1] = c1 + R * (d1 / nrm); p[2] = c2 + R * (d2 / nrm); }
+    } else {
+        const double d0 = p[0] - c0, d1 = p[1] - c1, d2 = 0.0 - 0.0;
+        const double nrm = sqrt(d0 * d0 + (d1 * d1 + d2 * d2));
+        if (R - nrm > 0) { const double pz = p[2]; p[0] = (c0 + R * (d0 / nrm)) + 0.0; p[1] = (c1 + R * (d1 / nrm)) + 0.0; p[2] = (0.0 + R * (d2 / nrm)) + pz; }
+    }
+}
 __device__ __forceinline__ void project_collision_block(const BatchDev &b, const double *__restrict__ x, const ShapeTable *__restrict__ shapes, const int lb) {
     const int e = b.e0 + lb * LOCAL_BLOCK + threadIdx.x;
     const int n = b.n;
@@ -404,20 +421,46 @@ __device__ __forceinline__ void project_collision_block(const BatchDev &b, const
         p[j] = dx[j] + u[j];
     }
     const int ns = shapes->n;
+    for (int q = 0; q < ns; ++q) collide_analytic(shapes, q, p);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double un = u[j] + (dx[j] - p[j]);
+        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
+        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
+    }
+}
+
+// ... with closed triangle meshes in the list (ADMM_SHAPE_MESH, mesh_query.hpp): one lane per node as above, the analytic shapes through
+// collide_analytic, a mesh instance through a BVH traversal whose stack is the lane's column of an LDS array (no private array indexed at
+// run time).  A point on or outside the instance's root box cannot be inside the mesh and skips the traversal.
+__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_mesh_kernel(BatchDev b, const double *__restrict__ x, const ShapeTable *__restrict__ shapes,
+                                                                             const admm_mesh::MeshDev *__restrict__ meshes) {
+    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
+    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
+    const int n = b.n;
+    if (e >= b.e1) return;
+    const int id = b.idx[e];
+    const int ds = b.dst[e];
+    const double s = b.w2h2[e];
+    double dx[3], u[3], p[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
+        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
+        u[j] = b.u[(size_t)j * n + e];
+        p[j] = dx[j] + u[j];
+    }
+    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
+    const int ns = shapes->n;
     for (int q = 0; q < ns; ++q) {
-        const double c0 = shapes->par[q][0], c1 = shapes->par[q][1], c2 = shapes->par[q][2], R = shapes->par[q][3];
-        const int ty = shapes->type[q];
-        if (ty == ADMM_SHAPE_FLOOR) {
-            if (c1 - p[1] > 0) p[1] = c1;
-        } else if (ty == ADMM_SHAPE_SPHERE) {
-            const double d0 = p[0] - c0, d1 = p[1] - c1, d2 = p[2] - c2;
-            const double nrm = sqrt(d0 * d0 + (d1 * d1 + d2 * d2));
-            if (R - nrm > 0) { p[0] = c0 + R * (d0 / nrm); p[1] = c1 + R * (d1 / nrm); p[2] = c2 + R * (d2 / nrm); }
-        } else {
-            const double d0 = p[0] - c0, d1 = p[1] - c1, d2 = 0.0 - 0.0;
-            const double nrm = sqrt(d0 * d0 + (d1 * d1 + d2 * d2));
-            if (R - nrm > 0) { const double pz = p[2]; p[0] = (c0 + R * (d0 / nrm)) + 0.0; p[1] = (c1 + R * (d1 / nrm)) + 0.0; p[2] = (0.0 + R * (d2 / nrm)) + pz; }
-        }
+        if (shapes->type[q] != ADMM_SHAPE_MESH) { collide_analytic(shapes, q, p); continue; }
+        const admm_mesh::MeshDev m = meshes[(int)shapes->par[q][3]];
+        const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
+        const double qq[3] = {p[0] - t[0], p[1] - t[1], p[2] - t[2]};
+        if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
+        admm_mesh::Hit h;
+        admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
+        if (admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0) { p[0] = t[0] + h.c[0]; p[1] = t[1] + h.c[1]; p[2] = t[2] + h.c[2]; }
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {

@@ -44,7 +44,7 @@ bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
         case ADMM_KIND_TRI_STRAIN: code = MK_TRI_STRAIN; break;
         case ADMM_KIND_TRI_AREA: code = MK_TRI_AREA; break;
         case ADMM_KIND_TRI_FUNG: code = MK_TRI_FUNG; break;
-        case ADMM_KIND_COLLISION: code = MK_COLLISION; break;
+        case ADMM_KIND_COLLISION: if (!ctx->meshes.empty()) continue; code = MK_COLLISION; break;      // (meshes: own launch, launch_local)
         default: break;
         }
         if (code < 0 || mb.n == MULTI_MAX) return false;
@@ -61,6 +61,14 @@ bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
     return true;
 }
 
+// a collision batch of a context with mesh obstacles
+void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
+    using namespace admm_dev;
+    const BatchDev d = batch_dev(ctx, b);
+    hipLaunchKernelGGL(project_collision_mesh_kernel, dim3((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), dim3(LOCAL_BLOCK), 0, ctx->stream, d, (const double *)ctx->d_xcur,
+                       (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes);
+}
+
 int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
     using namespace admm_dev;
     hipStream_t const st = ctx->stream;
@@ -69,6 +77,8 @@ int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
         MultiBatch mb{}; int blocks = 0;
         if (build_multi(ctx, mb, blocks)) {
             hipLaunchKernelGGL(project_multi_kernel, dim3(blocks), dim3(LOCAL_BLOCK), 0, st, mb, (const double *)ctx->d_xcur, (const ShapeTable *)ctx->d_shapes);
+            if (!ctx->meshes.empty())      // the collision batches were left out of the segments: their own launches
+                for (const Batch &b : ctx->batches) if (b.kind == ADMM_KIND_COLLISION && b.n_local > 0) launch_collision_mesh(ctx, b);
             HIPCHK(hipGetLastError());
             return ADMM_OK;
         }
@@ -114,7 +124,10 @@ int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
         case ADMM_KIND_TRI_STRAIN: hipLaunchKernelGGL(project_tri_kernel<0>, grid, block, 0, st, d, x); break;
         case ADMM_KIND_TRI_AREA: hipLaunchKernelGGL(project_tri_kernel<1>, grid, block, 0, st, d, x); break;
         case ADMM_KIND_TRI_FUNG: hipLaunchKernelGGL(project_tri_kernel<2>, grid, block, 0, st, d, x); break;
-        case ADMM_KIND_COLLISION: hipLaunchKernelGGL(project_collision_kernel, grid, block, 0, st, d, x, (const ShapeTable *)ctx->d_shapes); break;
+        case ADMM_KIND_COLLISION:
+            if (!ctx->meshes.empty()) launch_collision_mesh(ctx, b);
+            else hipLaunchKernelGGL(project_collision_kernel, grid, block, 0, st, d, x, (const ShapeTable *)ctx->d_shapes);
+            break;
         default: return fail(ctx, ADMM_ERR_UNSUPPORTED, "no kernel for kind %d", b.kind);
         }
     }

@@ -1,0 +1,200 @@
+// mesh.cpp -- closed triangle-mesh obstacles on the host: validation, pseudo-normals and the BVH of admm_hip_mesh_create, and
+// admm_hip_mesh_query, the host evaluation of the query the device runs (mesh_query.hpp).  Context-free: a context copies a mesh
+// at admm_hip_add_collision_mesh (abi_setup.inc).  Built with -ffp-contract=off like the device code, so both give the same bits.
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/admm_hip.h"
+#include "mesh_host.hpp"
+
+using namespace admm_mesh;
+
+namespace {
+
+int mesh_fail(char *err, int err_len, const char *fmt, ...) {
+    if (err && err_len > 0) { va_list ap; va_start(ap, fmt); vsnprintf(err, (size_t)err_len, fmt, ap); va_end(ap); }
+    return ADMM_ERR_ARG;
+}
+
+void cross(const double *a, const double *b, double *o) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; }
+double dot(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+void normalize(double *v) { const double l = std::sqrt(dot(v, v)); if (l > 0.0) for (int j = 0; j < 3; ++j) v[j] /= l; }
+
+struct Builder {
+    const std::vector<Tri> &src;              // canonical triangles, caller's order
+    std::vector<double> cen;                  // [nt][3] centroids
+    std::vector<int> ord;                     // triangles in leaf order
+    std::vector<Node> nodes;
+    int depth = 0;
+    Builder(const std::vector<Tri> &s) : src(s) {}
+    void box(int b, int e, Node &n) const {
+        for (int j = 0; j < 3; ++j) { n.lo[j] = INFINITY; n.hi[j] = -INFINITY; }
+        for (int i = b; i < e; ++i) for (int k = 0; k < 3; ++k) for (int j = 0; j < 3; ++j) {
+            const double v = src[ord[i]].v[3 * k + j];
+            n.lo[j] = std::min(n.lo[j], v); n.hi[j] = std::max(n.hi[j], v);
+        }
+    }
+    // node `ni` over ord[b, e): a leaf of at most LEAF_TRIS triangles, or split at the median of the centroids along the widest axis of
+    // their bounds (stable: ties in the centroid go by the original index) with its two children appended side by side
+    void build(int ni, int b, int e, int level) {
+        depth = std::max(depth, level);
+        Node n{}; box(b, e, n);
+        if (e - b <= LEAF_TRIS) { n.a = b; n.cnt = e - b; nodes[ni] = n; return; }
+        double clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int i = b; i < e; ++i) for (int j = 0; j < 3; ++j) { clo[j] = std::min(clo[j], cen[3 * ord[i] + j]); chi[j] = std::max(chi[j], cen[3 * ord[i] + j]); }
+        int ax = 0;
+        for (int j = 1; j < 3; ++j) if (chi[j] - clo[j] > chi[ax] - clo[ax]) ax = j;
+        std::sort(ord.begin() + b, ord.begin() + e, [&](int p, int q) {
+            const double cp = cen[3 * p + ax], cq = cen[3 * q + ax];
+            return cp < cq || (cp == cq && p < q);
+        });
+        const int mid = b + (e - b) / 2;
+        const int l = (int)nodes.size();
+        nodes.push_back(Node{}); nodes.push_back(Node{});
+        n.a = l; n.cnt = 0; nodes[ni] = n;
+        build(l, b, mid, level + 1);
+        build(l + 1, mid, e, level + 1);
+    }
+};
+
+int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, admm_hip_mesh &M, char *err, int err_len) {
+    if (nv < 4 || nt < 4 || !verts || !tris) return mesh_fail(err, err_len, "a closed mesh needs at least 4 vertices and 4 triangles (have %d, %d)", nv, nt);
+    for (int t = 0; t < nt; ++t) for (int k = 0; k < 3; ++k)
+        if (tris[3 * (size_t)t + k] < 0 || tris[3 * (size_t)t + k] >= nv)
+            return mesh_fail(err, err_len, "triangle %d: vertex index %d out of range [0, %d)", t, tris[3 * (size_t)t + k], nv);
+    for (int i = 0; i < 3 * nv; ++i) if (!std::isfinite(verts[i])) return mesh_fail(err, err_len, "vertex %d is not finite", i / 3);
+    // canonical corners: rotated so that the lowest vertex id comes first (orientation kept), so that a triangle listed with its
+    // corners rotated gives the same arithmetic
+    std::vector<Tri> src((size_t)nt);
+    std::vector<int> cid((size_t)nt * 3);
+    std::vector<double> fn((size_t)nt * 3);      // unit face normals
+    for (int t = 0; t < nt; ++t) {
+        const int32_t *T = tris + 3 * (size_t)t;
+        const int r = (T[1] < T[0] && T[1] <= T[2]) ? 1 : (T[2] < T[0] && T[2] < T[1]) ? 2 : 0;
+        Tri &tr = src[t];
+        std::memset(&tr, 0, sizeof tr);
+        for (int k = 0; k < 3; ++k) { cid[3 * (size_t)t + k] = T[(k + r) % 3]; for (int j = 0; j < 3; ++j) tr.v[3 * k + j] = verts[3 * (size_t)T[(k + r) % 3] + j]; }
+        tr.orig = t;
+        double e1[3], e2[3], n[3];
+        for (int j = 0; j < 3; ++j) { e1[j] = tr.v[3 + j] - tr.v[j]; e2[j] = tr.v[6 + j] - tr.v[j]; }
+        cross(e1, e2, n);
+        if (!(dot(n, n) > 0.0) || T[0] == T[1] || T[1] == T[2] || T[0] == T[2])
+            return mesh_fail(err, err_len, "triangle %d (%d, %d, %d) is degenerate (zero area)", t, T[0], T[1], T[2]);
+        normalize(n);
+        for (int j = 0; j < 3; ++j) fn[3 * (size_t)t + j] = n[j];
+    }
+    // edges: every undirected edge must be used by exactly two triangles, once in each direction
+    struct E { int lo, hi, t, k; bool fwd; };
+    std::vector<E> es((size_t)nt * 3);
+    for (int t = 0; t < nt; ++t) for (int k = 0; k < 3; ++k) {
+        const int a = cid[3 * (size_t)t + k], b = cid[3 * (size_t)t + (k + 1) % 3];
+        es[3 * (size_t)t + k] = E{std::min(a, b), std::max(a, b), t, k, a < b};
+    }
+    std::sort(es.begin(), es.end(), [](const E &p, const E &q) { return p.lo != q.lo ? p.lo < q.lo : p.hi != q.hi ? p.hi < q.hi : p.t != q.t ? p.t < q.t : p.k < q.k; });
+    std::vector<int> adj((size_t)nt * 3, -1);     // the triangle on the other side of edge k of triangle t
+    for (size_t i = 0; i < es.size();) {
+        size_t j = i;
+        while (j < es.size() && es[j].lo == es[i].lo && es[j].hi == es[i].hi) ++j;
+        if (j - i != 2)
+            return mesh_fail(err, err_len, "edge (%d, %d) is shared by %d triangle%s (first: triangle %d), not 2: the mesh is %s", es[i].lo, es[i].hi, (int)(j - i),
+                             j - i == 1 ? "" : "s", es[i].t, j - i == 1 ? "open" : "not edge-manifold");
+        if (es[i].fwd == es[i + 1].fwd)
+            return mesh_fail(err, err_len, "edge (%d, %d) is traversed in the same direction by triangles %d and %d: inconsistent orientation (a flipped triangle)",
+                             es[i].lo, es[i].hi, es[i].t, es[i + 1].t);
+        adj[3 * (size_t)es[i].t + es[i].k] = es[i + 1].t;
+        adj[3 * (size_t)es[i + 1].t + es[i + 1].k] = es[i].t;
+        i = j;
+    }
+    // outward normals: the enclosed volume is positive
+    double vol = 0.0;
+    for (int t = 0; t < nt; ++t) { double c[3]; cross(src[t].v + 3, src[t].v + 6, c); vol += dot(src[t].v, c); }
+    if (!(vol > 0.0)) return mesh_fail(err, err_len, "the mesh encloses a non-positive volume (%g): its triangles must be ordered counter-clockwise seen from outside", vol / 6.0);
+    // pseudo-normals: angle-weighted vertex normals, summed edge normals
+    std::vector<double> vn((size_t)nv * 3, 0.0);
+    for (int t = 0; t < nt; ++t) for (int k = 0; k < 3; ++k) {
+        const double *p = src[t].v + 3 * k, *p1 = src[t].v + 3 * ((k + 1) % 3), *p2 = src[t].v + 3 * ((k + 2) % 3);
+        double a[3], b[3];
+        for (int j = 0; j < 3; ++j) { a[j] = p1[j] - p[j]; b[j] = p2[j] - p[j]; }
+        double c = dot(a, b) / std::sqrt(dot(a, a) * dot(b, b));
+        c = std::max(-1.0, std::min(1.0, c));
+        const double ang = std::acos(c);
+        for (int j = 0; j < 3; ++j) vn[3 * (size_t)cid[3 * (size_t)t + k] + j] += ang * fn[3 * (size_t)t + j];
+    }
+    std::vector<Nrm> nrm((size_t)nt);
+    for (int t = 0; t < nt; ++t) {
+        Nrm &N = nrm[t];
+        for (int j = 0; j < 3; ++j) N.n[0][j] = fn[3 * (size_t)t + j];
+        for (int k = 0; k < 3; ++k) {
+            const int o = adj[3 * (size_t)t + k];
+            const int lo = std::min(t, o), hi = std::max(t, o);      // (the same sum seen from both sides)
+            for (int j = 0; j < 3; ++j) N.n[1 + k][j] = fn[3 * (size_t)lo + j] + fn[3 * (size_t)hi + j];
+            normalize(N.n[1 + k]);
+            for (int j = 0; j < 3; ++j) N.n[4 + k][j] = vn[3 * (size_t)cid[3 * (size_t)t + k] + j];
+            normalize(N.n[4 + k]);
+        }
+    }
+    // BVH
+    Builder B(src);
+    B.cen.resize((size_t)nt * 3);
+    for (int t = 0; t < nt; ++t) for (int j = 0; j < 3; ++j) B.cen[3 * (size_t)t + j] = (src[t].v[j] + src[t].v[3 + j] + src[t].v[6 + j]) / 3.0;
+    B.ord.resize(nt);
+    for (int t = 0; t < nt; ++t) B.ord[t] = t;
+    B.nodes.reserve(2 * (size_t)(nt / LEAF_TRIS + 1));
+    B.nodes.push_back(Node{});
+    B.build(0, 0, nt, 0);
+    if (B.depth > MAX_DEPTH) return mesh_fail(err, err_len, "BVH depth %d exceeds %d", B.depth, MAX_DEPTH);
+    M.nodes = std::move(B.nodes);
+    M.tris.resize(nt); M.nrm.resize(nt);
+    for (int i = 0; i < nt; ++i) { M.tris[i] = src[B.ord[i]]; M.nrm[i] = nrm[B.ord[i]]; }
+    M.depth = B.depth;
+    return ADMM_OK;
+}
+
+struct HostStack { int s[MAX_DEPTH]; int &operator[](int i) { return s[i]; } };
+
+} // namespace
+
+extern "C" {
+
+int admm_hip_mesh_create(admm_hip_mesh **out, int nv, const double *verts, int nt, const int32_t *tris, char *err, int err_len) {
+    if (err && err_len > 0) err[0] = 0;
+    if (!out) return mesh_fail(err, err_len, "out is NULL");
+    *out = nullptr;
+    admm_hip_mesh *M = new (std::nothrow) admm_hip_mesh();
+    if (!M) return mesh_fail(err, err_len, "out of memory");
+    const int rc = mesh_build(nv, verts, nt, tris, *M, err, err_len);
+    if (rc) { delete M; return rc; }
+    *out = M;
+    return ADMM_OK;
+}
+
+void admm_hip_mesh_destroy(admm_hip_mesh *mesh) { delete mesh; }
+
+int admm_hip_mesh_info(const admm_hip_mesh *mesh, int *n_tris, int *n_nodes, int *depth, double *box) {
+    if (!mesh) return ADMM_ERR_ARG;
+    if (n_tris) *n_tris = (int)mesh->tris.size();
+    if (n_nodes) *n_nodes = (int)mesh->nodes.size();
+    if (depth) *depth = mesh->depth;
+    if (box) for (int j = 0; j < 3; ++j) { box[j] = mesh->nodes[0].lo[j]; box[3 + j] = mesh->nodes[0].hi[j]; }
+    return ADMM_OK;
+}
+
+int admm_hip_mesh_query(const admm_hip_mesh *mesh, const double t[3], int64_t n_pts, const double *pts, double *proj, double *sdist) {
+    if (!mesh || !t || n_pts < 0 || (n_pts && !pts)) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n_pts; ++i) {
+        const double q[3] = {pts[3 * i] - t[0], pts[3 * i + 1] - t[1], pts[3 * i + 2] - t[2]};
+        HostStack stk; Hit h;
+        closest(mesh->nodes.data(), mesh->tris.data(), q, stk, h);
+        const bool in = inside(mesh->nodes[0], mesh->nrm.data(), q, h);
+        if (proj) for (int j = 0; j < 3; ++j) proj[3 * i + j] = t[j] + h.c[j];
+        if (sdist) { const double d = std::sqrt(h.d2); sdist[i] = in ? d : -d; }
+    }
+    return ADMM_OK;
+}
+
+} // extern "C"

@@ -520,6 +520,17 @@ int upload_all(admm_hip_ctx *ctx) {
     // collision shapes and the general explicit forces (index lists in factor order)
     TRY(dalloc(ctx, &ctx->d_shapes, 1));
     HIPCHK(hipMemcpy(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice));
+    if (!ctx->meshes.empty()) {      // mesh obstacles: BVH nodes, triangles, pseudo-normals, and the table of them the kernel reads
+        std::vector<admm_mesh::MeshDev> md;
+        for (const admm_hip_mesh &M : ctx->meshes) {
+            admm_mesh::MeshDev d{};
+            admm_mesh::Node *nd; admm_mesh::Tri *tr; admm_mesh::Nrm *nr;
+            TRY(upload(ctx, &nd, M.nodes)); TRY(upload(ctx, &tr, M.tris)); TRY(upload(ctx, &nr, M.nrm));
+            d.nodes = nd; d.tris = tr; d.nrm = nr; d.n_nodes = (int)M.nodes.size(); d.n_tris = (int)M.tris.size();
+            md.push_back(d);
+        }
+        TRY(upload(ctx, &ctx->d_meshes, md));
+    }
     for (Explicit &E : ctx->explicits) {
         std::vector<int> pidx(E.idx.size());
         for (size_t i = 0; i < E.idx.size(); ++i) pidx[i] = F.iperm[E.idx[i]];

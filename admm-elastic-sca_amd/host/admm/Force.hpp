@@ -21,11 +21,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <typeinfo>
 #include <vector>
 
 #include "Vec.hpp"
+#include "admm_hip.h"
 #include "admm_kinds.h"
 
 namespace admm {
@@ -246,6 +248,32 @@ public:
     int shape_type() const { return typeid(*this) == typeid(CollisionCylinder) ? ADMM_SHAPE_CYLINDER : -1; }
     double shape_radius() const { return radius; }
     double radius, length;
+};
+
+// Extension, no reference counterpart: a closed triangle mesh (verts [nv][3], tris [nt][3], counter-clockwise seen from outside)
+// translated by `center`.  isColliding / projectOut evaluate the library's query on the host (admm_hip_mesh_query: +distance
+// inside, -distance outside; the closest point); as the list's ADMM_SHAPE_MESH entry the device runs the same code.  The mesh is
+// validated and its BVH built once here; System registers it with its context before initialize (once per distinct mesh).
+// Invalid meshes throw std::runtime_error with the library's message.
+class CollisionMesh : public CollisionShape {
+public:
+    CollisionMesh(Vector3d shapeCenter, const std::vector<double> &verts, const std::vector<int> &tris) : CollisionShape(shapeCenter) {
+        std::vector<int32_t> t(tris.begin(), tris.end());
+        char err[512] = {0};
+        admm_hip_mesh *m = nullptr;
+        if (admm_hip_mesh_create(&m, (int)(verts.size() / 3), verts.data(), (int)(t.size() / 3), t.data(), err, (int)sizeof err) != ADMM_OK)
+            throw std::runtime_error(std::string("CollisionMesh: ") + err);
+        mesh = std::shared_ptr<admm_hip_mesh>(m, admm_hip_mesh_destroy);
+    }
+    double isColliding(Vector3d pos) const { double pr[3], sd; query(pos, pr, sd); return sd; }
+    Vector3d projectOut(const Vector3d currPos) const { double pr[3], sd; query(currPos, pr, sd); return Vector3d(pr[0], pr[1], pr[2]); }
+    int shape_type() const { return typeid(*this) == typeid(CollisionMesh) ? ADMM_SHAPE_MESH : -1; }
+    std::shared_ptr<admm_hip_mesh> mesh;
+private:
+    void query(const Vector3d &p, double *pr, double &sd) const {
+        const double t[3] = {center[0], center[1], center[2]}, q[3] = {p[0], p[1], p[2]};
+        admm_hip_mesh_query(mesh.get(), t, 1, q, pr, &sd);
+    }
 };
 
 // One force over ALL nodes (CollisionForce.hpp:31-46).  With analytic shapes only: a device batch with one element per

@@ -340,6 +340,7 @@ public:
 protected:
     bool initialized;
     admm_hip_ctx *gpu;
+    std::vector<std::pair<const admm_hip_mesh *, int> > mesh_ids;      // CollisionMesh obstacles registered with the context -> their mesh_id
     std::vector<int> batch_first, batch_count, batch_kind;
     std::vector<char> batch_moving;
     std::vector<long> batch_urow0;         // generic batches: first of their rows among the user rows (-1 otherwise)
@@ -408,6 +409,7 @@ protected:
     void release() {
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
+        mesh_ids.clear();
         initialized = false;
     }
 
@@ -416,7 +418,20 @@ protected:
         for (size_t q = 0; q < cf->collisionShapes.size(); ++q) {
             const CollisionShape &sh = *cf->collisionShapes[q];
             ty.push_back(sh.shape_type());
-            par.push_back(sh.center[0]); par.push_back(sh.center[1]); par.push_back(sh.center[2]); par.push_back(sh.shape_radius());
+            par.push_back(sh.center[0]); par.push_back(sh.center[1]); par.push_back(sh.center[2]);
+            if (sh.shape_type() == ADMM_SHAPE_MESH) {      // a mesh: registered with the context once (before finalize), then named by its id
+                const admm_hip_mesh *m = static_cast<const CollisionMesh &>(sh).mesh.get();
+                size_t k = 0;
+                while (k < mesh_ids.size() && mesh_ids[k].first != m) ++k;
+                if (k == mesh_ids.size()) {
+                    int id = -1;
+                    if (!check(admm_hip_add_collision_mesh(gpu, m, &id))) return false;
+                    mesh_ids.push_back(std::make_pair(m, id));
+                }
+                par.push_back((double)mesh_ids[k].second);
+            } else {
+                par.push_back(sh.shape_radius());
+            }
         }
         return check(admm_hip_set_collision_shapes(gpu, (int)ty.size(), ty.data(), par.data()));
     }

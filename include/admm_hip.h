@@ -117,6 +117,28 @@ int admm_hip_add_explicit(admm_hip_ctx *ctx, int type, const double *dir, int n_
  * (CollisionForce.cpp:55-70).  types [n], params [n][4] (admm_kinds.h).  May be updated between frames. */
 int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params);
 
+/* ---- closed triangle-mesh obstacles ------------------------------------------------------------------------------------------
+ * Extension, no reference counterpart: the reference's only route to a mesh obstacle is a user-written CollisionShape, which
+ * makes its CollisionForce host-projected.  A mesh is a context-free host object; a context registers it, then the shape list
+ * names it as ADMM_SHAPE_MESH { tx, ty, tz, mesh_id } (any position in the list, mixed with the analytic shapes, the same mesh
+ * several times with different translations; translations may change between frames like every shape parameter).
+ *   admm_hip_mesh_create    verts [nv][3], tris [nt][3] (int32): closed, edge-manifold, consistently oriented with outward
+ *                           normals by the right-hand rule, no degenerate triangle.  Validates that (ADMM_ERR_ARG, the offending
+ *                           edge or triangle named in err[0..err_len), NUL-terminated), computes the pseudo-normals and builds the BVH.
+ *   admm_hip_mesh_query     host evaluation for n_pts points [n][3] of the instance translated by t[3]: proj [n][3] = t + c with c the
+ *                           closest point of the mesh to p - t (ties: lowest triangle index), sdist [n] = +|p - t - c| inside,
+ *                           -|p - t - c| outside (CollisionShape.hpp:34-38: isColliding / projectOut).  Either output may be NULL.
+ *                           The device's collision kernel runs the same code and gives the same bits.
+ *   admm_hip_mesh_info      triangles, BVH nodes, BVH depth, root box [lo xyz, hi xyz]; any pointer may be NULL.
+ *   admm_hip_add_collision_mesh  copy the mesh into a context (before finalize: ADMM_ERR_STATE after) -> *mesh_id; the mesh may be
+ *                           destroyed afterwards.  Every rank of a sharded run registers the same meshes in the same order.        */
+typedef struct admm_hip_mesh admm_hip_mesh;
+int  admm_hip_mesh_create(admm_hip_mesh **out, int nv, const double *verts, int nt, const int32_t *tris, char *err, int err_len);
+void admm_hip_mesh_destroy(admm_hip_mesh *mesh);
+int  admm_hip_mesh_query(const admm_hip_mesh *mesh, const double t[3], int64_t n_pts, const double *pts, double *proj, double *sdist);
+int  admm_hip_mesh_info(const admm_hip_mesh *mesh, int *n_tris, int *n_nodes, int *depth, double *box);
+int  admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, int *mesh_id);
+
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
  * doubles of a DEVICE buffer in place across the ranks (an all-reduce), ordered on `stream`; every rank makes the same

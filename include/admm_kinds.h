@@ -82,7 +82,9 @@ static const int ADMM_KIND_STATE[ADMM_KIND_COUNT]  = { 0, 0, 0, 0, 4, 4, 0, 0, 0
 enum admm_shape {
     ADMM_SHAPE_FLOOR    = 0,   /* params { -, cy, -, - }        CollisionFloor.hpp:51-58    */
     ADMM_SHAPE_SPHERE   = 1,   /* params { cx, cy, cz, radius } CollisionSphere.hpp:50-66   */
-    ADMM_SHAPE_CYLINDER = 2    /* params { cx, cy, -, radius }  z-axis, CollisionCylinder.hpp:48-66 */
+    ADMM_SHAPE_CYLINDER = 2,   /* params { cx, cy, -, radius }  z-axis, CollisionCylinder.hpp:48-66 */
+    ADMM_SHAPE_MESH     = 3    /* params { tx, ty, tz, mesh_id } a closed triangle mesh registered with admm_hip_add_collision_mesh,
+                                  translated by t (extension, no reference counterpart; include/admm_hip.h) */
 };
 #define ADMM_MAX_SHAPES 64
 
