@@ -21,14 +21,17 @@ unsigned long long *g_swp_base; size_t g_swp_wgs; std::vector<int> g_swp_meta;
 // contribution rows landing on it, in the child order of Factor::cg4); the LDS offsets of the members' contributions.  Only the
 // subtree's root writes its contribution to C.  A subtree whose LDS does not leave two workgroups per CU, the subtree of a whole tree
 // (a root of the elimination tree at or below the cut) and trees whose front rows receive more than four contributions (no cg4) stay on
-// the per-level path.  fused[s] = 1 for the supernodes the fused launch sweeps.
+// the per-level path.  fused[s] = 1 for the supernodes the fused launch sweeps.  ADMM_HIP_VERBOSE: one "plan fused" line per call, early returns
+// included (tests/test_sweep_subtree*.py assert the shapes they reach from it).
 int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std::vector<char> &fused) {
     using namespace admm_dev;
     const Factor &F = ctx->F;
     const int ns = (int)F.sn.size();
     fused.assign(ns, 0);
     ctx->fuse_cut = -1; ctx->n_fuse = 0; ctx->fuse_lds = 0;
-    if (!ctx->sweep_fuse || F.cg4.empty() || F.levels.empty()) return ADMM_OK;
+    const bool verbose = getenv("ADMM_HIP_VERBOSE") != nullptr;
+    const char *why_off = !ctx->sweep_fuse ? "ADMM_HIP_SWEEP_FUSE=0" : (F.cg4.empty() ? "front rows with more than four contributions" : (F.levels.empty() ? "no cut level" : nullptr));
+    if (why_off) { if (verbose) fprintf(stderr, "admm_hip: plan fused off (%s)\n", why_off); return ADMM_OK; }
     auto mine = [&](int s) { return !own || (*own)[s] == want; };
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, ctx->device_id));
@@ -47,13 +50,16 @@ int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std:
         }
         if (roots >= 2 * cus) cut = l;
     }
-    if (cut < 0) return ADMM_OK;
+    if (cut < 0) { if (verbose) fprintf(stderr, "admm_hip: plan fused off (no cut level)\n"); return ADMM_OK; }
     std::vector<std::vector<int> > children(ns);
     for (int s = 0; s < ns; ++s) if (F.sn[s].parent >= 0) children[F.sn[s].parent].push_back(s);
     std::vector<int> local_slot(F.n_slots, -1);      // member's contribution slot -> LDS offset (doubles, from the contribution area)
     struct Rec { std::vector<int> v; double bytes; std::vector<int> members; };
     std::vector<Rec> recs;
     int lds_max = 0, left = 0;      // (left: subtrees that stay on the per-level path)
+    // the shapes the fused records reach (ADMM_HIP_VERBOSE only): levels per record, the most child contributions into one front row,
+    // members whose parent lies two or more levels up, non-root members without contribution rows
+    int lv_min = 0, lv_max = 0, maxin = 0, skip = 0, empty = 0;
     for (int t = 0; t < ns; ++t) {
         const int p = F.sn[t].parent;
         if (!mine(t) || F.sn[t].level > cut || p < 0 || F.sn[p].level <= cut) continue;
@@ -115,10 +121,16 @@ int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std:
         double bytes = 0.0;
         for (int s : mem) { const double k = F.sn[s].ncols, f = k + F.sn[s].nrows; bytes += 8.0 * (f * k - 0.5 * k * (k - 1)); }
         lds_max = std::max(lds_max, lds);
+        if (verbose) {
+            lv_min = recs.empty() ? nl : std::min(lv_min, nl); lv_max = std::max(lv_max, nl);
+            for (size_t q = 0; q < maps.size(); q += 4) maxin = std::max(maxin, (maps[q] >= 0) + (maps[q + 1] >= 0) + (maps[q + 2] >= 0) + (maps[q + 3] >= 0));
+            for (int s : mem) if (s != t) { skip += F.sn[F.sn[s].parent].level - F.sn[s].level >= 2; empty += F.sn[s].nrows == 0; }
+        }
         recs.push_back({std::move(v), bytes, std::move(mem)});
     }
-    if (getenv("ADMM_HIP_VERBOSE"))
-        fprintf(stderr, "admm_hip: plan fused cut %d subtrees %d left %d lds %d cap %d\n", cut, (int)recs.size(), left, lds_max, lds_cap);
+    if (verbose)
+        fprintf(stderr, "admm_hip: plan fused cut %d subtrees %d left %d lds %d cap %d levels %d..%d maxin %d skip %d empty %d\n", cut, (int)recs.size(), left, lds_max, lds_cap,
+                lv_min, lv_max, maxin, skip, empty);
     if (recs.empty()) return ADMM_OK;
     // the largest subtrees start first
     std::stable_sort(recs.begin(), recs.end(), [](const Rec &a, const Rec &b) { return a.bytes > b.bytes; });

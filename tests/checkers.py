@@ -602,13 +602,79 @@ class SparseReference:
         return xr, self.residual(xr, b), step
 
 
+def scene_reference(x, m3, forces, dt=0.04):
+    """SparseReference of any scene, through the oracle: nodes x (n x 3), masses m3 (3n), forces a list of (kind name, index array,
+    params) in the order the library gets them"""
+    o = Oracle(); o.settings(dt, 1)
+    o.add_nodes(np.asarray(x, dtype=np.float64).ravel(), m3)
+    for kind, idx, params in forces:
+        o.add_forces(KIND[kind], idx, params)
+    assert o.initialize()
+    return SparseReference(o, m3, dt)
+
+
 def bar_reference(mg, dims, mu=1e5, lam=1e5, max_iter=5, density=1000.0, dt=0.04):
     """SparseReference of the bar that make_bar_system builds (Neo-Hookean tets + anchors on the k = 0 face), through the oracle"""
     x, t = mg.bar(*dims)
     m3 = np.repeat(mg.lumped_tet_mass(x, t, density), 3)
-    o = Oracle(); o.settings(dt, 1)
-    o.add_nodes(x.ravel(), m3)
-    o.add_forces(KIND["TET_NH"], t, [mu, lam, max_iter])
-    o.add_forces(KIND["ANCHOR"], mg.bar_anchor_nodes(dims[0], dims[1]), [-1.0, 1.0])
-    assert o.initialize()
-    return SparseReference(o, m3, dt), x, m3
+    forces = [("TET_NH", t, [mu, lam, max_iter]), ("ANCHOR", mg.bar_anchor_nodes(dims[0], dims[1]), [-1.0, 1.0])]
+    return scene_reference(x, m3, forces, dt), x, m3
+
+
+# ---- scenes for the elimination-tree shapes structured bars do not give (tests/test_sweep_subtree_trees.py) ----
+def tet_volumes(x, t):
+    a = x[t[:, 1]] - x[t[:, 0]]
+    return np.einsum("ij,ij->i", a, np.cross(x[t[:, 2]] - x[t[:, 0]], x[t[:, 3]] - x[t[:, 0]])) / 6.0
+
+
+def delaunay_scene(n_pts, seed=42, box=(0.6, 0.6, 6.0), stiffness=5e4, density=1000.0):
+    """Delaunay tets of n_pts random points in a long box, slivers (quality 6 sqrt(2) volume / longest edge^3 <= 0.05) dropped, every
+    point still used; corotational tets, lumped masses, the points below z = 0.15 anchored -> (x, m3, forces).  The points are numbered
+    along the box (sorted by z): the oracle factors in natural order, and a band as narrow as a structured bar's keeps its fill alike."""
+    from scipy.spatial import Delaunay
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(0, 1, size=(n_pts, 3)) * np.array(box)
+    x = x[np.argsort(x[:, 2], kind="stable")]
+    t = Delaunay(x).simplices.astype(np.int32)
+    v = np.abs(tet_volumes(x, t))
+    lmax = np.stack([np.linalg.norm(x[t[:, i]] - x[t[:, j]], axis=1) for i, j in ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))], axis=1).max(axis=1)
+    keep = 6.0 * np.sqrt(2.0) * v > 0.05 * lmax ** 3      # (1 for a regular tet; slivers would take kappa1 to ~1e9)
+    t, v = t[keep], v[keep]
+    assert np.unique(t).size == n_pts
+    m = np.zeros(n_pts)
+    np.add.at(m, t.ravel(), np.repeat(v * density / 4.0, 4))
+    anchors = np.nonzero(x[:, 2] < 0.15)[0].astype(np.int32)
+    return x, np.repeat(m, 3), [("TET_LINEAR", t, [stiffness]), ("ANCHOR", anchors, [-1.0, 1.0])]
+
+
+def forest_scene(mg, n_small=400, big=(16, 16, 40), seed=5, stiffness=5e4, density=1000.0):
+    """n_small disconnected little bars of 1 x 1 x 1 up to 3 x 3 x 4 cells on a grid beside one larger bar, all in one system:
+    nested dissection splits between bodies (empty separators), so the elimination tree gets supernodes with no contribution rows
+    under a parent.  Corotational tets, lumped masses, the big bar's k = 0 face anchored -> (x, m3, forces)"""
+    rng = np.random.default_rng(seed)
+    xs, ts, off = [], [], 0
+    x, t = mg.bar(*big)
+    xs.append(x); ts.append(t); off = x.shape[0]
+    anchors = mg.bar_anchor_nodes(big[0], big[1])
+    side = int(np.ceil(np.sqrt(n_small)))
+    for b in range(n_small):
+        dims = (int(rng.integers(1, 4)), int(rng.integers(1, 4)), int(rng.integers(1, 5)))
+        x, t = mg.bar(*dims)
+        x = x + np.array([1.5 + 0.3 * (b % side), 0.3 * (b // side), 0.0])
+        xs.append(x); ts.append(t + off); off += x.shape[0]
+    x, t = np.concatenate(xs), np.concatenate(ts).astype(np.int32)
+    m3 = np.repeat(mg.lumped_tet_mass(x, t, density), 3)
+    return x, m3, [("TET_LINEAR", t, [stiffness]), ("ANCHOR", anchors, [-1.0, 1.0])]
+
+
+def scene_system(pkg, x, m3, forces, dt=0.04, device_id=0, rank=0, world=1):
+    """the library's System of a scene of delaunay_scene / forest_scene (gravity added), not yet initialized"""
+    s = pkg.System(device_id=device_id); s.set_timestep(dt)
+    s.add_nodes(np.asarray(x, dtype=np.float64).ravel(), m3)
+    for kind, idx, params in forces:
+        s.add_forces(pkg.KIND[kind], idx, params)
+    s.add_gravity([0.0, -9.8, 0.0])
+    if world > 1:
+        s.set_shard(rank, world)
+        s.set_shard_mode("subtree")
+    return s
