@@ -82,11 +82,9 @@ struct Explicit {
     int *d_level_ptr = nullptr; int n_levels = 0;
 };
 
-#ifndef ADMM_BWD_BIG_CW
-#define ADMM_BWD_BIG_CW 1            // backward kernel: columns per wave on levels with supernodes wider than 64
-#endif
+constexpr int BWD_BIG_CW = 1;         // backward kernel: columns per wave on levels with supernodes wider than bwd_small_k
 struct LevelDev {
-    int n_small = 0; admm_dev::SweepItem *d_small = nullptr;   // forward: wave items (levels below the split)
+    int n_small = 0; admm_dev::SweepItem *d_small = nullptr;   // forward: wave items (levels of supernodes with k <= fwd_small_k)
     int n_big = 0, big_nw = 16; admm_dev::SweepItem *d_big = nullptr;   // forward: block items; waves per tile (4 / 8 / 16 by the level's widest supernode)
     struct Root { int k, first; int64_t foff, inv_off; };
     std::vector<Root> roots;                                   // roots solved with their explicit inverse: gather + one row-wise product (no backward items)

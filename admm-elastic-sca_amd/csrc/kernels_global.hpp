@@ -154,12 +154,9 @@ __global__ void state_out_kernel(int n_nodes, const int *__restrict__ iperm, con
 
 // One lane per dof: b = base + sum of the node's incident per-corner
 // contributions.  The local kernels write every corner's 24 bytes straight to
-// its slot (layouts: admm_hip.hip upload_all), summed here in fixed (batch, element, corner) order.
+// its slot (layouts: upload.inc upload_all), summed here in fixed (batch, element, corner) order.
 // base = M x_bar exactly once across ranks: on rank 0 (contiguous sharding: add_base), or where base_mask says this
 // rank is responsible for the node (subtree sharding: the owner of the node's subtree; rank 0 for the replicated top).
-#ifndef ADMM_RHS_UNROLL
-#define ADMM_RHS_UNROLL 1
-#endif
 // The launch covers the nodes [node0, node1).
 // NORM (residual tracking, one rank): the launch also leaves the sum of squares of its block's results in norm_partial[block]
 // (fixed tree order), so that |s|^2 needs no pass of its own.
@@ -180,7 +177,6 @@ __global__ __launch_bounds__(256) void rhs_gather_kernel(int node0, int node1, c
             const int deg = (int)(p1 - p0);
             const double *f = fslot + i;
             int r = 0;
-#if ADMM_RHS_UNROLL
             for (; r + 8 <= deg; r += 8) {      // eight independent loads in flight; the sum keeps its order
                 double t[8];
 #pragma unroll
@@ -188,7 +184,6 @@ __global__ __launch_bounds__(256) void rhs_gather_kernel(int node0, int node1, c
 #pragma unroll
                 for (int q = 0; q < 8; ++q) acc += t[q];
             }
-#endif
             for (; r < deg; ++r) acc += f[3 * (size_t)r * slot_stride];
         } else {
             for (int64_t p = p0; p < p1; ++p) acc += fslot[3 * (size_t)p + c];
@@ -324,7 +319,6 @@ struct FactorDev {
     const int4 *cg4;         // same lists as fixed quadruples (-1 = none; trees with <= 4 contributions per front row), or NULL
 };
 
-// sum of the children's contributions that land on front row `fr` (fixed child order)
 // ---- workgroup timeline of the sweep kernels (tools/sweep_timeline.py; variant build -DADMM_SWEEP_PROFILE, never on in the shipped
 // library): every workgroup stamps the 100 MHz real-time counter at its start, after its first staging barrier and at its end
 #if defined(ADMM_SWEEP_PROFILE) && defined(__HIPCC__)
@@ -337,6 +331,7 @@ __device__ unsigned long long *g_sweep_prof;
 #define ADMM_SWEEP_SLOT(v)
 #define ADMM_SWEEP_STAMP(slot)
 #endif
+// sum of the children's contributions that land on front row `fr` (fixed child order)
 template <bool CG2>
 __device__ __forceinline__ void child_sum(const FactorDev &F, int64_t fr, const double *__restrict__ C, double &s0, double &s1, double &s2) {
     s0 = 0.0; s1 = 0.0; s2 = 0.0;
@@ -354,28 +349,61 @@ __device__ __forceinline__ void child_sum(const FactorDev &F, int64_t fr, const 
     }
 }
 
-#ifndef ADMM_FWD_DEPTH
-#define ADMM_FWD_DEPTH 8          // panel columns per load group in the big forward kernel
-#endif
-#ifndef ADMM_FWD_DEPTH16
-#define ADMM_FWD_DEPTH16 4        // ... with 16 waves per tile (the top levels: few, long tiles)
-#endif
-#ifndef ADMM_FWD_SMALL_DEPTH
-#define ADMM_FWD_SMALL_DEPTH 8    // same for the narrow-supernode (wave per tile) forward kernel
-#endif
-#ifndef ADMM_BWD_UNROLL
-#define ADMM_BWD_UNROLL 4         // 64-row groups per load batch in the CW = 1 backward kernel
-#endif
-#ifndef ADMM_FWD_SMALL_WAVES
-#define ADMM_FWD_SMALL_WAVES 4    // wave items per block in the narrow-supernode forward kernel
-#endif
-#ifndef ADMM_BWD_UNROLL2
-#define ADMM_BWD_UNROLL2 1        // 64-row groups per load batch in the CW = 2 backward kernel (1 / 2 / 4: 0.198-0.199 / 0.198-0.201 / 0.202-0.203 ms backward at 1M tets)
-#endif
-#ifndef ADMM_BWD_PREFETCH
-#define ADMM_BWD_PREFETCH 1       // CW > 1 backward kernel: first panel rows requested before the staging barrier
-#endif
 constexpr int FWD_SMALL_KMAX = 64;
+constexpr int FWD_SMALL_WAVES = 4;    // wave items per block in the narrow-supernode forward kernel
+constexpr int FWD_SMALL_DEPTH = 8;    // panel columns per load group in the wave-per-tile forward kernels
+
+// ---- the tile body of the wave-per-tile forward kernels (solve_fwd_small_kernel, solve_fwd_subtree_kernel): one wave = one
+// (supernode, 64-row tile), lane = row of the panel.  The pieces below are the arithmetic and the load order both kernels share;
+// each kernel orders the phases (staging, panel requests) itself.
+
+// The children's contributions to two front rows in the fixed child order: ab_c (the lane's pass-through row) into c, ab_t (its
+// staged column) into s.  The first and second slot of both quadruples are loaded together and unconditionally (an absent one reads
+// contribution 0 and counts as zero), the third and fourth only where present (four-way tree nodes).  row(o) is the address of
+// contribution o: C + 3 o in global memory, or an offset in LDS.
+template <class Row>
+__device__ __forceinline__ void quad_sums(int4 ab_c, int4 ab_t, Row row, double &c0, double &c1, double &c2, double &s0, double &s1, double &s2) {
+    const double *cxp = row(max(ab_c.x, 0)), *cyp = row(max(ab_c.y, 0));
+    const double *txp = row(max(ab_t.x, 0)), *typ = row(max(ab_t.y, 0));
+    const double cx0 = cxp[0], cx1 = cxp[1], cx2 = cxp[2], cy0 = cyp[0], cy1 = cyp[1], cy2 = cyp[2];
+    const double tx0 = txp[0], tx1 = txp[1], tx2 = txp[2], ty0 = typ[0], ty1 = typ[1], ty2 = typ[2];
+    c0 = 0.0; c1 = 0.0; c2 = 0.0;
+    c0 += ab_c.x >= 0 ? cx0 : 0.0; c1 += ab_c.x >= 0 ? cx1 : 0.0; c2 += ab_c.x >= 0 ? cx2 : 0.0;
+    c0 += ab_c.y >= 0 ? cy0 : 0.0; c1 += ab_c.y >= 0 ? cy1 : 0.0; c2 += ab_c.y >= 0 ? cy2 : 0.0;
+    s0 = 0.0; s1 = 0.0; s2 = 0.0;
+    s0 += ab_t.x >= 0 ? tx0 : 0.0; s1 += ab_t.x >= 0 ? tx1 : 0.0; s2 += ab_t.x >= 0 ? tx2 : 0.0;
+    s0 += ab_t.y >= 0 ? ty0 : 0.0; s1 += ab_t.y >= 0 ? ty1 : 0.0; s2 += ab_t.y >= 0 ? ty2 : 0.0;
+    if (ab_c.z >= 0) { const double *c = row(ab_c.z); c0 += c[0]; c1 += c[1]; c2 += c[2]; }
+    if (ab_c.w >= 0) { const double *c = row(ab_c.w); c0 += c[0]; c1 += c[1]; c2 += c[2]; }
+    if (ab_t.z >= 0) { const double *c = row(ab_t.z); s0 += c[0]; s1 += c[1]; s2 += c[2]; }
+    if (ab_t.w >= 0) { const double *c = row(ab_t.w); s0 += c[0]; s1 += c[1]; s2 += c[2]; }
+}
+
+// The first group of panel columns of the lane's row (P), columns [0, jend).  Unconditional loads: a column beyond the row's range
+// re-reads its last one; the caller zeroes those (cur[q] for q >= jend) once its staging is done.
+template <int DS>
+__device__ __forceinline__ void panel_first(const double *P, int f, int jend, double (&cur)[DS]) {
+    const int jl = max(jend - 1, 0);
+#pragma unroll
+    for (int q = 0; q < DS; ++q) cur[q] = P[(size_t)f * min(q, jl)];
+}
+
+// a = the lane's row of the panel times the staged vector t (3 doubles per column), columns [0, jend) ascending, starting from the
+// group panel_first requested (zeroed beyond jend); the next group is always requested before the current one is consumed.
+template <int DS>
+__device__ __forceinline__ void panel_dot(const double *P, int f, int jend, const double *t, double (&cur)[DS], double &a0, double &a1, double &a2) {
+    double nxt[DS];
+    a0 = 0.0; a1 = 0.0; a2 = 0.0;
+    for (int j = 0; j < jend; j += DS) {
+#pragma unroll
+        for (int q = 0; q < DS; ++q) nxt[q] = (j + DS + q < jend) ? P[(size_t)f * (j + DS + q)] : 0.0;
+        const double *tj = t + 3 * j;
+#pragma unroll
+        for (int q = 0; q < DS; ++q) if (j + q < jend) { a0 += cur[q] * tj[3 * q]; a1 += cur[q] * tj[3 * q + 1]; a2 += cur[q] * tj[3 * q + 2]; }
+#pragma unroll
+        for (int q = 0; q < DS; ++q) cur[q] = nxt[q];
+    }
+}
 
 // Forward sweep, supernodes with k <= 64: one wave = one (supernode, 64-row tile);
 // lane = row of the panel; t_s = y_s - children's contributions, staged per wave in LDS.
@@ -383,11 +411,11 @@ constexpr int FWD_SMALL_KMAX = 64;
 // row, the first panel columns) is requested before the staging barrier so that the
 // dependent index -> slot -> value chain overlaps with the panel stream.
 template <bool CG2>
-__global__ __launch_bounds__(64 * ADMM_FWD_SMALL_WAVES) void solve_fwd_small_kernel(int n_items, const SweepItem *__restrict__ items,
+__global__ __launch_bounds__(64 * FWD_SMALL_WAVES) void solve_fwd_small_kernel(int n_items, const SweepItem *__restrict__ items,
                                                               FactorDev F, const double *__restrict__ y, double *__restrict__ W, double *__restrict__ C) {
-    __shared__ double ts[ADMM_FWD_SMALL_WAVES][FWD_SMALL_KMAX * 3];
+    __shared__ double ts[FWD_SMALL_WAVES][FWD_SMALL_KMAX * 3];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int item = blockIdx.x * ADMM_FWD_SMALL_WAVES + wave;
+    const int item = blockIdx.x * FWD_SMALL_WAVES + wave;
     const bool live = item < n_items;
     ADMM_SWEEP_T0
     int tile = 0, k = 0, r = 0, first = 0;
@@ -403,8 +431,7 @@ __global__ __launch_bounds__(64 * ADMM_FWD_SMALL_WAVES) void solve_fwd_small_ker
     // (3) only then the first group of panel columns.  The staged vector is private to the wave (ts[wave]): no workgroup barrier --
     // LDS operations of one wave execute in order -- so nothing here waits for the panel columns or for the other waves.
     double c0 = 0.0, c1 = 0.0, c2 = 0.0;
-    constexpr int DS = ADMM_FWD_SMALL_DEPTH;
-    double cur[DS], nxt[DS];
+    double cur[FWD_SMALL_DEPTH];
     const bool pass = row_ok && i >= k, stage = live && lane < k;
     if (CG2) {
         int4 ab_c = F.cg4[foff + (pass ? i : 0)];                                 // (1)
@@ -413,20 +440,8 @@ __global__ __launch_bounds__(64 * ADMM_FWD_SMALL_WAVES) void solve_fwd_small_ker
         const double y0 = src[0], y1 = src[1], y2 = src[2];
         if (!pass) ab_c = make_int4(-1, -1, -1, -1);
         if (!stage) ab_t = make_int4(-1, -1, -1, -1);
-        const double *cxp = C + 3 * (size_t)max(ab_c.x, 0), *cyp = C + 3 * (size_t)max(ab_c.y, 0);      // (2)
-        const double *txp = C + 3 * (size_t)max(ab_t.x, 0), *typ = C + 3 * (size_t)max(ab_t.y, 0);
-        const double cx0 = cxp[0], cx1 = cxp[1], cx2 = cxp[2], cy0 = cyp[0], cy1 = cyp[1], cy2 = cyp[2];
-        const double tx0 = txp[0], tx1 = txp[1], tx2 = txp[2], ty0 = typ[0], ty1 = typ[1], ty2 = typ[2];
-        c0 += ab_c.x >= 0 ? cx0 : 0.0; c1 += ab_c.x >= 0 ? cx1 : 0.0; c2 += ab_c.x >= 0 ? cx2 : 0.0;
-        c0 += ab_c.y >= 0 ? cy0 : 0.0; c1 += ab_c.y >= 0 ? cy1 : 0.0; c2 += ab_c.y >= 0 ? cy2 : 0.0;
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-        s0 += ab_t.x >= 0 ? tx0 : 0.0; s1 += ab_t.x >= 0 ? tx1 : 0.0; s2 += ab_t.x >= 0 ? tx2 : 0.0;
-        s0 += ab_t.y >= 0 ? ty0 : 0.0; s1 += ab_t.y >= 0 ? ty1 : 0.0; s2 += ab_t.y >= 0 ? ty2 : 0.0;
-        // (third and fourth slot: only under four-way tree nodes)
-        if (ab_c.z >= 0) { const double *c = C + 3 * (size_t)ab_c.z; c0 += c[0]; c1 += c[1]; c2 += c[2]; }
-        if (ab_c.w >= 0) { const double *c = C + 3 * (size_t)ab_c.w; c0 += c[0]; c1 += c[1]; c2 += c[2]; }
-        if (ab_t.z >= 0) { const double *c = C + 3 * (size_t)ab_t.z; s0 += c[0]; s1 += c[1]; s2 += c[2]; }
-        if (ab_t.w >= 0) { const double *c = C + 3 * (size_t)ab_t.w; s0 += c[0]; s1 += c[1]; s2 += c[2]; }
+        double s0, s1, s2;
+        quad_sums(ab_c, ab_t, [C](int o) { return C + 3 * (size_t)o; }, c0, c1, c2, s0, s1, s2);      // (2)
         if (stage) { ts[wave][3 * lane] = y0 - s0; ts[wave][3 * lane + 1] = y1 - s1; ts[wave][3 * lane + 2] = y2 - s2; }
     } else {
         if (pass) child_sum<CG2>(F, foff + i, C, c0, c1, c2);   // pass-through of the children's rows beyond this supernode
@@ -437,28 +452,14 @@ __global__ __launch_bounds__(64 * ADMM_FWD_SMALL_WAVES) void solve_fwd_small_ker
             ts[wave][3 * lane] = src[0] - s0; ts[wave][3 * lane + 1] = src[1] - s1; ts[wave][3 * lane + 2] = src[2] - s2;
         }
     }
-    // (3) first group of panel columns; afterwards the next group is always requested before the current one is consumed.
-    // Unconditional loads: a column beyond the row's range re-reads its last one and counts as zero.
-    {
-        const int jl = max(jend - 1, 0);
-#pragma unroll
-        for (int q = 0; q < DS; ++q) cur[q] = P[(size_t)f * min(q, jl)];
-    }
+    panel_first(P, f, jend, cur);                              // (3)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the wave's own staged vector is in LDS (no workgroup barrier: ts[wave] is private)
 #pragma unroll
-    for (int q = 0; q < DS; ++q) cur[q] = (q < jend) ? cur[q] : 0.0;
+    for (int q = 0; q < FWD_SMALL_DEPTH; ++q) cur[q] = (q < jend) ? cur[q] : 0.0;
     ADMM_SWEEP_STAMP(1);
     if (!row_ok) { ADMM_SWEEP_STAMP(2); return; }
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    for (int j = 0; j < jend; j += DS) {
-#pragma unroll
-        for (int q = 0; q < DS; ++q) nxt[q] = (j + DS + q < jend) ? P[(size_t)f * (j + DS + q)] : 0.0;
-        const double *t = &ts[wave][3 * j];
-#pragma unroll
-        for (int q = 0; q < DS; ++q) if (j + q < jend) { a0 += cur[q] * t[3 * q]; a1 += cur[q] * t[3 * q + 1]; a2 += cur[q] * t[3 * q + 2]; }
-#pragma unroll
-        for (int q = 0; q < DS; ++q) cur[q] = nxt[q];
-    }
+    double a0, a1, a2;
+    panel_dot(P, f, jend, ts[wave], cur, a0, a1, a2);
     if (i < k) { double *dst = W + 3 * (size_t)(first + i); dst[0] = a0; dst[1] = a1; dst[2] = a2; }
     else {
         double *dst = C + 3 * (size_t)(soff + (i - k));
@@ -468,22 +469,20 @@ __global__ __launch_bounds__(64 * ADMM_FWD_SMALL_WAVES) void solve_fwd_small_ker
 }
 
 // Forward sweep over the bottom subtrees of the tree (upload.inc fuse_subtrees): one workgroup per subtree walks its levels bottom-up;
-// a wave takes one (supernode, 64-row tile) at a time with the arithmetic, the column order and the child order of
-// solve_fwd_small_kernel<true> -- bitwise the same w and root contributions.  The subtree's record (items, front maps) is copied to LDS
+// a wave takes one (supernode, 64-row tile) at a time through the same tile body as solve_fwd_small_kernel<true> (quad_sums,
+// panel_first, panel_dot) -- bitwise the same w and root contributions.  The subtree's record (items, front maps) is copied to LDS
 // once; the members' contributions stay in LDS, so past that copy the only global loads are y and the panels, neither of which depends
 // on a value computed here, and the levels are separated by barriers that wait for LDS alone.  Only the root's contribution goes to C.
-// Record (ints): [0] levels, [1] first item, [2] contribution area, [3] staged vectors (both in doubles from the start of LDS),
-// [4..5] the root's first contribution slot; from SUB_HDR the level pointers; items of SUB_ITEM ints: k, r, first, tile, front map
-// (int offset in the record, -1 = no children), destination of the contribution (double offset in the contribution area, -1 = C),
-// panel offset (two ints).  A front map holds four ints per front row: double offsets of the children's rows in the contribution area.
-constexpr int SUB_HDR = 8, SUB_ITEM = 8;
-#ifndef ADMM_SUBTREE_WAVES
-#define ADMM_SUBTREE_WAVES 8      // waves per subtree workgroup
-#endif
-#ifndef ADMM_SUBTREE_DEPTH
-#define ADMM_SUBTREE_DEPTH ADMM_FWD_SMALL_DEPTH      // panel columns per load group in the subtree kernel
-#endif
-constexpr int SUB_WAVES = ADMM_SUBTREE_WAVES;
+// The record (ints): a header of SUB_HDR ints -- the fields SUB_LEVELS.. below, the contribution area and the staged vectors in doubles
+// from the start of LDS -- then from SUB_HDR the level pointers, then items of SUB_ITEM ints (fields SUB_K..; the front map is an int
+// offset in the record, -1 = no children; the destination of the contribution a double offset in the contribution area, -1 = C).
+// A front map holds four ints per front row: double offsets of the children's rows in the contribution area.
+constexpr int SUB_LEVELS = 0, SUB_ITEM0 = 1, SUB_CBUF = 2, SUB_TS = 3, SUB_ROOT_SLOT = 4 /* two ints */, SUB_HDR = 8;
+constexpr int SUB_K = 0, SUB_R = 1, SUB_FIRST = 2, SUB_TILE = 3, SUB_MAP = 4, SUB_CDST = 5, SUB_POFF = 6 /* two ints */, SUB_ITEM = SUB_POFF + 2;
+// 64-bit record fields as (low, high) int pairs
+__host__ __device__ inline void sub_split64(int64_t v, int *lohi) { lohi[0] = (int)(uint32_t)(v & 0xffffffff); lohi[1] = (int)(v >> 32); }
+__host__ __device__ inline int64_t sub_join64(int lo, int hi) { return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo); }
+constexpr int SUB_WAVES = 8;      // waves per subtree workgroup
 __device__ __forceinline__ int sub_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __global__ __launch_bounds__(64 * SUB_WAVES) void solve_fwd_subtree_kernel(const int *__restrict__ recs, const int64_t *__restrict__ rec_off, const double *__restrict__ panels,
                                                                            const double *__restrict__ y, double *__restrict__ W, double *__restrict__ C) {
@@ -498,18 +497,17 @@ __global__ __launch_bounds__(64 * SUB_WAVES) void solve_fwd_subtree_kernel(const
         for (int q = threadIdx.x; q < n4; q += 64 * SUB_WAVES) dst[q] = src[q];
     }
     __syncthreads();
-    const int n_lv = meta[0], item0 = meta[1];
-    double *cb = sub_lds + meta[2];
-    double *ts = sub_lds + meta[3] + 3 * 64 * wave;
-    const int64_t root_soff = (int64_t)(((uint64_t)(uint32_t)meta[5] << 32) | (uint32_t)meta[4]);
-    constexpr int DS = ADMM_SUBTREE_DEPTH;
+    const int n_lv = meta[SUB_LEVELS], item0 = meta[SUB_ITEM0];
+    double *cb = sub_lds + meta[SUB_CBUF];
+    double *ts = sub_lds + meta[SUB_TS] + 3 * 64 * wave;
+    const int64_t root_soff = sub_join64(meta[SUB_ROOT_SLOT], meta[SUB_ROOT_SLOT + 1]);
     for (int lv = 0; lv < n_lv; ++lv) {
         const int e = meta[SUB_HDR + lv + 1];
         for (int itm = meta[SUB_HDR + lv] + wave; itm < e; itm += SUB_WAVES) {
             const int *I = meta + item0 + SUB_ITEM * itm;
-            const int k = sub_uniform(I[0]), r = sub_uniform(I[1]), first = sub_uniform(I[2]), tile = sub_uniform(I[3]);
-            const int moff = sub_uniform(I[4]), cdst = sub_uniform(I[5]);
-            const int64_t poff = (int64_t)(((uint64_t)(uint32_t)sub_uniform(I[7]) << 32) | (uint32_t)sub_uniform(I[6]));
+            const int k = sub_uniform(I[SUB_K]), r = sub_uniform(I[SUB_R]), first = sub_uniform(I[SUB_FIRST]), tile = sub_uniform(I[SUB_TILE]);
+            const int moff = sub_uniform(I[SUB_MAP]), cdst = sub_uniform(I[SUB_CDST]);
+            const int64_t poff = sub_join64(sub_uniform(I[SUB_POFF]), sub_uniform(I[SUB_POFF + 1]));
             const int f = k + r;
             const int i = tile * 64 + lane;
             const bool row_ok = i < f;
@@ -518,48 +516,23 @@ __global__ __launch_bounds__(64 * SUB_WAVES) void solve_fwd_subtree_kernel(const
             const bool pass = row_ok && i >= k, stage = lane < k;
             const double *src = y + 3 * (size_t)(first + (stage ? lane : 0));
             const double y0 = src[0], y1 = src[1], y2 = src[2];
-            double cur[DS], nxt[DS];
-            {
-                const int jl = max(jend - 1, 0);
-#pragma unroll
-                for (int q = 0; q < DS; ++q) cur[q] = P[(size_t)f * min(q, jl)];
-            }
+            double cur[FWD_SMALL_DEPTH];
+            panel_first(P, f, jend, cur);
             int4 ab_c = make_int4(-1, -1, -1, -1), ab_t = make_int4(-1, -1, -1, -1);
             if (moff >= 0) {
                 const int4 *M = reinterpret_cast<const int4 *>(meta + moff);
                 if (pass) ab_c = M[i];
                 if (stage) ab_t = M[lane];
             }
-            // the staging of solve_fwd_small_kernel<true>, with the contributions read from LDS
-            double c0 = 0.0, c1 = 0.0, c2 = 0.0;
-            const double *cxp = cb + max(ab_c.x, 0), *cyp = cb + max(ab_c.y, 0);
-            const double *txp = cb + max(ab_t.x, 0), *typ = cb + max(ab_t.y, 0);
-            const double cx0 = cxp[0], cx1 = cxp[1], cx2 = cxp[2], cy0 = cyp[0], cy1 = cyp[1], cy2 = cyp[2];
-            const double tx0 = txp[0], tx1 = txp[1], tx2 = txp[2], ty0 = typ[0], ty1 = typ[1], ty2 = typ[2];
-            c0 += ab_c.x >= 0 ? cx0 : 0.0; c1 += ab_c.x >= 0 ? cx1 : 0.0; c2 += ab_c.x >= 0 ? cx2 : 0.0;
-            c0 += ab_c.y >= 0 ? cy0 : 0.0; c1 += ab_c.y >= 0 ? cy1 : 0.0; c2 += ab_c.y >= 0 ? cy2 : 0.0;
-            double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-            s0 += ab_t.x >= 0 ? tx0 : 0.0; s1 += ab_t.x >= 0 ? tx1 : 0.0; s2 += ab_t.x >= 0 ? tx2 : 0.0;
-            s0 += ab_t.y >= 0 ? ty0 : 0.0; s1 += ab_t.y >= 0 ? ty1 : 0.0; s2 += ab_t.y >= 0 ? ty2 : 0.0;
-            if (ab_c.z >= 0) { const double *c = cb + ab_c.z; c0 += c[0]; c1 += c[1]; c2 += c[2]; }
-            if (ab_c.w >= 0) { const double *c = cb + ab_c.w; c0 += c[0]; c1 += c[1]; c2 += c[2]; }
-            if (ab_t.z >= 0) { const double *c = cb + ab_t.z; s0 += c[0]; s1 += c[1]; s2 += c[2]; }
-            if (ab_t.w >= 0) { const double *c = cb + ab_t.w; s0 += c[0]; s1 += c[1]; s2 += c[2]; }
+            double c0, c1, c2, s0, s1, s2;
+            quad_sums(ab_c, ab_t, [cb](int o) { return cb + o; }, c0, c1, c2, s0, s1, s2);
             if (stage) { ts[3 * lane] = y0 - s0; ts[3 * lane + 1] = y1 - s1; ts[3 * lane + 2] = y2 - s2; }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (ts is private to the wave)
 #pragma unroll
-            for (int q = 0; q < DS; ++q) cur[q] = (q < jend) ? cur[q] : 0.0;
+            for (int q = 0; q < FWD_SMALL_DEPTH; ++q) cur[q] = (q < jend) ? cur[q] : 0.0;
             if (row_ok) {
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-                for (int j = 0; j < jend; j += DS) {
-#pragma unroll
-                    for (int q = 0; q < DS; ++q) nxt[q] = (j + DS + q < jend) ? P[(size_t)f * (j + DS + q)] : 0.0;
-                    const double *t = &ts[3 * j];
-#pragma unroll
-                    for (int q = 0; q < DS; ++q) if (j + q < jend) { a0 += cur[q] * t[3 * q]; a1 += cur[q] * t[3 * q + 1]; a2 += cur[q] * t[3 * q + 2]; }
-#pragma unroll
-                    for (int q = 0; q < DS; ++q) cur[q] = nxt[q];
-                }
+                double a0, a1, a2;
+                panel_dot(P, f, jend, ts, cur, a0, a1, a2);
                 if (i < k) { double *dst = W + 3 * (size_t)(first + i); dst[0] = a0; dst[1] = a1; dst[2] = a2; }
                 else if (cdst >= 0) { double *dst = cb + cdst + 3 * (i - k); dst[0] = a0 + c0; dst[1] = a1 + c1; dst[2] = a2 + c2; }
                 else { double *dst = C + 3 * (size_t)(root_soff + (i - k)); dst[0] = a0 + c0; dst[1] = a1 + c1; dst[2] = a2 + c2; }
@@ -572,10 +545,11 @@ __global__ __launch_bounds__(64 * SUB_WAVES) void solve_fwd_subtree_kernel(const
 // Forward sweep, supernodes with k > 64: one block of NW waves = one
 // (supernode, 64-row tile); the waves split the columns, partial sums are
 // combined through LDS in wave order.  NW = 16 for the wide supernodes at the top of the tree; levels of narrower ones run
-// with 4 or 8 waves per tile (chosen per level from its widest supernode, admm_hip.hip upload_factor): a CU holds the same
+// with 4 or 8 waves per tile (chosen per level from its widest supernode, upload.inc upload_factor): a CU holds the same
 // number of waves either way, but four times as many tiles are resident at once and every wave has a full group of columns
 // to stream instead of a handful -- such levels are bound by the per-tile prologue latency, not by bytes.
-template <int NW> struct FwdBig { static constexpr int KCHUNK = NW == 16 ? 2048 : 512; };
+// DEPTH: panel columns per load group; 4 with 16 waves per tile (the top levels: few, long tiles).
+template <int NW> struct FwdBig { static constexpr int KCHUNK = NW == 16 ? 2048 : 512, DEPTH = NW == 16 ? 4 : 8; };
 template <bool CG2, int NW>
 __global__ __launch_bounds__(64 * NW) void solve_fwd_big_kernel(const SweepItem *__restrict__ items,
                                                              FactorDev F, const double *__restrict__ y, double *__restrict__ W, double *__restrict__ C) {
@@ -638,7 +612,7 @@ __global__ __launch_bounds__(64 * NW) void solve_fwd_big_kernel(const SweepItem 
         const int jb = c0 + wave * per;
         int je = min(jb + per, c0 + kc);
         je = row_ok ? min(je, jend) : jb;
-        constexpr int D = NW == 16 ? ADMM_FWD_DEPTH16 : ADMM_FWD_DEPTH;
+        constexpr int D = FwdBig<NW>::DEPTH;
         double cur[D], nxt[D];
         if (c0 > 0) __syncthreads();
         // columns this thread did not stage ahead (k beyond one per thread; without the quadruple lists: all of them)
@@ -717,10 +691,8 @@ __device__ __forceinline__ void wave_sum_transpose(double *v, int lane, int &bas
     if constexpr (off > 1) wave_sum_transpose<h, off / 2>(v, lane, base, cnt);
 }
 
-#ifndef ADMM_BWD_RCHUNK
-#define ADMM_BWD_RCHUNK 1024
-#endif
-constexpr int BWD_RCHUNK = ADMM_BWD_RCHUNK;
+constexpr int BWD_RCHUNK = 1024;
+constexpr int BWD_UNROLL = 4;         // 64-row groups per load batch in the CW = 1 backward kernel
 // NWB waves per block share one staging of the vector (4 is the original shape; 8 / 16 halve / quarter the staging work
 // per column on levels of tall fronts).
 template <int CW, int NWB = 4>
@@ -742,7 +714,7 @@ __global__ __launch_bounds__(64 * NWB) void solve_bwd_kernel(const SweepItem *__
     for (int c = 0; c < CW; ++c) { acc[c][0] = 0.0; acc[c][1] = 0.0; acc[c][2] = 0.0; }
     // the panel does not depend on the staged vector: its first rows are requested before the staging barrier
     double pf[CW];
-    if (CW != 1 && ADMM_BWD_PREFETCH) {
+    if (CW != 1) {
 #pragma unroll
         for (int c = 0; c < CW; ++c) { const int i = jc0 + lane; pf[c] = (j0 + c < k && i < f && i >= j0 + c) ? Pj[i + (size_t)f * c] : 0.0; }
     }
@@ -762,7 +734,7 @@ __global__ __launch_bounds__(64 * NWB) void solve_bwd_kernel(const SweepItem *__
         if (j0 < k) {
             if (CW == 1) {
                 int q = lane;
-                constexpr int U = ADMM_BWD_UNROLL;
+                constexpr int U = BWD_UNROLL;
                 for (; q + 64 * (U - 1) < rc; q += 64 * U) {
                     double p[U];
 #pragma unroll
@@ -776,26 +748,24 @@ __global__ __launch_bounds__(64 * NWB) void solve_bwd_kernel(const SweepItem *__
                 }
             } else {
                 int q = lane;
-                if (ADMM_BWD_PREFETCH && r0 == jc0 && q < rc) {      // the rows requested before the staging barrier
+                if (r0 == jc0 && q < rc) {      // the rows requested before the staging barrier
                     const double *v = &vs[3 * q];
 #pragma unroll
                     for (int c = 0; c < CW; ++c) { acc[c][0] += pf[c] * v[0]; acc[c][1] += pf[c] * v[1]; acc[c][2] += pf[c] * v[2]; }
                     q += 64;
                 }
-                constexpr int UC = CW == 2 ? ADMM_BWD_UNROLL2 : 1;
-                for (; q + 64 * (UC - 1) < rc; q += 64 * UC) {
-                    double p[UC][CW];
+                // one 64-row group per load batch (1 / 2 / 4 groups with CW = 2: 0.198-0.199 / 0.198-0.201 / 0.202-0.203 ms backward at 1M tets)
+                for (; q < rc; q += 64) {
+                    const int i = r0 + q;
+                    double p[CW];
 #pragma unroll
-                    for (int u = 0; u < UC; ++u)
+                    for (int c = 0; c < CW; ++c) p[c] = (j0 + c < k && i >= j0 + c) ? Pj[i + (size_t)f * c] : 0.0;
+                    const double *v = &vs[3 * q];
 #pragma unroll
-                        for (int c = 0; c < CW; ++c) { const int i = r0 + q + 64 * u; p[u][c] = (j0 + c < k && i >= j0 + c) ? Pj[i + (size_t)f * c] : 0.0; }
-#pragma unroll
-                    for (int u = 0; u < UC; ++u) {
-                        const double *v = &vs[3 * (q + 64 * u)];
-#pragma unroll
-                        for (int c = 0; c < CW; ++c) { acc[c][0] += p[u][c] * v[0]; acc[c][1] += p[u][c] * v[1]; acc[c][2] += p[u][c] * v[2]; }
-                    }
+                    for (int c = 0; c < CW; ++c) { acc[c][0] += p[c] * v[0]; acc[c][1] += p[c] * v[1]; acc[c][2] += p[c] * v[2]; }
                 }
+                // (never entered: the loop above leaves q >= rc.  The compiler keeps it all the same, and taking it out changes this
+                // kernel's code -- VGPRs and schedule -- which has not been measured.)
                 for (; q < rc; q += 64) {
                     const int i = r0 + q;
                     const double *v = &vs[3 * q];
@@ -865,19 +835,10 @@ __global__ __launch_bounds__(256) void dense_solve_kernel(int n, const double *_
 // A root's product x = S^-1 t at HBM rate: one wave per row of the symmetric inverse (16 rows per block), t staged through
 // LDS in chunks of 2048 columns (read once per block instead of once per row), eight independent 512-byte row pieces in
 // flight per wave.  Fixed summation order: a lane's columns ascending, then the transposing butterfly.
-#ifndef ADMM_ROOT_VEC2
-#define ADMM_ROOT_VEC2 1
-#endif
 constexpr int ROOT_KCHUNK = 2048;
-#ifndef ADMM_ROOT_ROWS
-#define ADMM_ROOT_ROWS 16         // rows (= waves) per block of root_product_kernel: one staging of t per block (4 / 8 / 16 rows: 37 / 22 / 20 us at k = 3301)
-#endif
-constexpr int ROOT_ROWS = ADMM_ROOT_ROWS;
-// ADMM_ROOT_NT: the root's explicit inverse is read ONCE per ADMM iteration (it serves both sweeps in one product): loaded
-// non-temporally it does not take the Infinity Cache away from the top levels' panels, which the backward sweep re-reads next.
-#ifndef ADMM_ROOT_NT
-#define ADMM_ROOT_NT 1
-#endif
+constexpr int ROOT_ROWS = 16;         // rows (= waves) per block of root_product_kernel: one staging of t per block (4 / 8 / 16 rows: 37 / 22 / 20 us at k = 3301)
+// The root's explicit inverse is read ONCE per ADMM iteration (it serves both sweeps in one product): loaded non-temporally
+// it does not take the Infinity Cache away from the top levels' panels, which the backward sweep re-reads next.
 // GATHER (roots of at most ROOT_KCHUNK columns): every block forms t = y - (children's contributions) itself instead of reading the T a
 // root_gather_kernel launch wrote -- one launch less where a launch is 4-5 us of pure latency (mid-size systems); T then carries y.
 template <bool GATHER, bool CG2>
@@ -904,7 +865,6 @@ __global__ __launch_bounds__(64 * ROOT_ROWS) void root_product_kernel(int k, int
         for (int q = threadIdx.x; q < 3 * kc; q += 64 * ROOT_ROWS) ts[q] = T[3 * (size_t)c0 + q];
         if (kc & 1) { if (threadIdx.x < 3) ts[3 * kc + threadIdx.x] = 0.0; }      // the pair loads below may reach one column past an odd chunk (padding of the row: finite)
         __syncthreads();
-#if ADMM_ROOT_VEC2
         // 16 bytes per lane and load: a wave covers 128 columns per instruction, eight instructions in flight
         const double2 *rp2 = reinterpret_cast<const double2 *>(rp + c0);
         const int kc2 = (kc + 1) >> 1;
@@ -913,8 +873,9 @@ __global__ __launch_bounds__(64 * ROOT_ROWS) void root_product_kernel(int k, int
             double2 a[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                if (ADMM_ROOT_NT) { typedef double d2_t __attribute__((ext_vector_type(2))); const d2_t t2 = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(&rp2[j + 64 * u])); a[u].x = t2.x; a[u].y = t2.y; }
-                else a[u] = rp2[j + 64 * u];
+                typedef double d2_t __attribute__((ext_vector_type(2)));
+                const d2_t t2 = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(&rp2[j + 64 * u]));
+                a[u].x = t2.x; a[u].y = t2.y;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -928,17 +889,6 @@ __global__ __launch_bounds__(64 * ROOT_ROWS) void root_product_kernel(int k, int
             v[0] += a.x * t[0]; v[1] += a.x * t[1]; v[2] += a.x * t[2];
             v[0] += a.y * t[3]; v[1] += a.y * t[4]; v[2] += a.y * t[5];
         }
-#else
-        int j = lane;
-        for (; j + 448 < kc; j += 512) {
-            double a[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) a[u] = ADMM_ROOT_NT ? __builtin_nontemporal_load(&rp[c0 + j + 64 * u]) : rp[c0 + j + 64 * u];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { const double *t = &ts[3 * (j + 64 * u)]; v[0] += a[u] * t[0]; v[1] += a[u] * t[1]; v[2] += a[u] * t[2]; }
-        }
-        for (; j < kc; j += 64) { const double a = rp[c0 + j]; const double *t = &ts[3 * j]; v[0] += a * t[0]; v[1] += a * t[1]; v[2] += a * t[2]; }
-#endif
     }
     int base = 0, cnt = 3;
     wave_sum_transpose<3, 32>(v, lane, base, cnt);

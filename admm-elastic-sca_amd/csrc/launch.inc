@@ -170,6 +170,9 @@ int launch_rhs(admm_hip_ctx *ctx) {
     return ADMM_OK;
 }
 
+// fn(std::integral_constant<int, V>) for the V among Vs that equals v: what fn returns, false where no V matches
+template <int... Vs, class Fn> bool with_int(int v, Fn &&fn) { bool r = false; (void)((v == Vs && (r = fn(std::integral_constant<int, Vs>{}), true)) || ...); return r; }
+
 // both triangular sweeps: d_y (rhs, destroyed) -> d_xcur
 int launch_solve(admm_hip_ctx *ctx, hipEvent_t mid, hipEvent_t ex0 = nullptr, hipEvent_t ex1 = nullptr, hipEvent_t ex2 = nullptr, hipEvent_t ex3 = nullptr) {
     using namespace admm_dev;
@@ -180,86 +183,81 @@ int launch_solve(admm_hip_ctx *ctx, hipEvent_t mid, hipEvent_t ex0 = nullptr, hi
         return ADMM_OK;
     }
     const FactorDev F = factor_dev(ctx);
-    auto forward = [&](const std::vector<LevelDev> &levels, hipStream_t st) {
-        for (const LevelDev &L : levels) {
-            if (L.n_small) {
-                                if (F.cg4) hipLaunchKernelGGL((solve_fwd_small_kernel<true>), dim3((L.n_small + ADMM_FWD_SMALL_WAVES - 1) / ADMM_FWD_SMALL_WAVES), dim3(64 * ADMM_FWD_SMALL_WAVES), 0, st, L.n_small, L.d_small, F, ctx->d_y, ctx->d_w, ctx->d_c);
-                else hipLaunchKernelGGL((solve_fwd_small_kernel<false>), dim3((L.n_small + ADMM_FWD_SMALL_WAVES - 1) / ADMM_FWD_SMALL_WAVES), dim3(64 * ADMM_FWD_SMALL_WAVES), 0, st, L.n_small, L.d_small, F, ctx->d_y, ctx->d_w, ctx->d_c);
-            }
-            if (L.n_big) {
-#define ADMM_FWD_BIG(CG, NW) hipLaunchKernelGGL((solve_fwd_big_kernel<CG, NW>), dim3(L.n_big), dim3(64 * NW), 0, st, L.d_big, F, ctx->d_y, ctx->d_w, ctx->d_c)
-                if (F.cg4) { if (L.big_nw == 4) ADMM_FWD_BIG(true, 4); else if (L.big_nw == 8) ADMM_FWD_BIG(true, 8); else ADMM_FWD_BIG(true, 16); }
-                else { if (L.big_nw == 4) ADMM_FWD_BIG(false, 4); else if (L.big_nw == 8) ADMM_FWD_BIG(false, 8); else ADMM_FWD_BIG(false, 16); }
-#undef ADMM_FWD_BIG
-            }
-            for (const LevelDev::Root &R : L.roots) {      // roots: both sweeps as one product with the explicit inverse, straight into x
-                const dim3 pg((R.k + ROOT_ROWS - 1) / ROOT_ROWS), pb(64 * ROOT_ROWS);
-                const double *Sinv = ctx->d_panels + R.inv_off;
-                double *Xr = ctx->d_xcur + 3 * (size_t)R.first;
-                if (R.k <= ctx->root_fuse_k) {      // small root: every block of the product gathers t itself (one launch less)
-                    if (F.cg4) hipLaunchKernelGGL((root_product_kernel<true, true>), pg, pb, 0, st, R.k, R.k, root_inv_ld(R.k), Sinv, (const double *)ctx->d_y, Xr, R.first, R.foff, F, (const double *)ctx->d_c);
-                    else hipLaunchKernelGGL((root_product_kernel<true, false>), pg, pb, 0, st, R.k, R.k, root_inv_ld(R.k), Sinv, (const double *)ctx->d_y, Xr, R.first, R.foff, F, (const double *)ctx->d_c);
-                    continue;
+    // CG2: the children's contributions of every front row as fixed quadruples (F.cg4) rather than lists -- one choice for the whole solve
+    auto sweeps = [&](auto cg2) -> int {
+        constexpr bool CG2 = decltype(cg2)::value;
+        auto forward = [&](const std::vector<LevelDev> &levels, hipStream_t st) {
+            for (const LevelDev &L : levels) {
+                if (L.n_small) hipLaunchKernelGGL((solve_fwd_small_kernel<CG2>), dim3((L.n_small + FWD_SMALL_WAVES - 1) / FWD_SMALL_WAVES), dim3(64 * FWD_SMALL_WAVES), 0, st, L.n_small, L.d_small, F, ctx->d_y, ctx->d_w, ctx->d_c);
+                if (L.n_big) with_int<4, 8, 16>(L.big_nw, [&](auto nw) {
+                    hipLaunchKernelGGL((solve_fwd_big_kernel<CG2, decltype(nw)::value>), dim3(L.n_big), dim3(64 * nw), 0, st, L.d_big, F, ctx->d_y, ctx->d_w, ctx->d_c); return true; });
+                for (const LevelDev::Root &R : L.roots) {      // roots: both sweeps as one product with the explicit inverse, straight into x
+                    const dim3 pg((R.k + ROOT_ROWS - 1) / ROOT_ROWS), pb(64 * ROOT_ROWS);
+                    const double *Sinv = ctx->d_panels + R.inv_off;
+                    double *Xr = ctx->d_xcur + 3 * (size_t)R.first;
+                    if (R.k <= ctx->root_fuse_k) {      // small root: every block of the product gathers t itself (one launch less)
+                        hipLaunchKernelGGL((root_product_kernel<true, CG2>), pg, pb, 0, st, R.k, R.k, root_inv_ld(R.k), Sinv, (const double *)ctx->d_y, Xr, R.first, R.foff, F, (const double *)ctx->d_c);
+                        continue;
+                    }
+                    double *T = ctx->d_w + 3 * (size_t)R.first;      // the root's own slice of W is free: it has no backward launch
+                    hipLaunchKernelGGL((root_gather_kernel<CG2>), dim3((R.k + 255) / 256), dim3(256), 0, st, R.k, R.first, R.foff, F, (const double *)ctx->d_y, (const double *)ctx->d_c, T);
+                    hipLaunchKernelGGL((root_product_kernel<false, false>), pg, pb, 0, st, R.k, R.k, root_inv_ld(R.k), Sinv, (const double *)T, Xr, 0, (int64_t)0, F, (const double *)nullptr);
                 }
-                double *T = ctx->d_w + 3 * (size_t)R.first;      // the root's own slice of W is free: it has no backward launch
-                if (F.cg4) hipLaunchKernelGGL((root_gather_kernel<true>), dim3((R.k + 255) / 256), dim3(256), 0, st, R.k, R.first, R.foff, F, (const double *)ctx->d_y, (const double *)ctx->d_c, T);
-                else hipLaunchKernelGGL((root_gather_kernel<false>), dim3((R.k + 255) / 256), dim3(256), 0, st, R.k, R.first, R.foff, F, (const double *)ctx->d_y, (const double *)ctx->d_c, T);
-                hipLaunchKernelGGL((root_product_kernel<false, false>), pg, pb, 0, st, R.k, R.k, root_inv_ld(R.k), Sinv, (const double *)T, Xr, 0, (int64_t)0, F, (const double *)nullptr);
             }
+        };
+        bool bad_pair = false;
+        auto backward = [&](const std::vector<LevelDev> &levels, hipStream_t st) {
+            for (int l = (int)levels.size() - 1; l >= 0; --l) {
+                const LevelDev &L = levels[l];
+                if (!L.n_bwd) continue;
+                // the level's work items were cut for bwd_nw * bwd_cw columns per block (upload_factor): the kernel must be THAT pair
+                // (two waves per block: four columns per wave only)
+                bad_pair |= !with_int<4, 2, 1>(L.bwd_cw, [&](auto cw) { return with_int<2, 4, 8, 16>(L.bwd_nw, [&](auto nwb) {
+                    constexpr int CW = decltype(cw)::value, NWB = decltype(nwb)::value;
+                    if constexpr (NWB != 2 || CW == 4) hipLaunchKernelGGL((solve_bwd_kernel<CW, NWB>), dim3(L.n_bwd), dim3(64 * NWB), 0, st, L.d_bwd, F, ctx->d_w, ctx->d_xcur);
+                    return NWB != 2 || CW == 4;
+                }); });
+            }
+        };
+        if (ctx->n_fuse)      // the bottom subtrees first, one workgroup each (then the levels above the cut)
+            hipLaunchKernelGGL(solve_fwd_subtree_kernel, dim3(ctx->n_fuse), dim3(64 * SUB_WAVES), ctx->fuse_lds, ctx->stream, (const int *)ctx->d_fuse_rec,
+                               (const int64_t *)ctx->d_fuse_off, (const double *)ctx->d_panels, (const double *)ctx->d_y, ctx->d_w, ctx->d_c);
+        forward(ctx->levels, ctx->stream);
+        if (!ctx->levels_top.empty()) {
+            // subtree sharding: own subtrees are done; ONE small all-reduce carries the top nodes' partial right-hand sides and the
+            // subtree roots' contributions to every rank, then everybody runs the (replicated) top of the tree
+            const int n = ctx->n_comm_top + ctx->n_comm_slots;
+            if (ex0) HIPCHK(hipEventRecord(ex0, ctx->stream));
+            if (n > 0) {
+                hipLaunchKernelGGL(shard_pack_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_comm_top, (const int *)ctx->d_comm_top, ctx->n_comm_slots,
+                                   (const int *)ctx->d_comm_slots, (const unsigned char *)ctx->d_comm_mine, (const double *)ctx->d_y, (const double *)ctx->d_c, ctx->d_comm_buf);
+                TRY(do_allreduce(ctx, ctx->d_comm_buf, 3 * (int64_t)n));
+                hipLaunchKernelGGL(shard_unpack_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_comm_top, (const int *)ctx->d_comm_top, ctx->n_comm_slots,
+                                   (const int *)ctx->d_comm_slots, (const double *)ctx->d_comm_buf, ctx->d_y, ctx->d_c);
+            }
+            if (ex1) HIPCHK(hipEventRecord(ex1, ctx->stream));
+            if (ctx->dist_top) {
+                // distributed top: the root IS the top.  t = y - (the subtrees' contributions) on every rank (3 k doubles), then THIS rank's rows of
+                // x = (L L^T)^-1 t straight into the root's range of x_cur, which the gather zeroed -- and a second small all-reduce (own rows + zeros: exact)
+                // hands every rank the whole x of the top.  No replicated sweep over the top, no backward work above the own subtrees.
+                const int k = ctx->root_k, nr = ctx->root_r1 - ctx->root_r0;
+                double *T = ctx->d_w + 3 * (size_t)ctx->root_first, *Xr = ctx->d_xcur + 3 * (size_t)ctx->root_first;
+                hipLaunchKernelGGL((root_gather_kernel<CG2>), dim3((k + 255) / 256), dim3(256), 0, ctx->stream, k, ctx->root_first, ctx->root_foff, F, (const double *)ctx->d_y, (const double *)ctx->d_c, T, Xr);
+                if (nr > 0) hipLaunchKernelGGL((root_product_kernel<false, false>), dim3((nr + ROOT_ROWS - 1) / ROOT_ROWS), dim3(64 * ROOT_ROWS), 0, ctx->stream, k, nr, root_inv_ld(k),
+                                               (const double *)(ctx->d_panels + ctx->dev_root_inv_off[ctx->root_sn]), (const double *)T, Xr + 3 * (size_t)ctx->root_r0, 0, (int64_t)0, F, (const double *)nullptr);
+                if (ex2) HIPCHK(hipEventRecord(ex2, ctx->stream));
+                TRY(do_allreduce(ctx, Xr, 3 * (int64_t)k));
+                if (ex3) HIPCHK(hipEventRecord(ex3, ctx->stream));
+            } else forward(ctx->levels_top, ctx->stream);
         }
+        if (mid) HIPCHK(hipEventRecord(mid, ctx->stream));
+        if (!ctx->levels_top.empty() && !ctx->dist_top) backward(ctx->levels_top, ctx->stream);
+        backward(ctx->levels, ctx->stream);
+        HIPCHK(hipGetLastError());
+        if (bad_pair) return fail(ctx, ADMM_ERR_STATE, "backward sweep: no kernel for a level's (columns per wave, waves per block) pair");
+        return ADMM_OK;
     };
-    bool bad_pair = false;
-    auto backward = [&](const std::vector<LevelDev> &levels, hipStream_t st) {
-        for (int l = (int)levels.size() - 1; l >= 0; --l) {
-            const LevelDev &L = levels[l];
-            if (!L.n_bwd) continue;
-            // the level's work items were cut for bwd_nw * bwd_cw columns per block (upload_factor): the kernel must be THAT pair
-#define ADMM_BWD(CW, NWB) if (L.bwd_cw == CW && L.bwd_nw == NWB) { hipLaunchKernelGGL((solve_bwd_kernel<CW, NWB>), dim3(L.n_bwd), dim3(64 * NWB), 0, st, L.d_bwd, F, ctx->d_w, ctx->d_xcur); continue; }
-            ADMM_BWD(4, 2) ADMM_BWD(4, 4) ADMM_BWD(4, 8) ADMM_BWD(4, 16)
-            ADMM_BWD(2, 4) ADMM_BWD(2, 8) ADMM_BWD(2, 16)
-            ADMM_BWD(1, 4) ADMM_BWD(1, 8) ADMM_BWD(1, 16)
-#undef ADMM_BWD
-            bad_pair = true;
-        }
-    };
-    if (ctx->n_fuse)      // the bottom subtrees first, one workgroup each (then the levels above the cut)
-        hipLaunchKernelGGL(solve_fwd_subtree_kernel, dim3(ctx->n_fuse), dim3(64 * SUB_WAVES), ctx->fuse_lds, ctx->stream, (const int *)ctx->d_fuse_rec,
-                           (const int64_t *)ctx->d_fuse_off, (const double *)ctx->d_panels, (const double *)ctx->d_y, ctx->d_w, ctx->d_c);
-    forward(ctx->levels, ctx->stream);
-    if (!ctx->levels_top.empty()) {
-        // subtree sharding: own subtrees are done; ONE small all-reduce carries the top nodes' partial right-hand sides and the
-        // subtree roots' contributions to every rank, then everybody runs the (replicated) top of the tree
-        const int n = ctx->n_comm_top + ctx->n_comm_slots;
-        if (ex0) HIPCHK(hipEventRecord(ex0, ctx->stream));
-        if (n > 0) {
-            hipLaunchKernelGGL(shard_pack_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_comm_top, (const int *)ctx->d_comm_top, ctx->n_comm_slots,
-                               (const int *)ctx->d_comm_slots, (const unsigned char *)ctx->d_comm_mine, (const double *)ctx->d_y, (const double *)ctx->d_c, ctx->d_comm_buf);
-            TRY(do_allreduce(ctx, ctx->d_comm_buf, 3 * (int64_t)n));
-            hipLaunchKernelGGL(shard_unpack_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_comm_top, (const int *)ctx->d_comm_top, ctx->n_comm_slots,
-                               (const int *)ctx->d_comm_slots, (const double *)ctx->d_comm_buf, ctx->d_y, ctx->d_c);
-        }
-        if (ex1) HIPCHK(hipEventRecord(ex1, ctx->stream));
-        if (ctx->dist_top) {
-            // distributed top: the root IS the top.  t = y - (the subtrees' contributions) on every rank (3 k doubles), then THIS rank's rows of
-            // x = (L L^T)^-1 t straight into the root's range of x_cur, which the gather zeroed -- and a second small all-reduce (own rows + zeros: exact)
-            // hands every rank the whole x of the top.  No replicated sweep over the top, no backward work above the own subtrees.
-            const int k = ctx->root_k, nr = ctx->root_r1 - ctx->root_r0;
-            double *T = ctx->d_w + 3 * (size_t)ctx->root_first, *Xr = ctx->d_xcur + 3 * (size_t)ctx->root_first;
-            if (F.cg4) hipLaunchKernelGGL((root_gather_kernel<true>), dim3((k + 255) / 256), dim3(256), 0, ctx->stream, k, ctx->root_first, ctx->root_foff, F, (const double *)ctx->d_y, (const double *)ctx->d_c, T, Xr);
-            else hipLaunchKernelGGL((root_gather_kernel<false>), dim3((k + 255) / 256), dim3(256), 0, ctx->stream, k, ctx->root_first, ctx->root_foff, F, (const double *)ctx->d_y, (const double *)ctx->d_c, T, Xr);
-            if (nr > 0) hipLaunchKernelGGL((root_product_kernel<false, false>), dim3((nr + ROOT_ROWS - 1) / ROOT_ROWS), dim3(64 * ROOT_ROWS), 0, ctx->stream, k, nr, root_inv_ld(k),
-                                           (const double *)(ctx->d_panels + ctx->dev_root_inv_off[ctx->root_sn]), (const double *)T, Xr + 3 * (size_t)ctx->root_r0, 0, (int64_t)0, F, (const double *)nullptr);
-            if (ex2) HIPCHK(hipEventRecord(ex2, ctx->stream));
-            TRY(do_allreduce(ctx, Xr, 3 * (int64_t)k));
-            if (ex3) HIPCHK(hipEventRecord(ex3, ctx->stream));
-        } else forward(ctx->levels_top, ctx->stream);
-    }
-    if (mid) HIPCHK(hipEventRecord(mid, ctx->stream));
-    if (!ctx->levels_top.empty() && !ctx->dist_top) backward(ctx->levels_top, ctx->stream);
-    backward(ctx->levels, ctx->stream);
-    HIPCHK(hipGetLastError());
-    if (bad_pair) return fail(ctx, ADMM_ERR_STATE, "backward sweep: no kernel for a level's (columns per wave, waves per block) pair");
-    return ADMM_OK;
+    return F.cg4 ? sweeps(std::true_type{}) : sweeps(std::false_type{});
 }
 
 // subtree sharding: after the solve a rank holds x only on its own subtrees and the top; rebuild the full vector

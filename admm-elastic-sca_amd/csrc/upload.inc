@@ -13,7 +13,7 @@ template <class T> std::vector<T> permute_nodes(const std::vector<T> &h, const s
 // of the LAST iteration stay); meta: (tag, level, workgroups, KB, list, first slot) per launch
 unsigned long long *g_swp_base; size_t g_swp_wgs; std::vector<int> g_swp_meta;
 #endif
-// ---- the bottom subtrees, one workgroup each (solve_fwd_subtree_kernel / solve_bwd_subtree_kernel) --------------------------------
+// ---- the bottom subtrees of the forward sweep, one workgroup each (solve_fwd_subtree_kernel) ---------------------------------------
 // Cut level c: the highest level such that every supernode at or below it has at most 64 columns (the wave-per-tile forward and the
 // 4-column backward shape) and the subtrees below it -- supernodes up to level c whose parent lies above c -- still number at least two
 // per CU.  Each such subtree becomes one record, loaded into LDS once by its workgroup (admm_dev::SUB_* for the layout): the items of
@@ -92,9 +92,12 @@ int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std:
                     }
                 }
                 const int cdst = s == t ? -1 : (S.nrows ? local_slot[S.slot_off] : 0);      // (-1: the root, to C)
-                const int64_t po = ctx->dev_panel_off[s];
+                int it[SUB_ITEM] = {};
+                it[SUB_K] = S.ncols; it[SUB_R] = S.nrows; it[SUB_FIRST] = S.first; it[SUB_MAP] = moff; it[SUB_CDST] = cdst;
+                sub_split64(ctx->dev_panel_off[s], it + SUB_POFF);
                 for (int tile = 0; tile < (f + 63) / 64; ++tile) {
-                    items.insert(items.end(), {S.ncols, S.nrows, S.first, tile, moff, cdst, (int)(uint32_t)(po & 0xffffffff), (int)(po >> 32)});
+                    it[SUB_TILE] = tile;
+                    items.insert(items.end(), it, it + SUB_ITEM);
                     ++n_items;
                 }
             }
@@ -109,11 +112,11 @@ int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std:
         const int64_t rs = F.sn[t].slot_off;
         const int cbuf = n_ints / 2;      // (doubles)
         const int ts_off = cbuf + cdoubles;
-        v[0] = nl; v[1] = item0; v[2] = cbuf; v[3] = ts_off; v[4] = (int)(uint32_t)(rs & 0xffffffff); v[5] = (int)(rs >> 32);
+        v[SUB_LEVELS] = nl; v[SUB_ITEM0] = item0; v[SUB_CBUF] = cbuf; v[SUB_TS] = ts_off; sub_split64(rs, &v[SUB_ROOT_SLOT]);
         for (int l = 0; l <= nl; ++l) v[SUB_HDR + l] = lvp[l];
         for (size_t q = 0; q < items.size(); ++q) {
             v[item0 + q] = items[q];
-            if (q % SUB_ITEM == 4 && items[q] >= 0) v[item0 + q] += map0;      // front map: offset in the record
+            if (q % SUB_ITEM == SUB_MAP && items[q] >= 0) v[item0 + q] += map0;      // front map: offset in the record
         }
         std::copy(maps.begin(), maps.end(), v.begin() + map0);
         const int lds = 8 * (ts_off + 3 * 64 * SUB_WAVES);
@@ -163,10 +166,9 @@ int upload_factor(admm_hip_ctx *ctx) {
     ctx->d_ainv = nullptr;
     if (ctx->dense) TRY(upload(ctx, &ctx->d_ainv, ctx->Ainv));
     ctx->levels.assign(F.levels.size(), LevelDev());
-    // Split level: the first level holding a supernode wider than FWD_SMALL_KMAX.  Below it every forward item is
-    // a wave item and the backward kernel takes 4 columns per wave; from it upwards block items / ADMM_BWD_BIG_CW.
     // Per level, by its widest supernode: forward as wave items (one wave per 64-row tile, k <= fwd_small_k <= 64) or block
-    // items (NW waves split a tile's columns); backward with 4 columns per wave (k <= bwd_small_k) or one.
+    // items (NW waves split a tile's columns); backward with 4 columns per wave (k <= bwd_small_k), otherwise BWD_BIG_CW
+    // (2 on levels whose column count lies in (bwd_cw2_min_cols, bwd_cw2_max_cols]).
     std::vector<int> level_kmax(F.levels.size(), 0);
     for (size_t l = 0; l < F.levels.size(); ++l) for (int s : F.levels[l]) level_kmax[l] = std::max(level_kmax[l], F.sn[s].ncols);
     const int fwd_small_k = std::min(ctx->fwd_small_k, admm_dev::FWD_SMALL_KMAX);
@@ -203,7 +205,7 @@ int upload_factor(admm_hip_ctx *ctx) {
             std::vector<admm_dev::SweepItem> sm, bg, bw;
             L.level = (int)l; L.mbytes = 0.0;
             const bool fwd_small = level_kmax[l] <= fwd_small_k, bwd_small = level_kmax[l] <= ctx->bwd_small_k;
-            L.bwd_cw = bwd_small ? 4 : ADMM_BWD_BIG_CW;   // columns per wave in the backward kernel
+            L.bwd_cw = bwd_small ? 4 : BWD_BIG_CW;   // columns per wave in the backward kernel
             // eight columns per block pay where a level has thousands of columns (one staging of the vector per 8 instead of 4
             // columns); on levels with few columns the larger number of blocks matters more (50k-tet bar: 4 waves 222 us / 8: 228)
             int level_cols = 0;
@@ -229,7 +231,7 @@ int upload_factor(admm_hip_ctx *ctx) {
                 if (subtree && ps.want < 0 && !top_needed[s]) continue;      // replicated top: no backward work for a separator this rank never reads
                 for (int c = 0; c < chunks; ++c) { it.part = c; bw.push_back(it); }
             }
-            if (ctx->xcd_min_supernodes > 0) { xcd_order(sm, ADMM_FWD_SMALL_WAVES, ctx->xcd_min_supernodes); xcd_order(bg, 1, ctx->xcd_min_supernodes); xcd_order(bw, 1, ctx->xcd_min_supernodes); }
+            if (ctx->xcd_min_supernodes > 0) { xcd_order(sm, admm_dev::FWD_SMALL_WAVES, ctx->xcd_min_supernodes); xcd_order(bg, 1, ctx->xcd_min_supernodes); xcd_order(bw, 1, ctx->xcd_min_supernodes); }
             L.n_small = (int)sm.size(); L.n_big = (int)bg.size(); L.n_bwd = (int)bw.size();
             int kmax = 0;
             for (const admm_dev::SweepItem &q : bg) kmax = std::max(kmax, q.k);
@@ -260,7 +262,7 @@ int upload_factor(admm_hip_ctx *ctx) {
                     for (int q : {tag, (int)l, n_wg, (int)(L.mbytes * 1024), list, (int)g_swp_wgs}) g_swp_meta.push_back(q);
                     g_swp_wgs += n_wg;
                 };
-                reg(sm, ADMM_FWD_SMALL_WAVES, 0); reg(bg, 1, L.big_nw); reg(bw, 1, 100 + 10 * L.bwd_cw + (L.bwd_nw == 16 ? 6 : L.bwd_nw));
+                reg(sm, admm_dev::FWD_SMALL_WAVES, 0); reg(bg, 1, L.big_nw); reg(bw, 1, 100 + 10 * L.bwd_cw + (L.bwd_nw == 16 ? 6 : L.bwd_nw));
             }
 #endif
             TRY(upload(ctx, &L.d_small, sm)); TRY(upload(ctx, &L.d_big, bg)); TRY(upload(ctx, &L.d_bwd, bw));
