@@ -150,6 +150,8 @@ def lib():
         L.admm_hip_mesh_query.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, _dp]
         L.admm_hip_mesh_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]
         L.admm_hip_add_collision_mesh.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.admm_hip_mesh_set_vertices.argtypes = [C.c_void_p, C.c_int, _dp, C.c_char_p, C.c_int]
+        L.admm_hip_update_collision_mesh.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
         _lib = L
     return _lib
 
@@ -191,6 +193,15 @@ class Mesh:
         if rc != 0:
             raise AdmmHipError("admm_hip_mesh_query error %d" % rc)
         return proj, sd
+
+    def set_vertices(self, verts):
+        """new vertex positions [nv][3] for the same topology (admm_hip_mesh_set_vertices): pseudo-normals recomputed, BVH boxes refit.
+        A refused update raises AdmmHipError and leaves the mesh as it was."""
+        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+        err = C.create_string_buffer(512)
+        rc = self.L.admm_hip_mesh_set_vertices(self.h, v.shape[0], _d(v), err, len(err))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_set_vertices error %d: %s" % (rc, err.value.decode()))
 
     def info(self):
         nt, nn, dep = C.c_int(), C.c_int(), C.c_int()
@@ -354,6 +365,11 @@ class System:
         mid = C.c_int()
         self._chk(self.L.admm_hip_add_collision_mesh(self.h, m.h, C.byref(mid)))
         return mid.value
+
+    def update_collision_mesh(self, mesh_id, verts):
+        """new vertex positions [nv][3] for a registered mesh (mesh_id of add_collision_mesh); after initialize on the device, in place"""
+        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+        self._chk(self.L.admm_hip_update_collision_mesh(self.h, int(mesh_id), v.shape[0], _d(v)))
 
     def set_gravity(self, which, g):
         self._chk(self.L.admm_hip_set_gravity(self.h, which, float(g[0]), float(g[1]), float(g[2])))

@@ -230,6 +230,23 @@ int admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, in
     return ADMM_OK;
 }
 
+// before finalize (or in a host-only context) the context's copy takes admm_hip_mesh_set_vertices; after it the device arrays are
+// rewritten in place (launch.inc: update_mesh_device)
+int admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, const double *verts) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    admm_hip_mesh &M = ctx->meshes[mesh_id];
+    if (!ctx->finalized || ctx->device_id < 0) {
+        char msg[512];
+        const int rc = admm_mesh::mesh_set_vertices(M, nv, verts, msg, (int)sizeof msg);
+        return rc ? fail(ctx, rc, "collision mesh %d: %s", mesh_id, msg) : ADMM_OK;
+    }
+    if (nv != M.nv || !verts) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: %d vertices given, the mesh has %d", mesh_id, nv, M.nv);
+    HIPCHK(hipSetDevice(ctx->device_id));
+    return update_mesh_device(ctx, mesh_id, verts);
+}
+
 int admm_hip_set_shard(admm_hip_ctx *ctx, int rank, int world) {
     if (!ctx || world < 1 || rank < 0 || rank >= world) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "shard must be set before finalize");

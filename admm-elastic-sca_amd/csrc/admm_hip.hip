@@ -22,6 +22,7 @@
 #include "kernels_global.hpp"
 #include "factor_dev.hpp"
 #include "kernels_local.hpp"
+#include "kernels_mesh.hpp"
 
 extern "C" int omp_get_max_threads(void);
 

@@ -121,6 +121,14 @@ struct admm_hip_ctx {
     // closed triangle meshes named by ADMM_SHAPE_MESH entries (admm_hip_add_collision_mesh, before finalize): with at least one, the collision
     // batches run project_collision_mesh_kernel instead of a segment of project_multi_kernel; their arrays are uploaded at finalize
     std::vector<admm_hip_mesh> meshes; admm_mesh::MeshDev *d_meshes = nullptr;
+    // admm_hip_update_collision_mesh after finalize (kernels_mesh.hpp) rewrites a mesh's device arrays in place; the host copy above
+    // then keeps only the topology.  Every buffer the update needs is allocated at finalize, one set per mesh:
+    struct MeshUpdate {
+        admm_mesh::Node *nodes; admm_mesh::Tri *tris; admm_mesh::Nrm *nrm;       // the live arrays (d_meshes points at them)
+        double *verts, *fn, *vn, *part;                                          // staged vertices, face / vertex normals, volume partials
+        int *cid, *adj, *inc_ptr, *inc, *lvl_nodes;                              // the topology (admm_hip_mesh)
+    };
+    std::vector<MeshUpdate> mesh_upd; admm_mesh::UpdateCheck *d_mesh_chk = nullptr;
     SymCSC A;
     Factor F;
     admm_hip_info info{};

@@ -61,6 +61,39 @@ bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
     return true;
 }
 
+// admm_hip_update_collision_mesh after finalize (kernels_mesh.hpp): check, refuse without touching the live arrays, or commit;
+// synchronous on ctx->stream
+int update_mesh_device(admm_hip_ctx *ctx, int id, const double *verts) {
+    using namespace admm_dev;
+    using namespace admm_mesh;
+    const admm_hip_mesh &M = ctx->meshes[id];
+    const admm_hip_ctx::MeshUpdate &u = ctx->mesh_upd[id];
+    const int nt = (int)M.tris.size(), nv = M.nv, nchunk = (nt + VOL_CHUNK - 1) / VOL_CHUNK;
+    const hipStream_t st = ctx->stream;
+    auto grid = [](int n) { return dim3((unsigned)((std::max(n, 1) + MESH_BLOCK - 1) / MESH_BLOCK)); };
+    HIPCHK(hipMemcpyAsync(u.verts, verts, sizeof(double) * 3 * (size_t)nv, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ctx->d_mesh_chk, NO_TRI, 2, st));      // bad_tri = bad_vtx = none
+    hipLaunchKernelGGL(mesh_check_kernel, grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, ctx->d_mesh_chk);
+    hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, ctx->d_mesh_chk);
+    UpdateCheck chk;
+    HIPCHK(hipMemcpyAsync(&chk, ctx->d_mesh_chk, sizeof chk, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    char msg[512];
+    if (mesh_refusal(M, verts, chk, msg, (int)sizeof msg)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: %s", id, msg);
+    hipLaunchKernelGGL(mesh_vertex_normal_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const double *)u.verts, (const int *)u.cid, (const double *)u.fn,
+                       (const int *)u.inc_ptr, (const int *)u.inc, u.vn);
+    hipLaunchKernelGGL(mesh_slot_kernel, grid(nt), dim3(MESH_BLOCK), 0, st, nt, (const double *)u.verts, (const int *)u.cid, (const int *)u.adj,
+                       (const double *)u.fn, (const double *)u.vn, u.tris, u.nrm);
+    for (int d = M.depth; d >= 0; --d) {
+        const int n = M.lvl_ptr[d + 1] - M.lvl_ptr[d];
+        hipLaunchKernelGGL(mesh_refit_kernel, grid(n), dim3(MESH_BLOCK), 0, st, (const int *)(u.lvl_nodes + M.lvl_ptr[d]), n, u.nodes, (const Tri *)u.tris);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return ADMM_OK;
+}
+
 // a collision batch of a context with mesh obstacles
 void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;

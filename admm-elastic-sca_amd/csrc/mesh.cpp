@@ -152,12 +152,83 @@ int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, admm_hi
     M.tris.resize(nt); M.nrm.resize(nt);
     for (int i = 0; i < nt; ++i) { M.tris[i] = src[B.ord[i]]; M.nrm[i] = nrm[B.ord[i]]; }
     M.depth = B.depth;
+    // the topology admm_hip_mesh_set_vertices recomputes the arrays from: corners, adjacency, each vertex's incidences in ascending
+    // (triangle, corner) order -- the order of the vertex-normal sum above --, the nodes by depth (children follow their parent)
+    M.nv = nv;
+    M.cid = std::move(cid); M.adj = std::move(adj);
+    M.inc_ptr.assign((size_t)nv + 1, 0);
+    for (int e = 0; e < 3 * nt; ++e) M.inc_ptr[M.cid[e] + 1]++;
+    for (int v = 0; v < nv; ++v) M.inc_ptr[v + 1] += M.inc_ptr[v];
+    M.inc.resize((size_t)nt * 3);
+    {
+        std::vector<int> pos(M.inc_ptr.begin(), M.inc_ptr.end() - 1);
+        for (int e = 0; e < 3 * nt; ++e) M.inc[pos[M.cid[e]]++] = e;
+    }
+    std::vector<int> dep(M.nodes.size(), 0);
+    for (size_t i = 0; i < M.nodes.size(); ++i)
+        if (M.nodes[i].cnt == 0) dep[M.nodes[i].a] = dep[M.nodes[i].a + 1] = dep[i] + 1;
+    M.lvl_ptr.assign((size_t)M.depth + 2, 0);
+    for (int d : dep) M.lvl_ptr[d + 1]++;
+    for (int d = 0; d <= M.depth; ++d) M.lvl_ptr[d + 1] += M.lvl_ptr[d];
+    M.lvl_nodes.resize(M.nodes.size());
+    {
+        std::vector<int> pos(M.lvl_ptr.begin(), M.lvl_ptr.end() - 1);
+        for (size_t i = 0; i < M.nodes.size(); ++i) M.lvl_nodes[pos[dep[i]]++] = (int)i;
+    }
     return ADMM_OK;
 }
 
 struct HostStack { int s[MAX_DEPTH]; int &operator[](int i) { return s[i]; } };
 
 } // namespace
+
+namespace admm_mesh {
+
+int mesh_refusal(const admm_hip_mesh &M, const double *verts, const UpdateCheck &c, char *err, int err_len) {
+    if (c.bad_tri != NO_TRI) {
+        const int *C = M.cid.data() + 3 * (size_t)c.bad_tri;
+        for (int k = 0; k < 3; ++k)
+            if (!finite3(verts + 3 * (size_t)C[k])) return mesh_fail(err, err_len, "triangle %d: vertex %d is not finite", c.bad_tri, C[k]);
+        return mesh_fail(err, err_len, "triangle %d (%d, %d, %d) is degenerate (zero area)", c.bad_tri, C[0], C[1], C[2]);
+    }
+    if (c.bad_vtx != NO_TRI) return mesh_fail(err, err_len, "vertex %d is not finite", c.bad_vtx);
+    if (!(c.vol6 > 0.0))
+        return mesh_fail(err, err_len, "the mesh encloses a non-positive volume (%g): its triangles must stay counter-clockwise seen from outside", c.vol6 / 6.0);
+    return ADMM_OK;
+}
+
+// checked first, the mesh untouched until the update is accepted; the same stages and arithmetic as the device update (kernels_mesh.hpp)
+int mesh_set_vertices(admm_hip_mesh &M, int nv, const double *verts, char *err, int err_len) {
+    if (err && err_len > 0) err[0] = 0;
+    if (nv != M.nv || !verts) return mesh_fail(err, err_len, "%d vertices given, the mesh has %d", nv, M.nv);
+    const int nt = (int)M.tris.size(), nchunk = (nt + VOL_CHUNK - 1) / VOL_CHUNK;
+    std::vector<double> fn((size_t)nt * 3), part((size_t)nchunk);
+    int bad = NO_TRI;
+#pragma omp parallel for schedule(static) reduction(min : bad)
+    for (int c = 0; c < nchunk; ++c) {
+        double s = 0.0;
+        for (int t = c * VOL_CHUNK; t < std::min(nt, (c + 1) * VOL_CHUNK); ++t) {
+            double v[9];
+            if (!tri_ok(verts, M.cid.data(), t, v, &fn[3 * (size_t)t])) bad = std::min(bad, t);
+            s += volume_term(v);
+        }
+        part[c] = s;
+    }
+    UpdateCheck chk{bad, NO_TRI, 0.0};
+    for (int v = 0; v < nv; ++v) if (!finite3(verts + 3 * (size_t)v)) { chk.bad_vtx = v; break; }
+    for (int c = 0; c < nchunk; ++c) chk.vol6 += part[c];
+    if (const int rc = mesh_refusal(M, verts, chk, err, err_len)) return rc;
+    std::vector<double> vn((size_t)nv * 3);
+#pragma omp parallel for schedule(static)
+    for (int v = 0; v < nv; ++v) vertex_normal(verts, M.cid.data(), fn.data(), M.inc_ptr.data(), M.inc.data(), v, &vn[3 * (size_t)v]);
+#pragma omp parallel for schedule(static)
+    for (int s = 0; s < nt; ++s) slot_data(verts, M.cid.data(), M.adj.data(), fn.data(), vn.data(), M.tris[s], M.nrm[s]);
+    for (int d = M.depth; d >= 0; --d)
+        for (int i = M.lvl_ptr[d]; i < M.lvl_ptr[d + 1]; ++i) refit_node(M.nodes.data(), M.tris.data(), M.lvl_nodes[i]);
+    return ADMM_OK;
+}
+
+} // namespace admm_mesh
 
 extern "C" {
 
@@ -171,6 +242,11 @@ int admm_hip_mesh_create(admm_hip_mesh **out, int nv, const double *verts, int n
     if (rc) { delete M; return rc; }
     *out = M;
     return ADMM_OK;
+}
+
+int admm_hip_mesh_set_vertices(admm_hip_mesh *mesh, int nv, const double *verts, char *err, int err_len) {
+    if (!mesh) return mesh_fail(err, err_len, "mesh is NULL");
+    return mesh_set_vertices(*mesh, nv, verts, err, err_len);
 }
 
 void admm_hip_mesh_destroy(admm_hip_mesh *mesh) { delete mesh; }

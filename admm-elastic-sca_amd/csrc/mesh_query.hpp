@@ -157,4 +157,126 @@ ADMM_HD bool inside(const Node &root, const Nrm *nrm, const double *q, const Hit
     return s < 0.0;
 }
 
+// ---- in-place deformation (admm_hip_mesh_set_vertices on the host, kernels_mesh.hpp on the device) --------------------------------
+// The topology, the tree and the leaf order stay; the arithmetic below recomputes the per-triangle data and refits the boxes.  Only
+// + - * / sqrt, comparisons and bit operations: correctly rounded on both sides, so the host and the device give the same bits.
+
+constexpr int VOL_CHUNK = 256;     // the enclosed volume: partial sums over chunks of this many triangles (original order), then the partials in order
+
+ADMM_HD double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+ADMM_HD void cross3(const double *a, const double *b, double *o) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; }
+ADMM_HD void normalize3(double *v) { const double l = sqrt(dot3(v, v)); if (l > 0.0) for (int j = 0; j < 3; ++j) v[j] /= l; }
+ADMM_HD bool finite3(const double *v) { return __builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]); }
+// std::min / std::max (the same operand order, so the same result for signed zeros)
+ADMM_HD double min_d(double a, double b) { return b < a ? b : a; }
+ADMM_HD double max_d(double a, double b) { return a < b ? b : a; }
+
+// the unit normal of the triangle with corners v[9] (canonical order): false when its area is zero (or not a number)
+ADMM_HD bool face_normal(const double *v, double *n) {
+    double e1[3], e2[3];
+    for (int j = 0; j < 3; ++j) { e1[j] = v[3 + j] - v[j]; e2[j] = v[6 + j] - v[j]; }
+    cross3(e1, e2, n);
+    if (!(dot3(n, n) > 0.0)) return false;
+    normalize3(n);
+    return true;
+}
+// the check of an update: the lowest original triangle with a non-finite corner or zero area (NO_TRI: none), the lowest non-finite
+// vertex (NO_TRI: none; also catches vertices no triangle uses), 6 x the enclosed volume (blocked sum, VOL_CHUNK)
+struct UpdateCheck { int bad_tri, bad_vtx; double vol6; };
+static_assert(sizeof(UpdateCheck) == 16, "the device update reads back 16 bytes");
+
+// the triangle's term of 6 x the enclosed volume
+ADMM_HD double volume_term(const double *v) { double c[3]; cross3(v + 3, v + 6, c); return dot3(v, c); }
+
+// the cosine of the angle at corner p between the edges to p1 and p2, clamped to [-1, 1] as std::max(-1, std::min(1, c)) does
+ADMM_HD double corner_cos(const double *p, const double *p1, const double *p2) {
+    double a[3], b[3];
+    for (int j = 0; j < 3; ++j) { a[j] = p1[j] - p[j]; b[j] = p2[j] - p[j]; }
+    const double c = dot3(a, b) / sqrt(dot3(a, a) * dot3(b, b));
+    const double m = c < 1.0 ? c : 1.0;
+    return -1.0 < m ? m : -1.0;
+}
+
+// acos on [-1, 1] from + - * / sqrt and one bit mask (the classic rational approximation of asin, Cody & Waite / fdlibm's scheme):
+// within an ulp of the libm value, and the same bits on the host and the device -- the vertex pseudo-normals of a deformed mesh
+ADMM_HD double acos_rt(double x) {
+    const double pi = 3.14159265358979311600e+00, pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17;
+    const double pS0 = 1.66666666666666657415e-01, pS1 = -3.25565818622400915405e-01, pS2 = 2.01212532134862925881e-01,
+                 pS3 = -4.00555345006794114027e-02, pS4 = 7.91534994289814532176e-04, pS5 = 3.47933107596021167570e-05,
+                 qS1 = -2.40339491173441421878e+00, qS2 = 2.02094576023350569471e+00, qS3 = -6.88283971605453293030e-01,
+                 qS4 = 7.70381505559019352791e-02;
+    if (x >= 1.0) return 0.0;
+    if (x <= -1.0) return pi + 2.0 * pio2_lo;
+    const double ax = x < 0.0 ? -x : x;
+    if (ax < 0.5) {
+        if (ax <= 0x1p-57) return pio2_hi + pio2_lo;
+        const double z = x * x;
+        const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+        const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+        return pio2_hi - (x - (pio2_lo - x * (p / q)));
+    }
+    const double z = (1.0 - ax) * 0.5;
+    const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const double s = sqrt(z), r = p / q;
+    if (x < 0.0) return pi - 2.0 * (s + (r * s - pio2_lo));
+    // x > 0.5: s split into a high part with its low 32 bits cleared and a correction, for accuracy near x = 1
+    uint64_t bits; __builtin_memcpy(&bits, &s, sizeof bits);
+    bits &= 0xffffffff00000000ull;
+    double df; __builtin_memcpy(&df, &bits, sizeof df);
+    const double c = (z - df * df) / (s + df);
+    return 2.0 * (df + (r * s + c));
+}
+
+// the corners of original triangle t (canonical order cid[3t..3t+3)) gathered from verts [nv][3]
+ADMM_HD void gather_tri(const double *verts, const int *cid, int t, double *v) {
+    for (int k = 0; k < 3; ++k) { const double *p = verts + 3 * (size_t)cid[3 * (size_t)t + k]; v[3 * k] = p[0]; v[3 * k + 1] = p[1]; v[3 * k + 2] = p[2]; }
+}
+// original triangle t gathered into v[9]; false if a corner is not finite or its area is zero, else its unit normal in n[3]
+ADMM_HD bool tri_ok(const double *verts, const int *cid, int t, double *v, double *n) {
+    gather_tri(verts, cid, t, v);
+    return finite3(v) && finite3(v + 3) && finite3(v + 6) && face_normal(v, n);
+}
+// the angle-weighted normal of vertex `vx`: the sum over its incidences inc[inc_ptr[vx], inc_ptr[vx + 1]) = 3 t + k, ascending (the
+// order in which admm_hip_mesh_create sums them), of angle(t, k) * fn[t]
+ADMM_HD void vertex_normal(const double *verts, const int *cid, const double *fn, const int *inc_ptr, const int *inc, int vx, double *o) {
+    o[0] = o[1] = o[2] = 0.0;
+    for (int i = inc_ptr[vx]; i < inc_ptr[vx + 1]; ++i) {
+        const int t = inc[i] / 3, k = inc[i] - 3 * t;
+        const int *c = cid + 3 * (size_t)t;
+        const double ang = acos_rt(corner_cos(verts + 3 * (size_t)c[k], verts + 3 * (size_t)c[(k + 1) % 3], verts + 3 * (size_t)c[(k + 2) % 3]));
+        for (int j = 0; j < 3; ++j) o[j] += ang * fn[3 * (size_t)t + j];
+    }
+}
+// leaf-order slot s (original triangle t = tri.orig): its corners and the seven pseudo-normals, from the face normals fn [nt][3] and
+// the (unnormalised) vertex normals vn [nv][3]; an edge's normal sums the lower-indexed face first
+ADMM_HD void slot_data(const double *verts, const int *cid, const int *adj, const double *fn, const double *vn, Tri &tri, Nrm &N) {
+    const int t = tri.orig;
+    gather_tri(verts, cid, t, tri.v);
+    for (int j = 0; j < 3; ++j) N.n[0][j] = fn[3 * (size_t)t + j];
+    for (int k = 0; k < 3; ++k) {
+        const int o = adj[3 * (size_t)t + k];
+        const int lo = t < o ? t : o, hi = t < o ? o : t;
+        for (int j = 0; j < 3; ++j) N.n[1 + k][j] = fn[3 * (size_t)lo + j] + fn[3 * (size_t)hi + j];
+        normalize3(N.n[1 + k]);
+        for (int j = 0; j < 3; ++j) N.n[4 + k][j] = vn[3 * (size_t)cid[3 * (size_t)t + k] + j];
+        normalize3(N.n[4 + k]);
+    }
+}
+// node ni's box from its triangles (a leaf, the loop order of the builder) or from its two children's boxes (already refit)
+ADMM_HD void refit_node(Node *nodes, const Tri *tris, int ni) {
+    Node &n = nodes[ni];
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (n.cnt > 0) {
+        for (int i = n.a; i < n.a + n.cnt; ++i) for (int k = 0; k < 3; ++k) for (int j = 0; j < 3; ++j) {
+            const double v = tris[i].v[3 * k + j];
+            lo[j] = min_d(lo[j], v); hi[j] = max_d(hi[j], v);
+        }
+    } else {
+        const Node &l = nodes[n.a], &r = nodes[n.a + 1];
+        for (int j = 0; j < 3; ++j) { lo[j] = min_d(l.lo[j], r.lo[j]); hi[j] = max_d(l.hi[j], r.hi[j]); }
+    }
+    for (int j = 0; j < 3; ++j) { n.lo[j] = lo[j]; n.hi[j] = hi[j]; }
+}
+
 } // namespace admm_mesh

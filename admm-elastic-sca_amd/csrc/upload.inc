@@ -536,14 +536,25 @@ int upload_all(admm_hip_ctx *ctx) {
     HIPCHK(hipMemcpy(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice));
     if (!ctx->meshes.empty()) {      // mesh obstacles: BVH nodes, triangles, pseudo-normals, and the table of them the kernel reads
         std::vector<admm_mesh::MeshDev> md;
+        ctx->mesh_upd.clear();
         for (const admm_hip_mesh &M : ctx->meshes) {
             admm_mesh::MeshDev d{};
             admm_mesh::Node *nd; admm_mesh::Tri *tr; admm_mesh::Nrm *nr;
             TRY(upload(ctx, &nd, M.nodes)); TRY(upload(ctx, &tr, M.tris)); TRY(upload(ctx, &nr, M.nrm));
             d.nodes = nd; d.tris = tr; d.nrm = nr; d.n_nodes = (int)M.nodes.size(); d.n_tris = (int)M.tris.size();
             md.push_back(d);
+            // what admm_hip_update_collision_mesh needs (kernels_mesh.hpp): neither it nor step allocates
+            admm_hip_ctx::MeshUpdate u{};
+            u.nodes = nd; u.tris = tr; u.nrm = nr;
+            const size_t nt = M.tris.size();
+            TRY(dalloc(ctx, &u.verts, 3 * (size_t)M.nv)); TRY(dalloc(ctx, &u.fn, 3 * nt)); TRY(dalloc(ctx, &u.vn, 3 * (size_t)M.nv));
+            TRY(dalloc(ctx, &u.part, (nt + admm_mesh::VOL_CHUNK - 1) / admm_mesh::VOL_CHUNK));
+            TRY(upload(ctx, &u.cid, M.cid)); TRY(upload(ctx, &u.adj, M.adj)); TRY(upload(ctx, &u.inc_ptr, M.inc_ptr)); TRY(upload(ctx, &u.inc, M.inc));
+            TRY(upload(ctx, &u.lvl_nodes, M.lvl_nodes));
+            ctx->mesh_upd.push_back(u);
         }
         TRY(upload(ctx, &ctx->d_meshes, md));
+        TRY(dalloc(ctx, &ctx->d_mesh_chk, 1));
     }
     for (Explicit &E : ctx->explicits) {
         std::vector<int> pidx(E.idx.size());

@@ -254,10 +254,11 @@ public:
 // translated by `center`.  isColliding / projectOut evaluate the library's query on the host (admm_hip_mesh_query: +distance
 // inside, -distance outside; the closest point); as the list's ADMM_SHAPE_MESH entry the device runs the same code.  The mesh is
 // validated and its BVH built once here; System registers it with its context before initialize (once per distinct mesh).
-// Invalid meshes throw std::runtime_error with the library's message.
+// Invalid meshes throw std::runtime_error with the library's message.  set_vertices deforms it (the same topology, new positions:
+// admm_hip_mesh_set_vertices) and bumps `version`; System's step() hands a changed mesh to its context (admm_hip_update_collision_mesh).
 class CollisionMesh : public CollisionShape {
 public:
-    CollisionMesh(Vector3d shapeCenter, const std::vector<double> &verts, const std::vector<int> &tris) : CollisionShape(shapeCenter) {
+    CollisionMesh(Vector3d shapeCenter, const std::vector<double> &verts, const std::vector<int> &tris) : CollisionShape(shapeCenter), vertices(verts), version(0) {
         std::vector<int32_t> t(tris.begin(), tris.end());
         char err[512] = {0};
         admm_hip_mesh *m = nullptr;
@@ -265,10 +266,20 @@ public:
             throw std::runtime_error(std::string("CollisionMesh: ") + err);
         mesh = std::shared_ptr<admm_hip_mesh>(m, admm_hip_mesh_destroy);
     }
+    // new positions [nv][3] for the same triangles; a refused update throws std::runtime_error and leaves the mesh as it was
+    void set_vertices(const std::vector<double> &verts) {
+        char err[512] = {0};
+        if (admm_hip_mesh_set_vertices(mesh.get(), (int)(verts.size() / 3), verts.data(), err, (int)sizeof err) != ADMM_OK)
+            throw std::runtime_error(std::string("CollisionMesh::set_vertices: ") + err);
+        vertices = verts;
+        ++version;
+    }
     double isColliding(Vector3d pos) const { double pr[3], sd; query(pos, pr, sd); return sd; }
     Vector3d projectOut(const Vector3d currPos) const { double pr[3], sd; query(currPos, pr, sd); return Vector3d(pr[0], pr[1], pr[2]); }
     int shape_type() const { return typeid(*this) == typeid(CollisionMesh) ? ADMM_SHAPE_MESH : -1; }
     std::shared_ptr<admm_hip_mesh> mesh;
+    std::vector<double> vertices;          // the current positions
+    long version;                          // set_vertices calls so far
 private:
     void query(const Vector3d &p, double *pr, double &sd) const {
         const double t[3] = {center[0], center[1], center[2]}, q[3] = {p[0], p[1], p[2]};

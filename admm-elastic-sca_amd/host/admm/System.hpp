@@ -341,6 +341,7 @@ protected:
     bool initialized;
     admm_hip_ctx *gpu;
     std::vector<std::pair<const admm_hip_mesh *, int> > mesh_ids;      // CollisionMesh obstacles registered with the context -> their mesh_id
+    std::vector<long> mesh_versions;                                  // ... and the CollisionMesh::version the context last received
     std::vector<int> batch_first, batch_count, batch_kind;
     std::vector<char> batch_moving;
     std::vector<long> batch_urow0;         // generic batches: first of their rows among the user rows (-1 otherwise)
@@ -409,7 +410,7 @@ protected:
     void release() {
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
-        mesh_ids.clear();
+        mesh_ids.clear(); mesh_versions.clear();
         initialized = false;
     }
 
@@ -420,13 +421,18 @@ protected:
             ty.push_back(sh.shape_type());
             par.push_back(sh.center[0]); par.push_back(sh.center[1]); par.push_back(sh.center[2]);
             if (sh.shape_type() == ADMM_SHAPE_MESH) {      // a mesh: registered with the context once (before finalize), then named by its id
-                const admm_hip_mesh *m = static_cast<const CollisionMesh &>(sh).mesh.get();
+                const CollisionMesh &cm = static_cast<const CollisionMesh &>(sh);
+                const admm_hip_mesh *m = cm.mesh.get();
                 size_t k = 0;
                 while (k < mesh_ids.size() && mesh_ids[k].first != m) ++k;
                 if (k == mesh_ids.size()) {
                     int id = -1;
                     if (!check(admm_hip_add_collision_mesh(gpu, m, &id))) return false;
                     mesh_ids.push_back(std::make_pair(m, id));
+                    mesh_versions.push_back(cm.version);
+                } else if (mesh_versions[k] != cm.version) {      // deformed since the context last saw it (CollisionMesh::set_vertices)
+                    if (!check(admm_hip_update_collision_mesh(gpu, mesh_ids[k].second, (int)(cm.vertices.size() / 3), cm.vertices.data()))) return false;
+                    mesh_versions[k] = cm.version;
                 }
                 par.push_back((double)mesh_ids[k].second);
             } else {

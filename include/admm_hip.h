@@ -131,13 +131,30 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
  *                           The device's collision kernel runs the same code and gives the same bits.
  *   admm_hip_mesh_info      triangles, BVH nodes, BVH depth, root box [lo xyz, hi xyz]; any pointer may be NULL.
  *   admm_hip_add_collision_mesh  copy the mesh into a context (before finalize: ADMM_ERR_STATE after) -> *mesh_id; the mesh may be
- *                           destroyed afterwards.  Every rank of a sharded run registers the same meshes in the same order.        */
+ *                           destroyed afterwards.  Every rank of a sharded run registers the same meshes in the same order.
+ *   admm_hip_mesh_set_vertices   new positions verts [nv][3] for the same topology (nv = the count at creation): recomputes the face,
+ *                           edge and vertex pseudo-normals and refits the BVH's boxes; the tree itself (built on the creation vertices)
+ *                           stays, so a large deformation loosens the boxes and slows the query but never changes its result.
+ *                           Refused with ADMM_ERR_ARG, the mesh left exactly as it was, for a wrong nv, a non-finite vertex, a
+ *                           zero-area triangle (the lowest such original triangle named in err) or a non-positive enclosed volume.
+ *                           Self-intersection is not checked: keeping the deformed mesh free of it is the caller's job.
+ *                           The vertex normals' corner angles come from a libm-free acos (the same bits on the host and the device),
+ *                           so an update to the creation vertices gives bit-identical closest points; the inside / outside decision
+ *                           can differ from the freshly created mesh only where the pseudo-normal's dot product is within rounding of 0.
+ *   admm_hip_update_collision_mesh  the same for a context's registered mesh (mesh_id of admm_hip_add_collision_mesh), verts a host
+ *                           array [nv][3].  Before finalize it updates the context's copy; after it the update runs on the device, on
+ *                           the context's stream, synchronously, writing in place (captured graphs stay valid) with the same bits as
+ *                           admm_hip_mesh_set_vertices; a refused update (ADMM_ERR_ARG, admm_hip_last_error) leaves the live mesh
+ *                           intact.  Every rank of a sharded run applies the same updates: no collective is needed, and a refusal is
+ *                           the same on every rank.                                                                                 */
 typedef struct admm_hip_mesh admm_hip_mesh;
 int  admm_hip_mesh_create(admm_hip_mesh **out, int nv, const double *verts, int nt, const int32_t *tris, char *err, int err_len);
 void admm_hip_mesh_destroy(admm_hip_mesh *mesh);
 int  admm_hip_mesh_query(const admm_hip_mesh *mesh, const double t[3], int64_t n_pts, const double *pts, double *proj, double *sdist);
 int  admm_hip_mesh_info(const admm_hip_mesh *mesh, int *n_tris, int *n_nodes, int *depth, double *box);
 int  admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, int *mesh_id);
+int  admm_hip_mesh_set_vertices(admm_hip_mesh *mesh, int nv, const double *verts, char *err, int err_len);
+int  admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, const double *verts);
 
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
