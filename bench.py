@@ -20,9 +20,13 @@ element ranges, whole RHS all-reduced, whole solve replicated).  Fixed total wor
 "scaling": "strong".
 
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement)
-with the extra objects "roofline" (dominant kernel, measured live with HIP
-events on the kernel's own stream) and "cpu_baseline" (the compiled reference,
-or the oracle port, timed on this host's cores on a bounded sample).
+with the extra object "roofline" (dominant kernel, measured live with HIP
+events on the kernel's own stream).  A plain run does nothing else: set-up,
+warm-up, the timed steps, --dump-outputs, the line.  --full adds what takes
+runs of its own after the timed steps (N = 1): "cpu_baseline" (the compiled
+reference, or the oracle port, timed on this host's cores on a bounded sample,
+and the GPU on that same sample), "class_api" (the frame cost with m_x / m_v
+travelling) and "other_configs" (the other BASELINE configs).
 """
 import argparse
 import json
@@ -68,9 +72,10 @@ def parse():
                         "contiguous = element ranges, full RHS all-reduce, replicated solve")
     p.add_argument("--timing-stride", type=int, default=10, help="HIP events around every k-th ADMM iteration of the timed region (1 = every iteration, all launches eager); "
                    "measured on identical frames (tools/probe/event_overhead.py): event-free 0.685-0.688 ms per iteration, k = 20 / 10: 0.690-0.693, k = 4: 0.695-0.696, k = 1: 0.71")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="skip the class-API frame cost and the other BASELINE configs (N = 1 only)")
-    p.add_argument("--cpu-dims", type=int, nargs=3, default=[16, 16, 65], help="bounded CPU-baseline sample (cubes)")
+    p.add_argument("--full", action="store_true", help="after the headline, also measure the CPU baseline, the class-API frame cost and the other BASELINE configs (N = 1 only)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip the class-API frame cost and the other BASELINE configs")
+    p.add_argument("--cpu-dims", type=int, nargs=3, default=[16, 16, 65], help="with --full: bounded CPU-baseline sample (cubes)")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the last timed step computed -- positions x and velocities v, float64, one row per node -- "
                         "as DIR/<name>.npy (rank 0; above %d MB in all, a fixed seeded sample of the nodes, their indices in node_index.npy)" % (DUMP_MAX_BYTES // 1000000))
@@ -770,7 +775,7 @@ def main():
         out["per_rank_summary"] = {k: {"slowest": max(out["per_rank"][k]), "fastest": min(out["per_rank"][k])} for k in keys}
         out["rccl_ranks_seen"] = ranks_seen              # head count from a checked all-reduce through the path config.allreduce names
         out["ranks_ok"] = bool(ranks_seen == a.gpus == world)
-    if rank == 0 and world == 1 and fake_world <= 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and fake_world <= 1 and not a.no_extras:
         # what an existing scene pays per frame through the class API (host/admm/System.hpp step(): m_x / m_v are public, so they
         # travel every frame): the same C-ABI sequence, upload_state -> step -> download_state, on page-locked vectors
         s.enable_timing(False)
@@ -821,7 +826,7 @@ def main():
                             "same_frames_both_ways": same}
         out["other_configs"] = other_configs(pkg, torch, a.steps)
     if rank == 0:
-        if not a.no_cpu_baseline and world == 1:   # the CPU baseline is a rank-0, N=1 side figure
+        if a.full and not a.no_cpu_baseline and world == 1:   # the CPU baseline is a rank-0, N=1 side figure
             try:
                 out["cpu_baseline"] = cpu_baseline(a.cpu_dims)
                 try:      # the like-for-like pair: the GPU on the CPU leg's own sample and frames (ms per ADMM iteration side by side; no ratio to the headline size)

@@ -68,6 +68,37 @@ def test_bench_dump_outputs_repeat_exactly(pkg, tmp_path):
     assert np.array_equal(dumps[0]["x"], dumps[1]["x"]) and np.array_equal(dumps[0]["v"], dumps[1]["v"])
 
 
+def test_side_figures_are_opt_in(monkeypatch):
+    """A plain run measures the headline only; the CPU baseline, the class-API frame cost and the other configs wait for --full."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_the_side_figures_after_the_same_steps(pkg):
+    """The plain line holds no side figures; --full adds cpu_baseline (with the GPU on its sample), class_api and other_configs,
+    and its headline comes from the same timed steps: the same positions, the same schema."""
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--dims", "8", "8", "40"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--cpu-dims", "4", "4", "12"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[mode] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    side = {"cpu_baseline", "class_api", "other_configs"}
+    assert not side & set(plain) and side <= set(full)
+    assert set(full) - side == set(plain)
+    cb = full["cpu_baseline"]
+    assert cb["kind"] in ("reference", "port") and cb["value"] > 0 and cb["gpu_same_sample"]["ms_per_iter"] > 0
+    assert full["class_api"]["ms_per_step"] > 0 and "error" not in full["other_configs"] and len(full["other_configs"]) == 3
+    assert plain["config"]["x_checksum"] == full["config"]["x_checksum"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+
+
 def test_up_to_date_build_writes_nothing(pkg, monkeypatch):
     """lib() calls build() on every load: with the library up to date that call must not write (no lock file, no directory),
     so that a process without write access to the tree can load it."""

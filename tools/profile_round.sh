@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 bash tools/pmc_collect.sh > $O/pmc_collect.log 2>&1
 mkdir -p profiles/$R && cp gpurun_out/pmc_1M.json profiles/$R/pmc_1M.json && cp gpurun_out/pmc_1M.json $O/pmc_1M.json
 # 2. the bench line
-ADMM_BENCH_PMC=$R/pmc_1M.json python bench.py > $O/bench_1M.json 2> $O/bench_1M.err
+ADMM_BENCH_PMC=$R/pmc_1M.json python bench.py --full > $O/bench_1M.json 2> $O/bench_1M.err
 tail -1 $O/bench_1M.json | cut -c1-300
 # 3. the same command under rocprofv3 --kernel-trace --stats
 rm -rf /tmp/prof_stats
