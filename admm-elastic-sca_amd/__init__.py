@@ -94,6 +94,7 @@ def lib():
         L.admm_hip_set_shard_mode.argtypes = [C.c_void_p, C.c_int]
         L.admm_hip_set_factor_local.argtypes = [C.c_void_p, C.c_int]
         L.admm_hip_debug_node_owner.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.admm_hip_debug_node_supernode.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.admm_hip_local_elements.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_enable_residuals.argtypes = [C.c_void_p, C.c_int]
         L.admm_hip_set_tolerance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int]
@@ -478,6 +479,13 @@ class System:
         self._chk(self.L.admm_hip_debug_node_owner(self.h, _i(o)))
         return o
 
+    def node_supernode(self):
+        """-> (supernode of each node's column, the column's place inside it, every supernode's parent (-1: a root))"""
+        sn = np.zeros(self.n_nodes, np.int32); col = np.zeros(self.n_nodes, np.int32)
+        par = np.zeros(max(1, self.info()["n_supernodes"]), np.int32)
+        self._chk(self.L.admm_hip_debug_node_supernode(self.h, _i(sn), _i(col), _i(par)))
+        return sn, col, par[:self.info()["n_supernodes"]]
+
     def set_shard_mode(self, mode):
         self._chk(self.L.admm_hip_set_shard_mode(self.h, SHARD[mode] if isinstance(mode, str) else int(mode)))
 
@@ -578,27 +586,61 @@ class System:
         return t.as_dict()
 
 
-def initialize_together(systems, timeout=3600.0):
-    """initialize() of several ranks' contexts living in ONE process (tests, tools/ranks_one_gpu.py), each from its own thread:
-    under rank-local factorization (subtree shards, the default) admm_hip_finalize is a collective call -- the ranks meet in the
-    all-reduce of the subtree roots' update matrices -- exactly like System::initialize() of N real processes."""
-    import threading
-    errs = []
+class RankErrors(AdmmHipError):
+    """A collective call of several ranks' contexts (call_together) failed on at least one rank.  errors[r]: rank r's exception,
+    None where the call returned, an AdmmHipError "still inside" where it had not returned when call_together gave up."""
 
-    def run(s):
+    def __init__(self, call, errors):
+        self.errors = errors
+        super().__init__("%s: %s" % (call, "; ".join("rank %d %s" % (r, "returned OK" if e is None else "raised: %s" % e)
+                                                     for r, e in enumerate(errors))))
+
+
+def call_together(systems, call, timeout=3600.0, grace=30.0):
+    """systems[r].<call>() of several ranks' contexts living in ONE process, each from its own thread -- for the collective calls
+    (initialize / recompute_weights under rank-local factorization), where every rank must be inside the call at the same time.
+    Returns when every rank has returned.  ONE deadline, `timeout` seconds from the start, covers all ranks; once a rank has raised,
+    the others get at most `grace` more seconds to come out.  Any failure raises RankErrors carrying every rank's outcome."""
+    import threading
+    import time
+    n = len(systems)
+    errors, done, first_fail = [None] * n, [False] * n, []
+    cv = threading.Condition()
+
+    def run(r):
         try:
-            s.initialize()
+            getattr(systems[r], call)()
         except BaseException as e:  # noqa: BLE001
-            errs.append(e)
-    th = [threading.Thread(target=run, args=(s,), daemon=True) for s in systems]
+            errors[r] = e
+        with cv:
+            done[r] = True
+            if errors[r] is not None and not first_fail:
+                first_fail.append(time.monotonic())
+            cv.notify_all()
+    th = [threading.Thread(target=run, args=(r,), daemon=True) for r in range(n)]
+    deadline = time.monotonic() + timeout
     for t in th:
         t.start()
-    for t in th:
-        t.join(timeout)
-    if errs:
-        raise errs[0]
-    if any(t.is_alive() for t in th):
-        raise AdmmHipError("initialize_together: a rank is still inside initialize() after %g s" % timeout)
+    with cv:
+        while not all(done):
+            end = min(deadline, first_fail[0] + grace) if first_fail else deadline
+            left = end - time.monotonic()
+            if left <= 0:
+                break
+            cv.wait(left)
+        hung = [r for r in range(n) if not done[r]]
+        out = list(errors)
+    for r in hung:
+        out[r] = AdmmHipError("still inside %s() %s" % (call, "%g s after another rank failed" % grace if first_fail else "after %g s" % timeout))
+    if any(e is not None for e in out):
+        raise RankErrors(call, out)
+
+
+def initialize_together(systems, timeout=3600.0, grace=30.0):
+    """initialize() of several ranks' contexts living in ONE process (tests, tools/ranks_one_gpu.py), each from its own thread:
+    under rank-local factorization (subtree shards, the default) admm_hip_finalize is a collective call -- the ranks meet in the
+    all-reduce of the subtree roots' update matrices -- exactly like System::initialize() of N real processes.  See call_together."""
+    call_together(systems, "initialize", timeout, grace)
 
 
 def make_bar_system(nx, ny, nz, kind=KIND["TET_NH"], mu=1e5, lam=1e5, max_iter=5, density=1000.0, h=0.05, dt=0.04,

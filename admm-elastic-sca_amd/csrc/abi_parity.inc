@@ -81,7 +81,7 @@ int admm_hip_keep_z(admm_hip_ctx *ctx, int on) {
 namespace { struct KeepZ { admm_hip_ctx *c; bool old; explicit KeepZ(admm_hip_ctx *c_) : c(c_), old(c_->keep_z) { c->keep_z = true; } ~KeepZ() { c->keep_z = old; } }; }
 
 int admm_hip_local_step_only(admm_hip_ctx *ctx, const double *x_cur) {
-    TRY(require_device(ctx));
+    TRY(require_factor(ctx));
     if (!x_cur) return ADMM_ERR_ARG;
     KeepZ kz(ctx);
     TRY(set_nodes(ctx, ctx->d_xcur, x_cur));
@@ -97,7 +97,7 @@ int admm_hip_local_step_only(admm_hip_ctx *ctx, const double *x_cur) {
 // caller-supplied D_i x rows (element-major [n_local][rows]) instead of the
 // gather from x -- replays the reference's recorded (Dx,u,state)->(u,z,state) tuples.
 int admm_hip_local_step_dx(admm_hip_ctx *ctx, int batch, const double *dx) {
-    TRY(require_device(ctx));
+    TRY(require_factor(ctx));
     if (batch < 0 || batch >= (int)ctx->batches.size() || !dx) return ADMM_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device_id));
     Batch &b = ctx->batches[batch];
@@ -119,7 +119,7 @@ int admm_hip_local_step_dx(admm_hip_ctx *ctx, int batch, const double *dx) {
 }
 
 int admm_hip_solve_only(admm_hip_ctx *ctx, const double *b, double *x) {
-    TRY(require_device(ctx));
+    TRY(require_factor(ctx));
     if (!b || !x) return ADMM_ERR_ARG;
     TRY(set_nodes(ctx, ctx->d_y, b));
     if (!ctx->levels_top.empty())   // subtree sharding sums the top rows over the ranks: every rank was handed the whole b, keep it once

@@ -277,6 +277,19 @@ int admm_hip_debug_node_owner(admm_hip_ctx *ctx, int32_t *owner) {
     for (int i = 0; i < ctx->n_nodes; ++i) owner[i] = (ctx->shard_mode == ADMM_SHARD_SUBTREE && ctx->world > 1) ? ctx->node_owner[ctx->F.iperm[i]] : 0;
     return ADMM_OK;
 }
+int admm_hip_debug_node_supernode(admm_hip_ctx *ctx, int32_t *supernode, int32_t *column, int32_t *parent) {
+    if (!ctx || !ctx->finalized) return ADMM_ERR_ARG;
+    const Factor &F = ctx->F;
+    for (int s = 0; s < (int)F.sn.size(); ++s) {
+        if (parent) parent[s] = F.sn[s].parent;
+        for (int j = 0; j < F.sn[s].ncols; ++j) {
+            const int i = F.perm[F.sn[s].first + j];
+            if (supernode) supernode[i] = s;
+            if (column) column[i] = j;
+        }
+    }
+    return ADMM_OK;
+}
 #ifdef ADMM_TET_TIMELINE
 // wave timeline of the NEXT tet launches (the buffer is overwritten by every launch: read it after the one of interest)
 static unsigned long long *g_wave_t_buf; static size_t g_wave_t_n;

@@ -10,8 +10,7 @@ int admm_hip_set_weights(admm_hip_ctx *ctx, int batch, const double *weights) {
     return ADMM_OK;
 }
 
-int admm_hip_recompute_weights(admm_hip_ctx *ctx) {
-    if (!ctx || !ctx->finalized) return ADMM_ERR_STATE;
+static int recompute_weights(admm_hip_ctx *ctx) {
     TRY(host_assemble(ctx, true));
     TRY(host_factor(ctx, true));
     if (ctx->device_id >= 0) {
@@ -37,6 +36,16 @@ int admm_hip_recompute_weights(admm_hip_ctx *ctx) {
         }
     }
     return ADMM_OK;
+}
+
+// a failure part-way leaves the panels (device: pivots replaced by 1.0), A^-1 or the weights of a half-done factorization: the factor stays
+// marked invalid -- the steps refuse (require_factor) -- until a recompute_weights succeeds
+int admm_hip_recompute_weights(admm_hip_ctx *ctx) {
+    if (!ctx || !ctx->finalized) return ADMM_ERR_STATE;
+    const int rc = recompute_weights(ctx);
+    ctx->factor_invalid = rc != ADMM_OK;
+    ctx->factor_error = rc ? ctx->err : std::string();
+    return rc;
 }
 
 int admm_hip_update_anchors(admm_hip_ctx *ctx, int batch, const double *targets, const int32_t *active) {
@@ -71,7 +80,7 @@ static int mark(admm_hip_ctx *ctx, bool on = true) {
 }
 
 int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
-    TRY(require_device(ctx));
+    TRY(require_factor(ctx));
     using namespace admm_dev;
     HIPCHK(hipSetDevice(ctx->device_id));
     const int n3 = 3 * ctx->n_nodes;

@@ -110,6 +110,9 @@ struct admm_hip_ctx {
     double *h_comm = nullptr; size_t h_comm_cap = 0;          // its pinned staging
     double *d_small = nullptr; size_t d_small_cap = 0;        // admm_hip_allreduce_host's device scratch
     bool finalized = false;
+    // a recompute_weights that failed (not positive definite, HIP error) leaves no usable factor: step / solve_only / local_step_* refuse
+    // with ADMM_ERR_STATE and factor_error until a later recompute_weights succeeds (require_factor)
+    bool factor_invalid = false; std::string factor_error;
     int leaf_size = 0;                        // nested-dissection leaf size; 0 = by system size (host_factor)
     // host state
     int n_nodes = 0;

@@ -19,6 +19,8 @@
 //            Distributed top (ctx->dist_top): the top is ONE root supernode; its front and L^-1 (k^2 doubles each) are temporaries of this
 //            phase, what stays on the device is this rank's rows [root_r0, root_r1) of (L L^T)^-1 (gemm with K_FROM_MAX + koff).
 // The own subtrees' fronts are freed before the top's are allocated (peak = the larger phase).  The call is collective in this mode (admm_hip_finalize / admm_hip_recompute_weights: see admm_hip_set_factor_local).
+//   outcome  one more all-reduce of `world` doubles, which every rank reaches whatever its phases did: every rank returns the same code and,
+//            for a matrix that is not positive definite, names the same supernode (a non-positive pivot in one rank's subtrees is not only its own).
 constexpr int ADMM_DEVFACTOR_NOFIT = 1000;
 // contexts of ONE process that share a device (the N-ranks-on-one-GPU tests and tools) factor their own subtrees one after the other: a rank's
 // fronts are the memory peak of its initialize, and they are gone again before the next rank's arrive.  One context per process: never contended.
@@ -51,18 +53,18 @@ int device_factorize(admm_hip_ctx *ctx) {
     const int64_t root_tmp = ctx->dist_top ? (int64_t)ctx->root_k * ctx->root_k : 0;      // distributed top: the root's L^-1, a temporary next to its front
     int nofit = ((double)(std::max(ftot_own, ftot_top + root_tmp) + xtot) * 8.0 + side_b > 0.8 * (double)free_b) ? 1 : 0;
     if (nofit && !local) return ADMM_DEVFACTOR_NOFIT;
-    double *d_xbuf = nullptr, *d_aval = nullptr; int *d_rel = nullptr, *d_fail = nullptr;
-    auto cleanup = [&]() { for (void *p : {(void *)d_xbuf, (void *)d_aval, (void *)d_rel, (void *)d_fail}) if (p) (void)hipFree(p); };
+    double *d_xbuf = nullptr, *d_aval = nullptr, *d_cons = nullptr; int *d_rel = nullptr, *d_fail = nullptr;
+    auto cleanup = [&]() { for (void *p : {(void *)d_xbuf, (void *)d_aval, (void *)d_cons, (void *)d_rel, (void *)d_fail}) if (p) (void)hipFree(p); };
+    const int world = ctx->world;
     if (local) {
         if (!nofit && xtot && hipMalloc(&d_xbuf, sizeof(double) * xtot) != hipSuccess) { (void)hipGetLastError(); d_xbuf = nullptr; nofit = 1; }
         // "does not fit" must be every rank's decision or nobody's: the ranks meet in a collective further down.  One more tiny all-reduce
-        // (through the same transport) makes it a consensus.
-        double h_flag = (double)nofit, *d_flag = nullptr;
-        if (hipMalloc(&d_flag, sizeof(double)) != hipSuccess) { cleanup(); (void)hipGetLastError(); return fail(ctx, ADMM_ERR_HIP, "device factorization: no memory for the consensus flag"); }
-        int rc = hipMemcpyAsync(d_flag, &h_flag, sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess ? ADMM_OK : ADMM_ERR_HIP;
-        if (!rc) rc = do_allreduce(ctx, d_flag, 1);
-        if (!rc) rc = (hipMemcpyAsync(&h_flag, d_flag, sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) ? ADMM_OK : ADMM_ERR_HIP;
-        (void)hipFree(d_flag);
+        // (through the same transport) makes it a consensus.  d_cons: [0] this flag, [1, 1 + world) every rank's outcome (the consensus at the end)
+        double h_flag = (double)nofit;
+        if (hipMalloc(&d_cons, sizeof(double) * (1 + world)) != hipSuccess) { cleanup(); (void)hipGetLastError(); return fail(ctx, ADMM_ERR_HIP, "device factorization: no memory for the consensus flag"); }
+        int rc = hipMemcpyAsync(d_cons, &h_flag, sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess ? ADMM_OK : ADMM_ERR_HIP;
+        if (!rc) rc = do_allreduce(ctx, d_cons, 1);
+        if (!rc) rc = (hipMemcpyAsync(&h_flag, d_cons, sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) ? ADMM_OK : ADMM_ERR_HIP;
         if (rc) { cleanup(); return rc == ADMM_ERR_HIP ? fail(ctx, ADMM_ERR_HIP, "device factorization: consensus all-reduce failed") : rc; }
         if (h_flag > 0.0) nofit = 1;
     }
@@ -314,17 +316,26 @@ int device_factorize(admm_hip_ctx *ctx) {
     };
 
     double t_exchange = 0.0;
-    int rc = ADMM_OK;
-    if (!local) rc = phase([](int) { return true; }, ftot_own, false);
-    else {
+    int rc = ADMM_OK, failed = 0;
+    if (!local) {
+        rc = phase([](int) { return true; }, ftot_own, false);
+        if (rc) { cleanup(); return rc; }
+        DF_CHK(hipMemcpyAsync(&failed, d_fail, sizeof(int), hipMemcpyDeviceToHost, st));
+        DF_CHK(hipStreamSynchronize(st));
+    } else {
+        // From here on every rank reaches both collectives whatever happens on it: a rank that returned early would leave the others
+        // waiting in the exchange or in the consensus.  A rank whose own phase failed contributes what its buffer holds and skips the top.
         {
             std::lock_guard<std::mutex> one_rank_at_a_time(g_own_fronts_mutex);
             rc = phase(is_mine, ftot_own, true);
         }
-        if (!rc && xtot) {      // the ONE collective of this factorization
+        if (xtot) {      // the ONE collective of this factorization
             const double tx = now_s();
             // (in pieces of at most 2^27 doubles = 1 GB: a host-staged transport allocates its pinned buffer by the largest call)
-            for (int64_t off = 0; off < xtot && !rc; off += (int64_t)1 << 27) rc = do_allreduce(ctx, d_xbuf + off, std::min<int64_t>((int64_t)1 << 27, xtot - off));
+            for (int64_t off = 0; off < xtot; off += (int64_t)1 << 27) {
+                const int xrc = do_allreduce(ctx, d_xbuf + off, std::min<int64_t>((int64_t)1 << 27, xtot - off));
+                if (!rc) rc = xrc;
+            }
             if (!rc && verbose) { (void)hipStreamSynchronize(st); t_exchange = now_s() - tx; }
         }
         if (!rc) {      // (distributed top: the root's front and L^-1 are k^2 doubles each -- contexts sharing a device take turns here too)
@@ -332,11 +343,28 @@ int device_factorize(admm_hip_ctx *ctx) {
             if (ctx->dist_top) one_rank_at_a_time.lock();
             rc = phase(is_top, ftot_top, false);
         }
+        if (!rc && (hipMemcpyAsync(&failed, d_fail, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+            rc = fail(ctx, ADMM_ERR_HIP, "device factorization: reading the pivot flag failed");
+        // the consensus: every rank's outcome (-error code, or the first failing supernode + 1, or 0) in its own slot of ONE all-reduce of `world`
+        // doubles.  Every rank then returns the same: the error of the lowest rank that had one (a rank keeps an error of its own), else
+        // ADMM_ERR_FACTOR naming the lowest-numbered failing supernode -- a descendant's number is lower than its ancestors', so that is the
+        // failure no other one caused (what the host factorization reports)
+        std::vector<double> outcome(world, 0.0);
+        outcome[me] = rc ? -(double)rc : (double)failed;
+        int crc = hipMemcpyAsync(d_cons + 1, outcome.data(), sizeof(double) * world, hipMemcpyHostToDevice, st) == hipSuccess ? ADMM_OK : ADMM_ERR_HIP;
+        { const int arc = do_allreduce(ctx, d_cons + 1, world); if (!crc) crc = arc; }
+        if (!crc && (hipMemcpyAsync(outcome.data(), d_cons + 1, sizeof(double) * world, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) crc = ADMM_ERR_HIP;
+        if (crc && !rc) rc = crc == ADMM_ERR_HIP ? fail(ctx, ADMM_ERR_HIP, "device factorization: the outcome consensus failed") : crc;
+        if (!crc) {
+            int bad_rank = -1; failed = 0;
+            for (int r = 0; r < world; ++r) {
+                if (outcome[r] < 0.0) { if (bad_rank < 0) bad_rank = r; }
+                else if (outcome[r] > 0.0) failed = failed ? std::min(failed, (int)outcome[r]) : (int)outcome[r];
+            }
+            if (bad_rank >= 0 && !rc) rc = fail(ctx, (int)-outcome[bad_rank], "device factorization failed on rank %d of %d (error %d)", bad_rank, world, (int)-outcome[bad_rank]);
+        }
+        if (rc) { cleanup(); return rc; }
     }
-    if (rc) { cleanup(); return rc; }
-    int failed = 0;
-    DF_CHK(hipMemcpyAsync(&failed, d_fail, sizeof(int), hipMemcpyDeviceToHost, st));
-    DF_CHK(hipStreamSynchronize(st));
 #undef DF_CHK
     cleanup();
     F.panels.clear(); F.panels.shrink_to_fit();

@@ -341,9 +341,9 @@ static void do_front(Numeric &N, int s, std::vector<int> &loc, int threads) {
     for (int j = 0; j < k; ++j) loc[S.first + j] = -1;
     for (int q = 0; q < r; ++q) loc[rows[q]] = -1;
     int err = partial_cholesky(f, k, Fm, f, threads);
-    if (err) {
-#pragma omp atomic write
-        N.fail = s + 1;
+    if (err) {      // the lowest-numbered failing supernode: a descendant's number is lower than its ancestors', so never one a failure below caused
+#pragma omp critical(admm_factor_fail)
+        if (!N.fail || s + 1 < N.fail) N.fail = s + 1;
     }
     // panel = [L11^-1 ; L21 L11^-1]
     double *P = N.panels->data() + S.panel_off;

@@ -76,8 +76,8 @@ void plan_panels(Factor &F);
 // A permuted into factor order (lower CSC).  with_source: val[q] = index of the entry of A it came from (as a double) instead of its value.
 void permuted_lower(const SymCSC &A, const Factor &F, SymCSC &PA, bool with_source);
 
-// Multifrontal numeric factorization; fills F.panels.  Returns 0 or a
-// non-zero code when A is not positive definite.
+// Multifrontal numeric factorization; fills F.panels.  Returns 0, or when A is not
+// positive definite 1 + the lowest-numbered supernode whose pivot is not positive.
 int factorize(const SymCSC &A, Factor &F, int threads);
 
 // CPU evaluation of the two sweeps on the panel form (used by the CPU tests to

@@ -431,3 +431,9 @@ int require_device(admm_hip_ctx *ctx) {
     if (!ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "admm_hip_finalize has not been called");
     return ADMM_OK;
 }
+
+int require_factor(admm_hip_ctx *ctx) {
+    TRY(require_device(ctx));
+    if (ctx->factor_invalid) return fail(ctx, ADMM_ERR_STATE, "no valid factorization: the last recompute_weights failed (%s); a recompute_weights that succeeds restores it", ctx->factor_error.c_str());
+    return ADMM_OK;
+}

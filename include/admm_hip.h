@@ -210,6 +210,10 @@ int admm_hip_set_shard_mode(admm_hip_ctx *ctx, int mode);
 int admm_hip_local_elements(admm_hip_ctx *ctx, int batch, int32_t *ids, int capacity, int *n_local);
 /* test hook: the rank that owns each node's subtree (original node order), -1 = replicated top; 0 everywhere without subtree sharding */
 int admm_hip_debug_node_owner(admm_hip_ctx *ctx, int32_t *owner);
+/* test hook: the supernode that holds each node's column (original node order; the number admm_hip_last_error names for a pivot that
+ * is not positive), the node's column inside it (0 = the supernode's first) and every supernode's parent ([admm_hip_info.n_supernodes],
+ * -1 = a root); any array may be NULL */
+int admm_hip_debug_node_supernode(admm_hip_ctx *ctx, int32_t *supernode, int32_t *column, int32_t *parent);
 
 /* ---- initialize -----------------------------------------------------------
  * replaces: System::initialize()                          (System.cpp:98-156)
@@ -222,7 +226,11 @@ int admm_hip_finalize(admm_hip_ctx *ctx);
  * elimination-tree level whose dependent latencies dominate at this size (the reference's shipped scenes have 777-1251 nodes). */
 
 /* replaces: System::recompute_weights()                   (System.cpp:159-179)
- * after admm_hip_set_weights changed per-element weights: re-assemble, re-factor, re-upload. */
+ * after admm_hip_set_weights changed per-element weights: re-assemble, re-factor, re-upload.
+ * A failure (ADMM_ERR_FACTOR "system matrix is not positive definite (supernode s)" for weights that make A_s indefinite or NaN, or an
+ * error of the device) leaves no usable factor: admm_hip_step, admm_hip_solve_only, admm_hip_local_step_only and admm_hip_local_step_dx
+ * then return ADMM_ERR_STATE, naming that failure, until a later admm_hip_recompute_weights succeeds.  Under rank-local factorization
+ * every rank returns the same code and names the same supernode (admm_hip_set_factor_local); so does admm_hip_finalize. */
 /* weights: [n_elems] (a generic batch: [n_rows], one per selector row as get_selector pushes them) */
 int admm_hip_set_weights(admm_hip_ctx *ctx, int batch, const double *weights);
 int admm_hip_recompute_weights(admm_hip_ctx *ctx);
