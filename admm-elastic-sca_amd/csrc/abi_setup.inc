@@ -351,6 +351,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     partition_subtrees(ctx);
     plan_device_panels(ctx);
     assign_elements(ctx);
+    TRY(check_split_elements(ctx));
     shard_accounting(ctx);
     if (ctx->device_id >= 0) TRY(upload_all(ctx));
     ctx->finalized = true;

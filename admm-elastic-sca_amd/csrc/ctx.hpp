@@ -278,6 +278,7 @@ void element_G(int kind, const double *rest, double G[4][3], int &cols);
 int idx_stride(int kind);
 void partition_subtrees(admm_hip_ctx *ctx);                                                        // partition.cpp
 void assign_elements(admm_hip_ctx *ctx);
+int check_split_elements(admm_hip_ctx *ctx);
 void top_needs(const admm_hip_ctx *ctx, std::vector<std::vector<char> > &need, std::vector<int> &provider);
 void shard_accounting(admm_hip_ctx *ctx);
 void plan_device_panels(admm_hip_ctx *ctx);

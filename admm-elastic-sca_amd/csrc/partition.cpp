@@ -229,6 +229,34 @@ void assign_elements(admm_hip_ctx *ctx) {
     ctx->info.n_elems_local = nloc;
 }
 
+// Subtree sharding needs every element's nodes in ONE rank's subtree plus separators above it: per iteration only the top nodes'
+// partial right-hand sides and the subtree roots' contributions are exchanged, and x of the other ranks' subtrees is rebuilt once per
+// frame.  A built-in element couples all its nodes in A, so the nested dissection never splits it across subtrees; a user force
+// couples only the nodes that share one of its rows, and one element may reach into two ranks' subtrees (a CollisionForce with
+// user-written shapes is one element over every node).  Such a scene is refused.  Every rank computes the same partition, so every
+// rank refuses alike, before any collective.
+int check_split_elements(admm_hip_ctx *ctx) {
+    if (ctx->shard_mode != 1 || ctx->world <= 1) return ADMM_OK;
+    const Factor &F = ctx->F;
+    for (size_t bi = 0; bi < ctx->batches.size(); ++bi) {
+        const Batch &b = ctx->batches[bi];
+        if (b.kind != ADMM_KIND_GENERIC) continue;
+        for (int e = 0; e < b.n_total; ++e) {
+            const int32_t *nd; const int nn = b.elem_nodes(e, &nd);
+            int r0 = -1, n0 = -1;
+            for (int c = 0; c < nn; ++c) {
+                const int o = ctx->node_owner[F.iperm[nd[c]]];
+                if (o < 0) continue;
+                if (r0 < 0) { r0 = o; n0 = nd[c]; continue; }
+                if (o != r0)
+                    return fail(ctx, ADMM_ERR_UNSUPPORTED, "subtree sharding: element %d of generic batch %d has node %d in rank %d's subtree and node %d in rank %d's "
+                                "(its rows do not couple them, so the ordering may part them); shard this scene with ADMM_SHARD_CONTIGUOUS", e, (int)bi, n0, r0, nd[c], o);
+            }
+        }
+    }
+    return ADMM_OK;
+}
+
 // XCD-aware order of a level's work items.  Workgroups are dealt round-robin to the 8 XCDs (workgroup i -> XCD i mod 8), each
 // with its own L2: in plain order the tiles of ONE supernode land on all eight, and every L2 fetches that supernode's staged
 // vector (y, contribution lists, the children's contributions / x of its rows) from HBM again.  Here every supernode of a level

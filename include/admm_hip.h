@@ -198,7 +198,8 @@ int admm_hip_allreduce_host(admm_hip_ctx *ctx, double *host_buf, int64_t count);
  *   ADMM_SHARD_CONTIGUOUS  every batch is cut into `world` contiguous element ranges; per ADMM iteration the whole right-hand
  *                          side (3 n doubles) is all-reduced and every rank runs the complete solve.
  *   ADMM_SHARD_SUBTREE     the elimination tree is cut below its top: every rank owns whole subtrees and the elements touching
- *                          them (an element's nodes lie in one subtree plus separators above it); per iteration ONE small
+ *                          them (an element's nodes lie in one subtree plus separators above it: a user force whose nodes lie
+ *                          in two ranks' subtrees is refused at finalize with ADMM_ERR_UNSUPPORTED); per iteration ONE small
  *                          all-reduce carries the top separators' partial right-hand sides and the subtree roots' contributions,
  *                          only the top levels of the solve are replicated, and the full x is rebuilt once per frame.  With
  *                          2 / 4 / 8 / 16 ranks and >= 300k nodes (ADMM_HIP_DIST_TOP) the top is ONE root supernode whose product

@@ -1273,6 +1273,18 @@ static void spmv_D(const orc_system *s, const double *x, double *y) {
     }
 }
 
+/* System::recompute_weights: the weight diagonal from the forces' current weight members (row for row as get_selector pushed it),
+ * then A refactored; D, x, v, u and z are kept */
+int orc_recompute_weights(orc_system *s) {
+    if (!s->initialized) return 0;
+    for (int i = 0; i < s->n_forces; ++i) {
+        const orc_force *f = &s->forces[i];
+        const int end = i + 1 < s->n_forces ? s->forces[i + 1].global_idx : s->nW;
+        for (int r = f->global_idx; r < end; ++r) s->W[r] = f->weight;
+    }
+    return factorize(s);
+}
+
 /* System::step, CORE/System.cpp:26-75 */
 int orc_step(orc_system *s) {
     const int n = s->dof, R = s->nW; const double dt = s->dt;

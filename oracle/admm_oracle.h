@@ -78,6 +78,7 @@ void orc_set_explicit_dir(orc_system *s, int which, const double *dir);
 /* CollisionForce's shape table (CollisionForce.cpp:55-70) */
 void orc_set_collision_shapes(orc_system *s, int n, const int *types, const double *params);
 int  orc_initialize(orc_system *s);
+int  orc_recompute_weights(orc_system *s);   /* W from the forces' weight members, A refactored (System::recompute_weights) */
 int  orc_step(orc_system *s);
 /* Residual norms per ADMM iteration of the last orc_step, as the comment at CORE/System.cpp:64-65 defines them:
  * r = W (Dx - z) with the Dx the local step used, s = D^T W^T W (z - z_prev).  tol_r > 0: the ADMM loop of a

@@ -339,6 +339,7 @@ class Oracle(_Sys):
             lib.orc_track_residuals.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
             lib.orc_track_residuals.restype = None
             lib.orc_get_residuals.argtypes = [C.c_void_p, dp, dp, C.c_int]
+            lib.orc_recompute_weights.argtypes = [C.c_void_p]
             for n in ("settings", "set_layout", "add_gravity", "destroy", "get_D", "set_control_point", "svd3", "svd32", "add_explicit", "set_collision_shapes",
                       "oriented_svd", "force_construct", "force_initialize", "force_project"):
                 getattr(lib, "orc_" + n).restype = None
@@ -417,6 +418,12 @@ class Oracle(_Sys):
     def hyper_state(self, i):
         f = self.force(i)
         return np.array(list(f.state)), f.n_iters
+
+    def set_weights(self, w):
+        """every force's weight member (Force::weight), then System::recompute_weights"""
+        for i, wi in enumerate(np.asarray(w, dtype=np.float64)):
+            self.force(i).weight = float(wi)
+        assert self.lib.orc_recompute_weights(self.h) == 1
 
     def solve(self, b):
         """the oracle's LDL^T solve of the same 3n x 3n system (admm_oracle.c ldl_solve = SimplicialCholesky.h:153-177)"""
@@ -558,9 +565,36 @@ class SparseReference:
         W[np.repeat(self.gidx, nrows) + (np.arange(nrows.sum()) - np.repeat(np.cumsum(nrows) - nrows, nrows))] = np.repeat(w, nrows)
         return W
 
+    @classmethod
+    def from_selector(cls, D, W, m3, dt):
+        """the reference of a system given by explicit selector triplets instead of an oracle: D = (rows, cols, values) over len(W) rows
+        (duplicates summed), W the weight of every row, m3 the masses (3n).  with_weights needs an oracle's force layout and is not
+        available here; rhs() builds M x_bar + dt^2 D^T W^2 (z - u) in np.longdouble."""
+        import scipy.sparse as sp
+        ref = cls.__new__(cls)
+        ref.dt, ref.m3 = float(dt), np.asarray(m3, dtype=np.float64).ravel()
+        rr, cc, vv = (np.asarray(a) for a in D)
+        W = np.asarray(W, dtype=np.float64).ravel()
+        ref.n, ref.rows = ref.m3.size, W.size
+        ref.D = sp.csr_matrix((np.asarray(vv, dtype=np.float64), (rr, cc)), shape=(ref.rows, ref.n))
+        ref.D.sum_duplicates()
+        ref.kinds = ref.gidx = ref.w0 = None
+        ref._factor(W)
+        return ref
+
+    def rhs(self, m_xbar, q):
+        """M x_bar + dt^2 D^T W^2 q in np.longdouble (q = z - u, one entry per row; m_xbar may be longdouble)"""
+        D = self.D.tocoo()
+        ld = np.longdouble
+        t = self.W.astype(ld) ** 2 * np.asarray(q, dtype=ld)
+        b = np.zeros(self.n, dtype=ld)
+        np.add.at(b, D.col, D.data.astype(ld) * t[D.row])
+        return np.asarray(m_xbar, dtype=ld) + ld(self.dt) * ld(self.dt) * b
+
     def _factor(self, W):
         import scipy.sparse as sp
         import scipy.sparse.linalg as sla
+        self.W = np.asarray(W, dtype=np.float64)
         A = (sp.diags(self.m3) + (self.dt * self.dt) * (self.D.T @ sp.diags(W * W) @ self.D)).tocsr()
         A.sum_duplicates(); A.sort_indices()
         self.A = A
@@ -600,6 +634,29 @@ class SparseReference:
             raise AssertionError("iterative refinement did not converge in %d steps" % max_steps)
         xr = x.astype(np.float64)
         return xr, self.residual(xr, b), step
+
+
+def selector_rows(oracle, f0, f1, rng=None, split=0.0):
+    """the oracle's forces [f0, f1) restated as ONE generic batch (admm_hip_add_generic_batch): element e is force f0 + e, its rows
+    those of the force in the oracle's order.  -> (elem_row_ptr, trip_row, trip_col, trip_val, row_weight, oracle_rows), oracle_rows[r]
+    the oracle's row of batch row r.  With rng the triplets come shuffled and a fraction `split` of them as two halves (v/2 + v/2 is v
+    exactly: the summed entry is the oracle's bit for bit)."""
+    rr, cc, vv = oracle.D_triplets()
+    gi = oracle.global_idx()
+    nrows = np.array([KIND_ROWS[oracle.force(i).kind] for i in range(f0, f1)], np.int64)
+    erp = np.concatenate([[0], np.cumsum(nrows)])
+    orows = np.repeat(gi[f0:f1], nrows) + (np.arange(erp[-1]) - np.repeat(erp[:-1], nrows))
+    bat = np.full(oracle.rows, -1, np.int64)
+    bat[orows] = np.arange(orows.size)
+    sel = bat[rr] >= 0
+    tr, tc, tv = bat[rr[sel]], cc[sel].astype(np.int64), vv[sel]
+    if rng is not None:
+        half = rng.random(tr.size) < split
+        tr = np.concatenate([tr[~half], tr[half], tr[half]]); tc = np.concatenate([tc[~half], tc[half], tc[half]])
+        tv = np.concatenate([tv[~half], 0.5 * tv[half], 0.5 * tv[half]])
+        p = rng.permutation(tr.size)
+        tr, tc, tv = tr[p], tc[p], tv[p]
+    return erp.astype(np.int32), tr.astype(np.int32), tc.astype(np.int32), tv, oracle.wdiag[orows], orows
 
 
 def scene_reference(x, m3, forces, dt=0.04):
