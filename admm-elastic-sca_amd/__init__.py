@@ -153,6 +153,10 @@ def lib():
         L.admm_hip_add_collision_mesh.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.admm_hip_mesh_set_vertices.argtypes = [C.c_void_p, C.c_int, _dp, C.c_char_p, C.c_int]
         L.admm_hip_update_collision_mesh.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        L.admm_hip_add_body_surface.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_int)]
+        L.admm_hip_set_collision_mesh_owner.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.admm_hip_get_body_surface_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        L.admm_hip_collision_mesh_copy.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         _lib = L
     return _lib
 
@@ -169,8 +173,11 @@ class Mesh:
     """A closed triangle mesh prepared for collision queries (admm_hip_mesh_create): validated, pseudo-normals and BVH built.
     verts [nv][3] float64, tris [nt][3] int32, counter-clockwise seen from outside.  Invalid input raises AdmmHipError."""
 
-    def __init__(self, verts, tris):
+    def __init__(self, verts, tris=None):
         self.L = lib()
+        if isinstance(verts, C.c_void_p):      # an admm_hip_mesh handle this object takes over (System.collision_mesh)
+            self.h = verts
+            return
         v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
         t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
         h = C.c_void_p()
@@ -371,6 +378,30 @@ class System:
         """new vertex positions [nv][3] for a registered mesh (mesh_id of add_collision_mesh); after initialize on the device, in place"""
         v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
         self._chk(self.L.admm_hip_update_collision_mesh(self.h, int(mesh_id), v.shape[0], _d(v)))
+
+    def add_body_surface(self, node_first, node_count, tris):
+        """registers a body surface (before initialize): a closed mesh of simulated nodes, tris [nt][3] global node ids inside
+        [node_first, node_first + node_count), rebuilt from x at every step and ignored by its own nodes -> its mesh_id"""
+        t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        mid = C.c_int()
+        self._chk(self.L.admm_hip_add_body_surface(self.h, int(node_first), int(node_count), t.shape[0], _i(t), C.byref(mid)))
+        return mid.value
+
+    def set_collision_mesh_owner(self, mesh_id, node_first, node_count):
+        """the nodes [node_first, node_first + node_count) skip mesh mesh_id (before initialize; node_count 0 clears the owner)"""
+        self._chk(self.L.admm_hip_set_collision_mesh_owner(self.h, int(mesh_id), int(node_first), int(node_count)))
+
+    def body_surface_status(self, mesh_id):
+        """-> dict(updated, refused, last_bad_tri): the frame-start updates of a body surface so far (after initialize)"""
+        u, r, b = C.c_int64(), C.c_int64(), C.c_int()
+        self._chk(self.L.admm_hip_get_body_surface_status(self.h, int(mesh_id), C.byref(u), C.byref(r), C.byref(b)))
+        return dict(updated=u.value, refused=r.value, last_bad_tri=b.value)
+
+    def collision_mesh(self, mesh_id):
+        """a standalone Mesh copied from registered mesh mesh_id, as registered"""
+        h = C.c_void_p()
+        self._chk(self.L.admm_hip_collision_mesh_copy(self.h, int(mesh_id), C.byref(h)))
+        return Mesh(h)
 
     def set_gravity(self, which, g):
         self._chk(self.L.admm_hip_set_gravity(self.h, which, float(g[0]), float(g[1]), float(g[2])))

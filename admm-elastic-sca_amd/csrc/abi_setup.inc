@@ -198,6 +198,19 @@ int admm_hip_set_gravity(admm_hip_ctx *ctx, int which, double gx, double gy, dou
     if (ctx->explicit_simple) { double *g = ctx->grav.g[which]; g[0] = gx; g[1] = gy; g[2] = gz; }
     return ADMM_OK;
 }
+// a body surface sits where its nodes are: an entry that names one with a translation is refused (here when the surface is already
+// registered, at finalize otherwise)
+static int check_body_translations(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
+    for (int j = 0; j < n_shapes; ++j) {
+        if (types[j] != ADMM_SHAPE_MESH) continue;
+        const double *p = params + 4 * (size_t)j;
+        const int id = (int)p[3];
+        if (id >= 0 && id < (int)ctx->mesh_role.size() && !ctx->mesh_role[id].body_nodes.empty() && (p[0] != 0.0 || p[1] != 0.0 || p[2] != 0.0))
+            return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which follows its nodes: its translation must be 0 (have %g, %g, %g)",
+                        j, id, p[0], p[1], p[2]);
+    }
+    return ADMM_OK;
+}
 int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
     if (!ctx || n_shapes < 0 || (n_shapes && (!types || !params))) return ADMM_ERR_ARG;
     if (n_shapes > ADMM_MAX_SHAPES) return fail(ctx, ADMM_ERR_UNSUPPORTED, "at most %d collision shapes", ADMM_MAX_SHAPES);
@@ -207,6 +220,7 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
             if (!(id >= 0.0 && id < (double)ctx->meshes.size() && id == (double)(int)id))
                 return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh_id %g is not a registered mesh (have %d)", j, id, (int)ctx->meshes.size());
         }
+    TRY(check_body_translations(ctx, n_shapes, types, params));
     ctx->shapes.n = n_shapes;
     for (int j = 0; j < n_shapes; ++j) {
         if (types[j] < ADMM_SHAPE_FLOOR || types[j] > ADMM_SHAPE_MESH) return fail(ctx, ADMM_ERR_UNSUPPORTED, "collision shape type %d", types[j]);
@@ -226,8 +240,96 @@ int admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, in
     if (!ctx || !mesh || mesh->nodes.empty()) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision meshes must be registered before finalize");
     ctx->meshes.push_back(*mesh);
+    ctx->mesh_role.emplace_back();
     if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
     return ADMM_OK;
+}
+
+// owner ranges of two meshes may be equal or disjoint (one body tag per node)
+static int check_owner_range(admm_hip_ctx *ctx, int mesh_id, int first, int count) {
+    if (first < 0 || count < 1 || first > ctx->n_nodes - count)
+        return fail(ctx, ADMM_ERR_ARG, "node range [%d, %d) is not inside the %d nodes added so far", first, first + count, ctx->n_nodes);
+    for (size_t i = 0; i < ctx->mesh_role.size(); ++i) {
+        const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+        if ((int)i == mesh_id || !R.own_count || (R.own_first == first && R.own_count == count)) continue;
+        if (first < R.own_first + R.own_count && R.own_first < first + count)
+            return fail(ctx, ADMM_ERR_ARG, "node range [%d, %d) overlaps the owner range [%d, %d) of mesh %d without being equal to it", first, first + count,
+                        R.own_first, R.own_first + R.own_count, (int)i);
+    }
+    return ADMM_OK;
+}
+
+// extension, no reference counterpart (include/admm_hip.h): a closed surface of simulated nodes, rebuilt on the device from the frame-start
+// x at every step (launch.inc: update_bodies); owned by its node range
+int admm_hip_add_body_surface(admm_hip_ctx *ctx, int node_first, int node_count, int n_tris, const int32_t *tris, int *mesh_id) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "body surfaces must be registered before finalize");
+    if (n_tris < 1 || !tris) return fail(ctx, ADMM_ERR_ARG, "body surface: no triangles");
+    TRY(check_owner_range(ctx, -1, node_first, node_count));
+    std::vector<int> nodes(tris, tris + 3 * (size_t)n_tris);
+    for (size_t i = 0; i < nodes.size(); ++i)
+        if (nodes[i] < node_first || nodes[i] >= node_first + node_count)
+            return fail(ctx, ADMM_ERR_ARG, "body surface: triangle %d names node %d outside [%d, %d)", (int)(i / 3), nodes[i], node_first, node_first + node_count);
+    std::sort(nodes.begin(), nodes.end());
+    nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
+    std::vector<int> local((size_t)node_count, -1);
+    std::vector<double> verts(3 * nodes.size());
+    for (size_t k = 0; k < nodes.size(); ++k) {
+        local[nodes[k] - node_first] = (int)k;
+        for (int j = 0; j < 3; ++j) verts[3 * k + j] = ctx->x[3 * (size_t)nodes[k] + j];
+    }
+    std::vector<int32_t> lt(3 * (size_t)n_tris);
+    for (size_t i = 0; i < lt.size(); ++i) lt[i] = local[tris[i] - node_first];
+    admm_hip_mesh *M = nullptr;
+    char msg[512];
+    const int rc = admm_hip_mesh_create(&M, (int)nodes.size(), verts.data(), n_tris, lt.data(), msg, (int)sizeof msg);
+    if (rc) return fail(ctx, rc, "body surface: %s", msg);
+    ctx->meshes.push_back(*M);
+    admm_hip_mesh_destroy(M);
+    admm_hip_ctx::MeshRole R;
+    R.own_first = node_first; R.own_count = node_count; R.body_nodes = std::move(nodes);
+    ctx->mesh_role.push_back(std::move(R));
+    if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
+    return ADMM_OK;
+}
+
+int admm_hip_set_collision_mesh_owner(admm_hip_ctx *ctx, int mesh_id, int node_first, int node_count) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "mesh owners must be set before finalize");
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    admm_hip_ctx::MeshRole &R = ctx->mesh_role[mesh_id];
+    if (node_count == 0) { R.own_first = R.own_count = 0; return ADMM_OK; }
+    TRY(check_owner_range(ctx, mesh_id, node_first, node_count));
+    R.own_first = node_first; R.own_count = node_count;
+    return ADMM_OK;
+}
+
+int admm_hip_get_body_surface_status(admm_hip_ctx *ctx, int mesh_id, int64_t *updated, int64_t *refused, int *last_bad_tri) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (!ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "body surface status before finalize");
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size() || ctx->mesh_role[mesh_id].body_nodes.empty())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a body surface", mesh_id);
+    admm_mesh::BodyStatus st{0, 0, -1, 0};
+    if (ctx->device_id >= 0) {
+        HIPCHK(hipSetDevice(ctx->device_id));
+        HIPCHK(hipMemcpyAsync(&st, ctx->mesh_upd[mesh_id].status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    if (updated) *updated = st.updated;
+    if (refused) *refused = st.refused;
+    if (last_bad_tri) *last_bad_tri = st.last_bad_tri;
+    return ADMM_OK;
+}
+
+// a standalone copy of a context's registered mesh as registered (and as updated on the host: before finalize, host-only contexts)
+int admm_hip_collision_mesh_copy(admm_hip_ctx *ctx, int mesh_id, admm_hip_mesh **out) {
+    if (!ctx || !out) return ADMM_ERR_ARG;
+    *out = nullptr;
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    *out = new (std::nothrow) admm_hip_mesh(ctx->meshes[mesh_id]);
+    return *out ? ADMM_OK : fail(ctx, ADMM_ERR_ARG, "out of memory");
 }
 
 // before finalize (or in a host-only context) the context's copy takes admm_hip_mesh_set_vertices; after it the device arrays are
@@ -236,6 +338,8 @@ int admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, const
     if (!ctx) return ADMM_ERR_ARG;
     if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
         return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    if (!ctx->mesh_role[mesh_id].body_nodes.empty())
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a body surface, which follows its nodes: it takes no vertices from the caller", mesh_id);
     admm_hip_mesh &M = ctx->meshes[mesh_id];
     if (!ctx->finalized || ctx->device_id < 0) {
         char msg[512];
@@ -344,6 +448,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     for (const Explicit &E : ctx->explicits) for (int32_t v : E.idx) if (v >= ctx->n_nodes) return fail(ctx, ADMM_ERR_ARG, "explicit force references node %d (have %d)", v, ctx->n_nodes);
     if (const char *e = getenv("ADMM_HIP_SHARD")) ctx->shard_mode = (std::string(e) == "subtree") ? ADMM_SHARD_SUBTREE : ADMM_SHARD_CONTIGUOUS;
     if (const char *g = getenv("ADMM_HIP_FACTOR_LOCAL")) ctx->factor_local = atoi(g) != 0;      // (overrides admm_hip_set_factor_local; host_factor picks the tree by it)
+    TRY(check_body_translations(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
     TRY(host_assemble(ctx, false));
     TRY(host_factor(ctx, false));
     ctx->info.rank = ctx->rank; ctx->info.world = ctx->world;
@@ -353,6 +458,10 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     assign_elements(ctx);
     TRY(check_split_elements(ctx));
     shard_accounting(ctx);
+    // Body surfaces under sharding need the full frame-start x on every rank; every mode has it, so none is refused: contiguous shards
+    // all-reduce the whole right-hand side and solve the whole system on every rank, subtree shards (either top) rebuild the full x by
+    // the masked all-reduce before the velocity update (shard_sync_x), and a dense solve is not sharded.  Every rank registers the same
+    // surfaces and updates them from the same bits, so nothing of them goes over the collectives.
     if (ctx->device_id >= 0) TRY(upload_all(ctx));
     ctx->finalized = true;
     return ADMM_OK;

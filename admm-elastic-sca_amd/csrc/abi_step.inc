@@ -85,13 +85,14 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     HIPCHK(hipSetDevice(ctx->device_id));
     const int n3 = 3 * ctx->n_nodes;
     if (ctx->graphs_stale) { drop_iteration_graphs(ctx); ctx->graphs_stale = false; }      // the transport changed since the iteration was captured
-    // event layout (timing mode): E0 | prologue | E1 | per TIMED iteration: S local E rhs E allreduce E [exchange: E E] fwd E bwd E | Ea | epilogue | Eb
+    // event layout (timing mode): E0 | prologue (body surfaces' frame-start updates first) | E1 | per TIMED iteration: S local E rhs E allreduce E [exchange: E E] fwd E bwd E | Ea | epilogue | Eb
     if (ctx->timing) {      // the last step's events become "the previous step's" (still readable), the older set is recorded over
         ctx->evpool.swap(ctx->evpool_prev);
         ctx->ev_used_prev = ctx->ev_used; ctx->ev_iters_prev = ctx->ev_iters; ctx->ev_timed_prev = ctx->ev_timed; ctx->ev_pending_prev = ctx->ev_pending;
     } else ctx->ev_pending_prev = false;      // an untimed step: there is no timed "step before the last one" any more
     ctx->ev_used = 0; ctx->ev_iters = admm_iters; ctx->ev_timed = 0; ctx->ev_pending = ctx->timing;
     TRY(mark(ctx));
+    if (ctx->d_body_tag) TRY(update_bodies(ctx));      // body surfaces from the frame-start x, before the explicit forces (eager, outside the graphs)
     if (ctx->frames++ > 0)      // the blocks of the large tet batches by what they cost in the frame before
         for (const Batch &b : ctx->batches) if (b.n_blocks_ordered)
             hipLaunchKernelGGL(order_by_cost_kernel, dim3(1), dim3(1024), 0, ctx->stream, b.n_blocks_ordered, b.d_cost, b.d_order);

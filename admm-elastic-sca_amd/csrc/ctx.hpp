@@ -130,8 +130,16 @@ struct admm_hip_ctx {
         admm_mesh::Node *nodes; admm_mesh::Tri *tris; admm_mesh::Nrm *nrm;       // the live arrays (d_meshes points at them)
         double *verts, *fn, *vn, *part;                                          // staged vertices, face / vertex normals, volume partials
         int *cid, *adj, *inc_ptr, *inc, *lvl_nodes;                              // the topology (admm_hip_mesh)
+        // body surfaces only (else null): the device node id of every vertex, the surface's own check and its BodyStatus
+        int *dnode; admm_mesh::UpdateCheck *chk; admm_mesh::BodyStatus *status;
     };
     std::vector<MeshUpdate> mesh_upd; admm_mesh::UpdateCheck *d_mesh_chk = nullptr;
+    // what a mesh is to the scene, parallel to `meshes`: its owner, the node range [own_first, own_first + own_count) whose collision
+    // elements skip it (own_count 0: none; admm_hip_set_collision_mesh_owner), and for a body surface (admm_hip_add_body_surface) the
+    // node behind every vertex, ascending -- the device rebuilds it from them at every step (launch.inc: update_bodies)
+    struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; };
+    std::vector<MeshRole> mesh_role;
+    int *d_body_tag = nullptr;      // contexts with an owner: the owner group of every node in device order (-1: none), for MeshDev::owner
     SymCSC A;
     Factor F;
     admm_hip_info info{};

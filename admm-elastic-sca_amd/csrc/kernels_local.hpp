@@ -432,9 +432,10 @@ __device__ __forceinline__ void project_collision_block(const BatchDev &b, const
 
 // ... with closed triangle meshes in the list (ADMM_SHAPE_MESH, mesh_query.hpp): one lane per node as above, the analytic shapes through
 // collide_analytic, a mesh instance through a BVH traversal whose stack is the lane's column of an LDS array (no private array indexed at
-// run time).  A point on or outside the instance's root box cannot be inside the mesh and skips the traversal.
+// run time).  A point on or outside the instance's root box cannot be inside the mesh and skips the traversal.  tag (contexts with a mesh
+// owner only, else null): the body tag of every node in device order; a node skips every mesh its body owns (its own surface).
 __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_mesh_kernel(BatchDev b, const double *__restrict__ x, const ShapeTable *__restrict__ shapes,
-                                                                             const admm_mesh::MeshDev *__restrict__ meshes) {
+                                                                             const admm_mesh::MeshDev *__restrict__ meshes, const int *__restrict__ tag) {
     __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
     const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
     const int n = b.n;
@@ -451,10 +452,12 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_mesh_kernel(Bat
         p[j] = dx[j] + u[j];
     }
     struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
+    const int own = tag ? tag[id] : -1;
     const int ns = shapes->n;
     for (int q = 0; q < ns; ++q) {
         if (shapes->type[q] != ADMM_SHAPE_MESH) { collide_analytic(shapes, q, p); continue; }
         const admm_mesh::MeshDev m = meshes[(int)shapes->par[q][3]];
+        if (own >= 0 && m.owner == own) continue;
         const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
         const double qq[3] = {p[0] - t[0], p[1] - t[1], p[2] - t[2]};
         if (!admm_mesh::in_box(qq, m.nodes[0])) continue;

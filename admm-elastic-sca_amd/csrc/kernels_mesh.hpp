@@ -7,6 +7,11 @@
 //   commit  mesh_vertex_normal_kernel (one lane per vertex, its incidences in order), mesh_slot_kernel (one lane per leaf-order slot:
 //           corners and the seven pseudo-normals), then mesh_refit_kernel once per BVH level, deepest first: leaves from their
 //           triangles, internal nodes from their children.  One launch per level and no hand-off between workgroups.
+// A body surface (admm_hip_add_body_surface) runs the same stages at the start of every admm_hip_step (launch.inc: update_bodies),
+// eagerly and without a read-back: mesh_gather_kernel stages its vertices from the frame-start x (device node ids mapped at finalize),
+// mesh_volume_kernel takes the verdict on the device (update_refused, the predicate mesh_refusal uses) into the surface's BodyStatus,
+// counts the frame and re-arms the check, and the commit kernels read the gate and return at once after a refusal, so that the last
+// good surface stays.  The host-driven update passes no status and no gate and runs exactly as before.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mesh_query.hpp"
@@ -36,8 +41,18 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_check_kernel(int nt, int nv, 
     }
 }
 
-// one workgroup: the partials staged through LDS a block at a time (parallel loads), lane 0 adds them in order
-__global__ __launch_bounds__(MESH_BLOCK) void mesh_volume_kernel(int nchunk, const double *__restrict__ part, admm_mesh::UpdateCheck *chk) {
+// a body surface's vertices from the simulated nodes: verts[k] = x[dnode[k]] (dnode: device node ids, fixed at finalize)
+__global__ __launch_bounds__(MESH_BLOCK) void mesh_gather_kernel(int nv, const int *__restrict__ dnode, const double *__restrict__ x, double *__restrict__ verts) {
+    const int k = blockIdx.x * MESH_BLOCK + threadIdx.x;
+    if (k >= nv) return;
+    const double *p = x + 3 * (size_t)dnode[k];
+    verts[3 * (size_t)k] = p[0]; verts[3 * (size_t)k + 1] = p[1]; verts[3 * (size_t)k + 2] = p[2];
+}
+
+// one workgroup: the partials staged through LDS a block at a time (parallel loads), lane 0 adds them in order.  bs (body surfaces
+// only): lane 0 also takes the verdict, counts the frame, sets the commit kernels' gate and resets the check for the next frame
+__global__ __launch_bounds__(MESH_BLOCK) void mesh_volume_kernel(int nchunk, const double *__restrict__ part, admm_mesh::UpdateCheck *chk,
+                                                                admm_mesh::BodyStatus *bs) {
     __shared__ double buf[MESH_BLOCK];
     double acc = 0.0;
     for (int b = 0; b < nchunk; b += MESH_BLOCK) {
@@ -47,14 +62,24 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_volume_kernel(int nchunk, con
         if (threadIdx.x == 0) for (int k = 0; k < n; ++k) acc += buf[k];
         __syncthreads();
     }
-    if (threadIdx.x == 0) chk->vol6 = acc;
+    if (threadIdx.x == 0) {
+        chk->vol6 = acc;
+        if (bs) {
+            const admm_mesh::UpdateCheck c = *chk;
+            const bool bad = admm_mesh::update_refused(c);
+            bs->gate = bad ? 1 : 0;
+            if (bad) { bs->refused += 1; bs->last_bad_tri = c.bad_tri != admm_mesh::NO_TRI ? c.bad_tri : -1; }
+            else bs->updated += 1;
+            chk->bad_tri = admm_mesh::NO_TRI; chk->bad_vtx = admm_mesh::NO_TRI;
+        }
+    }
 }
 
 __global__ __launch_bounds__(MESH_BLOCK) void mesh_vertex_normal_kernel(int nv, const double *__restrict__ verts, const int *__restrict__ cid,
                                                                        const double *__restrict__ fn, const int *__restrict__ inc_ptr,
-                                                                       const int *__restrict__ inc, double *__restrict__ vn) {
+                                                                       const int *__restrict__ inc, double *__restrict__ vn, const int *gate) {
     const int v = blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (v >= nv) return;
+    if (v >= nv || (gate && *gate)) return;
     double o[3];
     admm_mesh::vertex_normal(verts, cid, fn, inc_ptr, inc, v, o);
     vn[3 * (size_t)v] = o[0]; vn[3 * (size_t)v + 1] = o[1]; vn[3 * (size_t)v + 2] = o[2];
@@ -62,16 +87,17 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_vertex_normal_kernel(int nv, 
 
 __global__ __launch_bounds__(MESH_BLOCK) void mesh_slot_kernel(int nt, const double *__restrict__ verts, const int *__restrict__ cid, const int *__restrict__ adj,
                                                               const double *__restrict__ fn, const double *__restrict__ vn, admm_mesh::Tri *tris,
-                                                              admm_mesh::Nrm *nrm) {
+                                                              admm_mesh::Nrm *nrm, const int *gate) {
     const int s = blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (s >= nt) return;
+    if (s >= nt || (gate && *gate)) return;
     admm_mesh::slot_data(verts, cid, adj, fn, vn, tris[s], nrm[s]);
 }
 
 // the nodes lvl[0, n) of one BVH level; the level below is already refit
-__global__ __launch_bounds__(MESH_BLOCK) void mesh_refit_kernel(const int *__restrict__ lvl, int n, admm_mesh::Node *nodes, const admm_mesh::Tri *__restrict__ tris) {
+__global__ __launch_bounds__(MESH_BLOCK) void mesh_refit_kernel(const int *__restrict__ lvl, int n, admm_mesh::Node *nodes, const admm_mesh::Tri *__restrict__ tris,
+                                                               const int *gate) {
     const int i = blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (i < n) admm_mesh::refit_node(nodes, tris, lvl[i]);
+    if (i < n && !(gate && *gate)) admm_mesh::refit_node(nodes, tris, lvl[i]);
 }
 
 } // namespace admm_dev

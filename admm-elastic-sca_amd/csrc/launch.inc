@@ -74,7 +74,7 @@ int update_mesh_device(admm_hip_ctx *ctx, int id, const double *verts) {
     HIPCHK(hipMemcpyAsync(u.verts, verts, sizeof(double) * 3 * (size_t)nv, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ctx->d_mesh_chk, NO_TRI, 2, st));      // bad_tri = bad_vtx = none
     hipLaunchKernelGGL(mesh_check_kernel, grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, ctx->d_mesh_chk);
-    hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, ctx->d_mesh_chk);
+    hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, ctx->d_mesh_chk, (BodyStatus *)nullptr);
     UpdateCheck chk;
     HIPCHK(hipMemcpyAsync(&chk, ctx->d_mesh_chk, sizeof chk, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -82,15 +82,45 @@ int update_mesh_device(admm_hip_ctx *ctx, int id, const double *verts) {
     char msg[512];
     if (mesh_refusal(M, verts, chk, msg, (int)sizeof msg)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: %s", id, msg);
     hipLaunchKernelGGL(mesh_vertex_normal_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const double *)u.verts, (const int *)u.cid, (const double *)u.fn,
-                       (const int *)u.inc_ptr, (const int *)u.inc, u.vn);
+                       (const int *)u.inc_ptr, (const int *)u.inc, u.vn, (const int *)nullptr);
     hipLaunchKernelGGL(mesh_slot_kernel, grid(nt), dim3(MESH_BLOCK), 0, st, nt, (const double *)u.verts, (const int *)u.cid, (const int *)u.adj,
-                       (const double *)u.fn, (const double *)u.vn, u.tris, u.nrm);
+                       (const double *)u.fn, (const double *)u.vn, u.tris, u.nrm, (const int *)nullptr);
     for (int d = M.depth; d >= 0; --d) {
         const int n = M.lvl_ptr[d + 1] - M.lvl_ptr[d];
-        hipLaunchKernelGGL(mesh_refit_kernel, grid(n), dim3(MESH_BLOCK), 0, st, (const int *)(u.lvl_nodes + M.lvl_ptr[d]), n, u.nodes, (const Tri *)u.tris);
+        hipLaunchKernelGGL(mesh_refit_kernel, grid(n), dim3(MESH_BLOCK), 0, st, (const int *)(u.lvl_nodes + M.lvl_ptr[d]), n, u.nodes, (const Tri *)u.tris, (const int *)nullptr);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
+    return ADMM_OK;
+}
+
+// the frame-start update of every body surface (admm_hip_add_body_surface; kernels_mesh.hpp): the same stages as update_mesh_device
+// from the frame-start x, eager on ctx->stream (outside the iteration and frame graphs), no read-back: the verdict gates the commit
+// kernels on the device.  Every address was fixed at finalize.
+int update_bodies(admm_hip_ctx *ctx) {
+    using namespace admm_dev;
+    using namespace admm_mesh;
+    const hipStream_t st = ctx->stream;
+    auto grid = [](int n) { return dim3((unsigned)((std::max(n, 1) + MESH_BLOCK - 1) / MESH_BLOCK)); };
+    for (size_t id = 0; id < ctx->meshes.size(); ++id) {
+        const admm_hip_ctx::MeshUpdate &u = ctx->mesh_upd[id];
+        if (!u.dnode) continue;
+        const admm_hip_mesh &M = ctx->meshes[id];
+        const int nt = (int)M.tris.size(), nv = M.nv, nchunk = (nt + VOL_CHUNK - 1) / VOL_CHUNK;
+        const int *gate = &u.status->gate;
+        hipLaunchKernelGGL(mesh_gather_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_x, u.verts);
+        hipLaunchKernelGGL(mesh_check_kernel, grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, u.chk);
+        hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, u.chk, u.status);
+        hipLaunchKernelGGL(mesh_vertex_normal_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const double *)u.verts, (const int *)u.cid, (const double *)u.fn,
+                           (const int *)u.inc_ptr, (const int *)u.inc, u.vn, gate);
+        hipLaunchKernelGGL(mesh_slot_kernel, grid(nt), dim3(MESH_BLOCK), 0, st, nt, (const double *)u.verts, (const int *)u.cid, (const int *)u.adj,
+                           (const double *)u.fn, (const double *)u.vn, u.tris, u.nrm, gate);
+        for (int d = M.depth; d >= 0; --d) {
+            const int n = M.lvl_ptr[d + 1] - M.lvl_ptr[d];
+            hipLaunchKernelGGL(mesh_refit_kernel, grid(n), dim3(MESH_BLOCK), 0, st, (const int *)(u.lvl_nodes + M.lvl_ptr[d]), n, u.nodes, (const Tri *)u.tris, gate);
+        }
+    }
+    HIPCHK(hipGetLastError());
     return ADMM_OK;
 }
 
@@ -99,7 +129,7 @@ void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     hipLaunchKernelGGL(project_collision_mesh_kernel, dim3((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), dim3(LOCAL_BLOCK), 0, ctx->stream, d, (const double *)ctx->d_xcur,
-                       (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes);
+                       (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const int *)ctx->d_body_tag);
 }
 
 int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {

@@ -185,6 +185,7 @@ struct HostStack { int s[MAX_DEPTH]; int &operator[](int i) { return s[i]; } };
 namespace admm_mesh {
 
 int mesh_refusal(const admm_hip_mesh &M, const double *verts, const UpdateCheck &c, char *err, int err_len) {
+    if (!update_refused(c)) return ADMM_OK;
     if (c.bad_tri != NO_TRI) {
         const int *C = M.cid.data() + 3 * (size_t)c.bad_tri;
         for (int k = 0; k < 3; ++k)
@@ -192,9 +193,7 @@ int mesh_refusal(const admm_hip_mesh &M, const double *verts, const UpdateCheck 
         return mesh_fail(err, err_len, "triangle %d (%d, %d, %d) is degenerate (zero area)", c.bad_tri, C[0], C[1], C[2]);
     }
     if (c.bad_vtx != NO_TRI) return mesh_fail(err, err_len, "vertex %d is not finite", c.bad_vtx);
-    if (!(c.vol6 > 0.0))
-        return mesh_fail(err, err_len, "the mesh encloses a non-positive volume (%g): its triangles must stay counter-clockwise seen from outside", c.vol6 / 6.0);
-    return ADMM_OK;
+    return mesh_fail(err, err_len, "the mesh encloses a non-positive volume (%g): its triangles must stay counter-clockwise seen from outside", c.vol6 / 6.0);
 }
 
 // checked first, the mesh untouched until the update is accepted; the same stages and arithmetic as the device update (kernels_mesh.hpp)

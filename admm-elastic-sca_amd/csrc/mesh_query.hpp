@@ -34,8 +34,9 @@ struct Nrm { double n[7][3]; };
 static_assert(sizeof(Node) == 64, "Node is one 64-byte record");
 static_assert(sizeof(Tri) == 96, "Tri is 96 bytes");
 
-// a registered mesh as the device sees it (admm_hip_ctx::d_meshes)
-struct MeshDev { const Node *nodes; const Tri *tris; const Nrm *nrm; int n_nodes, n_tris; };
+// a registered mesh as the device sees it (admm_hip_ctx::d_meshes); owner >= 0: the collision elements of nodes whose body tag equals it
+// skip this mesh (admm_hip_set_collision_mesh_owner, admm_hip_add_body_surface), -1: no owner
+struct MeshDev { const Node *nodes; const Tri *tris; const Nrm *nrm; int n_nodes, n_tris, owner; };
 
 enum Region { R_FACE = 0, R_EAB = 1, R_EBC = 2, R_ECA = 3, R_VA = 4, R_VB = 5, R_VC = 6 };
 
@@ -184,6 +185,12 @@ ADMM_HD bool face_normal(const double *v, double *n) {
 // vertex (NO_TRI: none; also catches vertices no triangle uses), 6 x the enclosed volume (blocked sum, VOL_CHUNK)
 struct UpdateCheck { int bad_tri, bad_vtx; double vol6; };
 static_assert(sizeof(UpdateCheck) == 16, "the device update reads back 16 bytes");
+// the one refusal predicate of an update, shared by the host (mesh_refusal) and the device's frame-start body-surface update
+ADMM_HD bool update_refused(const UpdateCheck &c) { return c.bad_tri != NO_TRI || c.bad_vtx != NO_TRI || !(c.vol6 > 0.0); }
+// a body surface's device record (kernels_mesh.hpp): frame-start updates applied / refused, the lowest bad triangle of the last refusal
+// (-1: none), and the gate the commit kernels read (nonzero: this frame's update was refused, the live arrays stay)
+struct BodyStatus { long long updated, refused; int last_bad_tri, gate; };
+static_assert(sizeof(BodyStatus) == 24, "BodyStatus is read back as 24 bytes");
 
 // the triangle's term of 6 x the enclosed volume
 ADMM_HD double volume_term(const double *v) { double c[3]; cross3(v + 3, v + 6, c); return dot3(v, c); }

@@ -537,8 +537,29 @@ int upload_all(admm_hip_ctx *ctx) {
     if (!ctx->meshes.empty()) {      // mesh obstacles: BVH nodes, triangles, pseudo-normals, and the table of them the kernel reads
         std::vector<admm_mesh::MeshDev> md;
         ctx->mesh_upd.clear();
-        for (const admm_hip_mesh &M : ctx->meshes) {
+        // owners: one group per distinct node range (ranges overlap only when equal: admm_hip_set_collision_mesh_owner), the group of
+        // every node in device order -- uploaded only when some mesh has an owner, so that other contexts launch as before
+        std::vector<std::pair<int, int> > groups;
+        std::vector<int> owner(ctx->meshes.size(), -1);
+        for (size_t i = 0; i < ctx->meshes.size(); ++i) {
+            const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+            if (!R.own_count) continue;
+            size_t g = 0;
+            while (g < groups.size() && groups[g] != std::make_pair(R.own_first, R.own_count)) ++g;
+            if (g == groups.size()) groups.push_back(std::make_pair(R.own_first, R.own_count));
+            owner[i] = (int)g;
+        }
+        ctx->d_body_tag = nullptr;
+        if (!groups.empty()) {
+            std::vector<int> tag((size_t)n, -1);
+            for (size_t g = 0; g < groups.size(); ++g)
+                for (int k = groups[g].first; k < groups[g].first + groups[g].second; ++k) tag[F.iperm[k]] = (int)g;
+            TRY(upload(ctx, &ctx->d_body_tag, tag));
+        }
+        for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) {
+            const admm_hip_mesh &M = ctx->meshes[mi];
             admm_mesh::MeshDev d{};
+            d.owner = owner[mi];
             admm_mesh::Node *nd; admm_mesh::Tri *tr; admm_mesh::Nrm *nr;
             TRY(upload(ctx, &nd, M.nodes)); TRY(upload(ctx, &tr, M.tris)); TRY(upload(ctx, &nr, M.nrm));
             d.nodes = nd; d.tris = tr; d.nrm = nr; d.n_nodes = (int)M.nodes.size(); d.n_tris = (int)M.tris.size();
@@ -551,6 +572,14 @@ int upload_all(admm_hip_ctx *ctx) {
             TRY(dalloc(ctx, &u.part, (nt + admm_mesh::VOL_CHUNK - 1) / admm_mesh::VOL_CHUNK));
             TRY(upload(ctx, &u.cid, M.cid)); TRY(upload(ctx, &u.adj, M.adj)); TRY(upload(ctx, &u.inc_ptr, M.inc_ptr)); TRY(upload(ctx, &u.inc, M.inc));
             TRY(upload(ctx, &u.lvl_nodes, M.lvl_nodes));
+            const std::vector<int> &bn = ctx->mesh_role[mi].body_nodes;
+            if (!bn.empty()) {      // a body surface: its vertices' device node ids, its own check (re-armed by the device) and status
+                std::vector<int> dn(bn.size());
+                for (size_t k = 0; k < bn.size(); ++k) dn[k] = F.iperm[bn[k]];
+                TRY(upload(ctx, &u.dnode, dn));
+                TRY(upload(ctx, &u.chk, std::vector<admm_mesh::UpdateCheck>(1, admm_mesh::UpdateCheck{admm_mesh::NO_TRI, admm_mesh::NO_TRI, 0.0})));
+                TRY(upload(ctx, &u.status, std::vector<admm_mesh::BodyStatus>(1, admm_mesh::BodyStatus{0, 0, -1, 0})));
+            }
             ctx->mesh_upd.push_back(u);
         }
         TRY(upload(ctx, &ctx->d_meshes, md));

@@ -287,6 +287,21 @@ private:
     }
 };
 
+// Extension, no reference counterpart: the closed boundary surface of a simulated body, triangles tris [nt][3] of global node ids
+// inside [node_first, node_first + node_count) (meshgen.tet_surface's output, for example), counter-clockwise seen from outside.
+// System registers it with its context before initialize (admm_hip_add_body_surface); the device then rebuilds it from the nodes
+// at the start of every step, and the body's own nodes ignore it.  It has no host evaluation (it needs the nodes' positions):
+// a CollisionForce that projects on the host (a user-written shape in its list) refuses it at System::initialize.
+class CollisionBody : public CollisionShape {
+public:
+    CollisionBody(int node_first_, int node_count_, const std::vector<int> &tris_) : CollisionShape(Vector3d(0, 0, 0)), node_first(node_first_), node_count(node_count_), tris(tris_) {}
+    double isColliding(Vector3d) const { return -1.0; }
+    Vector3d projectOut(const Vector3d currPos) const { return currPos; }
+    int shape_type() const { return typeid(*this) == typeid(CollisionBody) ? ADMM_SHAPE_MESH : -1; }
+    int node_first, node_count;
+    std::vector<int> tris;
+};
+
 // One force over ALL nodes (CollisionForce.hpp:31-46).  With analytic shapes only: a device batch with one element per
 // node.  With a user-written shape in the list the shapes' virtuals have to run on the host, so the force describes itself
 // like any user force: identity rows (CollisionForce.cpp:29-36) and the projection loop of :38-70.

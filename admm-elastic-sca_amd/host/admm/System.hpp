@@ -153,7 +153,14 @@ public:
                 std::cerr << "\n**Solver Error: force " << i << " derives from a built-in force class; a subclass must override kind() to return -1 and bring its own get_selector()/project()" << std::endl;
                 return false;
             }
-            if (f.kind() < 0) f.initialize(m_x, m_v, m_masses, settings.timestep_s);
+            if (f.kind() < 0) {
+                if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))
+                    for (size_t q = 0; q < cf->collisionShapes.size(); ++q) if (dynamic_cast<const CollisionBody *>(cf->collisionShapes[q].get())) {
+                        std::cerr << "\n**Solver Error: force " << i << " projects on the host (a user-written shape in its list), where a CollisionBody has no evaluation" << std::endl;
+                        return false;
+                    }
+                f.initialize(m_x, m_v, m_masses, settings.timestep_s);
+            }
         }
         // consecutive forces of one kind (and one anchor flavour) -> one batch, order preserved
         batch_first.clear(); batch_count.clear(); batch_kind.clear(); batch_moving.clear(); batch_urow0.clear();
@@ -342,6 +349,7 @@ protected:
     admm_hip_ctx *gpu;
     std::vector<std::pair<const admm_hip_mesh *, int> > mesh_ids;      // CollisionMesh obstacles registered with the context -> their mesh_id
     std::vector<long> mesh_versions;                                  // ... and the CollisionMesh::version the context last received
+    std::vector<std::pair<const CollisionBody *, int> > body_ids;     // CollisionBody surfaces registered with the context -> their mesh_id
     std::vector<int> batch_first, batch_count, batch_kind;
     std::vector<char> batch_moving;
     std::vector<long> batch_urow0;         // generic batches: first of their rows among the user rows (-1 otherwise)
@@ -410,7 +418,7 @@ protected:
     void release() {
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
-        mesh_ids.clear(); mesh_versions.clear();
+        mesh_ids.clear(); mesh_versions.clear(); body_ids.clear();
         initialized = false;
     }
 
@@ -420,7 +428,18 @@ protected:
             const CollisionShape &sh = *cf->collisionShapes[q];
             ty.push_back(sh.shape_type());
             par.push_back(sh.center[0]); par.push_back(sh.center[1]); par.push_back(sh.center[2]);
-            if (sh.shape_type() == ADMM_SHAPE_MESH) {      // a mesh: registered with the context once (before finalize), then named by its id
+            if (sh.shape_type() == ADMM_SHAPE_MESH && typeid(sh) == typeid(CollisionBody)) {      // a body surface: registered once, then it follows its nodes
+                const CollisionBody &cb = static_cast<const CollisionBody &>(sh);
+                size_t k = 0;
+                while (k < body_ids.size() && body_ids[k].first != &cb) ++k;
+                if (k == body_ids.size()) {
+                    int id = -1;
+                    const std::vector<int32_t> t(cb.tris.begin(), cb.tris.end());
+                    if (!check(admm_hip_add_body_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), &id))) return false;
+                    body_ids.push_back(std::make_pair(&cb, id));
+                }
+                par.push_back((double)body_ids[k].second);
+            } else if (sh.shape_type() == ADMM_SHAPE_MESH) {      // a mesh: registered with the context once (before finalize), then named by its id
                 const CollisionMesh &cm = static_cast<const CollisionMesh &>(sh);
                 const admm_hip_mesh *m = cm.mesh.get();
                 size_t k = 0;

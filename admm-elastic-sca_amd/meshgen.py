@@ -51,6 +51,25 @@ def lumped_tet_mass(x, tets, density):
     return m
 
 
+def tet_surface(tets, x=None):
+    """the boundary of a tet mesh -> tris [nt][3] int32: the faces that occur once, in the tets' order (faces opposite corners 0, 1, 2, 3),
+    each oriented away from its tet's fourth corner -- by the corner order of a positively oriented tet (meshgen.bar's), or, given the
+    positions x [n][3], by the geometry whatever the tets' orientation"""
+    T = np.asarray(tets, dtype=np.int64).reshape(-1, 4)
+    # opposite corner 0, 1, 2, 3: counter-clockwise seen from outside when (v1 - v0) x (v2 - v0) . (v3 - v0) > 0
+    F = T[:, [[1, 2, 3], [0, 3, 2], [0, 1, 3], [0, 2, 1]]].reshape(-1, 3)
+    O = T.reshape(-1)
+    _, inv, cnt = np.unique(np.sort(F, axis=1), axis=0, return_inverse=True, return_counts=True)
+    once = cnt[inv.reshape(-1)] == 1
+    F, O = F[once], O[once]
+    if x is not None:
+        P = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+        n = np.cross(P[F[:, 1]] - P[F[:, 0]], P[F[:, 2]] - P[F[:, 0]])
+        inward = np.einsum("ij,ij->i", n, P[O] - P[F[:, 0]]) > 0
+        F[inward] = F[inward][:, [0, 2, 1]]
+    return np.ascontiguousarray(F, dtype=np.int32)
+
+
 def bar_anchor_nodes(nx, ny):
     """node ids of the k = 0 face."""
     return np.arange((nx + 1) * (ny + 1), dtype=np.int32)

@@ -155,6 +155,32 @@ int  admm_hip_mesh_info(const admm_hip_mesh *mesh, int *n_tris, int *n_nodes, in
 int  admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, int *mesh_id);
 int  admm_hip_mesh_set_vertices(admm_hip_mesh *mesh, int nv, const double *verts, char *err, int err_len);
 int  admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, const double *verts);
+/* Body surfaces and mesh owners.  Extension, no reference counterpart (the reference collides simulated nodes only with shapes that
+ * are not simulated).  A body surface is a closed triangle mesh whose vertices are simulated nodes: an ordinary registered mesh
+ * (mesh_id, named as ADMM_SHAPE_MESH { 0, 0, 0, mesh_id }, the same list order and projection rule as an obstacle) that
+ *   - follows its nodes: at the start of every admm_hip_step, before the explicit forces, the device reads its vertices from the
+ *     frame-start x and updates it in place with the arithmetic of admm_hip_update_collision_mesh; it stays frozen for the frame's
+ *     ADMM iterations.  No read-back: a frame whose positions the update would refuse (non-finite vertex, zero-area triangle,
+ *     non-positive volume) keeps the last good surface, is counted, and the step returns ADMM_OK;
+ *   - has an owner, its node range: the collision elements of those nodes skip the mesh (every interior node is inside its own body).
+ * Self-collision within one body, open surfaces, edge-edge contact and friction are out of scope.
+ *   admm_hip_add_body_surface  before finalize; tris [n_tris][3] are global node ids, all inside [node_first, node_first + node_count).
+ *                           Vertices: the distinct referenced nodes in ascending id order, at their current positions (admm_hip_add_nodes
+ *                           / admm_hip_set_x); triangles in the given order, renumbered.  Validated like admm_hip_mesh_create, with the
+ *                           same messages.  Also sets the owner to the same range.  -> *mesh_id
+ *   admm_hip_set_collision_mesh_owner  before finalize; any registered mesh; node_count 0 clears the owner.  Owner ranges of two meshes
+ *                           are equal or disjoint.
+ *   admm_hip_get_body_surface_status  after finalize: frame-start updates applied and refused so far, and the lowest bad triangle of
+ *                           the last refusal (-1: none).
+ *   admm_hip_collision_mesh_copy  a standalone copy of a registered mesh as registered (destroy with admm_hip_mesh_destroy).
+ * ADMM_ERR_ARG (admm_hip_last_error): node ids or a range outside the nodes, an open / non-manifold / inward surface, overlapping owner
+ * ranges, admm_hip_update_collision_mesh on a body surface, a body surface named with a nonzero translation (admm_hip_set_collision_shapes
+ * or finalize); ADMM_ERR_STATE: a call in the wrong phase.  Every rank of a sharded run registers the same surfaces in the same order;
+ * both shard modes hold the full frame-start x on every rank, so nothing of them goes over the collectives.                          */
+int  admm_hip_add_body_surface(admm_hip_ctx *ctx, int node_first, int node_count, int n_tris, const int32_t *tris, int *mesh_id);
+int  admm_hip_set_collision_mesh_owner(admm_hip_ctx *ctx, int mesh_id, int node_first, int node_count);
+int  admm_hip_get_body_surface_status(admm_hip_ctx *ctx, int mesh_id, int64_t *updated, int64_t *refused, int *last_bad_tri);
+int  admm_hip_collision_mesh_copy(admm_hip_ctx *ctx, int mesh_id, admm_hip_mesh **out);
 
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
