@@ -735,3 +735,155 @@ def scene_system(pkg, x, m3, forces, dt=0.04, device_id=0, rank=0, world=1):
         s.set_shard(rank, world)
         s.set_shard_mode("subtree")
     return s
+
+
+# ---- per-iteration ADMM residuals recomputed from captured states (tests/test_residual_reference.py) ----
+EPS = 2.0 ** -53      # unit roundoff of binary64: every device operation below is x (1 + d), |d| <= EPS
+
+
+def gamma(k):
+    """Higham's gamma_k = k EPS / (1 - k EPS): k roundings in a row"""
+    return k * EPS / (1.0 - k * EPS)
+
+
+class ResidualReference:
+    """The primal and dual residual of ONE ADMM iteration j, recomputed in np.longdouble from states captured on both sides of it, in the
+    oracle's definitions (orc_step; the comment at System.cpp:64-65):
+
+        r_j = | W (D x_j - z_{j+1}) |           = | W (u_{j+1} - u_j) |   since every kind updates u += D x - z
+        s_j = | D^T W^2 (z_{j+1} - zprev_j) |   zprev_0 = D m_x at the frame's start, zprev_j = z_j afterwards
+
+    D (compact row layout) and W are the ORACLE's (D_triplets, wdiag: pinned to the compiled reference by test_oracle_vs_ref.py); nothing here
+    calls the library under test.  All vectors are in the oracle's row order; rows_of() maps a batch's per-element [n][rows] arrays there.
+    Every method takes `drop`, a boolean mask over the rows left out of the sums (the sensitivity condition: one element removed).
+
+    The longdouble arithmetic (eps <= 2^-63, asserted) contributes errors 1000 times below anything bounded here and is not counted.
+
+    Error bounds, from the kernels' operation counts (EPS = 2^-53, gamma_k = k EPS / (1 - k EPS)); nothing measured goes into them:
+
+    |r_dev - r_from_u| <= c_r EPS r_from_u.  Per row the device forms du = fl(u_new - u_old) from the very doubles the reference subtracts
+      exactly (1 rounding), squares it (du^2: 2 + 1), adds the element's `rows` squares from 0 (rows - 1 inexact additions), multiplies by
+      w^2 = fl(w w) (1 + 1), then sums non-negative terms: the in-block reduction (6 levels of the 64-lane butterfly in the fused tet / anchor
+      kernels, 8 levels of the 256-entry tree in residual_primal_kernel: 8 covers both), sum_partials_kernel's strided serial part
+      (ceil(partials / 256) - 1 additions, partials = ceil(elements / elements per block) of the largest batch), its 256-entry tree (8), one
+      addition per further batch (the accumulate flag) and per further rank (the all-reduce).  For a sum of non-negative terms the relative
+      error is bounded by the deepest chain: C2 = 3 + (rows - 1) + 2 + 8 + serial + 8 + (batches - 1) + (ranks - 1) roundings in r^2.  The square
+      root halves that and adds its own rounding; one more unit absorbs the second-order terms:  c_r = ceil(C2 / 2) + 2  (c_r(): C2 = 29 -> 17 for a
+      lone 9-row batch and C2 = 30 -> 17 with its anchors, 18 on two ranks, 20 for the seven batches of the mixed scene, 17 + 1 per two
+      serial additions; every test prints the c_r, c_s and serial count it used).
+
+    |r_dev - r_from_dx| <= the above + 2 EPS |W u_{j+1}| + gamma_nnz |W |D| |x_j||.  The device's u_new = fl(u + fl(Dx_dev - z)) differs from
+      u + (D x - z) by the rounding of the sum (EPS |u_new|), of the difference (EPS |Dx - z| <= EPS (|u_new| + |u_old|), of which |u_new - u_old|
+      is already inside c_r) and of its own D x (nnz products and nnz - 1 additions per row: gamma_nnz |D||x|); the triangle inequality
+      carries the row-wise terms to the weighted norms.
+
+    |s_dev - s_ref| <= gamma_m | |D^T| W^2 |z_{j+1} - zprev_j| | + c_s EPS s_ref,   m = entries per selector row + largest node degree + 2.
+      Per corner the device rounds dz = fl(z - zprev), w^2, w^2 dz, every product with the selector entry and the additions of the element's
+      `cols` <= 3 products; the corner shares of a node then meet in at most (degree - 1) inexact additions (pre-reduced layout: the block's run
+      in LDS plus the node's slots; per-corner layout: the node's slots; sharded: plus one per further rank) -- `degree` counts every corner of
+      every element on the node.  c_s: the square (1), the gather's / norm2_partial_kernel's 256-entry tree (8), sum_partials_kernel's serial
+      part and tree (serial + 8): C2 = 17 + serial, c_s = ceil(C2 / 2) + 2.
+      At j = 0 the device's own warm start fl(D m_x) (residual_dx_kernel: gamma_nnz |D||m_x| per row) stands in for D m_x:
+      + gamma_nnz | |D^T| W^2 |D| |m_x| |."""
+
+    def __init__(self, oracle):
+        ld = np.longdouble
+        assert np.finfo(ld).eps <= 2.0 ** -63, "np.longdouble has no extended precision here (the tests that use this skip on such hosts)"
+        rr, cc, vv = oracle.D_triplets()
+        self.rows, self.n = oracle.rows, oracle.dof
+        self.rr, self.cc, self.vv = rr.astype(np.int64), cc.astype(np.int64), vv.astype(ld)
+        self.W = oracle.wdiag.astype(ld)
+        self.kinds = np.array([oracle.force(i).kind for i in range(oracle.n_forces)])
+        self.gidx = oracle.global_idx()
+        self.weights = oracle.weights()
+        self.nrows = np.array(KIND_ROWS)[self.kinds]
+        self.row_force = np.full(self.rows, -1, np.int64)
+        self.row_force[np.repeat(self.gidx, self.nrows) + (np.arange(self.nrows.sum()) - np.repeat(np.cumsum(self.nrows) - self.nrows, self.nrows))] = np.repeat(np.arange(self.kinds.size), self.nrows)
+        assert (self.row_force >= 0).all()
+        self.nnz_row = int(np.bincount(rr, minlength=self.rows).max())
+        # degree: corners of elements on a node = distinct (force, node) pairs
+        pairs = np.unique(np.stack([self.row_force[rr], cc // 3]), axis=1)
+        self.max_degree = int(np.bincount(pairs[1]).max())
+
+    # -- layout --
+    def rows_of(self, first_force, elements, kind):
+        """oracle rows [len(elements)][rows of kind] of a batch's elements (ids inside the batch, e.g. local_elements of a rank); first_force =
+        the oracle's force index of the batch's element 0"""
+        f = first_force + np.asarray(elements, dtype=np.int64)
+        assert (self.kinds[f] == kind).all()
+        return self.gidx[f][:, None] + np.arange(KIND_ROWS[kind])[None, :]
+
+    def force_rows(self, force):
+        return np.arange(self.gidx[force], self.gidx[force] + self.nrows[force])
+
+    def _keep(self, drop):
+        return np.ones(self.rows, bool) if drop is None else ~np.asarray(drop, bool)
+
+    def _D(self, x, absolute=False):
+        ld = np.longdouble
+        out = np.zeros(self.rows, ld)
+        xv = np.asarray(x, dtype=ld)
+        np.add.at(out, self.rr, (np.abs(self.vv) * np.abs(xv[self.cc])) if absolute else self.vv * xv[self.cc])
+        return out
+
+    def _DT(self, q, absolute=False):
+        ld = np.longdouble
+        out = np.zeros(self.n, ld)
+        qv = np.asarray(q, dtype=ld)
+        np.add.at(out, self.cc, (np.abs(self.vv) * np.abs(qv[self.rr])) if absolute else self.vv * qv[self.rr])
+        return out
+
+    @staticmethod
+    def _norm(v):
+        return np.sqrt(np.sum(v * v))
+
+    # -- the residuals --
+    def r_from_u(self, u0, u1, drop=None):
+        ld = np.longdouble
+        d = self.W * (np.asarray(u1, dtype=ld) - np.asarray(u0, dtype=ld))
+        return self._norm(d[self._keep(drop)])
+
+    def r_from_dx(self, x, z1, drop=None):
+        d = self.W * (self._D(x) - np.asarray(z1, dtype=np.longdouble))
+        return self._norm(d[self._keep(drop)])
+
+    def zprev_frame_start(self, x):
+        return self._D(x)
+
+    def s(self, z1, zprev, drop=None):
+        ld = np.longdouble
+        q = self.W * self.W * (np.asarray(z1, dtype=ld) - np.asarray(zprev, dtype=ld))
+        q[~self._keep(drop)] = 0
+        return self._norm(self._DT(q))
+
+    # -- the bounds --
+    def serial(self, partials):
+        """additions in sum_partials_kernel's strided serial part: ceil(count / 256) - 1 over the longest array it sums -- `partials`, the most
+        partials any batch leaves (one per block of its projection kernel or of residual_primal_kernel), or the 256-entry blocks of the 3n-vector s"""
+        part = max(int(partials), -(-self.n // 256))
+        return max(-(-part // 256) - 1, 0)
+
+    def c_r(self, batches=1, serial=0, ranks=1):
+        c2 = 3 + (int(self.nrows.max()) - 1) + 2 + 8 + serial + 8 + (batches - 1) + (ranks - 1)
+        return -(-c2 // 2) + 2
+
+    def c_s(self, serial=0):
+        return -(-(17 + serial) // 2) + 2
+
+    def bound_r_u(self, u0, u1, c_r):
+        return float(c_r * EPS * self.r_from_u(u0, u1))
+
+    def bound_r_dx(self, x, u0, u1, c_r):
+        ld = np.longdouble
+        extra = 2 * EPS * self._norm(self.W * np.asarray(u1, dtype=ld)) + gamma(self.nnz_row) * self._norm(self.W * self._D(x, absolute=True))
+        return self.bound_r_u(u0, u1, c_r) + float(extra)
+
+    def bound_s(self, z1, zprev, c_s, x_start=None, ranks=1):
+        """x_start: the frame's m_x when zprev is the warm start D m_x (iteration 0), None otherwise"""
+        ld = np.longdouble
+        m = self.nnz_row + self.max_degree + 2 + (ranks - 1)
+        w2 = self.W * self.W
+        b = gamma(m) * self._norm(self._DT(w2 * np.abs(np.asarray(z1, dtype=ld) - np.asarray(zprev, dtype=ld)), absolute=True))
+        if x_start is not None:
+            b = b + gamma(self.nnz_row) * self._norm(self._DT(w2 * self._D(x_start, absolute=True), absolute=True))
+        return float(b + c_s * EPS * self.s(z1, zprev))
