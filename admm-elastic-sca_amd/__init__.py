@@ -157,6 +157,8 @@ def lib():
         L.admm_hip_set_collision_mesh_owner.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.admm_hip_get_body_surface_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         L.admm_hip_collision_mesh_copy.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.admm_hip_set_collision_friction.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.admm_hip_friction_query.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip]
         _lib = L
     return _lib
 
@@ -221,6 +223,21 @@ class Mesh:
 def mesh_query(verts, tris, pts, t=(0.0, 0.0, 0.0)):
     """closest points and signed distances of pts to the closed mesh (verts, tris) translated by t -> (proj, sdist), sdist > 0 inside"""
     return Mesh(verts, tris).query(pts, t)
+
+
+def friction_query(p, p_out, x0, mu):
+    """the contact friction rule on the host (admm_hip_friction_query): p, p_out (where a shape put p), x0 (the frame-start positions)
+    [n][3], mu [n] or a scalar -> (result [n][3], mode [n]: 0 none, 1 stick, 2 slip); the device's kernel gives the same bits"""
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3)
+    po = np.ascontiguousarray(p_out, dtype=np.float64).reshape(-1, 3)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 3)
+    m = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float64), (p.shape[0],)))
+    assert po.shape == p.shape and x0.shape == p.shape
+    res = np.empty_like(p); mode = np.empty(p.shape[0], np.int32)
+    rc = lib().admm_hip_friction_query(p.shape[0], _d(p), _d(po), _d(x0), _d(m), _d(res), _i(mode))
+    if rc != 0:
+        raise AdmmHipError("admm_hip_friction_query error %d" % rc)
+    return res, mode
 
 
 class System:
@@ -366,6 +383,12 @@ class System:
         t = np.ascontiguousarray(types, dtype=np.int32)
         p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 4)
         self._chk(self.L.admm_hip_set_collision_shapes(self.h, t.size, _i(t), _d(p)))
+
+    def set_collision_friction(self, mu):
+        """one Coulomb coefficient >= 0 per entry of the current shape list (admm_hip_set_collision_friction); before or after
+        initialize, between frames.  All zero (the default): the frictionless kernels."""
+        m = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+        self._chk(self.L.admm_hip_set_collision_friction(self.h, m.size, _d(m)))
 
     def add_collision_mesh(self, verts, tris):
         """registers a closed triangle mesh (before initialize) -> its mesh_id for SHAPE["MESH"] entries {tx, ty, tz, mesh_id}"""

@@ -211,6 +211,17 @@ static int check_body_translations(admm_hip_ctx *ctx, int n_shapes, const int32_
     }
     return ADMM_OK;
 }
+// friction against a body surface would need the surface's velocity: an entry that names one takes no coefficient (checked wherever the
+// list or the coefficients change, and at finalize)
+static int check_body_friction(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params, const double *mu) {
+    for (int j = 0; j < n_shapes; ++j) {
+        if (types[j] != ADMM_SHAPE_MESH || mu[j] == 0.0) continue;
+        const int id = (int)params[4 * (size_t)j + 3];
+        if (id >= 0 && id < (int)ctx->mesh_role.size() && !ctx->mesh_role[id].body_nodes.empty())
+            return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which moves with its nodes: its friction coefficient must be 0 (have %g)", j, id, mu[j]);
+    }
+    return ADMM_OK;
+}
 int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
     if (!ctx || n_shapes < 0 || (n_shapes && (!types || !params))) return ADMM_ERR_ARG;
     if (n_shapes > ADMM_MAX_SHAPES) return fail(ctx, ADMM_ERR_UNSUPPORTED, "at most %d collision shapes", ADMM_MAX_SHAPES);
@@ -221,6 +232,11 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
                 return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh_id %g is not a registered mesh (have %d)", j, id, (int)ctx->meshes.size());
         }
     TRY(check_body_translations(ctx, n_shapes, types, params));
+    // (a list of the same length keeps its coefficients: one that now names a body surface where a coefficient is set is refused here
+    //  once finalized, by finalize before)
+    if (ctx->finalized && n_shapes == ctx->shapes.n) TRY(check_body_friction(ctx, n_shapes, types, params, ctx->shapes.mu));
+    const bool had_friction = friction_on(ctx);
+    if (n_shapes != ctx->shapes.n) for (double &m : ctx->shapes.mu) m = 0.0;      // a list of another length: its coefficients start at 0 (the same length keeps them)
     ctx->shapes.n = n_shapes;
     for (int j = 0; j < n_shapes; ++j) {
         if (types[j] < ADMM_SHAPE_FLOOR || types[j] > ADMM_SHAPE_MESH) return fail(ctx, ADMM_ERR_UNSUPPORTED, "collision shape type %d", types[j]);
@@ -231,6 +247,28 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
         HIPCHK(hipSetDevice(ctx->device_id));
         HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (had_friction != friction_on(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
+    }
+    return ADMM_OK;
+}
+
+// extension, no reference counterpart (include/admm_hip.h): one Coulomb coefficient per entry of the current shape list.  The values live in
+// d_shapes and change under a captured graph like shape parameters; only a change between "all zero" and "some positive" changes which
+// kernels the collision batches launch, and drops the captured graphs.
+int admm_hip_set_collision_friction(admm_hip_ctx *ctx, int n_shapes, const double *mu) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (n_shapes != ctx->shapes.n) return fail(ctx, ADMM_ERR_ARG, "collision friction: %d coefficients given, the shape list has %d entries", n_shapes, ctx->shapes.n);
+    if (n_shapes && !mu) return fail(ctx, ADMM_ERR_ARG, "collision friction: no coefficients");
+    for (int j = 0; j < n_shapes; ++j)
+        if (!(mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, mu[j]);
+    TRY(check_body_friction(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], mu));
+    const bool had_friction = friction_on(ctx);
+    for (int j = 0; j < n_shapes; ++j) ctx->shapes.mu[j] = mu[j];
+    if (ctx->finalized && ctx->device_id >= 0) {
+        HIPCHK(hipSetDevice(ctx->device_id));
+        HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (had_friction != friction_on(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
     }
     return ADMM_OK;
 }
@@ -449,6 +487,9 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (const char *e = getenv("ADMM_HIP_SHARD")) ctx->shard_mode = (std::string(e) == "subtree") ? ADMM_SHARD_SUBTREE : ADMM_SHARD_CONTIGUOUS;
     if (const char *g = getenv("ADMM_HIP_FACTOR_LOCAL")) ctx->factor_local = atoi(g) != 0;      // (overrides admm_hip_set_factor_local; host_factor picks the tree by it)
     TRY(check_body_translations(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
+    TRY(check_body_friction(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], ctx->shapes.mu));
+    for (int j = 0; j < ctx->shapes.n; ++j)
+        if (!(ctx->shapes.mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, ctx->shapes.mu[j]);
     TRY(host_assemble(ctx, false));
     TRY(host_factor(ctx, false));
     ctx->info.rank = ctx->rank; ctx->info.world = ctx->world;

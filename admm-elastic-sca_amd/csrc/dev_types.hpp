@@ -16,8 +16,9 @@ constexpr int LOCAL_BLOCK = ADMM_LOCAL_BLOCK;
 constexpr int MAX_GRAV = 4;
 struct Gravity { int n; double g[MAX_GRAV][3]; };
 
-// analytic collision shapes of a CollisionForce (collision/*.hpp), tested in list order by project_collision_block
-struct ShapeTable { int n; int type[ADMM_MAX_SHAPES]; double par[ADMM_MAX_SHAPES][4]; };
+// analytic collision shapes of a CollisionForce (collision/*.hpp), tested in list order by project_collision_block;
+// mu: every entry's Coulomb friction coefficient (admm_hip_set_collision_friction; all zero: the frictionless kernels run)
+struct ShapeTable { int n; int type[ADMM_MAX_SHAPES]; double par[ADMM_MAX_SHAPES][4]; double mu[ADMM_MAX_SHAPES]; };
 
 // One work item of a sweep launch with everything the block needs to start, in one 64-byte record
 // (one scalar load instead of an index load followed by six dependent per-supernode loads).

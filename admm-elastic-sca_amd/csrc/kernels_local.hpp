@@ -31,6 +31,7 @@
 #include "local_math.hpp"
 #include "dev_types.hpp"
 #include "mesh_query.hpp"
+#include "friction.hpp"
 #include "../../include/admm_kinds.h"
 
 namespace admm_dev {
@@ -464,6 +465,57 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_mesh_kernel(Bat
         admm_mesh::Hit h;
         admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
         if (admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0) { p[0] = t[0] + h.c[0]; p[1] = t[1] + h.c[1]; p[2] = t[2] + h.c[2]; }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double un = u[j] + (dx[j] - p[j]);
+        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
+        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
+    }
+}
+
+// ... with Coulomb friction at the contacts (friction.hpp; a context with any coefficient > 0 launches this form for its collision batches,
+// MESH: it has meshes registered).  One lane per node as above, the same pushes through collide_analytic and the same BVH traversal;
+// after every shape that moved the point, admm_friction::apply clamps the tangential part of p' - x0 against mu * depth, and the next shape
+// starts from the result.  xs: the frame-start x in device order (ctx->d_x, which no kernel writes during the ADMM loop): one more 24-byte
+// gather per node, issued beside the other loads, ahead of the u / z stores (see dst above).
+template <bool MESH>
+__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_friction_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
+                                                                                 const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
+                                                                                 const int *__restrict__ tag) {
+    __shared__ int stack[MESH ? admm_mesh::MAX_DEPTH : 1][LOCAL_BLOCK];
+    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
+    const int n = b.n;
+    if (e >= b.e1) return;
+    const int id = b.idx[e];
+    const int ds = b.dst[e];
+    const double s = b.w2h2[e];
+    double dx[3], u[3], p[3], x0[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
+        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
+        x0[j] = xs[3 * (size_t)id + j];
+        u[j] = b.u[(size_t)j * n + e];
+        p[j] = dx[j] + u[j];
+    }
+    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
+    const int own = (MESH && tag) ? tag[id] : -1;
+    const int ns = shapes->n;
+    for (int q = 0; q < ns; ++q) {
+        const double before[3] = {p[0], p[1], p[2]};
+        if (!MESH || shapes->type[q] != ADMM_SHAPE_MESH) collide_analytic(shapes, q, p);
+        else {
+            const admm_mesh::MeshDev m = meshes[(int)shapes->par[q][3]];
+            if (own >= 0 && m.owner == own) continue;
+            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
+            const double qq[3] = {p[0] - t[0], p[1] - t[1], p[2] - t[2]};
+            if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
+            admm_mesh::Hit h;
+            admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
+            if (admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0) { p[0] = t[0] + h.c[0]; p[1] = t[1] + h.c[1]; p[2] = t[2] + h.c[2]; }
+        }
+        admm_friction::apply(before, p, x0, shapes->mu[q]);      // (a shape that did not move the point: depth 0, nothing happens)
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {

@@ -15,6 +15,14 @@ void tet_trace_next(hipStream_t st) {
 #endif
 // The scene's batches as segments of ONE project_multi_kernel launch (false: launch batch after batch -- a kind without a segment
 // body, more than MULTI_MAX batches, or a tet batch with its anchors right behind it, which already is one launch).
+// does any entry of the shape list carry a friction coefficient?  Then the collision batches run project_collision_friction_kernel in a
+// launch of their own; with all of them zero every launch is the frictionless one.  Decided from the current coefficients at every launch
+// or capture: a call that flips it drops the captured graphs (abi_setup.inc).
+bool friction_on(const admm_hip_ctx *ctx) {
+    for (int q = 0; q < ctx->shapes.n; ++q) if (ctx->shapes.mu[q] > 0.0) return true;
+    return false;
+}
+
 bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
     using namespace admm_dev;
     mb = MultiBatch{}; blocks = 0;
@@ -44,7 +52,7 @@ bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
         case ADMM_KIND_TRI_STRAIN: code = MK_TRI_STRAIN; break;
         case ADMM_KIND_TRI_AREA: code = MK_TRI_AREA; break;
         case ADMM_KIND_TRI_FUNG: code = MK_TRI_FUNG; break;
-        case ADMM_KIND_COLLISION: if (!ctx->meshes.empty()) continue; code = MK_COLLISION; break;      // (meshes: own launch, launch_local)
+        case ADMM_KIND_COLLISION: if (!ctx->meshes.empty() || friction_on(ctx)) continue; code = MK_COLLISION; break;      // (meshes, friction: own launch, launch_local)
         default: break;
         }
         if (code < 0 || mb.n == MULTI_MAX) return false;
@@ -124,12 +132,20 @@ int update_bodies(admm_hip_ctx *ctx) {
     return ADMM_OK;
 }
 
-// a collision batch of a context with mesh obstacles
+// a collision batch of a context with mesh obstacles or friction
 void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
-    hipLaunchKernelGGL(project_collision_mesh_kernel, dim3((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), dim3(LOCAL_BLOCK), 0, ctx->stream, d, (const double *)ctx->d_xcur,
-                       (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const int *)ctx->d_body_tag);
+    const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
+    if (!friction_on(ctx))
+        hipLaunchKernelGGL(project_collision_mesh_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur,
+                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const int *)ctx->d_body_tag);
+    else if (!ctx->meshes.empty())      // x0 = the frame-start x: d_x is written by the epilogue only
+        hipLaunchKernelGGL(project_collision_friction_kernel<true>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const int *)ctx->d_body_tag);
+    else
+        hipLaunchKernelGGL(project_collision_friction_kernel<false>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)nullptr, (const int *)nullptr);
 }
 
 int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
@@ -140,7 +156,7 @@ int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
         MultiBatch mb{}; int blocks = 0;
         if (build_multi(ctx, mb, blocks)) {
             hipLaunchKernelGGL(project_multi_kernel, dim3(blocks), dim3(LOCAL_BLOCK), 0, st, mb, (const double *)ctx->d_xcur, (const ShapeTable *)ctx->d_shapes);
-            if (!ctx->meshes.empty())      // the collision batches were left out of the segments: their own launches
+            if (!ctx->meshes.empty() || friction_on(ctx))      // the collision batches were left out of the segments: their own launches
                 for (const Batch &b : ctx->batches) if (b.kind == ADMM_KIND_COLLISION && b.n_local > 0) launch_collision_mesh(ctx, b);
             HIPCHK(hipGetLastError());
             return ADMM_OK;
@@ -188,7 +204,7 @@ int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
         case ADMM_KIND_TRI_AREA: hipLaunchKernelGGL(project_tri_kernel<1>, grid, block, 0, st, d, x); break;
         case ADMM_KIND_TRI_FUNG: hipLaunchKernelGGL(project_tri_kernel<2>, grid, block, 0, st, d, x); break;
         case ADMM_KIND_COLLISION:
-            if (!ctx->meshes.empty()) launch_collision_mesh(ctx, b);
+            if (!ctx->meshes.empty() || friction_on(ctx)) launch_collision_mesh(ctx, b);
             else hipLaunchKernelGGL(project_collision_kernel, grid, block, 0, st, d, x, (const ShapeTable *)ctx->d_shapes);
             break;
         default: return fail(ctx, ADMM_ERR_UNSUPPORTED, "no kernel for kind %d", b.kind);

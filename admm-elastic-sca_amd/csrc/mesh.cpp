@@ -1,5 +1,6 @@
 // mesh.cpp -- closed triangle-mesh obstacles on the host: validation, pseudo-normals and the BVH of admm_hip_mesh_create, and
-// admm_hip_mesh_query, the host evaluation of the query the device runs (mesh_query.hpp).  Context-free: a context copies a mesh
+// admm_hip_mesh_query, the host evaluation of the query the device runs (mesh_query.hpp), and admm_hip_friction_query, the same for
+// the contact friction rule (friction.hpp).  Context-free: a context copies a mesh
 // at admm_hip_add_collision_mesh (abi_setup.inc).  Built with -ffp-contract=off like the device code, so both give the same bits.
 #include <algorithm>
 #include <cmath>
@@ -11,6 +12,7 @@
 
 #include "../../include/admm_hip.h"
 #include "mesh_host.hpp"
+#include "friction.hpp"
 
 using namespace admm_mesh;
 
@@ -268,6 +270,18 @@ int admm_hip_mesh_query(const admm_hip_mesh *mesh, const double t[3], int64_t n_
         const bool in = inside(mesh->nodes[0], mesh->nrm.data(), q, h);
         if (proj) for (int j = 0; j < 3; ++j) proj[3 * i + j] = t[j] + h.c[j];
         if (sdist) { const double d = std::sqrt(h.d2); sdist[i] = in ? d : -d; }
+    }
+    return ADMM_OK;
+}
+
+// the host evaluation of the friction rule the device applies after every shape that moved a point (friction.hpp); context-free
+int admm_hip_friction_query(int64_t n, const double *p, const double *p_out, const double *x0, const double *mu, double *result, int32_t *mode) {
+    if (n < 0 || (n && (!p || !p_out || !x0 || !mu))) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        double po[3] = {p_out[3 * i], p_out[3 * i + 1], p_out[3 * i + 2]};
+        const int m = admm_friction::apply(p + 3 * i, po, x0 + 3 * i, mu[i]);
+        if (result) for (int j = 0; j < 3; ++j) result[3 * i + j] = po[j];
+        if (mode) mode[i] = m;
     }
     return ADMM_OK;
 }

@@ -217,6 +217,10 @@ public:
     virtual int shape_type() const { return -1; }                  // ADMM_SHAPE_*, -1 = user code
     virtual double shape_radius() const { return 0.0; }
     Vector3d center;
+    // Extension, no reference counterpart: the Coulomb coefficient of contacts with this shape (admm_hip_set_collision_friction), for
+    // shapes with a device form; may change between frames.  System::initialize refuses it on a user-written (host-projected) shape
+    // and on a CollisionBody (a moving simulated surface: its velocity would be needed).
+    double friction = 0.0;
 };
 class CollisionFloor : public CollisionShape {
 public:

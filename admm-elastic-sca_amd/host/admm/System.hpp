@@ -153,6 +153,19 @@ public:
                 std::cerr << "\n**Solver Error: force " << i << " derives from a built-in force class; a subclass must override kind() to return -1 and bring its own get_selector()/project()" << std::endl;
                 return false;
             }
+            if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))      // friction is applied by the device's collision kernel only
+                for (size_t q = 0; q < cf->collisionShapes.size(); ++q) {
+                    const CollisionShape &sh = *cf->collisionShapes[q];
+                    if (sh.friction == 0.0) continue;
+                    if (f.kind() < 0) {
+                        std::cerr << "\n**Solver Error: force " << i << ", shape " << q << ": friction " << sh.friction << " on a force that projects on the host (a user-written shape in its list); friction needs the device form of every shape" << std::endl;
+                        return false;
+                    }
+                    if (dynamic_cast<const CollisionBody *>(&sh)) {
+                        std::cerr << "\n**Solver Error: force " << i << ", shape " << q << ": friction " << sh.friction << " on a CollisionBody; contact with a moving simulated surface takes no friction" << std::endl;
+                        return false;
+                    }
+                }
             if (f.kind() < 0) {
                 if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))
                     for (size_t q = 0; q < cf->collisionShapes.size(); ++q) if (dynamic_cast<const CollisionBody *>(cf->collisionShapes[q].get())) {
@@ -349,6 +362,7 @@ protected:
     admm_hip_ctx *gpu;
     std::vector<std::pair<const admm_hip_mesh *, int> > mesh_ids;      // CollisionMesh obstacles registered with the context -> their mesh_id
     std::vector<long> mesh_versions;                                  // ... and the CollisionMesh::version the context last received
+    bool friction_pushed = false;                                      // a CollisionShape::friction != 0 went to the context: keep handing the coefficients over
     std::vector<std::pair<const CollisionBody *, int> > body_ids;     // CollisionBody surfaces registered with the context -> their mesh_id
     std::vector<int> batch_first, batch_count, batch_kind;
     std::vector<char> batch_moving;
@@ -418,7 +432,7 @@ protected:
     void release() {
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
-        mesh_ids.clear(); mesh_versions.clear(); body_ids.clear();
+        mesh_ids.clear(); mesh_versions.clear(); body_ids.clear(); friction_pushed = false;
         initialized = false;
     }
 
@@ -458,7 +472,14 @@ protected:
                 par.push_back(sh.shape_radius());
             }
         }
-        return check(admm_hip_set_collision_shapes(gpu, (int)ty.size(), ty.data(), par.data()));
+        if (!check(admm_hip_set_collision_shapes(gpu, (int)ty.size(), ty.data(), par.data()))) return false;
+        // the shapes' friction coefficients (contexts that never saw one above 0 skip the call: they run the frictionless kernels anyway)
+        std::vector<double> mu;
+        bool any = false;
+        for (size_t q = 0; q < cf->collisionShapes.size(); ++q) { mu.push_back(cf->collisionShapes[q]->friction); any = any || mu.back() != 0.0; }
+        if (!any && !friction_pushed) return true;
+        friction_pushed = true;
+        return check(admm_hip_set_collision_friction(gpu, (int)mu.size(), mu.data()));
     }
 
     bool check(int rc) {

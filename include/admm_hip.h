@@ -163,7 +163,7 @@ int  admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, cons
  *     ADMM iterations.  No read-back: a frame whose positions the update would refuse (non-finite vertex, zero-area triangle,
  *     non-positive volume) keeps the last good surface, is counted, and the step returns ADMM_OK;
  *   - has an owner, its node range: the collision elements of those nodes skip the mesh (every interior node is inside its own body).
- * Self-collision within one body, open surfaces, edge-edge contact and friction are out of scope.
+ * Self-collision within one body, open surfaces, edge-edge contact and friction against a body surface are out of scope.
  *   admm_hip_add_body_surface  before finalize; tris [n_tris][3] are global node ids, all inside [node_first, node_first + node_count).
  *                           Vertices: the distinct referenced nodes in ascending id order, at their current positions (admm_hip_add_nodes
  *                           / admm_hip_set_x); triangles in the given order, renumbered.  Validated like admm_hip_mesh_create, with the
@@ -181,6 +181,35 @@ int  admm_hip_add_body_surface(admm_hip_ctx *ctx, int node_first, int node_count
 int  admm_hip_set_collision_mesh_owner(admm_hip_ctx *ctx, int mesh_id, int node_first, int node_count);
 int  admm_hip_get_body_surface_status(admm_hip_ctx *ctx, int mesh_id, int64_t *updated, int64_t *refused, int *last_bad_tri);
 int  admm_hip_collision_mesh_copy(admm_hip_ctx *ctx, int mesh_id, admm_hip_mesh **out);
+
+/* ---- Coulomb friction at collision contacts -------------------------------------------------------------------------------------
+ * Extension, no reference counterpart (the reference's contacts are frictionless).  Every entry q of the shape list carries a
+ * coefficient mu_q >= 0, default 0.  In the collision projection the candidate is p = Dx + u; at a resting contact u is the contact
+ * impulse over the weight, so the depth by which a shape pushes p out is the normal force, and the tangential part of p' - x0
+ * (x0: the node's position at the start of the frame) is the tangential force plus the slip.  After shape q moved the point from p to
+ * p' -- exactly when and how it does without friction -- and mu_q > 0:
+ *     d = p' - p,  depth = |d| (0: nothing happens),  n = d / depth,  r = p' - x0,  t = r - (r.n) n,  lim = mu_q depth
+ *     |t| <= lim:  p' <- p' - t              stick: tangentially back where the frame started
+ *     else      :  p' <- p' - (lim / |t|) t  slip: pulled back by the cone's radius
+ * and the next shape of the list starts from the new p'.  mu = +inf always sticks.  The result is not projected onto the shape again: on
+ * a curved surface it sits off the surface by O(|t|^2 / R), which the next ADMM iteration corrects.  Obstacles count as at rest: a shape
+ * or mesh that the caller moves between frames gets no velocity term, and an entry that names a body surface takes no coefficient
+ * (contact with a moving simulated surface needs its velocity: out of scope).
+ *   admm_hip_set_collision_friction  mu [n_shapes], n_shapes = the length of the current list; before or after finalize, between frames.
+ *                           ADMM_ERR_ARG (admm_hip_last_error names the entry): a negative or NaN coefficient, another count, a nonzero
+ *                           coefficient on a body-surface entry (also checked at finalize, and by admm_hip_set_collision_shapes after
+ *                           it).  admm_hip_set_collision_shapes keeps the coefficients when the list's length is unchanged and zeroes
+ *                           them when it changes.  With every coefficient 0 the collision batches launch exactly the frictionless
+ *                           kernels; with any above 0 they launch the friction form, which also gathers x0 (admm_hip_step: the frame's
+ *                           start; admm_hip_local_step_only / _dx: x as added or as admm_hip_set_x left it).  The values change under a
+ *                           captured graph like shape parameters; a change between the two cases drops the graphs, which are captured
+ *                           again.  Every rank of a sharded run sets the same values (both shard modes hold the full frame-start x): no
+ *                           collective is involved.
+ *   admm_hip_friction_query  host evaluation of the rule for n cases: p, p_out (= p'), x0 [n][3], mu [n] -> result [n][3] (p' after
+ *                           friction) and mode [n]: 0 none (mu == 0 or depth == 0: result = p_out), 1 stick, 2 slip.  Either output
+ *                           may be NULL.  The device's kernel runs the same code and gives the same bits.                            */
+int  admm_hip_set_collision_friction(admm_hip_ctx *ctx, int n_shapes, const double *mu);
+int  admm_hip_friction_query(int64_t n, const double *p, const double *p_out, const double *x0, const double *mu, double *result, int32_t *mode);
 
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
