@@ -159,6 +159,11 @@ def lib():
         L.admm_hip_collision_mesh_copy.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.admm_hip_set_collision_friction.argtypes = [C.c_void_p, C.c_int, _dp]
         L.admm_hip_friction_query.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip]
+        L.admm_hip_set_collision_motion.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.admm_hip_set_collision_mesh_velocity.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        L.admm_hip_set_body_surface_friction.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.admm_hip_friction_query_moving.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _ip]
+        L.admm_hip_mesh_velocity_query.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip]
         _lib = L
     return _lib
 
@@ -238,6 +243,37 @@ def friction_query(p, p_out, x0, mu):
     if rc != 0:
         raise AdmmHipError("admm_hip_friction_query error %d" % rc)
     return res, mode
+
+
+def friction_query_moving(p, p_out, x0, w, mu):
+    """the friction rule against a moving obstacle on the host (admm_hip_friction_query_moving): as friction_query, with w [n][3] the
+    displacement of the obstacle's surface over the frame at each contact; w = 0 gives the bits of friction_query"""
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3)
+    po = np.ascontiguousarray(p_out, dtype=np.float64).reshape(-1, 3)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 3)
+    w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), p.shape))
+    m = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float64), (p.shape[0],)))
+    assert po.shape == p.shape and x0.shape == p.shape
+    res = np.empty_like(p); mode = np.empty(p.shape[0], np.int32)
+    rc = lib().admm_hip_friction_query_moving(p.shape[0], _d(p), _d(po), _d(x0), _d(w), _d(m), _d(res), _i(mode))
+    if rc != 0:
+        raise AdmmHipError("admm_hip_friction_query_moving error %d" % rc)
+    return res, mode
+
+
+def mesh_velocity_query(verts, tris, pts, vel, t=(0.0, 0.0, 0.0)):
+    """the vertex field vel [nv][3] of the closed mesh (verts, tris; a Mesh for verts: tris ignored) translated by t, interpolated at the
+    closest point to each of pts (admm_hip_mesh_velocity_query) -> (out [n][3], weights [n][3], corner_ids [n][3]): the barycentric
+    weights of the closest point on its triangle and that triangle's vertex ids; the moving friction kernel gives the same bits"""
+    m = verts if isinstance(verts, Mesh) else Mesh(verts, tris)
+    p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+    tt = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+    v = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+    out = np.empty_like(p); wts = np.empty_like(p); ids = np.empty(p.shape, np.int32)
+    rc = lib().admm_hip_mesh_velocity_query(m.h, p.shape[0], _d(p), _d(tt), _d(v), _d(out), _d(wts), _i(ids))
+    if rc != 0:
+        raise AdmmHipError("admm_hip_mesh_velocity_query error %d" % rc)
+    return out, wts, ids
 
 
 class System:
@@ -389,6 +425,26 @@ class System:
         initialize, between frames.  All zero (the default): the frictionless kernels."""
         m = np.ascontiguousarray(mu, dtype=np.float64).ravel()
         self._chk(self.L.admm_hip_set_collision_friction(self.h, m.size, _d(m)))
+
+    def set_collision_motion(self, motion):
+        """the rigid motion of every entry of the current shape list (admm_hip_set_collision_motion): [n_shapes][9] = linear velocity,
+        angular velocity, pivot, world coordinates; contacts with mu > 0 then stick to the moving surface.  All zero: the default."""
+        m = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 9)
+        self._chk(self.L.admm_hip_set_collision_motion(self.h, m.shape[0], _d(m)))
+
+    def set_collision_mesh_velocity(self, mesh_id, vel):
+        """one velocity per vertex [nv][3] of a registered obstacle mesh (admm_hip_set_collision_mesh_velocity; after initialize, between
+        frames), interpolated at a contact for the friction rule; None clears them"""
+        if vel is None:
+            self._chk(self.L.admm_hip_set_collision_mesh_velocity(self.h, int(mesh_id), 0, None))
+            return
+        v = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+        self._chk(self.L.admm_hip_set_collision_mesh_velocity(self.h, int(mesh_id), v.shape[0], _d(v)))
+
+    def set_body_surface_friction(self, mesh_id, mu):
+        """the Coulomb coefficient of a body surface (admm_hip_set_body_surface_friction), for every entry that names it; the surface's
+        velocity at a contact comes from its nodes' frame-start v"""
+        self._chk(self.L.admm_hip_set_body_surface_friction(self.h, int(mesh_id), float(mu)))
 
     def add_collision_mesh(self, verts, tris):
         """registers a closed triangle mesh (before initialize) -> its mesh_id for SHAPE["MESH"] entries {tx, ty, tz, mesh_id}"""

@@ -222,6 +222,18 @@ static int check_body_friction(admm_hip_ctx *ctx, int n_shapes, const int32_t *t
     }
     return ADMM_OK;
 }
+// ... and no rigid motion: the surface's motion is its nodes' (admm_hip_set_body_surface_friction)
+static int check_body_motion(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params, const double *motion) {
+    for (int j = 0; j < n_shapes; ++j) {
+        if (types[j] != ADMM_SHAPE_MESH) continue;
+        const int id = (int)params[4 * (size_t)j + 3];
+        if (!(id >= 0 && id < (int)ctx->mesh_role.size() && !ctx->mesh_role[id].body_nodes.empty())) continue;
+        for (int k = 0; k < 9; ++k)
+            if (motion[9 * (size_t)j + k] != 0.0)
+                return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which moves with its nodes: its rigid motion must be 0 (component %d is %g)", j, id, k, motion[9 * (size_t)j + k]);
+    }
+    return ADMM_OK;
+}
 int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
     if (!ctx || n_shapes < 0 || (n_shapes && (!types || !params))) return ADMM_ERR_ARG;
     if (n_shapes > ADMM_MAX_SHAPES) return fail(ctx, ADMM_ERR_UNSUPPORTED, "at most %d collision shapes", ADMM_MAX_SHAPES);
@@ -235,8 +247,12 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
     // (a list of the same length keeps its coefficients: one that now names a body surface where a coefficient is set is refused here
     //  once finalized, by finalize before)
     if (ctx->finalized && n_shapes == ctx->shapes.n) TRY(check_body_friction(ctx, n_shapes, types, params, ctx->shapes.mu));
-    const bool had_friction = friction_on(ctx);
-    if (n_shapes != ctx->shapes.n) for (double &m : ctx->shapes.mu) m = 0.0;      // a list of another length: its coefficients start at 0 (the same length keeps them)
+    if (n_shapes == ctx->shapes.n) TRY(check_body_motion(ctx, n_shapes, types, params, &ctx->shapes.motion[0][0]));      // (kept motions likewise)
+    const int form = collision_form(ctx);
+    if (n_shapes != ctx->shapes.n) {      // a list of another length: its coefficients and motions start at 0 (the same length keeps them)
+        for (double &m : ctx->shapes.mu) m = 0.0;
+        for (auto &m : ctx->shapes.motion) for (double &c : m) c = 0.0;
+    }
     ctx->shapes.n = n_shapes;
     for (int j = 0; j < n_shapes; ++j) {
         if (types[j] < ADMM_SHAPE_FLOOR || types[j] > ADMM_SHAPE_MESH) return fail(ctx, ADMM_ERR_UNSUPPORTED, "collision shape type %d", types[j]);
@@ -247,7 +263,7 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
         HIPCHK(hipSetDevice(ctx->device_id));
         HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (had_friction != friction_on(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
+        if (form != collision_form(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
     }
     return ADMM_OK;
 }
@@ -262,15 +278,82 @@ int admm_hip_set_collision_friction(admm_hip_ctx *ctx, int n_shapes, const doubl
     for (int j = 0; j < n_shapes; ++j)
         if (!(mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, mu[j]);
     TRY(check_body_friction(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], mu));
-    const bool had_friction = friction_on(ctx);
+    const int form = collision_form(ctx);
     for (int j = 0; j < n_shapes; ++j) ctx->shapes.mu[j] = mu[j];
     if (ctx->finalized && ctx->device_id >= 0) {
         HIPCHK(hipSetDevice(ctx->device_id));
         HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (had_friction != friction_on(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
+        if (form != collision_form(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
     }
     return ADMM_OK;
+}
+
+// a call that changed what moves: the shape table and the mesh table go to the device again (between frames; the values change under a
+// captured graph like shape parameters), and a change of the collision batches' kernels drops the captured graphs
+static int push_motion(admm_hip_ctx *ctx, int form_before) {
+    if (!ctx->finalized || ctx->device_id < 0) return ADMM_OK;
+    HIPCHK(hipSetDevice(ctx->device_id));
+    HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<admm_mesh::MeshMotion> mo(ctx->meshes.size());
+    for (size_t mi = 0; mi < mo.size(); ++mi) {
+        const admm_hip_ctx::MeshMove &mv = ctx->mesh_move[mi];
+        const bool body = !ctx->mesh_role[mi].body_nodes.empty();
+        mo[mi] = admm_mesh::MeshMotion{ctx->mesh_upd[mi].cid, (body || mv.has_vel) ? mv.d_vel : nullptr, body ? mv.body_mu : 0.0, body ? 1 : 0, 0};
+    }
+    if (!mo.empty()) HIPCHK(hipMemcpyAsync(ctx->d_mesh_motion, mo.data(), sizeof(admm_mesh::MeshMotion) * mo.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (form_before != collision_form(ctx)) drop_iteration_graphs(ctx);
+    return ADMM_OK;
+}
+
+// extension, no reference counterpart (include/admm_hip.h): the rigid motion of every entry of the current list
+int admm_hip_set_collision_motion(admm_hip_ctx *ctx, int n_shapes, const double *motion) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (n_shapes != ctx->shapes.n) return fail(ctx, ADMM_ERR_ARG, "collision motion: %d motions given, the shape list has %d entries", n_shapes, ctx->shapes.n);
+    if (n_shapes && !motion) return fail(ctx, ADMM_ERR_ARG, "collision motion: no motions");
+    for (int j = 0; j < n_shapes; ++j)
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(motion[9 * (size_t)j + k])) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: motion component %d is not finite (%g)", j, k, motion[9 * (size_t)j + k]);
+    TRY(check_body_motion(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], motion));
+    const int form = collision_form(ctx);
+    for (int j = 0; j < n_shapes; ++j) for (int k = 0; k < 9; ++k) ctx->shapes.motion[j][k] = motion[9 * (size_t)j + k];
+    return push_motion(ctx, form);
+}
+
+// ... the velocity of every vertex of a registered obstacle mesh (vel NULL: none again)
+int admm_hip_set_collision_mesh_velocity(admm_hip_ctx *ctx, int mesh_id, int nv, const double *vel) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (!ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision mesh velocities are set after finalize");
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    if (!ctx->mesh_role[mesh_id].body_nodes.empty())
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a body surface, which moves with its nodes: it takes no velocities from the caller", mesh_id);
+    const admm_hip_mesh &M = ctx->meshes[mesh_id];
+    if (vel && nv != M.nv) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: %d vertex velocities given, the mesh has %d vertices", mesh_id, nv, M.nv);
+    if (vel) for (int v = 0; v < nv; ++v)
+        if (!admm_mesh::finite3(vel + 3 * (size_t)v)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: the velocity of vertex %d is not finite", mesh_id, v);
+    const int form = collision_form(ctx);
+    admm_hip_ctx::MeshMove &mv = ctx->mesh_move[mesh_id];
+    if (vel && ctx->device_id >= 0) {
+        HIPCHK(hipSetDevice(ctx->device_id));
+        if (!mv.d_vel) { TRY(dalloc(ctx, &mv.d_vel, 3 * (size_t)nv)); drop_iteration_graphs(ctx); }      // (allocated here, never by admm_hip_step)
+        HIPCHK(hipMemcpyAsync(mv.d_vel, vel, sizeof(double) * 3 * (size_t)nv, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (vel) mv.vel.assign(vel, vel + 3 * (size_t)nv); else mv.vel.clear();
+    mv.has_vel = vel != nullptr;
+    return push_motion(ctx, form);
+}
+
+// ... the coefficient of a body surface: of the body, for every entry that names the surface
+int admm_hip_set_body_surface_friction(admm_hip_ctx *ctx, int mesh_id, double mu) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size() || ctx->mesh_role[mesh_id].body_nodes.empty())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a body surface", mesh_id);
+    if (!(mu >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "body surface %d: friction coefficient %g is negative or not a number", mesh_id, mu);
+    const int form = collision_form(ctx);
+    ctx->mesh_move[mesh_id].body_mu = mu;
+    return push_motion(ctx, form);
 }
 
 // extension, no reference counterpart (include/admm_hip.h): the context keeps its own copy, uploaded at finalize
@@ -279,6 +362,7 @@ int admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, in
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision meshes must be registered before finalize");
     ctx->meshes.push_back(*mesh);
     ctx->mesh_role.emplace_back();
+    ctx->mesh_move.emplace_back();
     if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
     return ADMM_OK;
 }
@@ -327,6 +411,7 @@ int admm_hip_add_body_surface(admm_hip_ctx *ctx, int node_first, int node_count,
     admm_hip_ctx::MeshRole R;
     R.own_first = node_first; R.own_count = node_count; R.body_nodes = std::move(nodes);
     ctx->mesh_role.push_back(std::move(R));
+    ctx->mesh_move.emplace_back();
     if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
     return ADMM_OK;
 }
@@ -488,6 +573,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (const char *g = getenv("ADMM_HIP_FACTOR_LOCAL")) ctx->factor_local = atoi(g) != 0;      // (overrides admm_hip_set_factor_local; host_factor picks the tree by it)
     TRY(check_body_translations(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
     TRY(check_body_friction(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], ctx->shapes.mu));
+    TRY(check_body_motion(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], &ctx->shapes.motion[0][0]));
     for (int j = 0; j < ctx->shapes.n; ++j)
         if (!(ctx->shapes.mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, ctx->shapes.mu[j]);
     TRY(host_assemble(ctx, false));

@@ -139,6 +139,12 @@ struct admm_hip_ctx {
     // node behind every vertex, ascending -- the device rebuilds it from them at every step (launch.inc: update_bodies)
     struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; };
     std::vector<MeshRole> mesh_role;
+    // obstacles that move (admm_hip_set_collision_motion: shapes.motion; admm_hip_set_collision_mesh_velocity, admm_hip_set_body_surface_friction):
+    // per mesh, parallel to `meshes`, the host's record and the device table the moving friction kernel reads.  d_vel: an obstacle's
+    // vertex velocities, allocated by the call that first sets them (has_vel: in effect); a body surface's are allocated at finalize and
+    // gathered from the frame-start v at every step (launch.inc: update_bodies).  body_mu: a body surface's coefficient.
+    struct MeshMove { double *d_vel = nullptr; bool has_vel = false; double body_mu = 0.0; std::vector<double> vel; };
+    std::vector<MeshMove> mesh_move; admm_mesh::MeshMotion *d_mesh_motion = nullptr;
     int *d_body_tag = nullptr;      // contexts with an owner: the owner group of every node in device order (-1: none), for MeshDev::owner
     SymCSC A;
     Factor F;

@@ -525,6 +525,81 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_friction_kernel
     }
 }
 
+// ... against obstacles that move (a context where moving_friction_on holds, launch.inc, launches this form for its collision batches;
+// the two instantiations above stay as they are).  One lane per node, the same pushes, traversal and owner skip; after a shape moved the
+// point, w = the displacement of its surface over the frame at the contact p' (friction.hpp rigid_displacement from the entry's nine
+// doubles of shapes->motion, uniform across the wave; at a mesh hit whose mesh has vertex velocities plus dt times their interpolation
+// with the hit triangle's barycentric weights: three cid ints and three 24-byte gathers) goes into admm_friction::apply_moving.  A body
+// surface's entry takes the surface's coefficient (MeshMotion::mu) in place of the entry's, which is 0 for it.  Every load of an entry is
+// issued before the rule, and all of them ahead of the u / z stores (see dst above).  mm: null without meshes.
+template <bool MESH>
+__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_friction_moving_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
+                                                                                        const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
+                                                                                        const admm_mesh::MeshMotion *__restrict__ mm, const int *__restrict__ tag, const double dt) {
+    __shared__ int stack[MESH ? admm_mesh::MAX_DEPTH : 1][LOCAL_BLOCK];
+    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
+    const int n = b.n;
+    if (e >= b.e1) return;
+    const int id = b.idx[e];
+    const int ds = b.dst[e];
+    const double s = b.w2h2[e];
+    double dx[3], u[3], p[3], x0[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
+        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
+        x0[j] = xs[3 * (size_t)id + j];
+        u[j] = b.u[(size_t)j * n + e];
+        p[j] = dx[j] + u[j];
+    }
+    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
+    const int own = (MESH && tag) ? tag[id] : -1;
+    const int ns = shapes->n;
+    for (int q = 0; q < ns; ++q) {
+        const double before[3] = {p[0], p[1], p[2]};
+        double mu = shapes->mu[q];
+        double vi0 = 0.0, vi1 = 0.0, vi2 = 0.0;      // the mesh's vertex velocities at the hit
+        bool vhit = false;
+        if (!MESH || shapes->type[q] != ADMM_SHAPE_MESH) collide_analytic(shapes, q, p);
+        else {
+            const int mi = (int)shapes->par[q][3];
+            const admm_mesh::MeshDev m = meshes[mi];
+            if (own >= 0 && m.owner == own) continue;
+            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
+            const double qq[3] = {p[0] - t[0], p[1] - t[1], p[2] - t[2]};
+            if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
+            admm_mesh::Hit h;
+            admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
+            if (admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0) {
+                p[0] = t[0] + h.c[0]; p[1] = t[1] + h.c[1]; p[2] = t[2] + h.c[2];
+                const admm_mesh::MeshMotion mo = mm[mi];
+                if (mo.body) mu = mo.mu;
+                if (mo.vel && mu > 0.0) {
+                    const admm_mesh::Tri &tr = m.tris[h.slot];
+                    const int *c = mo.cid + 3 * (size_t)tr.orig;
+                    const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
+                    const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
+                    double bw[3];
+                    admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
+                    vi0 = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi1 = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi2 = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
+                    vhit = true;
+                }
+            }
+        }
+        if (!(mu > 0.0)) continue;
+        double w[3];
+        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
+        if (vhit) { w[0] = w[0] + dt * vi0; w[1] = w[1] + dt * vi1; w[2] = w[2] + dt * vi2; }
+        admm_friction::apply_moving(before, p, x0, w, mu);      // (a shape that did not move the point: depth 0, nothing happens)
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double un = u[j] + (dx[j] - p[j]);
+        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
+        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Spring, Force.cpp:52-71   (rows: x_a - x_b)
 // ---------------------------------------------------------------------------

@@ -49,6 +49,15 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_gather_kernel(int nv, const i
     verts[3 * (size_t)k] = p[0]; verts[3 * (size_t)k + 1] = p[1]; verts[3 * (size_t)k + 2] = p[2];
 }
 
+// ... and their velocities: vel[k] = v[dnode[k]], unless this frame's update was refused (gate: set by mesh_volume_kernel before)
+__global__ __launch_bounds__(MESH_BLOCK) void mesh_gather_vel_kernel(int nv, const int *__restrict__ dnode, const double *__restrict__ v, double *__restrict__ vel,
+                                                                     const int *__restrict__ gate) {
+    const int k = blockIdx.x * MESH_BLOCK + threadIdx.x;
+    if (k >= nv || *gate) return;
+    const double *p = v + 3 * (size_t)dnode[k];
+    vel[3 * (size_t)k] = p[0]; vel[3 * (size_t)k + 1] = p[1]; vel[3 * (size_t)k + 2] = p[2];
+}
+
 // one workgroup: the partials staged through LDS a block at a time (parallel loads), lane 0 adds them in order.  bs (body surfaces
 // only): lane 0 also takes the verdict, counts the frame, sets the commit kernels' gate and resets the check for the next frame
 __global__ __launch_bounds__(MESH_BLOCK) void mesh_volume_kernel(int nchunk, const double *__restrict__ part, admm_mesh::UpdateCheck *chk,

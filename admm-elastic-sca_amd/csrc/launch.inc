@@ -23,6 +23,23 @@ bool friction_on(const admm_hip_ctx *ctx) {
     return false;
 }
 
+// ... and does a contact's obstacle move?  An entry with a coefficient whose rigid motion is not all zero or whose mesh has vertex
+// velocities set, or a body surface with a coefficient named in the list: the collision batches then run the moving form of the
+// friction kernel.  Evaluated at every launch or capture like friction_on; a call that changes collision_form drops the captured graphs.
+bool moving_friction_on(const admm_hip_ctx *ctx) {
+    for (int q = 0; q < ctx->shapes.n; ++q) {
+        const int id = ctx->shapes.type[q] == ADMM_SHAPE_MESH ? (int)ctx->shapes.par[q][3] : -1;
+        const admm_hip_ctx::MeshMove *mv = id >= 0 && id < (int)ctx->mesh_move.size() ? &ctx->mesh_move[id] : nullptr;
+        if (mv && !ctx->mesh_role[id].body_nodes.empty() && mv->body_mu > 0.0) return true;
+        if (!(ctx->shapes.mu[q] > 0.0)) continue;
+        if (mv && mv->has_vel) return true;
+        for (int k = 0; k < 9; ++k) if (ctx->shapes.motion[q][k] != 0.0) return true;
+    }
+    return false;
+}
+// which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form
+int collision_form(const admm_hip_ctx *ctx) { return moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
+
 bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
     using namespace admm_dev;
     mb = MultiBatch{}; blocks = 0;
@@ -119,6 +136,9 @@ int update_bodies(admm_hip_ctx *ctx) {
         hipLaunchKernelGGL(mesh_gather_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_x, u.verts);
         hipLaunchKernelGGL(mesh_check_kernel, grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, u.chk);
         hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, u.chk, u.status);
+        // the vertices' frame-start velocities beside them, through the same map (d_v before the explicit forces); gated like the commit
+        // kernels: a refused frame keeps the velocities that went with the last good surface
+        hipLaunchKernelGGL(mesh_gather_vel_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_v, ctx->mesh_move[id].d_vel, gate);
         hipLaunchKernelGGL(mesh_vertex_normal_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const double *)u.verts, (const int *)u.cid, (const double *)u.fn,
                            (const int *)u.inc_ptr, (const int *)u.inc, u.vn, gate);
         hipLaunchKernelGGL(mesh_slot_kernel, grid(nt), dim3(MESH_BLOCK), 0, st, nt, (const double *)u.verts, (const int *)u.cid, (const int *)u.adj,
@@ -137,7 +157,15 @@ void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
-    if (!friction_on(ctx))
+    if (moving_friction_on(ctx)) {      // (a body surface with a coefficient implies meshes, an entry's motion implies friction_on: this launch is reached)
+        if (!ctx->meshes.empty())
+            hipLaunchKernelGGL(project_collision_friction_moving_kernel<true>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                               (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
+                               (const int *)ctx->d_body_tag, ctx->dt);
+        else
+            hipLaunchKernelGGL(project_collision_friction_moving_kernel<false>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                               (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)nullptr, (const admm_mesh::MeshMotion *)nullptr, (const int *)nullptr, ctx->dt);
+    } else if (!friction_on(ctx))
         hipLaunchKernelGGL(project_collision_mesh_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur,
                            (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const int *)ctx->d_body_tag);
     else if (!ctx->meshes.empty())      // x0 = the frame-start x: d_x is written by the epilogue only

@@ -1,6 +1,6 @@
 // mesh.cpp -- closed triangle-mesh obstacles on the host: validation, pseudo-normals and the BVH of admm_hip_mesh_create, and
 // admm_hip_mesh_query, the host evaluation of the query the device runs (mesh_query.hpp), and admm_hip_friction_query, the same for
-// the contact friction rule (friction.hpp).  Context-free: a context copies a mesh
+// the contact friction rule (friction.hpp) and its moving form's vertex-velocity interpolation.  Context-free: a context copies a mesh
 // at admm_hip_add_collision_mesh (abi_setup.inc).  Built with -ffp-contract=off like the device code, so both give the same bits.
 #include <algorithm>
 #include <cmath>
@@ -282,6 +282,38 @@ int admm_hip_friction_query(int64_t n, const double *p, const double *p_out, con
         const int m = admm_friction::apply(p + 3 * i, po, x0 + 3 * i, mu[i]);
         if (result) for (int j = 0; j < 3; ++j) result[3 * i + j] = po[j];
         if (mode) mode[i] = m;
+    }
+    return ADMM_OK;
+}
+
+// ... and of its moving form: w [n][3] = the displacement of the obstacle's surface over the frame at each contact
+int admm_hip_friction_query_moving(int64_t n, const double *p, const double *p_out, const double *x0, const double *w, const double *mu, double *result, int32_t *mode) {
+    if (n < 0 || (n && (!p || !p_out || !x0 || !w || !mu))) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        double po[3] = {p_out[3 * i], p_out[3 * i + 1], p_out[3 * i + 2]};
+        const int m = admm_friction::apply_moving(p + 3 * i, po, x0 + 3 * i, w + 3 * i, mu[i]);
+        if (result) for (int j = 0; j < 3; ++j) result[3 * i + j] = po[j];
+        if (mode) mode[i] = m;
+    }
+    return ADMM_OK;
+}
+
+// the host evaluation of the vertex-velocity interpolation the moving friction kernel does at a mesh hit: the closest point's triangle,
+// its barycentric weights (mesh_query.hpp tri_weights), its corners' vertex ids, and the field vel [nv][3] interpolated with them
+int admm_hip_mesh_velocity_query(const admm_hip_mesh *mesh, int64_t n, const double *q, const double t[3], const double *vel, double *out, double *weights, int32_t *corner_ids) {
+    if (!mesh || !t || n < 0 || (n && !q) || (out && !vel)) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        const double qq[3] = {q[3 * i] - t[0], q[3 * i + 1] - t[1], q[3 * i + 2] - t[2]};
+        HostStack stk; Hit h;
+        closest(mesh->nodes.data(), mesh->tris.data(), qq, stk, h);
+        if (h.slot < 0) return ADMM_ERR_ARG;
+        const Tri &tr = mesh->tris[h.slot];
+        const int *c = mesh->cid.data() + 3 * (size_t)tr.orig;
+        double b[3];
+        tri_weights(qq, tr.v, h.reg, b);
+        if (weights) for (int k = 0; k < 3; ++k) weights[3 * i + k] = b[k];
+        if (corner_ids) for (int k = 0; k < 3; ++k) corner_ids[3 * i + k] = c[k];
+        if (out) tri_interpolate(b, vel + 3 * (size_t)c[0], vel + 3 * (size_t)c[1], vel + 3 * (size_t)c[2], out + 3 * i);
     }
     return ADMM_OK;
 }

@@ -37,6 +37,10 @@ static_assert(sizeof(Tri) == 96, "Tri is 96 bytes");
 // a registered mesh as the device sees it (admm_hip_ctx::d_meshes); owner >= 0: the collision elements of nodes whose body tag equals it
 // skip this mesh (admm_hip_set_collision_mesh_owner, admm_hip_add_body_surface), -1: no owner
 struct MeshDev { const Node *nodes; const Tri *tris; const Nrm *nrm; int n_nodes, n_tris, owner; };
+// what the moving form of the friction kernel needs of a mesh beside MeshDev (admm_hip_ctx::d_mesh_motion, parallel to d_meshes): the
+// corner vertex ids of every original triangle, the vertices' velocities [nv][3] (null: none set), and for a body surface (body != 0)
+// the coefficient that replaces the entry's (admm_hip_set_body_surface_friction)
+struct MeshMotion { const int *cid; const double *vel; double mu; int body, pad; };
 
 enum Region { R_FACE = 0, R_EAB = 1, R_EBC = 2, R_ECA = 3, R_VA = 4, R_VB = 5, R_VC = 6 };
 
@@ -72,6 +76,36 @@ ADMM_HD void closest_on_tri(const double *p, const double *v, double *o, int &re
     const double den = 1.0 / (va + vb + vc);
     const double sv = vb * den, sw = vc * den;
     o[0] = a[0] + ab0 * sv + ac0 * sw; o[1] = a[1] + ab1 * sv + ac1 * sw; o[2] = a[2] + ab2 * sv + ac2 * sw; reg = R_FACE;
+}
+
+// the barycentric weights b[3] (corners a, b, c) of the point closest_on_tri returns for p in region reg: the expressions it evaluates,
+// recomputed for one triangle (the winning one of a query: the friction kernel's vertex-velocity interpolation).  A vertex region: 1 on
+// that corner; an edge: (1 - t, t) on its two corners in the order of the region's name; the face: (1 - sv - sw, sv, sw).
+ADMM_HD void tri_weights(const double *p, const double *v, const int reg, double *w) {
+    const double *a = v, *b = v + 3, *c = v + 6;
+    w[0] = w[1] = w[2] = 0.0;
+    if (reg == R_VA) { w[0] = 1.0; return; }
+    if (reg == R_VB) { w[1] = 1.0; return; }
+    if (reg == R_VC) { w[2] = 1.0; return; }
+    const double ab0 = b[0] - a[0], ab1 = b[1] - a[1], ab2 = b[2] - a[2];
+    const double ac0 = c[0] - a[0], ac1 = c[1] - a[1], ac2 = c[2] - a[2];
+    const double ap0 = p[0] - a[0], ap1 = p[1] - a[1], ap2 = p[2] - a[2];
+    const double d1 = ab0 * ap0 + ab1 * ap1 + ab2 * ap2, d2 = ac0 * ap0 + ac1 * ap1 + ac2 * ap2;
+    const double bp0 = p[0] - b[0], bp1 = p[1] - b[1], bp2 = p[2] - b[2];
+    const double d3 = ab0 * bp0 + ab1 * bp1 + ab2 * bp2, d4 = ac0 * bp0 + ac1 * bp1 + ac2 * bp2;
+    if (reg == R_EAB) { const double t = d1 / (d1 - d3); w[0] = 1.0 - t; w[1] = t; return; }
+    const double cp0 = p[0] - c[0], cp1 = p[1] - c[1], cp2 = p[2] - c[2];
+    const double d5 = ab0 * cp0 + ab1 * cp1 + ab2 * cp2, d6 = ac0 * cp0 + ac1 * cp1 + ac2 * cp2;
+    if (reg == R_ECA) { const double t = d2 / (d2 - d6); w[0] = 1.0 - t; w[2] = t; return; }
+    if (reg == R_EBC) { const double t = (d4 - d3) / ((d4 - d3) + (d5 - d6)); w[1] = 1.0 - t; w[2] = t; return; }
+    const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const double den = 1.0 / (va + vb + vc);
+    const double sv = vb * den, sw = vc * den;
+    w[0] = (1.0 - sv) - sw; w[1] = sv; w[2] = sw;
+}
+// a field given at the corners (fa, fb, fc: 3 doubles each), interpolated with the weights:  o_j = w0 fa_j + (w1 fb_j + w2 fc_j)
+ADMM_HD void tri_interpolate(const double *w, const double *fa, const double *fb, const double *fc, double *o) {
+    for (int j = 0; j < 3; ++j) o[j] = w[0] * fa[j] + (w[1] * fb[j] + w[2] * fc[j]);
 }
 
 // (d2, i) < (best_d2, best_i), lexicographically

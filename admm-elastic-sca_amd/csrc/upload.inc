@@ -582,6 +582,20 @@ int upload_all(admm_hip_ctx *ctx) {
             }
             ctx->mesh_upd.push_back(u);
         }
+        // the moving friction kernel's table: a body surface's velocity buffer lives from here on (zero: v at finalize); an obstacle's is
+        // allocated by admm_hip_set_collision_mesh_velocity
+        std::vector<admm_mesh::MeshMotion> mo(ctx->meshes.size());
+        for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) {
+            admm_hip_ctx::MeshMove &mv = ctx->mesh_move[mi];
+            const bool body = !ctx->mesh_role[mi].body_nodes.empty();
+            mv.d_vel = nullptr; mv.has_vel = false;
+            if (body) {
+                TRY(dalloc(ctx, &mv.d_vel, 3 * (size_t)ctx->meshes[mi].nv));
+                HIPCHK(hipMemset(mv.d_vel, 0, sizeof(double) * 3 * (size_t)ctx->meshes[mi].nv));
+            }
+            mo[mi] = admm_mesh::MeshMotion{ctx->mesh_upd[mi].cid, mv.d_vel, body ? mv.body_mu : 0.0, body ? 1 : 0, 0};
+        }
+        TRY(upload(ctx, &ctx->d_mesh_motion, mo));
         TRY(upload(ctx, &ctx->d_meshes, md));
         TRY(dalloc(ctx, &ctx->d_mesh_chk, 1));
     }

@@ -221,6 +221,10 @@ public:
     // shapes with a device form; may change between frames.  System::initialize refuses it on a user-written (host-projected) shape
     // and on a CollisionBody (a moving simulated surface: its velocity would be needed).
     double friction = 0.0;
+    // ... and the shape's rigid motion as the friction rule sees it (admm_hip_set_collision_motion): linear and angular velocity and the
+    // pivot, world coordinates, default zero; a contact with friction > 0 then sticks to the moving surface.  Moving `center` between
+    // frames does not set it.  Must stay zero on a CollisionBody (the library refuses it there).
+    Vector3d lin_velocity = Vector3d(0, 0, 0), ang_velocity = Vector3d(0, 0, 0), pivot = Vector3d(0, 0, 0);
 };
 class CollisionFloor : public CollisionShape {
 public:
@@ -278,12 +282,21 @@ public:
         vertices = verts;
         ++version;
     }
+    // one velocity per vertex [nv][3] for the friction rule (admm_hip_set_collision_mesh_velocity), an empty vector: none again; System's
+    // step() hands a change to its context.  Throws std::runtime_error for another count.
+    void set_vertex_velocities(const std::vector<double> &vel) {
+        if (!vel.empty() && vel.size() != vertices.size()) throw std::runtime_error("CollisionMesh::set_vertex_velocities: " + std::to_string(vel.size() / 3) + " velocities given, the mesh has " + std::to_string(vertices.size() / 3) + " vertices");
+        velocities = vel;
+        ++vel_version;
+    }
     double isColliding(Vector3d pos) const { double pr[3], sd; query(pos, pr, sd); return sd; }
     Vector3d projectOut(const Vector3d currPos) const { double pr[3], sd; query(currPos, pr, sd); return Vector3d(pr[0], pr[1], pr[2]); }
     int shape_type() const { return typeid(*this) == typeid(CollisionMesh) ? ADMM_SHAPE_MESH : -1; }
     std::shared_ptr<admm_hip_mesh> mesh;
     std::vector<double> vertices;          // the current positions
     long version;                          // set_vertices calls so far
+    std::vector<double> velocities;        // the vertices' velocities (empty: none)
+    long vel_version = 0;                  // set_vertex_velocities calls so far
 private:
     void query(const Vector3d &p, double *pr, double &sd) const {
         const double t[3] = {center[0], center[1], center[2]}, q[3] = {p[0], p[1], p[2]};
@@ -304,6 +317,9 @@ public:
     int shape_type() const { return typeid(*this) == typeid(CollisionBody) ? ADMM_SHAPE_MESH : -1; }
     int node_first, node_count;
     std::vector<int> tris;
+    // the Coulomb coefficient of contacts with this surface (admm_hip_set_body_surface_friction): a property of the body, whatever list
+    // names it; the surface's velocity at a contact is its nodes'.  `friction` (the per-entry coefficient) stays refused on a CollisionBody.
+    double surface_friction = 0.0;
 };
 
 // One force over ALL nodes (CollisionForce.hpp:31-46).  With analytic shapes only: a device batch with one element per

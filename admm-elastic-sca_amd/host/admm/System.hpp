@@ -363,6 +363,9 @@ protected:
     std::vector<std::pair<const admm_hip_mesh *, int> > mesh_ids;      // CollisionMesh obstacles registered with the context -> their mesh_id
     std::vector<long> mesh_versions;                                  // ... and the CollisionMesh::version the context last received
     bool friction_pushed = false;                                      // a CollisionShape::friction != 0 went to the context: keep handing the coefficients over
+    bool motion_pushed = false;                                        // ... likewise a nonzero rigid motion
+    std::vector<long> mesh_vel_versions;                               // the CollisionMesh::vel_version the context last received
+    std::vector<double> body_mu;                                       // the CollisionBody::surface_friction the context last received
     std::vector<std::pair<const CollisionBody *, int> > body_ids;     // CollisionBody surfaces registered with the context -> their mesh_id
     std::vector<int> batch_first, batch_count, batch_kind;
     std::vector<char> batch_moving;
@@ -433,6 +436,7 @@ protected:
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
         mesh_ids.clear(); mesh_versions.clear(); body_ids.clear(); friction_pushed = false;
+        motion_pushed = false; mesh_vel_versions.clear(); body_mu.clear();
         initialized = false;
     }
 
@@ -451,6 +455,11 @@ protected:
                     const std::vector<int32_t> t(cb.tris.begin(), cb.tris.end());
                     if (!check(admm_hip_add_body_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), &id))) return false;
                     body_ids.push_back(std::make_pair(&cb, id));
+                    body_mu.push_back(0.0);
+                }
+                if (body_mu[k] != cb.surface_friction) {
+                    if (!check(admm_hip_set_body_surface_friction(gpu, body_ids[k].second, cb.surface_friction))) return false;
+                    body_mu[k] = cb.surface_friction;
                 }
                 par.push_back((double)body_ids[k].second);
             } else if (sh.shape_type() == ADMM_SHAPE_MESH) {      // a mesh: registered with the context once (before finalize), then named by its id
@@ -463,9 +472,15 @@ protected:
                     if (!check(admm_hip_add_collision_mesh(gpu, m, &id))) return false;
                     mesh_ids.push_back(std::make_pair(m, id));
                     mesh_versions.push_back(cm.version);
+                    mesh_vel_versions.push_back(0);
                 } else if (mesh_versions[k] != cm.version) {      // deformed since the context last saw it (CollisionMesh::set_vertices)
                     if (!check(admm_hip_update_collision_mesh(gpu, mesh_ids[k].second, (int)(cm.vertices.size() / 3), cm.vertices.data()))) return false;
                     mesh_versions[k] = cm.version;
+                }
+                // its vertex velocities, once the context is finalized (the library takes them from then on: step() calls this every frame)
+                if (initialized && mesh_vel_versions[k] != cm.vel_version) {
+                    if (!check(admm_hip_set_collision_mesh_velocity(gpu, mesh_ids[k].second, (int)(cm.velocities.size() / 3), cm.velocities.empty() ? nullptr : cm.velocities.data()))) return false;
+                    mesh_vel_versions[k] = cm.vel_version;
                 }
                 par.push_back((double)mesh_ids[k].second);
             } else {
@@ -477,9 +492,23 @@ protected:
         std::vector<double> mu;
         bool any = false;
         for (size_t q = 0; q < cf->collisionShapes.size(); ++q) { mu.push_back(cf->collisionShapes[q]->friction); any = any || mu.back() != 0.0; }
-        if (!any && !friction_pushed) return true;
-        friction_pushed = true;
-        return check(admm_hip_set_collision_friction(gpu, (int)mu.size(), mu.data()));
+        if (any || friction_pushed) {
+            friction_pushed = true;
+            if (!check(admm_hip_set_collision_friction(gpu, (int)mu.size(), mu.data()))) return false;
+        }
+        // ... and their rigid motions, the same way
+        std::vector<double> mo;
+        bool moving = false;
+        for (size_t q = 0; q < cf->collisionShapes.size(); ++q) {
+            const CollisionShape &sh = *cf->collisionShapes[q];
+            for (int j = 0; j < 3; ++j) mo.push_back(sh.lin_velocity[j]);
+            for (int j = 0; j < 3; ++j) mo.push_back(sh.ang_velocity[j]);
+            for (int j = 0; j < 3; ++j) mo.push_back(sh.pivot[j]);
+        }
+        for (size_t i = 0; i < mo.size(); ++i) moving = moving || mo[i] != 0.0;
+        if (!moving && !motion_pushed) return true;
+        motion_pushed = true;
+        return check(admm_hip_set_collision_motion(gpu, (int)cf->collisionShapes.size(), mo.data()));
     }
 
     bool check(int rc) {

@@ -163,7 +163,8 @@ int  admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, cons
  *     ADMM iterations.  No read-back: a frame whose positions the update would refuse (non-finite vertex, zero-area triangle,
  *     non-positive volume) keeps the last good surface, is counted, and the step returns ADMM_OK;
  *   - has an owner, its node range: the collision elements of those nodes skip the mesh (every interior node is inside its own body).
- * Self-collision within one body, open surfaces, edge-edge contact and friction against a body surface are out of scope.
+ * Self-collision within one body, open surfaces and edge-edge contact are out of scope.  Friction against a body surface:
+ * admm_hip_set_body_surface_friction below; it acts on the node in contact only, the surface's own nodes feel no reaction from it.
  *   admm_hip_add_body_surface  before finalize; tris [n_tris][3] are global node ids, all inside [node_first, node_first + node_count).
  *                           Vertices: the distinct referenced nodes in ascending id order, at their current positions (admm_hip_add_nodes
  *                           / admm_hip_set_x); triangles in the given order, renumbered.  Validated like admm_hip_mesh_create, with the
@@ -192,9 +193,9 @@ int  admm_hip_collision_mesh_copy(admm_hip_ctx *ctx, int mesh_id, admm_hip_mesh 
  *     |t| <= lim:  p' <- p' - t              stick: tangentially back where the frame started
  *     else      :  p' <- p' - (lim / |t|) t  slip: pulled back by the cone's radius
  * and the next shape of the list starts from the new p'.  mu = +inf always sticks.  The result is not projected onto the shape again: on
- * a curved surface it sits off the surface by O(|t|^2 / R), which the next ADMM iteration corrects.  Obstacles count as at rest: a shape
- * or mesh that the caller moves between frames gets no velocity term, and an entry that names a body surface takes no coefficient
- * (contact with a moving simulated surface needs its velocity: out of scope).
+ * a curved surface it sits off the surface by O(|t|^2 / R), which the next ADMM iteration corrects.  By default obstacles count as at
+ * rest; "friction against moving obstacles" below gives them a motion.  An entry that names a body surface takes no coefficient from this
+ * list (the surface's own: admm_hip_set_body_surface_friction).
  *   admm_hip_set_collision_friction  mu [n_shapes], n_shapes = the length of the current list; before or after finalize, between frames.
  *                           ADMM_ERR_ARG (admm_hip_last_error names the entry): a negative or NaN coefficient, another count, a nonzero
  *                           coefficient on a body-surface entry (also checked at finalize, and by admm_hip_set_collision_shapes after
@@ -210,6 +211,51 @@ int  admm_hip_collision_mesh_copy(admm_hip_ctx *ctx, int mesh_id, admm_hip_mesh 
  *                           may be NULL.  The device's kernel runs the same code and gives the same bits.                            */
 int  admm_hip_set_collision_friction(admm_hip_ctx *ctx, int n_shapes, const double *mu);
 int  admm_hip_friction_query(int64_t n, const double *p, const double *p_out, const double *x0, const double *mu, double *result, int32_t *mode);
+
+/* ---- friction against moving obstacles and body surfaces ---------------------------------------------------------------------------
+ * Extension, no reference counterpart.  Moving a shape or a mesh between frames (admm_hip_set_collision_shapes,
+ * admm_hip_update_collision_mesh) does not by itself tell the friction rule that the obstacle moves.  With the displacement w of the
+ * obstacle's surface over the frame at the contact, one line of the rule above changes:   r = (p' - x0) - w   (per component, in that
+ * order); stick then means tangentially where the node would be had it ridden on the surface for the frame.  w = 0 gives the same bits.
+ * w has two sources, both zero by default and both evaluated at the contact c = p' (where the shape put the point, world coordinates):
+ *   rigid motion of a list entry, nine doubles { a (linear velocity), om (angular velocity), o (pivot) }, any entry type:
+ *       e = c - o;   x = (om1 e2 - om2 e1,  om2 e0 - om0 e2,  om0 e1 - om1 e0), each a difference of two rounded products;
+ *       w_rigid_j = dt * (a_j + x_j)                                   dt: the context's timestep
+ *   per-vertex velocities of a mesh, interpolated at the hit with the barycentric weights b of the closest point on the winning triangle
+ *   (vertex region: 1 on that corner; edge: (1 - t, t); face: (1 - sv - sw, sv, sw) with 1 - sv - sw = (1 - sv) - sw; t, sv, sw the
+ *   expressions of the closest-point routine), the corners' vertex ids in the triangle's canonical order (lowest vertex id first):
+ *       vi_j = b0 va_j + (b1 vb_j + b2 vc_j);   w_vertex_j = dt * vi_j
+ *   an entry whose mesh has vertex velocities:  w_j = w_rigid_j + w_vertex_j;  every other entry:  w = w_rigid.
+ * All of it without fused multiply-adds, the same on the host and the device.
+ *   admm_hip_set_collision_motion  motion [n_shapes][9], n_shapes = the length of the current list; before or after finalize, between
+ *                           frames.  ADMM_ERR_ARG (the entry named): another count, a non-finite value, a nonzero motion on an entry that
+ *                           names a body surface (also checked at finalize and, for kept motions, by admm_hip_set_collision_shapes).
+ *                           admm_hip_set_collision_shapes keeps the motions when the list's length is unchanged and zeroes them when it
+ *                           changes, as it does the coefficients.
+ *   admm_hip_set_collision_mesh_velocity  vel [nv][3] for a registered obstacle mesh, after finalize (ADMM_ERR_STATE before), between
+ *                           frames; NULL clears them (nv is then ignored).  ADMM_ERR_ARG: another nv, a non-finite value (the vertex
+ *                           named), a body surface.  The first call for a mesh allocates its device buffer and drops the captured graphs;
+ *                           admm_hip_step never allocates.
+ *   admm_hip_set_body_surface_friction  the coefficient mu >= 0 (+inf allowed) of a body surface, a property of the body: it applies to
+ *                           every entry that names the surface; before or after finalize.  ADMM_ERR_ARG on a mesh that is not a body
+ *                           surface or a negative / NaN mu.  The surface's vertex velocities are its nodes' frame-start v (before the
+ *                           explicit forces), gathered beside its vertices at the start of every admm_hip_step; a refused frame keeps the
+ *                           last good surface and the velocities that went with it; admm_hip_local_step_only / _dx use both as finalize
+ *                           (v = 0) or the last admm_hip_step left them.  One-sided like the push itself: the node in contact feels the
+ *                           friction, the surface's nodes no reaction; two bodies that list each other's surfaces get friction both ways.
+ * The collision batches launch the moving form of the friction kernel when an entry with mu > 0 has a nonzero motion or a mesh with
+ * velocities set, or a body surface named in the list has a coefficient above 0; otherwise exactly what they launched before (the same
+ * bits).  The values live in device memory and change under a captured graph; a call that changes the launched kernels drops the graphs.
+ * Every rank of a sharded run makes the same calls (both shard modes hold the full frame-start x and v): no collective is involved.
+ *   admm_hip_friction_query_moving  admm_hip_friction_query with w [n][3]; the same bits as the device.
+ *   admm_hip_mesh_velocity_query    host evaluation of the interpolation for n points q [n][3] against the instance translated by t[3]:
+ *                           out [n][3] = vi at the closest point (vel [nv][3]; may be NULL with out), weights [n][3] = b, corner_ids
+ *                           [n][3] = the winning triangle's vertex ids; any output may be NULL.  The same bits as the device.        */
+int  admm_hip_set_collision_motion(admm_hip_ctx *ctx, int n_shapes, const double *motion);
+int  admm_hip_set_collision_mesh_velocity(admm_hip_ctx *ctx, int mesh_id, int nv, const double *vel);
+int  admm_hip_set_body_surface_friction(admm_hip_ctx *ctx, int mesh_id, double mu);
+int  admm_hip_friction_query_moving(int64_t n, const double *p, const double *p_out, const double *x0, const double *w, const double *mu, double *result, int32_t *mode);
+int  admm_hip_mesh_velocity_query(const admm_hip_mesh *mesh, int64_t n, const double *q, const double t[3], const double *vel, double *out, double *weights, int32_t *corner_ids);
 
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
