@@ -25,7 +25,8 @@ KIND_NODES = [1, 2, 4, 4, 4, 4, 3, 4, 1, 3, 3]
 KIND_ROWS = [3, 3, 9, 9, 9, 9, 6, 9, 3, 6, 6]
 KIND_PARAMS = [2, 1, 1, 3, 3, 3, 4, 1, 1, 4, 3]
 KIND_STATE = [0, 0, 0, 0, 4, 4, 0, 0, 0, 0, 4]
-SHAPE = dict(FLOOR=0, SPHERE=1, CYLINDER=2, MESH=3)
+SHAPE = dict(FLOOR=0, SPHERE=1, CYLINDER=2, MESH=3, BOX=4)
+SHAPE_BOX = SHAPE["BOX"]
 EXPLICIT = dict(CONST=0, WIND=1)
 
 _dp = C.POINTER(C.c_double)
@@ -164,6 +165,9 @@ def lib():
         L.admm_hip_set_body_surface_friction.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.admm_hip_friction_query_moving.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _ip]
         L.admm_hip_mesh_velocity_query.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip]
+        L.admm_hip_set_collision_frames.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.admm_hip_shape_query.argtypes = [C.c_int, _dp, _dp, C.c_int64, _dp, _dp, _ip]
+        L.admm_hip_mesh_query_framed.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, _dp, _dp, _dp]
         _lib = L
     return _lib
 
@@ -199,11 +203,18 @@ class Mesh:
             self.L.admm_hip_mesh_destroy(self.h)
             self.h = None
 
-    def query(self, pts, t=(0.0, 0.0, 0.0)):
-        """-> (proj [n][3], sdist [n]) for the instance translated by t: proj = t + the closest point, sdist > 0 inside (host evaluation)"""
+    def query(self, pts, t=(0.0, 0.0, 0.0), frame=None):
+        """-> (proj [n][3], sdist [n]) for the instance translated by t: proj = t + the closest point, sdist > 0 inside (host evaluation);
+        frame [12] = (R row-major, pivot): the instance rotated by R about the pivot (admm_hip_mesh_query_framed), proj in world coordinates"""
         p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
         tt = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
         proj = np.empty_like(p); sd = np.empty(p.shape[0])
+        if frame is not None:
+            f = frame_array(frame)
+            rc = self.L.admm_hip_mesh_query_framed(self.h, _d(tt), _d(f), p.shape[0], _d(p), _d(proj), _d(sd))
+            if rc != 0:
+                raise AdmmHipError("admm_hip_mesh_query_framed error %d" % rc)
+            return proj, sd
         rc = self.L.admm_hip_mesh_query(self.h, _d(tt), p.shape[0], _d(p), _d(proj), _d(sd))
         if rc != 0:
             raise AdmmHipError("admm_hip_mesh_query error %d" % rc)
@@ -225,9 +236,30 @@ class Mesh:
         return dict(n_tris=nt.value, n_nodes=nn.value, depth=dep.value, lo=box[:3].copy(), hi=box[3:].copy())
 
 
-def mesh_query(verts, tris, pts, t=(0.0, 0.0, 0.0)):
-    """closest points and signed distances of pts to the closed mesh (verts, tris) translated by t -> (proj, sdist), sdist > 0 inside"""
-    return Mesh(verts, tris).query(pts, t)
+def mesh_query(verts, tris, pts, t=(0.0, 0.0, 0.0), frame=None):
+    """closest points and signed distances of pts to the closed mesh (verts, tris; a Mesh for verts: tris ignored) translated by t and, with
+    frame [12], rotated about its pivot -> (proj, sdist), sdist > 0 inside"""
+    return (verts if isinstance(verts, Mesh) else Mesh(verts, tris)).query(pts, t, frame)
+
+
+def frame_array(frame):
+    """one frame as the ABI takes it, 12 doubles (R row-major, pivot), from that or from a pair (R [3][3], pivot [3])"""
+    if isinstance(frame, (tuple, list)) and len(frame) == 2:
+        frame = np.concatenate([np.asarray(frame[0], dtype=np.float64).reshape(9), np.asarray(frame[1], dtype=np.float64).reshape(3)])
+    return np.ascontiguousarray(frame, dtype=np.float64).reshape(12)
+
+
+def shape_query(type_, params, pts, frame=None):
+    """one analytic entry of a shape list (floor, sphere, cylinder, box) with its frame on the host (admm_hip_shape_query) ->
+    (out [n][3]: the points after the entry, moved [n] bool); the device's kernels give the same bits"""
+    p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+    par = np.ascontiguousarray(params, dtype=np.float64).reshape(4)
+    f = None if frame is None else frame_array(frame)
+    out = np.empty_like(p); moved = np.empty(p.shape[0], np.int32)
+    rc = lib().admm_hip_shape_query(int(type_), _d(par), _d(f), p.shape[0], _d(p), _d(out), _i(moved))
+    if rc != 0:
+        raise AdmmHipError("admm_hip_shape_query error %d" % rc)
+    return out, moved.astype(bool)
 
 
 def friction_query(p, p_out, x0, mu):
@@ -419,12 +451,25 @@ class System:
         t = np.ascontiguousarray(types, dtype=np.int32)
         p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 4)
         self._chk(self.L.admm_hip_set_collision_shapes(self.h, t.size, _i(t), _d(p)))
+        self._n_shapes = int(t.size)
 
     def set_collision_friction(self, mu):
         """one Coulomb coefficient >= 0 per entry of the current shape list (admm_hip_set_collision_friction); before or after
         initialize, between frames.  All zero (the default): the frictionless kernels."""
         m = np.ascontiguousarray(mu, dtype=np.float64).ravel()
         self._chk(self.L.admm_hip_set_collision_friction(self.h, m.size, _d(m)))
+
+    def set_collision_frames(self, frames):
+        """the rigid frame of every entry of the current shape list (admm_hip_set_collision_frames): [n_shapes][12] = R (row-major), pivot;
+        the entry's shape is rotated by R about the pivot, and a box is centred at it.  None: every entry back to the identity."""
+        if frames is None:
+            self._chk(self.L.admm_hip_set_collision_frames(self.h, self.n_collision_shapes(), None))
+            return
+        f = np.ascontiguousarray(frames, dtype=np.float64).reshape(-1, 12)
+        self._chk(self.L.admm_hip_set_collision_frames(self.h, f.shape[0], _d(f)))
+
+    def n_collision_shapes(self):
+        return getattr(self, "_n_shapes", 0)
 
     def set_collision_motion(self, motion):
         """the rigid motion of every entry of the current shape list (admm_hip_set_collision_motion): [n_shapes][9] = linear velocity,

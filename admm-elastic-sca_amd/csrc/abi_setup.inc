@@ -1,6 +1,13 @@
 // abi_setup.inc -- C ABI: context, nodes, batches, explicit forces, shapes, sharding, finalize (System::add_nodes / forces.push_back / initialize)
 // (a part of the device translation unit admm_hip.hip: the kernels can live in one translation unit only)
 
+// every entry's frame back to the identity about the origin
+static void reset_frames(admm_hip_ctx *ctx) {
+    for (int j = 0; j < ADMM_MAX_SHAPES; ++j) {
+        for (int k = 0; k < 12; ++k) ctx->shapes.frame[j][k] = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
+        ctx->shapes.framed[j] = 0;
+    }
+}
 
 int admm_hip_create(admm_hip_ctx **out, int device_id) {
     if (!out) return ADMM_ERR_ARG;
@@ -20,6 +27,7 @@ int admm_hip_create(admm_hip_ctx **out, int device_id) {
         ctx->own_stream = true;
     }
     ctx->info.device_id = device_id; ctx->info.world = 1;
+    reset_frames(ctx);
     const char *ls = getenv("ADMM_HIP_LEAF");
     if (ls && atoi(ls) > 0) ctx->leaf_size = atoi(ls);
     if (const char *g = getenv("ADMM_HIP_GRAPH")) { ctx->graph_enabled = atoi(g) != 0; ctx->graph_forced = ctx->graph_enabled; }
@@ -234,28 +242,46 @@ static int check_body_motion(admm_hip_ctx *ctx, int n_shapes, const int32_t *typ
     }
     return ADMM_OK;
 }
+// ... and no frame: it sits where its nodes are (frames: [n_shapes][12]; the identity rotation passes whatever its pivot)
+static int check_body_frames(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params, const double *frames) {
+    for (int j = 0; j < n_shapes; ++j) {
+        if (types[j] != ADMM_SHAPE_MESH || admm_frame::identity(frames + 12 * (size_t)j)) continue;
+        const int id = (int)params[4 * (size_t)j + 3];
+        if (id >= 0 && id < (int)ctx->mesh_role.size() && !ctx->mesh_role[id].body_nodes.empty())
+            return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which follows its nodes: its frame must be the identity", j, id);
+    }
+    return ADMM_OK;
+}
 int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
     if (!ctx || n_shapes < 0 || (n_shapes && (!types || !params))) return ADMM_ERR_ARG;
     if (n_shapes > ADMM_MAX_SHAPES) return fail(ctx, ADMM_ERR_UNSUPPORTED, "at most %d collision shapes", ADMM_MAX_SHAPES);
-    for (int j = 0; j < n_shapes; ++j)      // (checked before the table changes: a refused list leaves the last good one in place)
+    for (int j = 0; j < n_shapes; ++j) {      // (checked before the table changes: a refused list leaves the last good one in place)
+        if (types[j] < ADMM_SHAPE_FLOOR || types[j] > ADMM_SHAPE_BOX) return fail(ctx, ADMM_ERR_UNSUPPORTED, "collision shape type %d", types[j]);
         if (types[j] == ADMM_SHAPE_MESH) {
             const double id = params[4 * (size_t)j + 3];
             if (!(id >= 0.0 && id < (double)ctx->meshes.size() && id == (double)(int)id))
                 return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh_id %g is not a registered mesh (have %d)", j, id, (int)ctx->meshes.size());
         }
+        if (types[j] == ADMM_SHAPE_BOX)
+            for (int k = 0; k < 3; ++k) {
+                const double h = params[4 * (size_t)j + k];
+                if (!(h > 0.0 && std::isfinite(h))) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: the box's half extent %d is %g: it must be positive and finite", j, k, h);
+            }
+    }
     TRY(check_body_translations(ctx, n_shapes, types, params));
     // (a list of the same length keeps its coefficients: one that now names a body surface where a coefficient is set is refused here
     //  once finalized, by finalize before)
     if (ctx->finalized && n_shapes == ctx->shapes.n) TRY(check_body_friction(ctx, n_shapes, types, params, ctx->shapes.mu));
     if (n_shapes == ctx->shapes.n) TRY(check_body_motion(ctx, n_shapes, types, params, &ctx->shapes.motion[0][0]));      // (kept motions likewise)
+    if (n_shapes == ctx->shapes.n) TRY(check_body_frames(ctx, n_shapes, types, params, &ctx->shapes.frame[0][0]));       // (and kept frames)
     const int form = collision_form(ctx);
-    if (n_shapes != ctx->shapes.n) {      // a list of another length: its coefficients and motions start at 0 (the same length keeps them)
+    if (n_shapes != ctx->shapes.n) {      // a list of another length: its coefficients and motions start at 0, its frames at the identity (the same length keeps them)
         for (double &m : ctx->shapes.mu) m = 0.0;
         for (auto &m : ctx->shapes.motion) for (double &c : m) c = 0.0;
+        reset_frames(ctx);
     }
     ctx->shapes.n = n_shapes;
     for (int j = 0; j < n_shapes; ++j) {
-        if (types[j] < ADMM_SHAPE_FLOOR || types[j] > ADMM_SHAPE_MESH) return fail(ctx, ADMM_ERR_UNSUPPORTED, "collision shape type %d", types[j]);
         ctx->shapes.type[j] = types[j];
         for (int q = 0; q < 4; ++q) ctx->shapes.par[j][q] = params[4 * (size_t)j + q];
     }
@@ -280,6 +306,35 @@ int admm_hip_set_collision_friction(admm_hip_ctx *ctx, int n_shapes, const doubl
     TRY(check_body_friction(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], mu));
     const int form = collision_form(ctx);
     for (int j = 0; j < n_shapes; ++j) ctx->shapes.mu[j] = mu[j];
+    if (ctx->finalized && ctx->device_id >= 0) {
+        HIPCHK(hipSetDevice(ctx->device_id));
+        HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (form != collision_form(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
+    }
+    return ADMM_OK;
+}
+
+// extension, no reference counterpart (include/admm_hip.h): the rigid frame of every entry of the current list (NULL: the identity)
+int admm_hip_set_collision_frames(admm_hip_ctx *ctx, int n_shapes, const double *frames) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (n_shapes != ctx->shapes.n) return fail(ctx, ADMM_ERR_ARG, "collision frames: %d frames given, the shape list has %d entries", n_shapes, ctx->shapes.n);
+    if (frames) {
+        for (int j = 0; j < n_shapes; ++j) {
+            int which = 0; double by = 0.0;
+            const int bad = admm_frame::check(frames + 12 * (size_t)j, &which, &by);
+            if (bad == 1) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: frame component %d is not finite (%g)", j, which, by);
+            if (bad == 2 && which < 9) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: its frame's R is not a rotation: element (%d, %d) of R^T R - I is %g, beyond 1e-12", j, which / 3, which % 3, by);
+            if (bad == 2) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: its frame's R is not a rotation: det R - 1 is %g, beyond 1e-12", j, by);
+        }
+        TRY(check_body_frames(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], frames));
+    }
+    const int form = collision_form(ctx);
+    if (!frames) reset_frames(ctx);
+    else for (int j = 0; j < n_shapes; ++j) {
+        for (int k = 0; k < 12; ++k) ctx->shapes.frame[j][k] = frames[12 * (size_t)j + k];
+        ctx->shapes.framed[j] = admm_frame::identity(ctx->shapes.frame[j]) ? 0 : 1;
+    }
     if (ctx->finalized && ctx->device_id >= 0) {
         HIPCHK(hipSetDevice(ctx->device_id));
         HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
@@ -574,6 +629,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     TRY(check_body_translations(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
     TRY(check_body_friction(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], ctx->shapes.mu));
     TRY(check_body_motion(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], &ctx->shapes.motion[0][0]));
+    TRY(check_body_frames(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], &ctx->shapes.frame[0][0]));
     for (int j = 0; j < ctx->shapes.n; ++j)
         if (!(ctx->shapes.mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, ctx->shapes.mu[j]);
     TRY(host_assemble(ctx, false));

@@ -19,8 +19,13 @@ struct Gravity { int n; double g[MAX_GRAV][3]; };
 // analytic collision shapes of a CollisionForce (collision/*.hpp), tested in list order by project_collision_block;
 // mu: every entry's Coulomb friction coefficient (admm_hip_set_collision_friction; all zero: the frictionless kernels run);
 // motion: every entry's rigid motion { linear velocity, angular velocity, pivot } (admm_hip_set_collision_motion; read by the moving
-// form of the friction kernel only, behind the fields the other kernels read)
-struct ShapeTable { int n; int type[ADMM_MAX_SHAPES]; double par[ADMM_MAX_SHAPES][4]; double mu[ADMM_MAX_SHAPES]; double motion[ADMM_MAX_SHAPES][9]; };
+// form of the friction kernel only, behind the fields the other kernels read);
+// frame: every entry's rigid frame { R row-major, pivot } (admm_hip_set_collision_frames; frame.hpp), framed: R is not the identity --
+// read by project_collision_framed_kernel only, which a list with a framed entry or a box launches, behind everything else
+struct ShapeTable {
+    int n; int type[ADMM_MAX_SHAPES]; double par[ADMM_MAX_SHAPES][4]; double mu[ADMM_MAX_SHAPES]; double motion[ADMM_MAX_SHAPES][9];
+    double frame[ADMM_MAX_SHAPES][12]; int framed[ADMM_MAX_SHAPES];
+};
 
 // One work item of a sweep launch with everything the block needs to start, in one 64-byte record
 // (one scalar load instead of an index load followed by six dependent per-supernode loads).

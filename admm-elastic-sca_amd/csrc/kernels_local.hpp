@@ -32,6 +32,7 @@
 #include "dev_types.hpp"
 #include "mesh_query.hpp"
 #include "friction.hpp"
+#include "frame.hpp"
 #include "../../include/admm_kinds.h"
 
 namespace admm_dev {
@@ -390,21 +391,11 @@ void project_tet_kernel(BatchDev b, const double *__restrict__ x, BatchDev tail,
 // the point Dx+u is pushed out of every analytic shape it penetrates, in list
 // order (CollisionFloor.hpp:51-58, CollisionSphere.hpp:50-66, CollisionCylinder.hpp:48-66)
 // ---------------------------------------------------------------------------
-// one analytic shape of the list (floor, sphere, z-cylinder) pushes p out; shared by project_collision_block and project_collision_mesh_kernel
+// one analytic shape of the list (floor, sphere, z-cylinder: frame.hpp collide_round, which names each of them) pushes p out; shared by
+// project_collision_block and project_collision_mesh_kernel.  A list with a box or a framed entry never comes here (launch.inc framed_on).
 __device__ __forceinline__ void collide_analytic(const ShapeTable *__restrict__ shapes, const int q, double p[3]) {
     const double c0 = shapes->par[q][0], c1 = shapes->par[q][1], c2 = shapes->par[q][2], R = shapes->par[q][3];
-    const int ty = shapes->type[q];
-    if (ty == ADMM_SHAPE_FLOOR) {
-        if (c1 - p[1] > 0) p[1] = c1;
-    } else if (ty == ADMM_SHAPE_SPHERE) {
-        const double d0 = p[0] - c0, d1 = p[1] - c1, d2 = p[2] - c2;
-        const double nrm = sqrt(d0 * d0 + (d1 * d1 + d2 * d2));
-        if (R - nrm > 0) { p[0] = c0 + R * (d0 / nrm); p[1] = c1 + R * (d1 / nrm); p[2] = c2 + R * (d2 / nrm); }
-    } else {
-        const double d0 = p[0] - c0, d1 = p[1] - c1, d2 = 0.0 - 0.0;
-        const double nrm = sqrt(d0 * d0 + (d1 * d1 + d2 * d2));
-        if (R - nrm > 0) { const double pz = p[2]; p[0] = (c0 + R * (d0 / nrm)) + 0.0; p[1] = (c1 + R * (d1 / nrm)) + 0.0; p[2] = (0.0 + R * (d2 / nrm)) + pz; }
-    }
+    admm_frame::collide_round(shapes->type[q], c0, c1, c2, R, p);
 }
 __device__ __forceinline__ void project_collision_block(const BatchDev &b, const double *__restrict__ x, const ShapeTable *__restrict__ shapes, const int lb) {
     const int e = b.e0 + lb * LOCAL_BLOCK + threadIdx.x;
@@ -591,6 +582,89 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_friction_moving
         admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
         if (vhit) { w[0] = w[0] + dt * vi0; w[1] = w[1] + dt * vi1; w[2] = w[2] + dt * vi2; }
         admm_friction::apply_moving(before, p, x0, w, mu);      // (a shape that did not move the point: depth 0, nothing happens)
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double un = u[j] + (dx[j] - p[j]);
+        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
+        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
+    }
+}
+
+// ... with a rigid frame per entry and the oriented box (frame.hpp; a context where framed_on holds, launch.inc, launches this form for
+// its collision batches whatever else the list holds; every kernel above stays as it is).  One lane per node.  For an entry whose frame
+// is not the identity (shapes->framed, uniform across the wave) the candidate goes to local coordinates, the entry's unframed code runs
+// there -- collide_round or collide_box, or for a mesh the box test, closest and inside with the translation t -- and only a point that
+// code moved goes back to world coordinates; every other point keeps its bits.  Then, for mu > 0, the moving form of the friction rule on
+// the world-space before, p', x0 and w as in project_collision_friction_moving_kernel (a zero motion gives w = 0 and the bits of the rule
+// at rest); a framed mesh's interpolated vertex velocity is in the mesh's own coordinates and is rotated by R first.  mm: null without
+// meshes.
+template <bool MESH>
+__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_framed_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
+                                                                               const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
+                                                                               const admm_mesh::MeshMotion *__restrict__ mm, const int *__restrict__ tag, const double dt) {
+    __shared__ int stack[MESH ? admm_mesh::MAX_DEPTH : 1][LOCAL_BLOCK];
+    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
+    const int n = b.n;
+    if (e >= b.e1) return;
+    const int id = b.idx[e];
+    const int ds = b.dst[e];
+    const double s = b.w2h2[e];
+    double dx[3], u[3], p[3], x0[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
+        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
+        x0[j] = xs[3 * (size_t)id + j];
+        u[j] = b.u[(size_t)j * n + e];
+        p[j] = dx[j] + u[j];
+    }
+    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
+    const int own = (MESH && tag) ? tag[id] : -1;
+    const int ns = shapes->n;
+    for (int q = 0; q < ns; ++q) {
+        const double before[3] = {p[0], p[1], p[2]};
+        const double *f = shapes->frame[q];
+        const bool framed = shapes->framed[q] != 0;
+        const int ty = shapes->type[q];
+        double mu = shapes->mu[q];
+        double vi[3] = {0.0, 0.0, 0.0};      // the mesh's vertex velocities at the hit, world axes
+        bool vhit = false;
+        if (!MESH || ty != ADMM_SHAPE_MESH) {
+            if (!admm_frame::collide_entry(ty, shapes->par[q], f, framed, p)) continue;
+        } else {
+            const int mi = (int)shapes->par[q][3];
+            const admm_mesh::MeshDev m = meshes[mi];
+            if (own >= 0 && m.owner == own) continue;
+            double l[3] = {p[0], p[1], p[2]};
+            if (framed) admm_frame::to_local(f, p, l);
+            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
+            const double qq[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
+            if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
+            admm_mesh::Hit h;
+            admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
+            if (!(admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0)) continue;
+            l[0] = t[0] + h.c[0]; l[1] = t[1] + h.c[1]; l[2] = t[2] + h.c[2];
+            if (framed) admm_frame::to_world(f, l, p); else { p[0] = l[0]; p[1] = l[1]; p[2] = l[2]; }
+            const admm_mesh::MeshMotion mo = mm[mi];
+            if (mo.body) mu = mo.mu;
+            if (mo.vel && mu > 0.0) {
+                const admm_mesh::Tri &tr = m.tris[h.slot];
+                const int *c = mo.cid + 3 * (size_t)tr.orig;
+                const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
+                const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
+                double bw[3];
+                admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
+                vi[0] = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi[1] = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi[2] = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
+                if (framed) admm_frame::rotate(f, vi, vi);
+                vhit = true;
+            }
+        }
+        if (!(mu > 0.0)) continue;
+        double w[3];
+        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
+        if (vhit) { w[0] = w[0] + dt * vi[0]; w[1] = w[1] + dt * vi[1]; w[2] = w[2] + dt * vi[2]; }
+        admm_friction::apply_moving(before, p, x0, w, mu);
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {

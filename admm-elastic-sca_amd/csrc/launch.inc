@@ -37,8 +37,18 @@ bool moving_friction_on(const admm_hip_ctx *ctx) {
     }
     return false;
 }
-// which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form
-int collision_form(const admm_hip_ctx *ctx) { return moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
+// ... and does the list hold an entry whose frame is not the identity (admm_hip_set_collision_frames) or a box?  Then the collision
+// batches run project_collision_framed_kernel, the one kernel that knows frames and boxes, in a launch of their own, in both launch modes
+// (the fused launch leaves them out like it does with meshes or friction; the per-batch path goes through launch_collision_mesh too).  A
+// framed instantiation beside the kernels, not a flag inside them: every other list launches exactly the kernels it launched before.
+bool framed_on(const admm_hip_ctx *ctx) {
+    for (int q = 0; q < ctx->shapes.n; ++q) if (ctx->shapes.framed[q] || ctx->shapes.type[q] == ADMM_SHAPE_BOX) return true;
+    return false;
+}
+// which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form, 3 the framed form
+int collision_form(const admm_hip_ctx *ctx) { return framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
+// ... in a launch of their own (launch_collision_mesh) instead of a segment of project_multi_kernel or project_collision_kernel
+bool collision_own_launch(const admm_hip_ctx *ctx) { return !ctx->meshes.empty() || friction_on(ctx) || framed_on(ctx); }
 
 bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
     using namespace admm_dev;
@@ -69,7 +79,7 @@ bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
         case ADMM_KIND_TRI_STRAIN: code = MK_TRI_STRAIN; break;
         case ADMM_KIND_TRI_AREA: code = MK_TRI_AREA; break;
         case ADMM_KIND_TRI_FUNG: code = MK_TRI_FUNG; break;
-        case ADMM_KIND_COLLISION: if (!ctx->meshes.empty() || friction_on(ctx)) continue; code = MK_COLLISION; break;      // (meshes, friction: own launch, launch_local)
+        case ADMM_KIND_COLLISION: if (collision_own_launch(ctx)) continue; code = MK_COLLISION; break;      // (meshes, friction, frames, boxes: own launch, launch_local)
         default: break;
         }
         if (code < 0 || mb.n == MULTI_MAX) return false;
@@ -152,12 +162,20 @@ int update_bodies(admm_hip_ctx *ctx) {
     return ADMM_OK;
 }
 
-// a collision batch of a context with mesh obstacles or friction
+// a collision batch of a context with mesh obstacles, friction, framed entries or boxes
 void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
-    if (moving_friction_on(ctx)) {      // (a body surface with a coefficient implies meshes, an entry's motion implies friction_on: this launch is reached)
+    if (framed_on(ctx)) {
+        if (!ctx->meshes.empty())
+            hipLaunchKernelGGL(project_collision_framed_kernel<true>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                               (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
+                               (const int *)ctx->d_body_tag, ctx->dt);
+        else
+            hipLaunchKernelGGL(project_collision_framed_kernel<false>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                               (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)nullptr, (const admm_mesh::MeshMotion *)nullptr, (const int *)nullptr, ctx->dt);
+    } else if (moving_friction_on(ctx)) {      // (a body surface with a coefficient implies meshes, an entry's motion implies friction_on: this launch is reached)
         if (!ctx->meshes.empty())
             hipLaunchKernelGGL(project_collision_friction_moving_kernel<true>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
                                (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
@@ -184,7 +202,7 @@ int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
         MultiBatch mb{}; int blocks = 0;
         if (build_multi(ctx, mb, blocks)) {
             hipLaunchKernelGGL(project_multi_kernel, dim3(blocks), dim3(LOCAL_BLOCK), 0, st, mb, (const double *)ctx->d_xcur, (const ShapeTable *)ctx->d_shapes);
-            if (!ctx->meshes.empty() || friction_on(ctx))      // the collision batches were left out of the segments: their own launches
+            if (collision_own_launch(ctx))      // the collision batches were left out of the segments: their own launches
                 for (const Batch &b : ctx->batches) if (b.kind == ADMM_KIND_COLLISION && b.n_local > 0) launch_collision_mesh(ctx, b);
             HIPCHK(hipGetLastError());
             return ADMM_OK;
@@ -232,7 +250,7 @@ int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
         case ADMM_KIND_TRI_AREA: hipLaunchKernelGGL(project_tri_kernel<1>, grid, block, 0, st, d, x); break;
         case ADMM_KIND_TRI_FUNG: hipLaunchKernelGGL(project_tri_kernel<2>, grid, block, 0, st, d, x); break;
         case ADMM_KIND_COLLISION:
-            if (!ctx->meshes.empty() || friction_on(ctx)) launch_collision_mesh(ctx, b);
+            if (collision_own_launch(ctx)) launch_collision_mesh(ctx, b);
             else hipLaunchKernelGGL(project_collision_kernel, grid, block, 0, st, d, x, (const ShapeTable *)ctx->d_shapes);
             break;
         default: return fail(ctx, ADMM_ERR_UNSUPPORTED, "no kernel for kind %d", b.kind);

@@ -1,6 +1,7 @@
 // mesh.cpp -- closed triangle-mesh obstacles on the host: validation, pseudo-normals and the BVH of admm_hip_mesh_create, and
 // admm_hip_mesh_query, the host evaluation of the query the device runs (mesh_query.hpp), and admm_hip_friction_query, the same for
-// the contact friction rule (friction.hpp) and its moving form's vertex-velocity interpolation.  Context-free: a context copies a mesh
+// the contact friction rule (friction.hpp) and its moving form's vertex-velocity interpolation, and admm_hip_shape_query and
+// admm_hip_mesh_query_framed, the same for an entry with a rigid frame and for the box (frame.hpp).  Context-free: a context copies a mesh
 // at admm_hip_add_collision_mesh (abi_setup.inc).  Built with -ffp-contract=off like the device code, so both give the same bits.
 #include <algorithm>
 #include <cmath>
@@ -13,6 +14,7 @@
 #include "../../include/admm_hip.h"
 #include "mesh_host.hpp"
 #include "friction.hpp"
+#include "frame.hpp"
 
 using namespace admm_mesh;
 
@@ -269,6 +271,49 @@ int admm_hip_mesh_query(const admm_hip_mesh *mesh, const double t[3], int64_t n_
         closest(mesh->nodes.data(), mesh->tris.data(), q, stk, h);
         const bool in = inside(mesh->nodes[0], mesh->nrm.data(), q, h);
         if (proj) for (int j = 0; j < 3; ++j) proj[3 * i + j] = t[j] + h.c[j];
+        if (sdist) { const double d = std::sqrt(h.d2); sdist[i] = in ? d : -d; }
+    }
+    return ADMM_OK;
+}
+
+// the host evaluation of one analytic list entry with its frame (frame.hpp collide_entry: what project_collision_framed_kernel runs, and
+// for frame NULL or the identity what the unframed kernels run)
+int admm_hip_shape_query(int type, const double params[4], const double *frame, int64_t n, const double *p, double *out, int32_t *moved) {
+    if (!params || n < 0 || (n && !p)) return ADMM_ERR_ARG;
+    if (type != ADMM_SHAPE_FLOOR && type != ADMM_SHAPE_SPHERE && type != ADMM_SHAPE_CYLINDER && type != ADMM_SHAPE_BOX) return ADMM_ERR_ARG;
+    if (type == ADMM_SHAPE_BOX) for (int k = 0; k < 3; ++k) if (!(params[k] > 0.0 && std::isfinite(params[k]))) return ADMM_ERR_ARG;
+    const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    const double *f = frame ? frame : ident;
+    int which; double by;
+    if (admm_frame::check(f, &which, &by)) return ADMM_ERR_ARG;
+    const bool framed = !admm_frame::identity(f);
+    for (int64_t i = 0; i < n; ++i) {
+        double q[3] = {p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+        const bool mv = admm_frame::collide_entry(type, params, f, framed, q);
+        if (out) for (int j = 0; j < 3; ++j) out[3 * i + j] = q[j];
+        if (moved) moved[i] = mv ? 1 : 0;
+    }
+    return ADMM_OK;
+}
+
+// admm_hip_mesh_query for an instance with a frame: the query runs on q = to_local(p), proj = to_world(t + c); NULL or the identity: the
+// bits of admm_hip_mesh_query
+int admm_hip_mesh_query_framed(const admm_hip_mesh *mesh, const double t[3], const double *frame, int64_t n_pts, const double *pts, double *proj, double *sdist) {
+    if (!mesh || !t || n_pts < 0 || (n_pts && !pts)) return ADMM_ERR_ARG;
+    int which; double by;
+    if (frame && admm_frame::check(frame, &which, &by)) return ADMM_ERR_ARG;
+    if (!frame || admm_frame::identity(frame)) return admm_hip_mesh_query(mesh, t, n_pts, pts, proj, sdist);
+    for (int64_t i = 0; i < n_pts; ++i) {
+        double l[3];
+        admm_frame::to_local(frame, pts + 3 * i, l);
+        const double q[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
+        HostStack stk; Hit h;
+        closest(mesh->nodes.data(), mesh->tris.data(), q, stk, h);
+        const bool in = inside(mesh->nodes[0], mesh->nrm.data(), q, h);
+        if (proj) {
+            const double c[3] = {t[0] + h.c[0], t[1] + h.c[1], t[2] + h.c[2]};
+            admm_frame::to_world(frame, c, proj + 3 * i);
+        }
         if (sdist) { const double d = std::sqrt(h.d2); sdist[i] = in ? d : -d; }
     }
     return ADMM_OK;

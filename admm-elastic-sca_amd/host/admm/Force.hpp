@@ -225,6 +225,18 @@ public:
     // pivot, world coordinates, default zero; a contact with friction > 0 then sticks to the moving surface.  Moving `center` between
     // frames does not set it.  Must stay zero on a CollisionBody (the library refuses it there).
     Vector3d lin_velocity = Vector3d(0, 0, 0), ang_velocity = Vector3d(0, 0, 0), pivot = Vector3d(0, 0, 0);
+    // ... and the shape's rigid frame (admm_hip_set_collision_frames): the shape, as its other members describe it, rotated by
+    // `orientation` (3x3, row-major, a rotation; default the identity) about `orientation_pivot`, world coordinates.  May change between
+    // frames; turning it does not set ang_velocity.  The device applies it; the built-in shapes' host isColliding / projectOut do not,
+    // except CollisionBox's.  Must stay the identity on a CollisionBody (the library refuses it there).
+    double orientation[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    Vector3d orientation_pivot = Vector3d(0, 0, 0);
+    // the twelve doubles of the ABI, about `about`
+    void frame(const Vector3d &about, double *f) const {
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) f[3 * i + j] = orientation[i][j];
+        for (int j = 0; j < 3; ++j) f[9 + j] = about[j];
+    }
+    virtual Vector3d frame_pivot() const { return orientation_pivot; }
 };
 class CollisionFloor : public CollisionShape {
 public:
@@ -256,6 +268,29 @@ public:
     int shape_type() const { return typeid(*this) == typeid(CollisionCylinder) ? ADMM_SHAPE_CYLINDER : -1; }
     double shape_radius() const { return radius; }
     double radius, length;
+};
+
+// Extension, no reference counterpart: a box of half extents `half` centred at `center`, turned by `orientation` about its centre
+// (ADMM_SHAPE_BOX; orientation_pivot is not used: the centre is the pivot).  isColliding / projectOut evaluate the library's rule on
+// the host (admm_hip_shape_query: the code the device runs): isColliding is +1 where the box would move the point and -1 elsewhere.
+class CollisionBox : public CollisionShape {
+public:
+    CollisionBox(Vector3d shapeCenter, Vector3d halfExtents) : CollisionShape(shapeCenter), half(halfExtents) {}
+    double isColliding(Vector3d pos) const { double o[3]; return query(pos, o) ? 1.0 : -1.0; }
+    Vector3d projectOut(const Vector3d currPos) const { double o[3]; query(currPos, o); return Vector3d(o[0], o[1], o[2]); }
+    int shape_type() const { return typeid(*this) == typeid(CollisionBox) ? ADMM_SHAPE_BOX : -1; }
+    Vector3d frame_pivot() const { return center; }
+    Vector3d half;
+private:
+    bool query(const Vector3d &p, double *o) const {
+        const double par[4] = {half[0], half[1], half[2], 0.0}, q[3] = {p[0], p[1], p[2]};
+        double f[12];
+        frame(center, f);
+        int32_t moved = 0;
+        o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+        admm_hip_shape_query(ADMM_SHAPE_BOX, par, f, 1, q, o, &moved);
+        return moved != 0;
+    }
 };
 
 // Extension, no reference counterpart: a closed triangle mesh (verts [nv][3], tris [nt][3], counter-clockwise seen from outside)

@@ -167,6 +167,16 @@ public:
                     }
                 }
             if (f.kind() < 0) {
+                if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))      // a built-in shape's orientation is applied by the device only (CollisionBox applies its own)
+                    for (size_t q = 0; q < cf->collisionShapes.size(); ++q) {
+                        const CollisionShape &sh = *cf->collisionShapes[q];
+                        bool turned = false;
+                        for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) turned = turned || sh.orientation[a][c] != (a == c ? 1.0 : 0.0);
+                        if (turned && !dynamic_cast<const CollisionBox *>(&sh)) {
+                            std::cerr << "\n**Solver Error: force " << i << ", shape " << q << ": an orientation on a force that projects on the host (a user-written shape in its list); it needs the device form of every shape" << std::endl;
+                            return false;
+                        }
+                    }
                 if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))
                     for (size_t q = 0; q < cf->collisionShapes.size(); ++q) if (dynamic_cast<const CollisionBody *>(cf->collisionShapes[q].get())) {
                         std::cerr << "\n**Solver Error: force " << i << " projects on the host (a user-written shape in its list), where a CollisionBody has no evaluation" << std::endl;
@@ -363,6 +373,7 @@ protected:
     std::vector<std::pair<const admm_hip_mesh *, int> > mesh_ids;      // CollisionMesh obstacles registered with the context -> their mesh_id
     std::vector<long> mesh_versions;                                  // ... and the CollisionMesh::version the context last received
     bool friction_pushed = false;                                      // a CollisionShape::friction != 0 went to the context: keep handing the coefficients over
+    bool frames_pushed = false;                                        // ... likewise a frame that is not the identity, or a box
     bool motion_pushed = false;                                        // ... likewise a nonzero rigid motion
     std::vector<long> mesh_vel_versions;                               // the CollisionMesh::vel_version the context last received
     std::vector<double> body_mu;                                       // the CollisionBody::surface_friction the context last received
@@ -436,7 +447,7 @@ protected:
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
         mesh_ids.clear(); mesh_versions.clear(); body_ids.clear(); friction_pushed = false;
-        motion_pushed = false; mesh_vel_versions.clear(); body_mu.clear();
+        motion_pushed = false; frames_pushed = false; mesh_vel_versions.clear(); body_mu.clear();
         initialized = false;
     }
 
@@ -483,11 +494,28 @@ protected:
                     mesh_vel_versions[k] = cm.vel_version;
                 }
                 par.push_back((double)mesh_ids[k].second);
+            } else if (sh.shape_type() == ADMM_SHAPE_BOX) {       // a box: its half extents; its centre goes into the frame below
+                const CollisionBox &bx = static_cast<const CollisionBox &>(sh);
+                for (int j = 0; j < 3; ++j) par[par.size() - 3 + j] = bx.half[j];
+                par.push_back(0.0);
             } else {
                 par.push_back(sh.shape_radius());
             }
         }
         if (!check(admm_hip_set_collision_shapes(gpu, (int)ty.size(), ty.data(), par.data()))) return false;
+        // the shapes' frames (contexts that never saw a turned shape or a box skip the call: every frame is the identity anyway)
+        std::vector<double> fr(12 * cf->collisionShapes.size());
+        bool oriented = false;
+        for (size_t q = 0; q < cf->collisionShapes.size(); ++q) {
+            const CollisionShape &sh = *cf->collisionShapes[q];
+            sh.frame(sh.frame_pivot(), &fr[12 * q]);
+            oriented = oriented || sh.shape_type() == ADMM_SHAPE_BOX;
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) oriented = oriented || sh.orientation[i][j] != (i == j ? 1.0 : 0.0);
+        }
+        if (oriented || frames_pushed) {
+            frames_pushed = true;
+            if (!check(admm_hip_set_collision_frames(gpu, (int)cf->collisionShapes.size(), fr.data()))) return false;
+        }
         // the shapes' friction coefficients (contexts that never saw one above 0 skip the call: they run the frictionless kernels anyway)
         std::vector<double> mu;
         bool any = false;

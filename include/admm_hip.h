@@ -257,6 +257,43 @@ int  admm_hip_set_body_surface_friction(admm_hip_ctx *ctx, int mesh_id, double m
 int  admm_hip_friction_query_moving(int64_t n, const double *p, const double *p_out, const double *x0, const double *w, const double *mu, double *result, int32_t *mode);
 int  admm_hip_mesh_velocity_query(const admm_hip_mesh *mesh, int64_t n, const double *q, const double t[3], const double *vel, double *out, double *weights, int32_t *corner_ids);
 
+/* ---- oriented obstacles: a rigid frame per list entry, and a box --------------------------------------------------------------------
+ * Extension, no reference counterpart.  Every entry q of the shape list carries a frame of twelve doubles { R (3x3, row-major), o (pivot) },
+ * default the identity about the origin: the entry's shape, exactly as its params describe it, rotated by R about o.  For an entry whose R
+ * is not exactly the identity, in every collision kernel:
+ *     e = p - o;    q_j = o_j + (R_0j e_0 + (R_1j e_1 + R_2j e_2))          the candidate in local coordinates, q = o + R^T (p - o)
+ *     the entry's unframed rule runs on q (for a mesh: the box test, closest point and inside test with the translation t) -> q'
+ *     only if that moved the point:   e = q' - o;   p'_j = o_j + (R_j0 e_0 + (R_j1 e_1 + R_j2 e_2))           p' = o + R (q' - o)
+ * every product rounded, the sums associated as written, no fused multiply-adds, the same on the host and the device.  A point the shape
+ * did not move keeps its bits (no round trip).  Friction and its moving form then run on the world-space p, p', x0 and w unchanged; the
+ * interpolated vertex velocity vi of a framed mesh is in the mesh's own coordinates and is rotated first, vi'_j = R_j0 vi_0 + (R_j1 vi_1 +
+ * R_j2 vi_2), before w_vertex = dt vi'.  Turning a frame between frames does not by itself tell the friction rule that the obstacle
+ * moves: admm_hip_set_collision_motion does (its pivot and angular velocity are in world coordinates).
+ * ADMM_SHAPE_BOX { hx, hy, hz, - }: half extents > 0, the box centred at its frame's pivot o (the origin without a frame; for the box the
+ * pivot counts even when R is the identity), axes along the local coordinate axes.  With d = q - o and depth_j = h_j - |d_j|: the point
+ * collides exactly when all three depths are > 0, and moves to the face of least depth (ties: the lowest axis), to o_j + h_j when d_j >= 0
+ * and to o_j - h_j otherwise; the other two coordinates are untouched.
+ *   admm_hip_set_collision_frames  frames [n_shapes][12], n_shapes = the length of the current list; NULL: every entry back to the identity.
+ *                           Before or after finalize, between frames.  ADMM_ERR_ARG (admm_hip_last_error names the entry): another count,
+ *                           a non-finite value, an R that is not a rotation (an element of R^T R - I, or det R - 1, beyond 1e-12 in
+ *                           size), a non-identity R on an entry that names a body surface (also checked at finalize and, for kept frames,
+ *                           by admm_hip_set_collision_shapes).  A refused call leaves the frames as they were.
+ *                           admm_hip_set_collision_shapes keeps the frames when the list's length is unchanged and resets them when it
+ *                           changes, as it does the coefficients and motions; it refuses (ADMM_ERR_ARG, the entry named) a box whose half
+ *                           extents are not positive and finite.
+ * A list with a non-identity R or a box launches the framed form of the collision kernel for its collision batches, a launch of their own
+ * in both launch modes; every other list launches exactly what it launched before (the same bits).  The values live in device memory and
+ * change under a captured graph; a call that changes the launched kernels drops the graphs.  Every rank of a sharded run makes the same
+ * calls: no collective is involved.
+ *   admm_hip_shape_query    host evaluation of one analytic entry (floor, sphere, cylinder, box; ADMM_ERR_ARG for a mesh, bad half extents
+ *                           or a bad frame) with its frame (NULL: none) for n points p [n][3]: out [n][3] = the point after the entry,
+ *                           moved [n] = 1 where the entry moved it.  Either output may be NULL.  The same bits as the device.
+ *   admm_hip_mesh_query_framed  admm_hip_mesh_query for an instance with a frame: proj in world coordinates, sdist as measured in local
+ *                           coordinates.  frame NULL (or the identity): the bits of admm_hip_mesh_query.                               */
+int  admm_hip_set_collision_frames(admm_hip_ctx *ctx, int n_shapes, const double *frames);
+int  admm_hip_shape_query(int type, const double params[4], const double *frame, int64_t n, const double *p, double *out, int32_t *moved);
+int  admm_hip_mesh_query_framed(const admm_hip_mesh *mesh, const double t[3], const double *frame, int64_t n_pts, const double *pts, double *proj, double *sdist);
+
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
  * doubles of a DEVICE buffer in place across the ranks (an all-reduce), ordered on `stream`; every rank makes the same

@@ -83,8 +83,10 @@ enum admm_shape {
     ADMM_SHAPE_FLOOR    = 0,   /* params { -, cy, -, - }        CollisionFloor.hpp:51-58    */
     ADMM_SHAPE_SPHERE   = 1,   /* params { cx, cy, cz, radius } CollisionSphere.hpp:50-66   */
     ADMM_SHAPE_CYLINDER = 2,   /* params { cx, cy, -, radius }  z-axis, CollisionCylinder.hpp:48-66 */
-    ADMM_SHAPE_MESH     = 3    /* params { tx, ty, tz, mesh_id } a closed triangle mesh registered with admm_hip_add_collision_mesh,
+    ADMM_SHAPE_MESH     = 3,   /* params { tx, ty, tz, mesh_id } a closed triangle mesh registered with admm_hip_add_collision_mesh,
                                   translated by t (extension, no reference counterpart; include/admm_hip.h) */
+    ADMM_SHAPE_BOX      = 4    /* params { hx, hy, hz, - } half extents > 0; centred at its frame's pivot (admm_hip_set_collision_frames),
+                                  at the origin without one (extension, no reference counterpart; include/admm_hip.h) */
 };
 #define ADMM_MAX_SHAPES 64
 
