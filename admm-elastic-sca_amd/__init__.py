@@ -168,6 +168,12 @@ def lib():
         L.admm_hip_set_collision_frames.argtypes = [C.c_void_p, C.c_int, _dp]
         L.admm_hip_shape_query.argtypes = [C.c_int, _dp, _dp, C.c_int64, _dp, _dp, _ip]
         L.admm_hip_mesh_query_framed.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, _dp, _dp, _dp]
+        L.admm_hip_debug_collision_form.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.admm_hip_mesh_create_open.argtypes = [C.POINTER(C.c_void_p), C.c_int, _dp, C.c_int, _ip, C.c_double, C.c_char_p, C.c_int]
+        L.admm_hip_mesh_thickness.argtypes = [C.c_void_p, _dp]
+        L.admm_hip_mesh_closest.argtypes = [C.c_void_p, C.c_int64, _dp, C.c_double, _dp, _dp, _ip, _ip, _ip]
+        L.admm_hip_set_collision_mesh_thickness.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.admm_hip_add_sheet_surface.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, C.c_double, C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -182,9 +188,11 @@ def _i(a):
 
 class Mesh:
     """A closed triangle mesh prepared for collision queries (admm_hip_mesh_create): validated, pseudo-normals and BVH built.
-    verts [nv][3] float64, tris [nt][3] int32, counter-clockwise seen from outside.  Invalid input raises AdmmHipError."""
+    verts [nv][3] float64, tris [nt][3] int32, counter-clockwise seen from outside.  Invalid input raises AdmmHipError.
+    half_thickness given: an open surface (admm_hip_mesh_create_open; boundary edges allowed, a closed input too), which collides as
+    a shell of that half thickness: query then returns the point after the shell rule and sdist = r - d (-inf beyond r)."""
 
-    def __init__(self, verts, tris=None):
+    def __init__(self, verts, tris=None, half_thickness=None):
         self.L = lib()
         if isinstance(verts, C.c_void_p):      # an admm_hip_mesh handle this object takes over (System.collision_mesh)
             self.h = verts
@@ -193,10 +201,35 @@ class Mesh:
         t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
         h = C.c_void_p()
         err = C.create_string_buffer(512)
+        if half_thickness is not None:
+            rc = self.L.admm_hip_mesh_create_open(C.byref(h), v.shape[0], _d(v), t.shape[0], _i(t), float(half_thickness), err, len(err))
+            if rc != 0:
+                raise AdmmHipError("admm_hip_mesh_create_open error %d: %s" % (rc, err.value.decode()))
+            self.h = h
+            return
         rc = self.L.admm_hip_mesh_create(C.byref(h), v.shape[0], _d(v), t.shape[0], _i(t), err, len(err))
         if rc != 0:
             raise AdmmHipError("admm_hip_mesh_create error %d: %s" % (rc, err.value.decode()))
         self.h = h
+
+    @property
+    def thickness(self):
+        """the half thickness of an open mesh (a shell); 0.0 for a closed mesh"""
+        r = np.zeros(1)
+        self.L.admm_hip_mesh_thickness(self.h, _d(r))
+        return float(r[0])
+
+    def closest(self, q, r2=None):
+        """the closest-point search as it runs (admm_hip_mesh_closest) for q [n][3] relative to the mesh: the unbounded one, or with r2
+        the one bounded by it -> dict(c [n][3], d2 [n], slot [n], reg [n], tri [n]); slot -1: no triangle nearer than sqrt(r2)"""
+        p = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 3)
+        n = p.shape[0]
+        c = np.empty((n, 3)); d2 = np.empty(n)
+        slot = np.empty(n, dtype=np.int32); reg = np.empty(n, dtype=np.int32); tri = np.empty(n, dtype=np.int32)
+        rc = self.L.admm_hip_mesh_closest(self.h, n, _d(p), -1.0 if r2 is None else float(r2), _d(c), _d(d2), _i(slot), _i(reg), _i(tri))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_closest error %d" % rc)
+        return dict(c=c, d2=d2, slot=slot, reg=reg, tri=tri)
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -459,6 +492,13 @@ class System:
         m = np.ascontiguousarray(mu, dtype=np.float64).ravel()
         self._chk(self.L.admm_hip_set_collision_friction(self.h, m.size, _d(m)))
 
+    def collision_form(self):
+        """which kernels the collision batches launch for the current list (admm_hip_debug_collision_form): 0 frictionless, 1 friction,
+        2 moving friction, 3 framed, 4 shell"""
+        f = C.c_int()
+        self._chk(self.L.admm_hip_debug_collision_form(self.h, C.byref(f)))
+        return f.value
+
     def set_collision_frames(self, frames):
         """the rigid frame of every entry of the current shape list (admm_hip_set_collision_frames): [n_shapes][12] = R (row-major), pivot;
         the entry's shape is rotated by R about the pivot, and a box is centred at it.  None: every entry back to the identity."""
@@ -492,7 +532,8 @@ class System:
         self._chk(self.L.admm_hip_set_body_surface_friction(self.h, int(mesh_id), float(mu)))
 
     def add_collision_mesh(self, verts, tris):
-        """registers a closed triangle mesh (before initialize) -> its mesh_id for SHAPE["MESH"] entries {tx, ty, tz, mesh_id}"""
+        """registers a triangle mesh (before initialize; closed, or an open one: Mesh(verts, tris, half_thickness)) -> its mesh_id for
+        SHAPE["MESH"] entries {tx, ty, tz, mesh_id}"""
         m = verts if isinstance(verts, Mesh) else Mesh(verts, tris)
         mid = C.c_int()
         self._chk(self.L.admm_hip_add_collision_mesh(self.h, m.h, C.byref(mid)))
@@ -502,6 +543,19 @@ class System:
         """new vertex positions [nv][3] for a registered mesh (mesh_id of add_collision_mesh); after initialize on the device, in place"""
         v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
         self._chk(self.L.admm_hip_update_collision_mesh(self.h, int(mesh_id), v.shape[0], _d(v)))
+
+    def set_collision_mesh_thickness(self, mesh_id, half_thickness):
+        """the half thickness of a registered open mesh (admm_hip_set_collision_mesh_thickness): before or after initialize, between
+        frames; captured graphs stay.  A closed mesh, or a value that is not finite and > 0, raises AdmmHipError."""
+        self._chk(self.L.admm_hip_set_collision_mesh_thickness(self.h, int(mesh_id), float(half_thickness)))
+
+    def add_sheet_surface(self, node_first, node_count, tris, half_thickness):
+        """registers a sheet surface (before initialize): add_body_surface for an open surface of simulated nodes such as a cloth, a
+        shell of the given half thickness that follows its nodes and is ignored by them -> its mesh_id"""
+        t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        mid = C.c_int()
+        self._chk(self.L.admm_hip_add_sheet_surface(self.h, int(node_first), int(node_count), t.shape[0], _i(t), float(half_thickness), C.byref(mid)))
+        return mid.value
 
     def add_body_surface(self, node_first, node_count, tris):
         """registers a body surface (before initialize): a closed mesh of simulated nodes, tris [nt][3] global node ids inside

@@ -437,8 +437,8 @@ static int check_owner_range(admm_hip_ctx *ctx, int mesh_id, int first, int coun
 }
 
 // extension, no reference counterpart (include/admm_hip.h): a closed surface of simulated nodes, rebuilt on the device from the frame-start
-// x at every step (launch.inc: update_bodies); owned by its node range
-int admm_hip_add_body_surface(admm_hip_ctx *ctx, int node_first, int node_count, int n_tris, const int32_t *tris, int *mesh_id) {
+// x at every step (launch.inc: update_bodies); owned by its node range.  half_thickness > 0: an open one (admm_hip_add_sheet_surface)
+static int add_node_surface(admm_hip_ctx *ctx, int node_first, int node_count, int n_tris, const int32_t *tris, double half_thickness, int *mesh_id) {
     if (!ctx) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "body surfaces must be registered before finalize");
     if (n_tris < 1 || !tris) return fail(ctx, ADMM_ERR_ARG, "body surface: no triangles");
@@ -459,7 +459,8 @@ int admm_hip_add_body_surface(admm_hip_ctx *ctx, int node_first, int node_count,
     for (size_t i = 0; i < lt.size(); ++i) lt[i] = local[tris[i] - node_first];
     admm_hip_mesh *M = nullptr;
     char msg[512];
-    const int rc = admm_hip_mesh_create(&M, (int)nodes.size(), verts.data(), n_tris, lt.data(), msg, (int)sizeof msg);
+    const int rc = half_thickness > 0.0 ? admm_hip_mesh_create_open(&M, (int)nodes.size(), verts.data(), n_tris, lt.data(), half_thickness, msg, (int)sizeof msg)
+                                        : admm_hip_mesh_create(&M, (int)nodes.size(), verts.data(), n_tris, lt.data(), msg, (int)sizeof msg);
     if (rc) return fail(ctx, rc, "body surface: %s", msg);
     ctx->meshes.push_back(*M);
     admm_hip_mesh_destroy(M);
@@ -468,6 +469,34 @@ int admm_hip_add_body_surface(admm_hip_ctx *ctx, int node_first, int node_count,
     ctx->mesh_role.push_back(std::move(R));
     ctx->mesh_move.emplace_back();
     if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
+    return ADMM_OK;
+}
+
+int admm_hip_add_body_surface(admm_hip_ctx *ctx, int node_first, int node_count, int n_tris, const int32_t *tris, int *mesh_id) {
+    return add_node_surface(ctx, node_first, node_count, n_tris, tris, 0.0, mesh_id);
+}
+// ... an open one, such as a cloth: a thick shell that follows its nodes
+int admm_hip_add_sheet_surface(admm_hip_ctx *ctx, int node_first, int node_count, int n_tris, const int32_t *tris, double half_thickness, int *mesh_id) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (!(half_thickness > 0.0 && std::isfinite(half_thickness))) return fail(ctx, ADMM_ERR_ARG, "sheet surface: half thickness %g: it must be positive and finite", half_thickness);
+    return add_node_surface(ctx, node_first, node_count, n_tris, tris, half_thickness, mesh_id);
+}
+
+// the half thickness of a registered open mesh, between frames: one entry of the device table project_collision_shell_kernel reads
+// (no kernel changes, captured graphs stay)
+int admm_hip_set_collision_mesh_thickness(admm_hip_ctx *ctx, int mesh_id, double half_thickness) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    if (!(ctx->meshes[mesh_id].thickness > 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed mesh: it has no thickness", mesh_id);
+    if (!(half_thickness > 0.0 && std::isfinite(half_thickness)))
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: half thickness %g: it must be positive and finite", mesh_id, half_thickness);
+    ctx->meshes[mesh_id].thickness = half_thickness;
+    if (ctx->finalized && ctx->device_id >= 0) {
+        HIPCHK(hipSetDevice(ctx->device_id));
+        HIPCHK(hipMemcpyAsync(ctx->d_mesh_thick + mesh_id, &ctx->meshes[mesh_id].thickness, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
     return ADMM_OK;
 }
 

@@ -225,6 +225,13 @@ int admm_hip_debug_graph_state(admm_hip_ctx *ctx, int *iter_graph, int *frame_gr
     return ADMM_OK;
 }
 
+// which kernels the collision batches launch for the current list (launch.inc: collision_form)
+int admm_hip_debug_collision_form(admm_hip_ctx *ctx, int *form) {
+    if (!ctx || !form) return ADMM_ERR_ARG;
+    *form = collision_form(ctx);
+    return ADMM_OK;
+}
+
 int admm_hip_sync(admm_hip_ctx *ctx) {
     TRY(require_device(ctx));
     HIPCHK(hipStreamSynchronize(ctx->stream));

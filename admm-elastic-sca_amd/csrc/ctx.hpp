@@ -145,6 +145,9 @@ struct admm_hip_ctx {
     // gathered from the frame-start v at every step (launch.inc: update_bodies).  body_mu: a body surface's coefficient.
     struct MeshMove { double *d_vel = nullptr; bool has_vel = false; double body_mu = 0.0; std::vector<double> vel; };
     std::vector<MeshMove> mesh_move; admm_mesh::MeshMotion *d_mesh_motion = nullptr;
+    // open meshes (thick shells, admm_hip_mesh::thickness > 0): the half thickness of every mesh, parallel to d_meshes (0: a closed mesh), a
+    // table of its own that project_collision_shell_kernel alone reads; admm_hip_set_collision_mesh_thickness writes one entry
+    double *d_mesh_thick = nullptr;
     int *d_body_tag = nullptr;      // contexts with an owner: the owner group of every node in device order (-1: none), for MeshDev::owner
     SymCSC A;
     Factor F;

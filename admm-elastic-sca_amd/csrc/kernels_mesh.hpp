@@ -7,7 +7,7 @@
 //   commit  mesh_vertex_normal_kernel (one lane per vertex, its incidences in order), mesh_slot_kernel (one lane per leaf-order slot:
 //           corners and the seven pseudo-normals), then mesh_refit_kernel once per BVH level, deepest first: leaves from their
 //           triangles, internal nodes from their children.  One launch per level and no hand-off between workgroups.
-// A body surface (admm_hip_add_body_surface) runs the same stages at the start of every admm_hip_step (launch.inc: update_bodies),
+// A body surface (admm_hip_add_body_surface; admm_hip_add_sheet_surface: an open one) runs the same stages at the start of every admm_hip_step (launch.inc: update_bodies),
 // eagerly and without a read-back: mesh_gather_kernel stages its vertices from the frame-start x (device node ids mapped at finalize),
 // mesh_volume_kernel takes the verdict on the device (update_refused, the predicate mesh_refusal uses) into the surface's BodyStatus,
 // counts the frame and re-arms the check, and the commit kernels read the gate and return at once after a refusal, so that the last
@@ -59,9 +59,10 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_gather_vel_kernel(int nv, con
 }
 
 // one workgroup: the partials staged through LDS a block at a time (parallel loads), lane 0 adds them in order.  bs (body surfaces
-// only): lane 0 also takes the verdict, counts the frame, sets the commit kernels' gate and resets the check for the next frame
+// only): lane 0 also takes the verdict (open: a sheet surface, no volume condition), counts the frame, sets the commit kernels' gate and
+// resets the check for the next frame
 __global__ __launch_bounds__(MESH_BLOCK) void mesh_volume_kernel(int nchunk, const double *__restrict__ part, admm_mesh::UpdateCheck *chk,
-                                                                admm_mesh::BodyStatus *bs) {
+                                                                admm_mesh::BodyStatus *bs, const int open) {
     __shared__ double buf[MESH_BLOCK];
     double acc = 0.0;
     for (int b = 0; b < nchunk; b += MESH_BLOCK) {
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_volume_kernel(int nchunk, con
         chk->vol6 = acc;
         if (bs) {
             const admm_mesh::UpdateCheck c = *chk;
-            const bool bad = admm_mesh::update_refused(c);
+            const bool bad = admm_mesh::update_refused(c, open != 0);
             bs->gate = bad ? 1 : 0;
             if (bad) { bs->refused += 1; bs->last_bad_tri = c.bad_tri != admm_mesh::NO_TRI ? c.bad_tri : -1; }
             else bs->updated += 1;

@@ -45,8 +45,20 @@ bool framed_on(const admm_hip_ctx *ctx) {
     for (int q = 0; q < ctx->shapes.n; ++q) if (ctx->shapes.framed[q] || ctx->shapes.type[q] == ADMM_SHAPE_BOX) return true;
     return false;
 }
-// which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form, 3 the framed form
-int collision_form(const admm_hip_ctx *ctx) { return framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
+// ... and does an entry of the current list name an open mesh (a thick shell, admm_hip_mesh_create_open / admm_hip_add_sheet_surface)?
+// Then the collision batches run project_collision_shell_kernel, the one kernel that knows the shell rule (and everything the framed
+// kernel knows), in a launch of their own in both launch modes.  A list that names none launches exactly what it launched before.
+bool shell_on(const admm_hip_ctx *ctx) {
+    for (int q = 0; q < ctx->shapes.n; ++q) {
+        if (ctx->shapes.type[q] != ADMM_SHAPE_MESH) continue;
+        const int id = (int)ctx->shapes.par[q][3];
+        if (id >= 0 && id < (int)ctx->meshes.size() && ctx->meshes[id].thickness > 0.0) return true;
+    }
+    return false;
+}
+// which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form, 3 the framed form, 4 the
+// shell form
+int collision_form(const admm_hip_ctx *ctx) { return shell_on(ctx) ? 4 : framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
 // ... in a launch of their own (launch_collision_mesh) instead of a segment of project_multi_kernel or project_collision_kernel
 bool collision_own_launch(const admm_hip_ctx *ctx) { return !ctx->meshes.empty() || friction_on(ctx) || framed_on(ctx); }
 
@@ -109,7 +121,7 @@ int update_mesh_device(admm_hip_ctx *ctx, int id, const double *verts) {
     HIPCHK(hipMemcpyAsync(u.verts, verts, sizeof(double) * 3 * (size_t)nv, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ctx->d_mesh_chk, NO_TRI, 2, st));      // bad_tri = bad_vtx = none
     hipLaunchKernelGGL(mesh_check_kernel, grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, ctx->d_mesh_chk);
-    hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, ctx->d_mesh_chk, (BodyStatus *)nullptr);
+    hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, ctx->d_mesh_chk, (BodyStatus *)nullptr, M.thickness > 0.0 ? 1 : 0);
     UpdateCheck chk;
     HIPCHK(hipMemcpyAsync(&chk, ctx->d_mesh_chk, sizeof chk, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -145,7 +157,7 @@ int update_bodies(admm_hip_ctx *ctx) {
         const int *gate = &u.status->gate;
         hipLaunchKernelGGL(mesh_gather_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_x, u.verts);
         hipLaunchKernelGGL(mesh_check_kernel, grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, u.chk);
-        hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, u.chk, u.status);
+        hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, u.chk, u.status, M.thickness > 0.0 ? 1 : 0);
         // the vertices' frame-start velocities beside them, through the same map (d_v before the explicit forces); gated like the commit
         // kernels: a refused frame keeps the velocities that went with the last good surface
         hipLaunchKernelGGL(mesh_gather_vel_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_v, ctx->mesh_move[id].d_vel, gate);
@@ -167,7 +179,11 @@ void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
-    if (framed_on(ctx)) {
+    if (shell_on(ctx)) {      // (implies meshes)
+        hipLaunchKernelGGL(project_collision_shell_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
+                           (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, ctx->dt);
+    } else if (framed_on(ctx)) {
         if (!ctx->meshes.empty())
             hipLaunchKernelGGL(project_collision_framed_kernel<true>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
                                (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,

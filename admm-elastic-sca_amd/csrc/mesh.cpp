@@ -1,4 +1,4 @@
-// mesh.cpp -- closed triangle-mesh obstacles on the host: validation, pseudo-normals and the BVH of admm_hip_mesh_create, and
+// mesh.cpp -- triangle-mesh obstacles (closed meshes, and open surfaces as thick shells) on the host: validation, pseudo-normals and the BVH of admm_hip_mesh_create, and
 // admm_hip_mesh_query, the host evaluation of the query the device runs (mesh_query.hpp), and admm_hip_friction_query, the same for
 // the contact friction rule (friction.hpp) and its moving form's vertex-velocity interpolation, and admm_hip_shape_query and
 // admm_hip_mesh_query_framed, the same for an entry with a rigid frame and for the box (frame.hpp).  Context-free: a context copies a mesh
@@ -66,8 +66,11 @@ struct Builder {
     }
 };
 
-int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, admm_hip_mesh &M, char *err, int err_len) {
-    if (nv < 4 || nt < 4 || !verts || !tris) return mesh_fail(err, err_len, "a closed mesh needs at least 4 vertices and 4 triangles (have %d, %d)", nv, nt);
+// thickness 0: a closed mesh; > 0: an open surface (boundary edges allowed, no volume condition), a shell of that half thickness
+int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, double thickness, admm_hip_mesh &M, char *err, int err_len) {
+    const bool open = thickness > 0.0;
+    if (!open && (nv < 4 || nt < 4 || !verts || !tris)) return mesh_fail(err, err_len, "a closed mesh needs at least 4 vertices and 4 triangles (have %d, %d)", nv, nt);
+    if (open && (nv < 3 || nt < 1 || !verts || !tris)) return mesh_fail(err, err_len, "an open mesh needs at least 3 vertices and 1 triangle (have %d, %d)", nv, nt);
     for (int t = 0; t < nt; ++t) for (int k = 0; k < 3; ++k)
         if (tris[3 * (size_t)t + k] < 0 || tris[3 * (size_t)t + k] >= nv)
             return mesh_fail(err, err_len, "triangle %d: vertex index %d out of range [0, %d)", t, tris[3 * (size_t)t + k], nv);
@@ -104,6 +107,10 @@ int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, admm_hi
     for (size_t i = 0; i < es.size();) {
         size_t j = i;
         while (j < es.size() && es[j].lo == es[i].lo && es[j].hi == es[i].hi) ++j;
+        if (open && j - i == 1) { i = j; continue; }      // a boundary edge: adj stays -1
+        if (open && j - i > 2)
+            return mesh_fail(err, err_len, "edge (%d, %d) is shared by %d triangles (first: triangles %d, %d, %d): the mesh is not edge-manifold", es[i].lo, es[i].hi, (int)(j - i),
+                             es[i].t, es[i + 1].t, es[i + 2].t);
         if (j - i != 2)
             return mesh_fail(err, err_len, "edge (%d, %d) is shared by %d triangle%s (first: triangle %d), not 2: the mesh is %s", es[i].lo, es[i].hi, (int)(j - i),
                              j - i == 1 ? "" : "s", es[i].t, j - i == 1 ? "open" : "not edge-manifold");
@@ -117,7 +124,7 @@ int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, admm_hi
     // outward normals: the enclosed volume is positive
     double vol = 0.0;
     for (int t = 0; t < nt; ++t) { double c[3]; cross(src[t].v + 3, src[t].v + 6, c); vol += dot(src[t].v, c); }
-    if (!(vol > 0.0)) return mesh_fail(err, err_len, "the mesh encloses a non-positive volume (%g): its triangles must be ordered counter-clockwise seen from outside", vol / 6.0);
+    if (!open && !(vol > 0.0)) return mesh_fail(err, err_len, "the mesh encloses a non-positive volume (%g): its triangles must be ordered counter-clockwise seen from outside", vol / 6.0);
     // pseudo-normals: angle-weighted vertex normals, summed edge normals
     std::vector<double> vn((size_t)nv * 3, 0.0);
     for (int t = 0; t < nt; ++t) for (int k = 0; k < 3; ++k) {
@@ -135,9 +142,12 @@ int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, admm_hi
         for (int j = 0; j < 3; ++j) N.n[0][j] = fn[3 * (size_t)t + j];
         for (int k = 0; k < 3; ++k) {
             const int o = adj[3 * (size_t)t + k];
-            const int lo = std::min(t, o), hi = std::max(t, o);      // (the same sum seen from both sides)
-            for (int j = 0; j < 3; ++j) N.n[1 + k][j] = fn[3 * (size_t)lo + j] + fn[3 * (size_t)hi + j];
-            normalize(N.n[1 + k]);
+            if (o < 0) { for (int j = 0; j < 3; ++j) N.n[1 + k][j] = fn[3 * (size_t)t + j]; }      // a boundary edge: its one face's normal
+            else {
+                const int lo = std::min(t, o), hi = std::max(t, o);      // (the same sum seen from both sides)
+                for (int j = 0; j < 3; ++j) N.n[1 + k][j] = fn[3 * (size_t)lo + j] + fn[3 * (size_t)hi + j];
+                normalize(N.n[1 + k]);
+            }
             for (int j = 0; j < 3; ++j) N.n[4 + k][j] = vn[3 * (size_t)cid[3 * (size_t)t + k] + j];
             normalize(N.n[4 + k]);
         }
@@ -156,6 +166,7 @@ int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, admm_hi
     M.tris.resize(nt); M.nrm.resize(nt);
     for (int i = 0; i < nt; ++i) { M.tris[i] = src[B.ord[i]]; M.nrm[i] = nrm[B.ord[i]]; }
     M.depth = B.depth;
+    M.thickness = open ? thickness : 0.0;
     // the topology admm_hip_mesh_set_vertices recomputes the arrays from: corners, adjacency, each vertex's incidences in ascending
     // (triangle, corner) order -- the order of the vertex-normal sum above --, the nodes by depth (children follow their parent)
     M.nv = nv;
@@ -184,12 +195,26 @@ int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, admm_hi
 
 struct HostStack { int s[MAX_DEPTH]; int &operator[](int i) { return s[i]; } };
 
+// the shell rule (mesh_query.hpp) on q, relative to the instance: true when q collides, o = p' then; *sd = r - d, -inf where the bounded
+// search found nothing or did not run
+bool shell_query(const admm_hip_mesh &M, const double *q, double *o, double *sd) {
+    const double r = M.thickness;
+    *sd = -INFINITY;
+    if (!in_shell_box(q, M.nodes[0], r)) return false;
+    HostStack stk; Hit h;
+    closest_within(M.nodes.data(), M.tris.data(), q, r * r, stk, h);
+    if (h.slot >= 0) *sd = r - std::sqrt(h.d2);
+    if (!shell_collides(h, r)) return false;
+    shell_push(q, h, M.nrm.data(), r, o);
+    return true;
+}
+
 } // namespace
 
 namespace admm_mesh {
 
 int mesh_refusal(const admm_hip_mesh &M, const double *verts, const UpdateCheck &c, char *err, int err_len) {
-    if (!update_refused(c)) return ADMM_OK;
+    if (!update_refused(c, M.thickness > 0.0)) return ADMM_OK;
     if (c.bad_tri != NO_TRI) {
         const int *C = M.cid.data() + 3 * (size_t)c.bad_tri;
         for (int k = 0; k < 3; ++k)
@@ -241,9 +266,46 @@ int admm_hip_mesh_create(admm_hip_mesh **out, int nv, const double *verts, int n
     *out = nullptr;
     admm_hip_mesh *M = new (std::nothrow) admm_hip_mesh();
     if (!M) return mesh_fail(err, err_len, "out of memory");
-    const int rc = mesh_build(nv, verts, nt, tris, *M, err, err_len);
+    const int rc = mesh_build(nv, verts, nt, tris, 0.0, *M, err, err_len);
     if (rc) { delete M; return rc; }
     *out = M;
+    return ADMM_OK;
+}
+
+// an open surface (a closed one is accepted too and simply is a shell): every directed edge at most once, no degenerate triangle
+int admm_hip_mesh_create_open(admm_hip_mesh **out, int nv, const double *verts, int nt, const int32_t *tris, double half_thickness, char *err, int err_len) {
+    if (err && err_len > 0) err[0] = 0;
+    if (!out) return mesh_fail(err, err_len, "out is NULL");
+    *out = nullptr;
+    if (!(half_thickness > 0.0 && std::isfinite(half_thickness))) return mesh_fail(err, err_len, "half thickness %g: it must be positive and finite", half_thickness);
+    admm_hip_mesh *M = new (std::nothrow) admm_hip_mesh();
+    if (!M) return mesh_fail(err, err_len, "out of memory");
+    const int rc = mesh_build(nv, verts, nt, tris, half_thickness, *M, err, err_len);
+    if (rc) { delete M; return rc; }
+    *out = M;
+    return ADMM_OK;
+}
+
+int admm_hip_mesh_thickness(const admm_hip_mesh *mesh, double *r) {
+    if (!mesh || !r) return ADMM_ERR_ARG;
+    *r = mesh->thickness;
+    return ADMM_OK;
+}
+
+// the two closest-point searches of mesh_query.hpp as they are (for tests): r2 < 0: closest, else closest_within with the bound r2;
+// q relative to the instance; slot: the leaf-order slot (-1: none), tri: the original triangle index
+int admm_hip_mesh_closest(const admm_hip_mesh *mesh, int64_t n, const double *q, double r2, double *c, double *d2, int32_t *slot, int32_t *reg, int32_t *tri) {
+    if (!mesh || n < 0 || (n && !q)) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        HostStack stk; Hit h;
+        if (r2 < 0.0) closest(mesh->nodes.data(), mesh->tris.data(), q + 3 * i, stk, h);
+        else closest_within(mesh->nodes.data(), mesh->tris.data(), q + 3 * i, r2, stk, h);
+        if (c) for (int j = 0; j < 3; ++j) c[3 * i + j] = h.c[j];
+        if (d2) d2[i] = h.d2;
+        if (slot) slot[i] = h.slot;
+        if (reg) reg[i] = h.reg;
+        if (tri) tri[i] = h.slot >= 0 ? mesh->tris[h.slot].orig : -1;
+    }
     return ADMM_OK;
 }
 
@@ -267,6 +329,13 @@ int admm_hip_mesh_query(const admm_hip_mesh *mesh, const double t[3], int64_t n_
     if (!mesh || !t || n_pts < 0 || (n_pts && !pts)) return ADMM_ERR_ARG;
     for (int64_t i = 0; i < n_pts; ++i) {
         const double q[3] = {pts[3 * i] - t[0], pts[3 * i + 1] - t[1], pts[3 * i + 2] - t[2]};
+        if (mesh->thickness > 0.0) {      // a shell: proj = the point after the rule (the input where it does not move it), sdist = r - d
+            double o[3], sd;
+            const bool hit = shell_query(*mesh, q, o, &sd);
+            if (proj) for (int j = 0; j < 3; ++j) proj[3 * i + j] = hit ? t[j] + o[j] : pts[3 * i + j];
+            if (sdist) sdist[i] = sd;
+            continue;
+        }
         HostStack stk; Hit h;
         closest(mesh->nodes.data(), mesh->tris.data(), q, stk, h);
         const bool in = inside(mesh->nodes[0], mesh->nrm.data(), q, h);
@@ -307,6 +376,16 @@ int admm_hip_mesh_query_framed(const admm_hip_mesh *mesh, const double t[3], con
         double l[3];
         admm_frame::to_local(frame, pts + 3 * i, l);
         const double q[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
+        if (mesh->thickness > 0.0) {
+            double o[3], sd;
+            const bool hit = shell_query(*mesh, q, o, &sd);
+            if (proj) {
+                const double c[3] = {t[0] + o[0], t[1] + o[1], t[2] + o[2]};
+                if (hit) admm_frame::to_world(frame, c, proj + 3 * i); else for (int j = 0; j < 3; ++j) proj[3 * i + j] = pts[3 * i + j];
+            }
+            if (sdist) sdist[i] = sd;
+            continue;
+        }
         HostStack stk; Hit h;
         closest(mesh->nodes.data(), mesh->tris.data(), q, stk, h);
         const bool in = inside(mesh->nodes[0], mesh->nrm.data(), q, h);

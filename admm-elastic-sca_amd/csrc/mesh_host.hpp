@@ -10,6 +10,7 @@ struct admm_hip_mesh {
     std::vector<admm_mesh::Tri> tris;       // leaf order
     std::vector<admm_mesh::Nrm> nrm;        // leaf order
     int depth = 0;                          // levels below the root
+    double thickness = 0.0;                 // 0: a closed mesh; > 0: an open surface (admm_hip_mesh_create_open), a shell of this half thickness
     // topology (fixed at creation)
     int nv = 0;
     std::vector<int> cid;                   // [nt][3] canonical corner ids (rotated: lowest id first) by original triangle

@@ -1,4 +1,4 @@
-// mesh_query.hpp -- closed triangle-mesh obstacles (ADMM_SHAPE_MESH): the point query shared by the host (mesh.cpp:
+// mesh_query.hpp -- triangle-mesh obstacles (ADMM_SHAPE_MESH: closed meshes, and open surfaces as thick shells): the point query shared by the host (mesh.cpp:
 // admm_hip_mesh_query, the class mirror's CollisionMesh) and the device (kernels_local.hpp project_collision_mesh_kernel).
 // Both sides compile it with -ffp-contract=off and run the same traversal in the same order, so they give the same bits.
 //
@@ -8,6 +8,20 @@
 //   routine that also classifies q into the triangle's vertex / edge / face region (Ericson, Real-Time Collision Detection 5.1.5);
 //   inside  iff  q lies strictly inside the root box and dot(q - c, n) < 0, n = the pseudo-normal of c's feature (face normal, sum of
 //   the edge's two face normals, angle-weighted vertex normal; Baerentzen & Aanaes 2005), all precomputed on the host.
+//
+// Open surfaces (admm_hip_mesh_create_open: boundary edges allowed) collide as thick shells.  A shell of half thickness r > 0 occupies
+// every point whose distance to the surface is below r.  The rule is unsigned -- no inside, no outside: a point is pushed to distance r
+// on the side it is on.  For a candidate q (relative to the instance's translation t, in local coordinates under a frame), every
+// product and sum rounded, no fused multiply-adds, in this order:
+//   1. box test   the traversal runs only when  lo_j - r < q_j < hi_j + r  holds strictly for j = 0, 1, 2 (lo, hi: the root box; in_shell_box);
+//                 a point that fails keeps its bits
+//   2. hit        h = closest_within(q, r * r): the hit of `closest` whenever that one's d2 < r * r, slot = -1 otherwise
+//   3. decision   the point collides exactly when  h.slot >= 0 && h.d2 < r * r
+//   4. push       e_j = q_j - c_j,  d = sqrt(h.d2);   d > 0:  s = r / d,  p'_j = c_j + s * e_j;
+//                 d == 0:  p'_j = c_j + r * n_j,  n = the unit face normal of the winning triangle (Nrm::n[0])          (shell_push)
+//   5. world      p_j = t_j + p'_j, then under a frame to_world -- only for a point that was moved
+// The rule does not know on which side a node started the frame: a node that crosses the mid-surface within one frame leaves on the far
+// side.  Callers keep r above closing speed x dt.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -176,6 +190,66 @@ ADMM_HD void closest(const Node *__restrict__ nodes, const Tri *__restrict__ tri
     }
 }
 
+// `closest` started from the bound r2: no box farther than sqrt(r2) is opened (box_open's tie margin aside), only a triangle with
+// d2 < r2 is taken.  The hit of `closest` whenever that one's d2 < r2 (the winner's boxes pass box_open against any bound >= its d2, as
+// they do there); otherwise slot = -1 and d2 = INFINITY.
+template <class Stack>
+ADMM_HD void closest_within(const Node *__restrict__ nodes, const Tri *__restrict__ tris, const double *q, const double r2, Stack &stk, Hit &h) {
+    h.d2 = r2; h.slot = -1; h.reg = 0; h.c[0] = h.c[1] = h.c[2] = 0.0;
+    int best_i = NO_TRI;
+    int sp = 0, cur = 0;
+    for (;;) {
+        const Node &n = nodes[cur];
+        int next = -1;
+        if (n.cnt > 0) {
+            for (int t = n.a; t < n.a + n.cnt; ++t) {
+                double o[3]; int reg;
+                closest_on_tri(q, tris[t].v, o, reg);
+                const double e0 = q[0] - o[0], e1 = q[1] - o[1], e2 = q[2] - o[2];
+                const double d2 = e0 * e0 + e1 * e1 + e2 * e2;
+                const int oi = tris[t].orig;
+                if (d2 < r2 && closer(d2, oi, h.d2, best_i)) { h.d2 = d2; best_i = oi; h.slot = t; h.reg = reg; h.c[0] = o[0]; h.c[1] = o[1]; h.c[2] = o[2]; }
+            }
+        } else {
+            const int l = n.a, r = n.a + 1;
+            const double dl = box_d2(q, nodes[l]), dr = box_d2(q, nodes[r]);
+            const bool rf = dr < dl || (dr == dl && centre_d2(q, nodes[r]) < centre_d2(q, nodes[l]));
+            const int near = rf ? r : l, far = rf ? l : r;
+            const double dn = rf ? dr : dl, df = rf ? dl : dr;
+            if (box_open(df, h.d2) && sp < MAX_DEPTH) { stk[sp] = far; ++sp; }
+            if (box_open(dn, h.d2)) next = near;
+        }
+        while (next < 0 && sp > 0) {
+            --sp;
+            const int cand = stk[sp];
+            if (box_open(box_d2(q, nodes[cand]), h.d2)) next = cand;
+        }
+        if (next < 0) break;
+        cur = next;
+    }
+    if (h.slot < 0) h.d2 = INFINITY;
+}
+
+// ---- open surfaces as thick shells (the rule at the top of this file) ------------------------------------------------------------
+// step 1: q strictly inside the root box inflated by r
+ADMM_HD bool in_shell_box(const double *q, const Node &n, const double r) {
+    return n.lo[0] - r < q[0] && q[0] < n.hi[0] + r && n.lo[1] - r < q[1] && q[1] < n.hi[1] + r && n.lo[2] - r < q[2] && q[2] < n.hi[2] + r;
+}
+// step 3
+ADMM_HD bool shell_collides(const Hit &h, const double r) { return h.slot >= 0 && h.d2 < r * r; }
+// step 4: o = p' (relative to the instance, like q and h.c)
+ADMM_HD void shell_push(const double *q, const Hit &h, const Nrm *__restrict__ nrm, const double r, double *o) {
+    const double e0 = q[0] - h.c[0], e1 = q[1] - h.c[1], e2 = q[2] - h.c[2];
+    const double d = sqrt(h.d2);
+    if (d > 0.0) {
+        const double s = r / d;
+        o[0] = h.c[0] + s * e0; o[1] = h.c[1] + s * e1; o[2] = h.c[2] + s * e2;
+    } else {
+        const double *n = nrm[h.slot].n[0];
+        o[0] = h.c[0] + r * n[0]; o[1] = h.c[1] + r * n[1]; o[2] = h.c[2] + r * n[2];
+    }
+}
+
 // the pseudo-normal of the hit's feature
 ADMM_HD const double *feature_normal(const Nrm &nr, int reg) {
     switch (reg) {
@@ -219,8 +293,9 @@ ADMM_HD bool face_normal(const double *v, double *n) {
 // vertex (NO_TRI: none; also catches vertices no triangle uses), 6 x the enclosed volume (blocked sum, VOL_CHUNK)
 struct UpdateCheck { int bad_tri, bad_vtx; double vol6; };
 static_assert(sizeof(UpdateCheck) == 16, "the device update reads back 16 bytes");
-// the one refusal predicate of an update, shared by the host (mesh_refusal) and the device's frame-start body-surface update
-ADMM_HD bool update_refused(const UpdateCheck &c) { return c.bad_tri != NO_TRI || c.bad_vtx != NO_TRI || !(c.vol6 > 0.0); }
+// the one refusal predicate of an update, shared by the host (mesh_refusal) and the device's frame-start body-surface update; an open
+// mesh (a shell) encloses nothing: no volume condition
+ADMM_HD bool update_refused(const UpdateCheck &c, const bool open) { return c.bad_tri != NO_TRI || c.bad_vtx != NO_TRI || (!open && !(c.vol6 > 0.0)); }
 // a body surface's device record (kernels_mesh.hpp): frame-start updates applied / refused, the lowest bad triangle of the last refusal
 // (-1: none), and the gate the commit kernels read (nonzero: this frame's update was refused, the live arrays stay)
 struct BodyStatus { long long updated, refused; int last_bad_tri, gate; };
@@ -290,16 +365,20 @@ ADMM_HD void vertex_normal(const double *verts, const int *cid, const double *fn
     }
 }
 // leaf-order slot s (original triangle t = tri.orig): its corners and the seven pseudo-normals, from the face normals fn [nt][3] and
-// the (unnormalised) vertex normals vn [nv][3]; an edge's normal sums the lower-indexed face first
+// the (unnormalised) vertex normals vn [nv][3]; an edge's normal sums the lower-indexed face first; a boundary edge of an open mesh
+// (adj < 0) takes its one face's normal
 ADMM_HD void slot_data(const double *verts, const int *cid, const int *adj, const double *fn, const double *vn, Tri &tri, Nrm &N) {
     const int t = tri.orig;
     gather_tri(verts, cid, t, tri.v);
     for (int j = 0; j < 3; ++j) N.n[0][j] = fn[3 * (size_t)t + j];
     for (int k = 0; k < 3; ++k) {
         const int o = adj[3 * (size_t)t + k];
-        const int lo = t < o ? t : o, hi = t < o ? o : t;
-        for (int j = 0; j < 3; ++j) N.n[1 + k][j] = fn[3 * (size_t)lo + j] + fn[3 * (size_t)hi + j];
-        normalize3(N.n[1 + k]);
+        if (o < 0) { for (int j = 0; j < 3; ++j) N.n[1 + k][j] = fn[3 * (size_t)t + j]; }
+        else {
+            const int lo = t < o ? t : o, hi = t < o ? o : t;
+            for (int j = 0; j < 3; ++j) N.n[1 + k][j] = fn[3 * (size_t)lo + j] + fn[3 * (size_t)hi + j];
+            normalize3(N.n[1 + k]);
+        }
         for (int j = 0; j < 3; ++j) N.n[4 + k][j] = vn[3 * (size_t)cid[3 * (size_t)t + k] + j];
         normalize3(N.n[4 + k]);
     }

@@ -596,6 +596,9 @@ int upload_all(admm_hip_ctx *ctx) {
             mo[mi] = admm_mesh::MeshMotion{ctx->mesh_upd[mi].cid, mv.d_vel, body ? mv.body_mu : 0.0, body ? 1 : 0, 0};
         }
         TRY(upload(ctx, &ctx->d_mesh_motion, mo));
+        std::vector<double> thick(ctx->meshes.size());
+        for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) thick[mi] = ctx->meshes[mi].thickness;
+        TRY(upload(ctx, &ctx->d_mesh_thick, thick));
         TRY(upload(ctx, &ctx->d_meshes, md));
         TRY(dalloc(ctx, &ctx->d_mesh_chk, 1));
     }

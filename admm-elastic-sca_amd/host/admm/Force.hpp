@@ -299,8 +299,19 @@ private:
 // validated and its BVH built once here; System registers it with its context before initialize (once per distinct mesh).
 // Invalid meshes throw std::runtime_error with the library's message.  set_vertices deforms it (the same topology, new positions:
 // admm_hip_mesh_set_vertices) and bumps `version`; System's step() hands a changed mesh to its context (admm_hip_update_collision_mesh).
+// With a half thickness > 0 (the second constructor) the surface may be open -- a sheet, a terrain patch, a half pipe -- and collides as a
+// thick shell (admm_hip_mesh_create_open): isColliding then returns r - distance (-inf beyond r) and projectOut the point after the shell
+// rule.  `half_thickness` may be changed between frames; System's step() hands a change to its context.
 class CollisionMesh : public CollisionShape {
 public:
+    CollisionMesh(Vector3d shapeCenter, const std::vector<double> &verts, const std::vector<int> &tris, double half_thickness_) : CollisionShape(shapeCenter), vertices(verts), version(0), half_thickness(half_thickness_) {
+        std::vector<int32_t> t(tris.begin(), tris.end());
+        char err[512] = {0};
+        admm_hip_mesh *m = nullptr;
+        if (admm_hip_mesh_create_open(&m, (int)(verts.size() / 3), verts.data(), (int)(t.size() / 3), t.data(), half_thickness_, err, (int)sizeof err) != ADMM_OK)
+            throw std::runtime_error(std::string("CollisionMesh: ") + err);
+        mesh = std::shared_ptr<admm_hip_mesh>(m, admm_hip_mesh_destroy);
+    }
     CollisionMesh(Vector3d shapeCenter, const std::vector<double> &verts, const std::vector<int> &tris) : CollisionShape(shapeCenter), vertices(verts), version(0) {
         std::vector<int32_t> t(tris.begin(), tris.end());
         char err[512] = {0};
@@ -332,6 +343,7 @@ public:
     long version;                          // set_vertices calls so far
     std::vector<double> velocities;        // the vertices' velocities (empty: none)
     long vel_version = 0;                  // set_vertex_velocities calls so far
+    double half_thickness = 0.0;           // 0: a closed mesh; > 0: an open surface, a shell of this half thickness (the host query uses the value at construction)
 private:
     void query(const Vector3d &p, double *pr, double &sd) const {
         const double t[3] = {center[0], center[1], center[2]}, q[3] = {p[0], p[1], p[2]};
@@ -355,6 +367,15 @@ public:
     // the Coulomb coefficient of contacts with this surface (admm_hip_set_body_surface_friction): a property of the body, whatever list
     // names it; the surface's velocity at a contact is its nodes'.  `friction` (the per-entry coefficient) stays refused on a CollisionBody.
     double surface_friction = 0.0;
+};
+
+// Extension, no reference counterpart: CollisionBody for an open surface of simulated nodes such as a cloth (admm_hip_add_sheet_surface):
+// a thick shell of half thickness r that follows its nodes and is ignored by them; every rule and refusal of a CollisionBody holds.
+class CollisionSheet : public CollisionBody {
+public:
+    CollisionSheet(int node_first_, int node_count_, const std::vector<int> &tris_, double half_thickness_) : CollisionBody(node_first_, node_count_, tris_), half_thickness(half_thickness_) {}
+    int shape_type() const { return typeid(*this) == typeid(CollisionSheet) ? ADMM_SHAPE_MESH : -1; }
+    double half_thickness;
 };
 
 // One force over ALL nodes (CollisionForce.hpp:31-46).  With analytic shapes only: a device batch with one element per

@@ -375,6 +375,7 @@ protected:
     bool friction_pushed = false;                                      // a CollisionShape::friction != 0 went to the context: keep handing the coefficients over
     bool frames_pushed = false;                                        // ... likewise a frame that is not the identity, or a box
     bool motion_pushed = false;                                        // ... likewise a nonzero rigid motion
+    std::vector<double> mesh_thick;                                    // the CollisionMesh::half_thickness the context last received
     std::vector<long> mesh_vel_versions;                               // the CollisionMesh::vel_version the context last received
     std::vector<double> body_mu;                                       // the CollisionBody::surface_friction the context last received
     std::vector<std::pair<const CollisionBody *, int> > body_ids;     // CollisionBody surfaces registered with the context -> their mesh_id
@@ -447,7 +448,7 @@ protected:
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
         mesh_ids.clear(); mesh_versions.clear(); body_ids.clear(); friction_pushed = false;
-        motion_pushed = false; frames_pushed = false; mesh_vel_versions.clear(); body_mu.clear();
+        motion_pushed = false; frames_pushed = false; mesh_vel_versions.clear(); mesh_thick.clear(); body_mu.clear();
         initialized = false;
     }
 
@@ -457,14 +458,16 @@ protected:
             const CollisionShape &sh = *cf->collisionShapes[q];
             ty.push_back(sh.shape_type());
             par.push_back(sh.center[0]); par.push_back(sh.center[1]); par.push_back(sh.center[2]);
-            if (sh.shape_type() == ADMM_SHAPE_MESH && typeid(sh) == typeid(CollisionBody)) {      // a body surface: registered once, then it follows its nodes
+            if (sh.shape_type() == ADMM_SHAPE_MESH && (typeid(sh) == typeid(CollisionBody) || typeid(sh) == typeid(CollisionSheet))) {      // a body surface (a sheet: an open one): registered once, then it follows its nodes
                 const CollisionBody &cb = static_cast<const CollisionBody &>(sh);
                 size_t k = 0;
                 while (k < body_ids.size() && body_ids[k].first != &cb) ++k;
                 if (k == body_ids.size()) {
                     int id = -1;
                     const std::vector<int32_t> t(cb.tris.begin(), cb.tris.end());
-                    if (!check(admm_hip_add_body_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), &id))) return false;
+                    const CollisionSheet *cs = dynamic_cast<const CollisionSheet *>(&cb);
+                    if (!check(cs ? admm_hip_add_sheet_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), cs->half_thickness, &id)
+                                  : admm_hip_add_body_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), &id))) return false;
                     body_ids.push_back(std::make_pair(&cb, id));
                     body_mu.push_back(0.0);
                 }
@@ -484,9 +487,14 @@ protected:
                     mesh_ids.push_back(std::make_pair(m, id));
                     mesh_versions.push_back(cm.version);
                     mesh_vel_versions.push_back(0);
+                    mesh_thick.push_back(cm.half_thickness);
                 } else if (mesh_versions[k] != cm.version) {      // deformed since the context last saw it (CollisionMesh::set_vertices)
                     if (!check(admm_hip_update_collision_mesh(gpu, mesh_ids[k].second, (int)(cm.vertices.size() / 3), cm.vertices.data()))) return false;
                     mesh_versions[k] = cm.version;
+                }
+                if (mesh_thick[k] != cm.half_thickness) {      // an open mesh's half thickness, changed since the context last saw it
+                    if (!check(admm_hip_set_collision_mesh_thickness(gpu, mesh_ids[k].second, cm.half_thickness))) return false;
+                    mesh_thick[k] = cm.half_thickness;
                 }
                 // its vertex velocities, once the context is finalized (the library takes them from then on: step() calls this every frame)
                 if (initialized && mesh_vel_versions[k] != cm.vel_version) {

@@ -98,6 +98,12 @@ def sym_plane(w, l, size=1.0):
     return x, np.array(tris, dtype=np.int32)
 
 
+def sheet_tris(w, l, node_first=0):
+    """The triangles of a (w x l)-cell sym_plane cloth as a sheet surface: global node ids for a cloth whose nodes start at
+    node_first (System.add_sheet_surface), in sym_plane's order and (consistent) orientation."""
+    return (sym_plane(w, l)[1] + np.int32(node_first)).astype(np.int32)
+
+
 def bend_hinges(tris):
     """One hinge (i0, i1, i2, i3) per interior edge: i2,i3 the shared edge,
     i0/i1 the opposite vertices (BendForce rows are x0-x2, x3-x2, x1-x2;

@@ -163,7 +163,7 @@ int  admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, cons
  *     ADMM iterations.  No read-back: a frame whose positions the update would refuse (non-finite vertex, zero-area triangle,
  *     non-positive volume) keeps the last good surface, is counted, and the step returns ADMM_OK;
  *   - has an owner, its node range: the collision elements of those nodes skip the mesh (every interior node is inside its own body).
- * Self-collision within one body, open surfaces and edge-edge contact are out of scope.  Friction against a body surface:
+ * Self-collision within one body and edge-edge contact are out of scope (open surfaces: the thick-shell section below).  Friction against a body surface:
  * admm_hip_set_body_surface_friction below; it acts on the node in contact only, the surface's own nodes feel no reaction from it.
  *   admm_hip_add_body_surface  before finalize; tris [n_tris][3] are global node ids, all inside [node_first, node_first + node_count).
  *                           Vertices: the distinct referenced nodes in ascending id order, at their current positions (admm_hip_add_nodes
@@ -293,6 +293,54 @@ int  admm_hip_mesh_velocity_query(const admm_hip_mesh *mesh, int64_t n, const do
 int  admm_hip_set_collision_frames(admm_hip_ctx *ctx, int n_shapes, const double *frames);
 int  admm_hip_shape_query(int type, const double params[4], const double *frame, int64_t n, const double *p, double *out, int32_t *moved);
 int  admm_hip_mesh_query_framed(const admm_hip_mesh *mesh, const double t[3], const double *frame, int64_t n_pts, const double *pts, double *proj, double *sdist);
+
+/* ---- open triangle surfaces as thick shells ----------------------------------------------------------------------------------------
+ * Extension, no reference counterpart.  An open surface -- a sheet, a flag, a terrain patch, a half pipe, a cloth -- has no inside, so
+ * the closed-mesh rule has no meaning for it.  It collides as a shell of half thickness r > 0: it occupies every point whose distance to
+ * the surface is below r, and a point is pushed to distance r on the side it is currently on.  For a candidate q (relative to the entry's
+ * translation t, in local coordinates under a frame), every product and sum rounded, no fused multiply-adds, in this order:
+ *     1. the traversal runs only when  lo_j - r < q_j < hi_j + r  holds strictly for j = 0, 1, 2 (lo, hi: the root box); a point that
+ *        fails keeps its bits;
+ *     2. h = the closest point c (ties: the lowest triangle index) and its squared distance d2, from a search bounded by r * r: the
+ *        hit of the closed meshes' search whenever d2 < r * r, none otherwise;
+ *     3. the point collides exactly when a hit exists and  d2 < r * r;
+ *     4. e_j = q_j - c_j,  d = sqrt(d2);   d > 0:  s = r / d,  p'_j = c_j + s * e_j;   d == 0:  p'_j = c_j + r * n_j  with n the unit
+ *        normal of the winning triangle;
+ *     5. p_j = t_j + p'_j, then under a frame to_world -- only for a point that was moved.
+ * Everything after the push is what a closed mesh's entry does on the world-space points: the coefficient, the vertex velocities
+ * interpolated at the hit, the rigid motion, the friction rule.  The rule has no memory of the side a node started the frame on: a node
+ * that crosses the mid-surface within one frame leaves on the far side, so keep r above closing speed x dt.  Self-collision of a sheet,
+ * edge-edge contact, continuous detection, a thickness on closed meshes and reactions on a sheet's own nodes are out of scope.
+ *   admm_hip_mesh_create_open   like admm_hip_mesh_create for a surface that may have boundary edges: every directed edge at most once
+ *                           (edge-manifold, consistently oriented where two faces meet), no degenerate triangle, half_thickness finite
+ *                           and > 0; at least one triangle.  A closed input is accepted and simply is a shell.  ADMM_ERR_ARG with the
+ *                           edge or triangle named in err otherwise.  The same BVH, leaf order and topology tables as a closed mesh; a
+ *                           boundary edge's pseudo-normal is its one face's normal.
+ *   admm_hip_mesh_thickness     *r = the half thickness; 0 for a closed mesh.
+ *   on an open mesh, admm_hip_mesh_query / _framed return  proj = the point after the rule (bitwise the input where the rule does not move
+ *                           it)  and  sdist = r - d  where a triangle is nearer than r (positive: colliding), -inf where the bounded
+ *                           search found none or the box test failed; admm_hip_mesh_velocity_query, admm_hip_mesh_info: unchanged;
+ *                           admm_hip_mesh_set_vertices / admm_hip_update_collision_mesh refuse a wrong count, a non-finite vertex and a
+ *                           zero-area triangle only (no volume condition).
+ *   admm_hip_mesh_closest       the two searches as they are, for tests: r2 < 0: the unbounded one, else the one bounded by r2, for n
+ *                           points q [n][3] relative to the instance: c [n][3], d2 [n], slot [n] (leaf order; -1: none), reg [n] (the
+ *                           feature: 0 face, 1-3 edges, 4-6 vertices), tri [n] (the original triangle).  Any output may be NULL.
+ *   admm_hip_add_collision_mesh accepts an open mesh; an ADMM_SHAPE_MESH entry names it like any other.  A list that names an open mesh
+ *                           makes the collision batches launch project_collision_shell_kernel; a list that names none launches exactly
+ *                           what it launched before.  Only admm_hip_set_collision_shapes can change that; it drops the captured graphs then.
+ *   admm_hip_set_collision_mesh_thickness  a registered open mesh's half thickness, before or after finalize, between frames; it lives in a
+ *                           device table and changes under a captured graph like a shape parameter.  ADMM_ERR_ARG: a closed mesh, r not
+ *                           finite or not > 0.
+ *   admm_hip_add_sheet_surface  admm_hip_add_body_surface for an open surface of simulated nodes, such as a cloth: the same vertex
+ *                           numbering, owner range, frame-start update (verdict on the device, counted in the status, a refused frame
+ *                           keeps the last good surface; no volume condition) and refusals (a per-entry coefficient, a translation, a
+ *                           frame, admm_hip_update_collision_mesh); admm_hip_get_body_surface_status and
+ *                           admm_hip_set_body_surface_friction apply to it.  Its own nodes skip it: no self-collision.                  */
+int  admm_hip_mesh_create_open(admm_hip_mesh **out, int nv, const double *verts, int nt, const int32_t *tris, double half_thickness, char *err, int err_len);
+int  admm_hip_mesh_thickness(const admm_hip_mesh *mesh, double *r);
+int  admm_hip_mesh_closest(const admm_hip_mesh *mesh, int64_t n, const double *q, double r2, double *c, double *d2, int32_t *slot, int32_t *reg, int32_t *tri);
+int  admm_hip_set_collision_mesh_thickness(admm_hip_ctx *ctx, int mesh_id, double half_thickness);
+int  admm_hip_add_sheet_surface(admm_hip_ctx *ctx, int node_first, int node_count, int n_tris, const int32_t *tris, double half_thickness, int *mesh_id);
 
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
@@ -463,6 +511,9 @@ int admm_hip_debug_potrf_inv(admm_hip_ctx *ctx, int w, int ld, double *blk, doub
  * *iter_graph = 1 when a per-iteration HIP graph exists, *frame_graph = ADMM iterations of the whole-frame graph (0: none),
  * *graph_launches = graph launches issued by the context so far.  Any pointer may be NULL.                               */
 int admm_hip_debug_graph_state(admm_hip_ctx *ctx, int *iter_graph, int *frame_graph, int64_t *graph_launches);
+/* which kernels the collision batches launch for the current shape list: 0 the frictionless ones, 1 the friction form, 2 its moving form,
+ * 3 the framed form, 4 the shell form (a list that names an open mesh).  A call that changes the value drops the captured graphs.         */
+int admm_hip_debug_collision_form(admm_hip_ctx *ctx, int *form);
 
 typedef struct admm_hip_info {
     int64_t n_nodes, n_elems_total, n_elems_local, rows_compact;

@@ -83,8 +83,10 @@ enum admm_shape {
     ADMM_SHAPE_FLOOR    = 0,   /* params { -, cy, -, - }        CollisionFloor.hpp:51-58    */
     ADMM_SHAPE_SPHERE   = 1,   /* params { cx, cy, cz, radius } CollisionSphere.hpp:50-66   */
     ADMM_SHAPE_CYLINDER = 2,   /* params { cx, cy, -, radius }  z-axis, CollisionCylinder.hpp:48-66 */
-    ADMM_SHAPE_MESH     = 3,   /* params { tx, ty, tz, mesh_id } a closed triangle mesh registered with admm_hip_add_collision_mesh,
-                                  translated by t (extension, no reference counterpart; include/admm_hip.h) */
+    ADMM_SHAPE_MESH     = 3,   /* params { tx, ty, tz, mesh_id } a triangle mesh registered with admm_hip_add_collision_mesh, translated by
+                                  t: a closed mesh (points inside it are pushed to its surface) or an open surface with a half thickness
+                                  (admm_hip_mesh_create_open, admm_hip_add_sheet_surface: a thick shell, points nearer than the half
+                                  thickness are pushed to that distance) (extension, no reference counterpart; include/admm_hip.h) */
     ADMM_SHAPE_BOX      = 4    /* params { hx, hy, hz, - } half extents > 0; centred at its frame's pivot (admm_hip_set_collision_frames),
                                   at the origin without one (extension, no reference counterpart; include/admm_hip.h) */
 };
