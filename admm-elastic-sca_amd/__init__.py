@@ -174,6 +174,9 @@ def lib():
         L.admm_hip_mesh_closest.argtypes = [C.c_void_p, C.c_int64, _dp, C.c_double, _dp, _dp, _ip, _ip, _ip]
         L.admm_hip_set_collision_mesh_thickness.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.admm_hip_add_sheet_surface.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, C.c_double, C.POINTER(C.c_int)]
+        L.admm_hip_set_sheet_self_collision.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.admm_hip_mesh_query_excluding.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, _dp, _dp, _dp, _dp, _ip]
+        L.admm_hip_mesh_velocity_query_excluding.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, _dp, _dp, _dp, _dp, _ip]
         _lib = L
     return _lib
 
@@ -252,6 +255,34 @@ class Mesh:
         if rc != 0:
             raise AdmmHipError("admm_hip_mesh_query error %d" % rc)
         return proj, sd
+
+    def query_excluding(self, pts, skip_vertex, t=(0.0, 0.0, 0.0), frame=None):
+        """the shell rule of an open mesh with a per-point excluded vertex (admm_hip_mesh_query_excluding; self-collision of a sheet): the
+        bounded search of point i ignores every triangle that has vertex skip_vertex[i] as a corner (-1: none, the bits of query) ->
+        (proj [n][3], sdist [n], tri [n]: the winning original triangle, -1: none nearer than the half thickness).  A closed mesh or an
+        id outside [-1, nv) raises AdmmHipError."""
+        p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(skip_vertex, dtype=np.int32), (p.shape[0],)))
+        tt = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        f = None if frame is None else frame_array(frame)
+        proj = np.empty_like(p); sd = np.empty(p.shape[0]); tri = np.empty(p.shape[0], np.int32)
+        rc = self.L.admm_hip_mesh_query_excluding(self.h, p.shape[0], _d(p), _i(sk), _d(tt), _d(f), _d(proj), _d(sd), _i(tri))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_query_excluding error %d" % rc)
+        return proj, sd, tri
+
+    def velocity_query_excluding(self, pts, skip_vertex, vel, t=(0.0, 0.0, 0.0)):
+        """mesh_velocity_query at the hit of query_excluding's search (admm_hip_mesh_velocity_query_excluding) -> (out, weights,
+        corner_ids); zeros and ids -1 where no triangle outside the excluded 1-ring is nearer than the half thickness"""
+        p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(skip_vertex, dtype=np.int32), (p.shape[0],)))
+        tt = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        v = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+        out = np.empty_like(p); wts = np.empty_like(p); ids = np.empty(p.shape, np.int32)
+        rc = self.L.admm_hip_mesh_velocity_query_excluding(self.h, p.shape[0], _d(p), _i(sk), _d(tt), _d(v), _d(out), _d(wts), _i(ids))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_velocity_query_excluding error %d" % rc)
+        return out, wts, ids
 
     def set_vertices(self, verts):
         """new vertex positions [nv][3] for the same topology (admm_hip_mesh_set_vertices): pseudo-normals recomputed, BVH boxes refit.
@@ -494,7 +525,7 @@ class System:
 
     def collision_form(self):
         """which kernels the collision batches launch for the current list (admm_hip_debug_collision_form): 0 frictionless, 1 friction,
-        2 moving friction, 3 framed, 4 shell"""
+        2 moving friction, 3 framed, 4 shell, 5 sheet self-collision"""
         f = C.c_int()
         self._chk(self.L.admm_hip_debug_collision_form(self.h, C.byref(f)))
         return f.value
@@ -549,13 +580,21 @@ class System:
         frames; captured graphs stay.  A closed mesh, or a value that is not finite and > 0, raises AdmmHipError."""
         self._chk(self.L.admm_hip_set_collision_mesh_thickness(self.h, int(mesh_id), float(half_thickness)))
 
-    def add_sheet_surface(self, node_first, node_count, tris, half_thickness):
+    def add_sheet_surface(self, node_first, node_count, tris, half_thickness, self_collision=False):
         """registers a sheet surface (before initialize): add_body_surface for an open surface of simulated nodes such as a cloth, a
-        shell of the given half thickness that follows its nodes and is ignored by them -> its mesh_id"""
+        shell of the given half thickness that follows its nodes and is ignored by them -> its mesh_id.  self_collision: its own nodes
+        meet it too, outside their 1-ring (set_sheet_self_collision)."""
         t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
         mid = C.c_int()
         self._chk(self.L.admm_hip_add_sheet_surface(self.h, int(node_first), int(node_count), t.shape[0], _i(t), float(half_thickness), C.byref(mid)))
+        if self_collision:
+            self.set_sheet_self_collision(mid.value, True)
         return mid.value
+
+    def set_sheet_self_collision(self, mesh_id, on=True):
+        """a sheet surface's own nodes collide with it outside their 1-ring (admm_hip_set_sheet_self_collision; before initialize, which
+        refuses a sheet with a vertex nearer than the half thickness to a triangle it is not a corner of)"""
+        self._chk(self.L.admm_hip_set_sheet_self_collision(self.h, int(mesh_id), 1 if on else 0))
 
     def add_body_surface(self, node_first, node_count, tris):
         """registers a body surface (before initialize): a closed mesh of simulated nodes, tris [nt][3] global node ids inside

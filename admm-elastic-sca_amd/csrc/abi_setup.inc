@@ -482,6 +482,42 @@ int admm_hip_add_sheet_surface(admm_hip_ctx *ctx, int node_first, int node_count
     return add_node_surface(ctx, node_first, node_count, n_tris, tris, half_thickness, mesh_id);
 }
 
+// extension, no reference counterpart (include/admm_hip.h): a sheet surface whose own nodes meet it outside their 1-ring instead of
+// skipping it (project_collision_self_kernel); before finalize, which checks the rest pose against the half thickness
+int admm_hip_set_sheet_self_collision(admm_hip_ctx *ctx, int mesh_id, int on) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "sheet self-collision must be set before finalize");
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    if (ctx->mesh_role[mesh_id].body_nodes.empty())
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is an obstacle mesh, not a sheet surface: it has no nodes to collide with itself", mesh_id);
+    if (!(ctx->meshes[mesh_id].thickness > 0.0))
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed body surface, not a sheet surface: self-collision of a closed surface is not supported", mesh_id);
+    ctx->mesh_role[mesh_id].self_collision = on != 0;
+    return ADMM_OK;
+}
+
+// finalize: every sheet that collides with itself must be clear of itself where it stands -- no vertex nearer than the half thickness to
+// a triangle it is not a corner of, or every node would be pushed by its own neighbourhood from the first frame -- and a node takes its
+// vertex id from one such sheet only
+static int check_sheet_self_collision(admm_hip_ctx *ctx) {
+    for (size_t i = 0; i < ctx->meshes.size(); ++i) {
+        const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+        if (!R.self_collision) continue;
+        for (size_t k = 0; k < i; ++k)      // (owner ranges overlap only when they are equal)
+            if (ctx->mesh_role[k].self_collision && ctx->mesh_role[k].own_first == R.own_first && ctx->mesh_role[k].own_count == R.own_count)
+                return fail(ctx, ADMM_ERR_ARG, "sheet surfaces %d and %d both collide with themselves and share the node range [%d, %d): a node takes its vertex id from one such sheet",
+                            (int)k, (int)i, R.own_first, R.own_first + R.own_count);
+        int v = -1, t = -1; double d = 0.0;
+        if (admm_mesh::sheet_rest_violation(ctx->meshes[i], &v, &t, &d)) {
+            const int *c = ctx->meshes[i].cid.data() + 3 * (size_t)t;
+            return fail(ctx, ADMM_ERR_ARG, "sheet surface %d: vertex %d (node %d) lies at distance %g from triangle %d (%d, %d, %d), which it is not a corner of: nearer than the half "
+                        "thickness %g, the sheet would collide with itself at rest", (int)i, v, R.body_nodes[v], d, t, c[0], c[1], c[2], ctx->meshes[i].thickness);
+        }
+    }
+    return ADMM_OK;
+}
+
 // the half thickness of a registered open mesh, between frames: one entry of the device table project_collision_shell_kernel reads
 // (no kernel changes, captured graphs stay)
 int admm_hip_set_collision_mesh_thickness(admm_hip_ctx *ctx, int mesh_id, double half_thickness) {
@@ -661,6 +697,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     TRY(check_body_frames(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], &ctx->shapes.frame[0][0]));
     for (int j = 0; j < ctx->shapes.n; ++j)
         if (!(ctx->shapes.mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, ctx->shapes.mu[j]);
+    TRY(check_sheet_self_collision(ctx));
     TRY(host_assemble(ctx, false));
     TRY(host_factor(ctx, false));
     ctx->info.rank = ctx->rank; ctx->info.world = ctx->world;

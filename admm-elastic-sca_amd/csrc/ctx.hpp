@@ -137,7 +137,8 @@ struct admm_hip_ctx {
     // what a mesh is to the scene, parallel to `meshes`: its owner, the node range [own_first, own_first + own_count) whose collision
     // elements skip it (own_count 0: none; admm_hip_set_collision_mesh_owner), and for a body surface (admm_hip_add_body_surface) the
     // node behind every vertex, ascending -- the device rebuilds it from them at every step (launch.inc: update_bodies)
-    struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; };
+    // self_collision (a sheet surface only, admm_hip_set_sheet_self_collision): its own nodes meet it outside their 1-ring instead of skipping it
+    struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; bool self_collision = false; };
     std::vector<MeshRole> mesh_role;
     // obstacles that move (admm_hip_set_collision_motion: shapes.motion; admm_hip_set_collision_mesh_velocity, admm_hip_set_body_surface_friction):
     // per mesh, parallel to `meshes`, the host's record and the device table the moving friction kernel reads.  d_vel: an obstacle's
@@ -148,6 +149,9 @@ struct admm_hip_ctx {
     // open meshes (thick shells, admm_hip_mesh::thickness > 0): the half thickness of every mesh, parallel to d_meshes (0: a closed mesh), a
     // table of its own that project_collision_shell_kernel alone reads; admm_hip_set_collision_mesh_thickness writes one entry
     double *d_mesh_thick = nullptr;
+    // contexts where some sheet collides with itself (else both null): the flag of every mesh, parallel to d_meshes, and for every node in
+    // device order its vertex id on the self-colliding sheet that owns it (-1: none); project_collision_self_kernel alone reads them
+    int *d_mesh_self = nullptr, *d_self_vid = nullptr;
     int *d_body_tag = nullptr;      // contexts with an owner: the owner group of every node in device order (-1: none), for MeshDev::owner
     SymCSC A;
     Factor F;

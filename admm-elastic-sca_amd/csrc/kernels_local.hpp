@@ -766,6 +766,103 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_shell_kernel(Ba
     }
 }
 
+// ... with a sheet surface that collides with itself (admm_hip_set_sheet_self_collision; a context where self_on holds, launch.inc,
+// launches this form for its collision batches; every kernel above stays as it is).  A sibling of project_collision_shell_kernel: the
+// same lane per node, LDS stack column, owner skip, frames, box, coefficients, motions and vertex velocities.  For an entry whose mesh
+// the node's body owns: self[mesh] == 0 (uniform across the wave): skipped, as there; != 0: the shell branch with
+// closest_within_excluding and the node's vertex id vid[node], so that the triangles around the node are left out.  Any other entry runs
+// the shell kernel's code and gives its bits (skip = -1).  The surface is the frame-start one: a node meets where the rest of the cloth
+// was at the start of the frame.  self: the flag of every mesh, parallel to meshes; vid: one id per node in device order (-1: none).
+__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_self_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
+                                                                               const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
+                                                                               const admm_mesh::MeshMotion *__restrict__ mm, const double *__restrict__ thick, const int *__restrict__ tag,
+                                                                              const int *__restrict__ self, const int *__restrict__ vid,
+                                                                              const double dt) {
+    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
+    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
+    const int n = b.n;
+    if (e >= b.e1) return;
+    const int id = b.idx[e];
+    const int ds = b.dst[e];
+    const double s = b.w2h2[e];
+    double dx[3], u[3], p[3], x0[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
+        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
+        x0[j] = xs[3 * (size_t)id + j];
+        u[j] = b.u[(size_t)j * n + e];
+        p[j] = dx[j] + u[j];
+    }
+    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
+    const int own = tag ? tag[id] : -1;
+    const int vi_own = vid[id];      // the node's vertex id on the self-colliding sheet that owns it (-1: none)
+    const int ns = shapes->n;
+    for (int q = 0; q < ns; ++q) {
+        const double before[3] = {p[0], p[1], p[2]};
+        const double *f = shapes->frame[q];
+        const bool framed = shapes->framed[q] != 0;
+        const int ty = shapes->type[q];
+        double mu = shapes->mu[q];
+        double vi[3] = {0.0, 0.0, 0.0};      // the mesh's vertex velocities at the hit, world axes
+        bool vhit = false;
+        if (ty != ADMM_SHAPE_MESH) {
+            if (!admm_frame::collide_entry(ty, shapes->par[q], f, framed, p)) continue;
+        } else {
+            const int mi = (int)shapes->par[q][3];
+            const admm_mesh::MeshDev m = meshes[mi];
+            const bool mine = own >= 0 && m.owner == own;
+            if (mine && !self[mi]) continue;
+            double l[3] = {p[0], p[1], p[2]};
+            if (framed) admm_frame::to_local(f, p, l);
+            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
+            const double qq[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
+            const double r = thick[mi];
+            admm_mesh::Hit h;
+            if (r > 0.0) {      // an open mesh: the shell rule (mesh_query.hpp), steps 1 to 4
+                if (!admm_mesh::in_shell_box(qq, m.nodes[0], r)) continue;
+                // the node's own sheet: without the triangles around its vertex (their corner ids: three loads per leaf triangle, per lane);
+                // any other entry: skip = -1, nothing is left out and cid is not read -- closest_within's operations
+                admm_mesh::closest_within_excluding(m.nodes, m.tris, mm[mi].cid, mine ? vi_own : -1, qq, r * r, stk, h);
+                if (!admm_mesh::shell_collides(h, r)) continue;
+                double o[3];
+                admm_mesh::shell_push(qq, h, m.nrm, r, o);
+                l[0] = t[0] + o[0]; l[1] = t[1] + o[1]; l[2] = t[2] + o[2];
+            } else {
+                if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
+                admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
+                if (!(admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0)) continue;
+                l[0] = t[0] + h.c[0]; l[1] = t[1] + h.c[1]; l[2] = t[2] + h.c[2];
+            }
+            if (framed) admm_frame::to_world(f, l, p); else { p[0] = l[0]; p[1] = l[1]; p[2] = l[2]; }
+            const admm_mesh::MeshMotion mo = mm[mi];
+            if (mo.body) mu = mo.mu;
+            if (mo.vel && mu > 0.0) {
+                const admm_mesh::Tri &tr = m.tris[h.slot];
+                const int *c = mo.cid + 3 * (size_t)tr.orig;
+                const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
+                const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
+                double bw[3];
+                admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
+                vi[0] = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi[1] = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi[2] = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
+                if (framed) admm_frame::rotate(f, vi, vi);
+                vhit = true;
+            }
+        }
+        if (!(mu > 0.0)) continue;
+        double w[3];
+        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
+        if (vhit) { w[0] = w[0] + dt * vi[0]; w[1] = w[1] + dt * vi[1]; w[2] = w[2] + dt * vi[2]; }
+        admm_friction::apply_moving(before, p, x0, w, mu);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double un = u[j] + (dx[j] - p[j]);
+        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
+        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Spring, Force.cpp:52-71   (rows: x_a - x_b)
 // ---------------------------------------------------------------------------

@@ -56,9 +56,20 @@ bool shell_on(const admm_hip_ctx *ctx) {
     }
     return false;
 }
+// ... and does an entry of the current list name a sheet surface that collides with itself (admm_hip_set_sheet_self_collision)?  Then the
+// collision batches run project_collision_self_kernel, the shell form plus the search that leaves out a node's own 1-ring, in a launch of
+// their own in both launch modes.  A context where no sheet self-collides launches exactly what it launched before.
+bool self_on(const admm_hip_ctx *ctx) {
+    for (int q = 0; q < ctx->shapes.n; ++q) {
+        if (ctx->shapes.type[q] != ADMM_SHAPE_MESH) continue;
+        const int id = (int)ctx->shapes.par[q][3];
+        if (id >= 0 && id < (int)ctx->mesh_role.size() && ctx->mesh_role[id].self_collision) return true;
+    }
+    return false;
+}
 // which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form, 3 the framed form, 4 the
-// shell form
-int collision_form(const admm_hip_ctx *ctx) { return shell_on(ctx) ? 4 : framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
+// shell form, 5 the self-collision form
+int collision_form(const admm_hip_ctx *ctx) { return self_on(ctx) ? 5 : shell_on(ctx) ? 4 : framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
 // ... in a launch of their own (launch_collision_mesh) instead of a segment of project_multi_kernel or project_collision_kernel
 bool collision_own_launch(const admm_hip_ctx *ctx) { return !ctx->meshes.empty() || friction_on(ctx) || framed_on(ctx); }
 
@@ -179,7 +190,11 @@ void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
-    if (shell_on(ctx)) {      // (implies meshes)
+    if (self_on(ctx)) {      // (implies shell_on; d_mesh_self and d_self_vid were uploaded at finalize: the flag is set before it)
+        hipLaunchKernelGGL(project_collision_self_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
+                           (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, (const int *)ctx->d_mesh_self, (const int *)ctx->d_self_vid, ctx->dt);
+    } else if (shell_on(ctx)) {      // (implies meshes)
         hipLaunchKernelGGL(project_collision_shell_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
                            (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
                            (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, ctx->dt);

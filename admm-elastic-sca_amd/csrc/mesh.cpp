@@ -209,6 +209,20 @@ bool shell_query(const admm_hip_mesh &M, const double *q, double *o, double *sd)
     return true;
 }
 
+// ... with the triangles around vertex `skip` left out of step 2 (closest_within_excluding; skip < 0: none, the bits of shell_query);
+// *tri = the winning original triangle, -1: none
+bool shell_query_excluding(const admm_hip_mesh &M, const double *q, int skip, double *o, double *sd, int *tri) {
+    const double r = M.thickness;
+    *sd = -INFINITY; *tri = -1;
+    if (!in_shell_box(q, M.nodes[0], r)) return false;
+    HostStack stk; Hit h;
+    closest_within_excluding(M.nodes.data(), M.tris.data(), M.cid.data(), skip, q, r * r, stk, h);
+    if (h.slot >= 0) { *sd = r - std::sqrt(h.d2); *tri = M.tris[h.slot].orig; }
+    if (!shell_collides(h, r)) return false;
+    shell_push(q, h, M.nrm.data(), r, o);
+    return true;
+}
+
 } // namespace
 
 namespace admm_mesh {
@@ -254,6 +268,23 @@ int mesh_set_vertices(admm_hip_mesh &M, int nv, const double *verts, char *err, 
     for (int d = M.depth; d >= 0; --d)
         for (int i = M.lvl_ptr[d]; i < M.lvl_ptr[d + 1]; ++i) refit_node(M.nodes.data(), M.tris.data(), M.lvl_nodes[i]);
     return ADMM_OK;
+}
+
+// the rest-pose condition of a sheet that collides with itself: the lowest vertex that lies nearer than the half thickness to a triangle
+// it is not a corner of (the host form of the self-collision query over the sheet's own vertices) -> true, with the triangle and the
+// distance; false: none
+bool sheet_rest_violation(const admm_hip_mesh &M, int *vtx, int *tri, double *dist) {
+    std::vector<double> verts(3 * (size_t)M.nv, 0.0);
+    for (size_t s = 0; s < M.tris.size(); ++s)
+        for (int k = 0; k < 3; ++k) for (int j = 0; j < 3; ++j) verts[3 * (size_t)M.cid[3 * (size_t)M.tris[s].orig + k] + j] = M.tris[s].v[3 * k + j];
+    const double r = M.thickness;
+    for (int v = 0; v < M.nv; ++v) {
+        if (M.inc_ptr[v] == M.inc_ptr[v + 1]) continue;      // (a vertex no triangle uses)
+        HostStack stk; Hit h;
+        closest_within_excluding(M.nodes.data(), M.tris.data(), M.cid.data(), v, &verts[3 * (size_t)v], r * r, stk, h);
+        if (shell_collides(h, r)) { *vtx = v; *tri = M.tris[h.slot].orig; *dist = std::sqrt(h.d2); return true; }
+    }
+    return false;
 }
 
 } // namespace admm_mesh
@@ -394,6 +425,64 @@ int admm_hip_mesh_query_framed(const admm_hip_mesh *mesh, const double t[3], con
             admm_frame::to_world(frame, c, proj + 3 * i);
         }
         if (sdist) { const double d = std::sqrt(h.d2); sdist[i] = in ? d : -d; }
+    }
+    return ADMM_OK;
+}
+
+// the shell rule with a per-point excluded vertex (self-collision of a sheet: a node that is vertex skip_vertex[i] of the surface does not
+// meet the triangles around it), the host evaluation of what project_collision_self_kernel runs: admm_hip_mesh_query_framed on an open
+// mesh with closest_within_excluding in step 2.  tri: the winning original triangle (-1: none nearer than r).  skip_vertex[i] = -1 (or
+// skip_vertex NULL): the bits of admm_hip_mesh_query_framed.  Refused on a closed mesh and for an id outside [-1, nv).
+int admm_hip_mesh_query_excluding(const admm_hip_mesh *mesh, int64_t n_pts, const double *pts, const int32_t *skip_vertex, const double t[3], const double *frame,
+                                  double *proj, double *sdist, int32_t *tri) {
+    if (!mesh || !t || n_pts < 0 || (n_pts && !pts)) return ADMM_ERR_ARG;
+    if (!(mesh->thickness > 0.0)) return ADMM_ERR_ARG;
+    int which; double by;
+    if (frame && admm_frame::check(frame, &which, &by)) return ADMM_ERR_ARG;
+    if (skip_vertex) for (int64_t i = 0; i < n_pts; ++i) if (skip_vertex[i] < -1 || skip_vertex[i] >= mesh->nv) return ADMM_ERR_ARG;
+    const bool framed = frame && !admm_frame::identity(frame);
+    for (int64_t i = 0; i < n_pts; ++i) {
+        double l[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        if (framed) admm_frame::to_local(frame, pts + 3 * i, l);
+        const double q[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
+        double o[3] = {0.0, 0.0, 0.0}, sd; int ti;
+        const bool hit = shell_query_excluding(*mesh, q, skip_vertex ? skip_vertex[i] : -1, o, &sd, &ti);
+        if (proj) {
+            const double c[3] = {t[0] + o[0], t[1] + o[1], t[2] + o[2]};
+            if (hit && framed) admm_frame::to_world(frame, c, proj + 3 * i);
+            else for (int j = 0; j < 3; ++j) proj[3 * i + j] = hit ? c[j] : pts[3 * i + j];
+        }
+        if (sdist) sdist[i] = sd;
+        if (tri) tri[i] = ti;
+    }
+    return ADMM_OK;
+}
+
+// admm_hip_mesh_velocity_query at the hit of that search: the winning triangle among those that do not have skip_vertex[i] as a corner and
+// lie nearer than the mesh's half thickness; a point without such a triangle gets zeros and corner ids -1
+int admm_hip_mesh_velocity_query_excluding(const admm_hip_mesh *mesh, int64_t n, const double *q, const int32_t *skip_vertex, const double t[3], const double *vel,
+                                           double *out, double *weights, int32_t *corner_ids) {
+    if (!mesh || !t || n < 0 || (n && !q) || (out && !vel)) return ADMM_ERR_ARG;
+    if (!(mesh->thickness > 0.0)) return ADMM_ERR_ARG;
+    if (skip_vertex) for (int64_t i = 0; i < n; ++i) if (skip_vertex[i] < -1 || skip_vertex[i] >= mesh->nv) return ADMM_ERR_ARG;
+    const double r = mesh->thickness;
+    for (int64_t i = 0; i < n; ++i) {
+        const double qq[3] = {q[3 * i] - t[0], q[3 * i + 1] - t[1], q[3 * i + 2] - t[2]};
+        HostStack stk; Hit h;
+        h.slot = -1;
+        if (in_shell_box(qq, mesh->nodes[0], r))
+            closest_within_excluding(mesh->nodes.data(), mesh->tris.data(), mesh->cid.data(), skip_vertex ? skip_vertex[i] : -1, qq, r * r, stk, h);
+        if (h.slot < 0) {
+            for (int k = 0; k < 3; ++k) { if (weights) weights[3 * i + k] = 0.0; if (corner_ids) corner_ids[3 * i + k] = -1; if (out) out[3 * i + k] = 0.0; }
+            continue;
+        }
+        const Tri &tr = mesh->tris[h.slot];
+        const int *c = mesh->cid.data() + 3 * (size_t)tr.orig;
+        double b[3];
+        tri_weights(qq, tr.v, h.reg, b);
+        if (weights) for (int k = 0; k < 3; ++k) weights[3 * i + k] = b[k];
+        if (corner_ids) for (int k = 0; k < 3; ++k) corner_ids[3 * i + k] = c[k];
+        if (out) tri_interpolate(b, vel + 3 * (size_t)c[0], vel + 3 * (size_t)c[1], vel + 3 * (size_t)c[2], out + 3 * i);
     }
     return ADMM_OK;
 }

@@ -24,4 +24,7 @@ namespace admm_mesh {
 int mesh_set_vertices(admm_hip_mesh &M, int nv, const double *verts, char *err, int err_len);
 // ADMM_OK, or ADMM_ERR_ARG with the refusal's message (the lowest bad triangle first)
 int mesh_refusal(const admm_hip_mesh &M, const double *verts, const UpdateCheck &c, char *err, int err_len);
+// a sheet that collides with itself (admm_hip_set_sheet_self_collision): does a vertex lie nearer than the half thickness to a triangle it
+// is not a corner of?  The lowest such vertex, its triangle and the distance
+bool sheet_rest_violation(const admm_hip_mesh &M, int *vtx, int *tri, double *dist);
 }

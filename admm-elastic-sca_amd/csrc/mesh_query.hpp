@@ -22,6 +22,10 @@
 //   5. world      p_j = t_j + p'_j, then under a frame to_world -- only for a point that was moved
 // The rule does not know on which side a node started the frame: a node that crosses the mid-surface within one frame leaves on the far
 // side.  Callers keep r above closing speed x dt.
+//
+// Self-collision of a sheet (admm_hip_set_sheet_self_collision): a node that is vertex vi of the surface runs steps 1 to 5 with one change
+// in step 2 -- closest_within_excluding leaves out every triangle that has vi as a corner (the node's 1-ring: cid[3 orig + k] == vi for
+// k = 0, 1, 2); among the others the winner is the minimum of (d2, original triangle index) with d2 < r * r, as before.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -208,6 +212,52 @@ ADMM_HD void closest_within(const Node *__restrict__ nodes, const Tri *__restric
                 const double e0 = q[0] - o[0], e1 = q[1] - o[1], e2 = q[2] - o[2];
                 const double d2 = e0 * e0 + e1 * e1 + e2 * e2;
                 const int oi = tris[t].orig;
+                if (d2 < r2 && closer(d2, oi, h.d2, best_i)) { h.d2 = d2; best_i = oi; h.slot = t; h.reg = reg; h.c[0] = o[0]; h.c[1] = o[1]; h.c[2] = o[2]; }
+            }
+        } else {
+            const int l = n.a, r = n.a + 1;
+            const double dl = box_d2(q, nodes[l]), dr = box_d2(q, nodes[r]);
+            const bool rf = dr < dl || (dr == dl && centre_d2(q, nodes[r]) < centre_d2(q, nodes[l]));
+            const int near = rf ? r : l, far = rf ? l : r;
+            const double dn = rf ? dr : dl, df = rf ? dl : dr;
+            if (box_open(df, h.d2) && sp < MAX_DEPTH) { stk[sp] = far; ++sp; }
+            if (box_open(dn, h.d2)) next = near;
+        }
+        while (next < 0 && sp > 0) {
+            --sp;
+            const int cand = stk[sp];
+            if (box_open(box_d2(q, nodes[cand]), h.d2)) next = cand;
+        }
+        if (next < 0) break;
+        cur = next;
+    }
+    if (h.slot < 0) h.d2 = INFINITY;
+}
+
+// `closest_within` without the triangles that have vertex skip_vertex as a corner (cid: the corner vertex ids [nt][3] by original
+// triangle): the minimum of (d2, original triangle index) over the others, d2 < r2.  The test comes before the triangle's distance, so a
+// left-out triangle never tightens the bound; the boxes only prune (box_open), so the result does not depend on the tree.
+// skip_vertex < 0: nothing is left out, cid is not read, and every operation is closest_within's -- the same bits, ties included.
+template <class Stack>
+ADMM_HD void closest_within_excluding(const Node *__restrict__ nodes, const Tri *__restrict__ tris, const int *__restrict__ cid, const int skip_vertex,
+                                      const double *q, const double r2, Stack &stk, Hit &h) {
+    h.d2 = r2; h.slot = -1; h.reg = 0; h.c[0] = h.c[1] = h.c[2] = 0.0;
+    int best_i = NO_TRI;
+    int sp = 0, cur = 0;
+    for (;;) {
+        const Node &n = nodes[cur];
+        int next = -1;
+        if (n.cnt > 0) {
+            for (int t = n.a; t < n.a + n.cnt; ++t) {
+                const int oi = tris[t].orig;
+                if (skip_vertex >= 0) {
+                    const int *c = cid + 3 * (size_t)oi;
+                    if (c[0] == skip_vertex || c[1] == skip_vertex || c[2] == skip_vertex) continue;
+                }
+                double o[3]; int reg;
+                closest_on_tri(q, tris[t].v, o, reg);
+                const double e0 = q[0] - o[0], e1 = q[1] - o[1], e2 = q[2] - o[2];
+                const double d2 = e0 * e0 + e1 * e1 + e2 * e2;
                 if (d2 < r2 && closer(d2, oi, h.d2, best_i)) { h.d2 = d2; best_i = oi; h.slot = t; h.reg = reg; h.c[0] = o[0]; h.c[1] = o[1]; h.c[2] = o[2]; }
             }
         } else {

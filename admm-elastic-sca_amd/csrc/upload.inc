@@ -556,6 +556,20 @@ int upload_all(admm_hip_ctx *ctx) {
                 for (int k = groups[g].first; k < groups[g].first + groups[g].second; ++k) tag[F.iperm[k]] = (int)g;
             TRY(upload(ctx, &ctx->d_body_tag, tag));
         }
+        // sheets that collide with themselves: the per-mesh flag and every node's vertex id on its sheet, in this rank's device order --
+        // uploaded only when there is one, so that other contexts hold and launch what they did
+        ctx->d_mesh_self = nullptr; ctx->d_self_vid = nullptr;
+        {
+            std::vector<int> flag(ctx->meshes.size(), 0), vid((size_t)n, -1);
+            bool any = false;
+            for (size_t i = 0; i < ctx->meshes.size(); ++i) {
+                const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+                if (!R.self_collision) continue;
+                any = true; flag[i] = 1;
+                for (size_t k = 0; k < R.body_nodes.size(); ++k) vid[F.iperm[R.body_nodes[k]]] = (int)k;
+            }
+            if (any) { TRY(upload(ctx, &ctx->d_mesh_self, flag)); TRY(upload(ctx, &ctx->d_self_vid, vid)); }
+        }
         for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) {
             const admm_hip_mesh &M = ctx->meshes[mi];
             admm_mesh::MeshDev d{};

@@ -370,12 +370,14 @@ public:
 };
 
 // Extension, no reference counterpart: CollisionBody for an open surface of simulated nodes such as a cloth (admm_hip_add_sheet_surface):
-// a thick shell of half thickness r that follows its nodes and is ignored by them; every rule and refusal of a CollisionBody holds.
+// a thick shell of half thickness r that follows its nodes and is ignored by them -- or, with self_collision set before initialize, met by
+// them outside their 1-ring (cloth self-collision); every rule and refusal of a CollisionBody holds.
 class CollisionSheet : public CollisionBody {
 public:
     CollisionSheet(int node_first_, int node_count_, const std::vector<int> &tris_, double half_thickness_) : CollisionBody(node_first_, node_count_, tris_), half_thickness(half_thickness_) {}
     int shape_type() const { return typeid(*this) == typeid(CollisionSheet) ? ADMM_SHAPE_MESH : -1; }
     double half_thickness;
+    bool self_collision = false;      // the sheet's own nodes meet it outside their 1-ring (admm_hip_set_sheet_self_collision); read at System::initialize
 };
 
 // One force over ALL nodes (CollisionForce.hpp:31-46).  With analytic shapes only: a device batch with one element per

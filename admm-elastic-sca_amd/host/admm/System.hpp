@@ -468,6 +468,7 @@ protected:
                     const CollisionSheet *cs = dynamic_cast<const CollisionSheet *>(&cb);
                     if (!check(cs ? admm_hip_add_sheet_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), cs->half_thickness, &id)
                                   : admm_hip_add_body_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), &id))) return false;
+                    if (cs && cs->self_collision && !check(admm_hip_set_sheet_self_collision(gpu, id, 1))) return false;
                     body_ids.push_back(std::make_pair(&cb, id));
                     body_mu.push_back(0.0);
                 }

@@ -104,6 +104,27 @@ def sheet_tris(w, l, node_first=0):
     return (sym_plane(w, l)[1] + np.int32(node_first)).astype(np.int32)
 
 
+def folded_strip(w, l, gap):
+    """A (w x l)-cell sym_plane strip (cell size h = 1 / w) bent into a U whose two flat flaps are `gap` apart: the lower flap in the
+    plane y = 0, a straight fold of height gap, the upper flap in the plane y = gap running back over the lower one.  A vertex at arc
+    length s along the strip (s = j / w for grid row j, (j + 0.5) / w for the centre vertices of cell row j) sits on the path
+    (y, z) = (0, s) for s <= a,  (s - a, a) for a < s <= a + gap,  (gap, a - (s - a - gap)) beyond,  a = (l // 2 + 1 / 16) / w:
+    the fold starts a sixteenth of a cell past the middle grid row, so for gap < 7 h / 16 no vertex lies on the fold.  -> (x [nv][3],
+    tris): sym_plane's vertex order and sheet_tris' topology, unchanged.  Only + - * / on float64 and exact constants, so every host
+    gives the same bits."""
+    x, tris = sym_plane(w, l)
+    nv = (w + 1) * (l + 1)
+    jj = np.concatenate([np.repeat(np.arange(l + 1, dtype=np.float64), w + 1), np.repeat(np.arange(l, dtype=np.float64) + 0.5, w)])
+    assert len(jj) == len(x) and nv + w * l == len(x)
+    s = jj / w
+    a = (l // 2 + 0.0625) / w
+    g = float(gap)
+    lower, fold = s <= a, (s > a) & (s <= a + g)
+    x[:, 1] = np.where(lower, 0.0, np.where(fold, s - a, g))
+    x[:, 2] = np.where(lower, s, np.where(fold, a, a - ((s - a) - g)))
+    return x, tris
+
+
 def bend_hinges(tris):
     """One hinge (i0, i1, i2, i3) per interior edge: i2,i3 the shared edge,
     i0/i1 the opposite vertices (BendForce rows are x0-x2, x3-x2, x1-x2;

@@ -309,8 +309,7 @@ int  admm_hip_mesh_query_framed(const admm_hip_mesh *mesh, const double t[3], co
  *     5. p_j = t_j + p'_j, then under a frame to_world -- only for a point that was moved.
  * Everything after the push is what a closed mesh's entry does on the world-space points: the coefficient, the vertex velocities
  * interpolated at the hit, the rigid motion, the friction rule.  The rule has no memory of the side a node started the frame on: a node
- * that crosses the mid-surface within one frame leaves on the far side, so keep r above closing speed x dt.  Self-collision of a sheet,
- * edge-edge contact, continuous detection, a thickness on closed meshes and reactions on a sheet's own nodes are out of scope.
+ * that crosses the mid-surface within one frame leaves on the far side, so keep r above closing speed x dt.  Edge-edge contact, continuous detection, a thickness on closed meshes and reactions on a sheet's own nodes are out of scope.
  *   admm_hip_mesh_create_open   like admm_hip_mesh_create for a surface that may have boundary edges: every directed edge at most once
  *                           (edge-manifold, consistently oriented where two faces meet), no degenerate triangle, half_thickness finite
  *                           and > 0; at least one triangle.  A closed input is accepted and simply is a shell.  ADMM_ERR_ARG with the
@@ -335,12 +334,49 @@ int  admm_hip_mesh_query_framed(const admm_hip_mesh *mesh, const double t[3], co
  *                           numbering, owner range, frame-start update (verdict on the device, counted in the status, a refused frame
  *                           keeps the last good surface; no volume condition) and refusals (a per-entry coefficient, a translation, a
  *                           frame, admm_hip_update_collision_mesh); admm_hip_get_body_surface_status and
- *                           admm_hip_set_body_surface_friction apply to it.  Its own nodes skip it: no self-collision.                  */
+ *                           admm_hip_set_body_surface_friction apply to it.  Its own nodes skip it unless
+ *                           admm_hip_set_sheet_self_collision says otherwise (the next section).                                        */
 int  admm_hip_mesh_create_open(admm_hip_mesh **out, int nv, const double *verts, int nt, const int32_t *tris, double half_thickness, char *err, int err_len);
 int  admm_hip_mesh_thickness(const admm_hip_mesh *mesh, double *r);
 int  admm_hip_mesh_closest(const admm_hip_mesh *mesh, int64_t n, const double *q, double r2, double *c, double *d2, int32_t *slot, int32_t *reg, int32_t *tri);
 int  admm_hip_set_collision_mesh_thickness(admm_hip_ctx *ctx, int mesh_id, double half_thickness);
 int  admm_hip_add_sheet_surface(admm_hip_ctx *ctx, int node_first, int node_count, int n_tris, const int32_t *tris, double half_thickness, int *mesh_id);
+
+/* ---- a sheet surface that collides with itself: cloth self-collision ------------------------------------------------------------------
+ * Extension, no reference counterpart.  By default the collision elements of a sheet surface's own nodes skip the surface.  With
+ * self-collision switched on they do not: node i of the sheet, which is vertex vi of the surface (the numbering of
+ * admm_hip_add_sheet_surface: the referenced nodes in ascending order, vi = i - node_first when every node of the range is referenced),
+ * runs the shell rule above, steps 1 to 5, every product and sum rounded, no fused multiply-adds, with one change in step 2:
+ *     2'. the bounded search ignores every triangle that has vi as a corner (the node's 1-ring); among the remaining triangles the winner
+ *         is the minimum of (d2, original triangle index), compared lexicographically, with d2 < r * r.  The BVH only prunes, so the
+ *         result does not depend on its shape.
+ * Everything else is the shell rule: the decision d2 < r * r, the push to distance r on the side the point is on (d == 0: along the
+ * winning face's normal), the translation, and everything after the push -- the surface's own coefficient
+ * (admm_hip_set_body_surface_friction), the frame-start v of the winning triangle's nodes interpolated at the hit, the friction rule.
+ * Nodes that do not belong to the sheet meet it exactly as before.  The surface is frozen at the frame-start x for the frame's
+ * iterations: a node meets where the rest of the cloth was at the start of the frame.  Contact is vertex-triangle outside a node's
+ * 1-ring only: edge-edge contact, side memory, continuous detection and self-collision of a closed body surface are out of scope, and
+ * the push is one-sided (the winning triangle's nodes feel no reaction).
+ *   admm_hip_set_sheet_self_collision  before finalize (ADMM_ERR_STATE after it); on != 0 switches it on for the sheet surface mesh_id.
+ *                           ADMM_ERR_ARG, naming the mesh, for an obstacle mesh or a closed body surface.  The collision batches of a
+ *                           list that names such a sheet launch project_collision_self_kernel; a context where no sheet self-collides
+ *                           launches exactly what it launched before.
+ *   admm_hip_finalize       refuses (ADMM_ERR_ARG, naming the vertex, the triangle and the distance) a self-colliding sheet in whose
+ *                           positions a vertex lies nearer than r to a triangle it is not a corner of: every such node would be pushed by
+ *                           its own neighbourhood from the first frame.  On a regular grid of spacing h this bounds r below roughly
+ *                           0.7 h.  Two self-colliding sheets over the same node range are refused too.
+ *   admm_hip_mesh_query_excluding  the context-free host evaluation of the rule with a per-point excluded vertex, the same bits as the
+ *                           device: admm_hip_mesh_query_framed on an open mesh with step 2'; tri [n] = the winning original triangle (-1:
+ *                           none nearer than r).  frame NULL: the identity; skip_vertex NULL or skip_vertex[i] = -1: nothing is left out,
+ *                           the bits of admm_hip_mesh_query_framed.  ADMM_ERR_ARG on a closed mesh (admm_hip_mesh_create) and for a
+ *                           skip_vertex outside [-1, nv).  Any output may be NULL.
+ *   admm_hip_mesh_velocity_query_excluding  admm_hip_mesh_velocity_query at the hit of that search (q, t as there); a point with no
+ *                           triangle nearer than r outside the excluded 1-ring gets zeros and corner ids -1.                            */
+int  admm_hip_set_sheet_self_collision(admm_hip_ctx *ctx, int mesh_id, int on);
+int  admm_hip_mesh_query_excluding(const admm_hip_mesh *mesh, int64_t n_pts, const double *pts, const int32_t *skip_vertex, const double t[3], const double *frame,
+                                   double *proj, double *sdist, int32_t *tri);
+int  admm_hip_mesh_velocity_query_excluding(const admm_hip_mesh *mesh, int64_t n, const double *q, const int32_t *skip_vertex, const double t[3], const double *vel,
+                                            double *out, double *weights, int32_t *corner_ids);
 
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
@@ -512,7 +548,8 @@ int admm_hip_debug_potrf_inv(admm_hip_ctx *ctx, int w, int ld, double *blk, doub
  * *graph_launches = graph launches issued by the context so far.  Any pointer may be NULL.                               */
 int admm_hip_debug_graph_state(admm_hip_ctx *ctx, int *iter_graph, int *frame_graph, int64_t *graph_launches);
 /* which kernels the collision batches launch for the current shape list: 0 the frictionless ones, 1 the friction form, 2 its moving form,
- * 3 the framed form, 4 the shell form (a list that names an open mesh).  A call that changes the value drops the captured graphs.         */
+ * 3 the framed form, 4 the shell form (a list that names an open mesh), 5 the self-collision form (a list that names a sheet surface that
+ * collides with itself).  A call that changes the value drops the captured graphs.                                                       */
 int admm_hip_debug_collision_form(admm_hip_ctx *ctx, int *form);
 
 typedef struct admm_hip_info {
