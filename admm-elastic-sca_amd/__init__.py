@@ -177,6 +177,15 @@ def lib():
         L.admm_hip_set_sheet_self_collision.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.admm_hip_mesh_query_excluding.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, _dp, _dp, _dp, _dp, _ip]
         L.admm_hip_mesh_velocity_query_excluding.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, _dp, _dp, _dp, _dp, _ip]
+        L.admm_hip_set_collision_mesh_side_memory.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.admm_hip_get_collision_sides.argtypes = [C.c_void_p, C.c_int, _ip]
+        L.admm_hip_set_collision_sides.argtypes = [C.c_void_p, C.c_int, _ip]
+        L.admm_hip_latch_collision_sides.argtypes = [C.c_void_p]
+        L.admm_hip_reset_collision_sides.argtypes = [C.c_void_p]
+        L.admm_hip_mesh_side_latch.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, C.c_double, _dp, _dp, _ip]
+        L.admm_hip_mesh_query_sided.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, C.c_double, _dp, _dp, _dp, _dp, _ip, _ip]
+        L.admm_hip_mesh_boundary_table.argtypes = [C.c_void_p, _ip, _ip]
+        L.admm_hip_mesh_feature_normal.argtypes = [C.c_void_p, C.c_int64, _ip, _ip, _dp]
         _lib = L
     return _lib
 
@@ -283,6 +292,50 @@ class Mesh:
         if rc != 0:
             raise AdmmHipError("admm_hip_mesh_velocity_query_excluding error %d" % rc)
         return out, wts, ids
+
+    def side_latch(self, pts, prev, reach, t=(0.0, 0.0, 0.0), frame=None):
+        """the latch of side memory (admm_hip_mesh_side_latch) on an open mesh with the given reach: the new side [n] int32 of every point
+        from its previous one (prev: [n] in {-1, 0, 1}, a scalar, or None for all 0), for the instance translated by t under a frame"""
+        p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        pv = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if prev is None else prev, dtype=np.int32), (p.shape[0],)))
+        tt = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        f = None if frame is None else frame_array(frame)
+        out = np.empty(p.shape[0], np.int32)
+        rc = self.L.admm_hip_mesh_side_latch(self.h, p.shape[0], _d(p), _i(pv), float(reach), _d(tt), _d(f), _i(out))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_side_latch error %d" % rc)
+        return out
+
+    def query_sided(self, pts, side, reach, t=(0.0, 0.0, 0.0), frame=None):
+        """the projection of side memory (admm_hip_mesh_query_sided) -> (proj [n][3], sdist [n], tri [n], crossed [n]): a point with side 0
+        runs the shell rule (the bits of query), one with side +-1 stays on that side of the surface within the reach; sdist = r - d for
+        an unsigned push, r + d for a crossed one, -inf for none"""
+        p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        sd_ = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if side is None else side, dtype=np.int32), (p.shape[0],)))
+        tt = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        f = None if frame is None else frame_array(frame)
+        proj = np.empty_like(p); sd = np.empty(p.shape[0]); tri = np.empty(p.shape[0], np.int32); cr = np.empty(p.shape[0], np.int32)
+        rc = self.L.admm_hip_mesh_query_sided(self.h, p.shape[0], _d(p), _i(sd_), float(reach), _d(tt), _d(f), _d(proj), _d(sd), _i(tri), _i(cr))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_query_sided error %d" % rc)
+        return proj, sd, tri, cr
+
+    def boundary_table(self):
+        """-> (bits [nt], orig [nt]) per leaf slot (admm_hip_mesh_boundary_table): bit reg (1..6) set where that feature of the slot's
+        triangle is a boundary edge or a vertex incident to one; orig: the slot's original triangle"""
+        nt = self.info()["n_tris"]
+        bits = np.empty(nt, np.int32); orig = np.empty(nt, np.int32)
+        self.L.admm_hip_mesh_boundary_table(self.h, _i(bits), _i(orig))
+        return bits, orig
+
+    def feature_normal(self, slot, reg):
+        """the stored pseudo-normal [n][3] of the features (slot, reg) that closest returns (admm_hip_mesh_feature_normal)"""
+        sl = np.ascontiguousarray(slot, dtype=np.int32).ravel(); rg = np.ascontiguousarray(reg, dtype=np.int32).ravel()
+        out = np.empty((sl.size, 3))
+        rc = self.L.admm_hip_mesh_feature_normal(self.h, sl.size, _i(sl), _i(rg), _d(out))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_feature_normal error %d" % rc)
+        return out
 
     def set_vertices(self, verts):
         """new vertex positions [nv][3] for the same topology (admm_hip_mesh_set_vertices): pseudo-normals recomputed, BVH boxes refit.
@@ -525,7 +578,7 @@ class System:
 
     def collision_form(self):
         """which kernels the collision batches launch for the current list (admm_hip_debug_collision_form): 0 frictionless, 1 friction,
-        2 moving friction, 3 framed, 4 shell, 5 sheet self-collision"""
+        2 moving friction, 3 framed, 4 shell, 5 sheet self-collision, 6 side memory"""
         f = C.c_int()
         self._chk(self.L.admm_hip_debug_collision_form(self.h, C.byref(f)))
         return f.value
@@ -579,6 +632,32 @@ class System:
         """the half thickness of a registered open mesh (admm_hip_set_collision_mesh_thickness): before or after initialize, between
         frames; captured graphs stay.  A closed mesh, or a value that is not finite and > 0, raises AdmmHipError."""
         self._chk(self.L.admm_hip_set_collision_mesh_thickness(self.h, int(mesh_id), float(half_thickness)))
+
+    def set_collision_mesh_side_memory(self, mesh_id, reach):
+        """side memory for a registered open mesh (admm_hip_set_collision_mesh_side_memory; before initialize): every node remembers
+        the side of the surface it is on while it is within the reach, and a node that crosses the mid-surface within a frame is put
+        back on that side.  reach 0 switches it off.  Keep the reach above closing speed x dt + the half thickness."""
+        self._chk(self.L.admm_hip_set_collision_mesh_side_memory(self.h, int(mesh_id), float(reach)))
+
+    def collision_sides(self, mesh_id):
+        """-> the side [n_nodes] int32 (+1: where the normals point, -1, 0: none) of every node on a mesh with memory, caller's node
+        order (admm_hip_get_collision_sides; after initialize).  Part of a checkpoint beside x, v and u."""
+        out = np.empty(self.n_nodes, np.int32)
+        self._chk(self.L.admm_hip_get_collision_sides(self.h, int(mesh_id), _i(out)))
+        return out
+
+    def set_collision_sides(self, mesh_id, side):
+        s = np.ascontiguousarray(side, dtype=np.int32).ravel()
+        if s.size != self.n_nodes:
+            raise AdmmHipError("set_collision_sides: %d sides given, the system has %d nodes" % (s.size, self.n_nodes))
+        self._chk(self.L.admm_hip_set_collision_sides(self.h, int(mesh_id), _i(s)))
+
+    def latch_collision_sides(self):
+        """the launches a step begins with (body surfaces, then the latch of every side) from the current x (admm_hip_latch_collision_sides)"""
+        self._chk(self.L.admm_hip_latch_collision_sides(self.h))
+
+    def reset_collision_sides(self):
+        self._chk(self.L.admm_hip_reset_collision_sides(self.h))
 
     def add_sheet_surface(self, node_first, node_count, tris, half_thickness, self_collision=False):
         """registers a sheet surface (before initialize): add_body_surface for an open surface of simulated nodes such as a cloth, a

@@ -252,6 +252,18 @@ static int check_body_frames(admm_hip_ctx *ctx, int n_shapes, const int32_t *typ
     }
     return ADMM_OK;
 }
+// side memory: a node has one side per mesh, so a list names a mesh with memory in one entry at most
+static int check_side_entries(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
+    for (int j = 0; j < n_shapes; ++j) {
+        if (types[j] != ADMM_SHAPE_MESH) continue;
+        const int id = (int)params[4 * (size_t)j + 3];
+        if (!(id >= 0 && id < (int)ctx->mesh_role.size() && ctx->mesh_role[id].side_reach > 0.0)) continue;
+        for (int k = 0; k < j; ++k)
+            if (types[k] == ADMM_SHAPE_MESH && (int)params[4 * (size_t)k + 3] == id)
+                return fail(ctx, ADMM_ERR_ARG, "collision shapes %d and %d both name mesh %d, which has side memory: a node has one side per mesh", k, j, id);
+    }
+    return ADMM_OK;
+}
 int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
     if (!ctx || n_shapes < 0 || (n_shapes && (!types || !params))) return ADMM_ERR_ARG;
     if (n_shapes > ADMM_MAX_SHAPES) return fail(ctx, ADMM_ERR_UNSUPPORTED, "at most %d collision shapes", ADMM_MAX_SHAPES);
@@ -269,6 +281,7 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
             }
     }
     TRY(check_body_translations(ctx, n_shapes, types, params));
+    TRY(check_side_entries(ctx, n_shapes, types, params));
     // (a list of the same length keeps its coefficients: one that now names a body surface where a coefficient is set is refused here
     //  once finalized, by finalize before)
     if (ctx->finalized && n_shapes == ctx->shapes.n) TRY(check_body_friction(ctx, n_shapes, types, params, ctx->shapes.mu));
@@ -527,12 +540,35 @@ int admm_hip_set_collision_mesh_thickness(admm_hip_ctx *ctx, int mesh_id, double
     if (!(ctx->meshes[mesh_id].thickness > 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed mesh: it has no thickness", mesh_id);
     if (!(half_thickness > 0.0 && std::isfinite(half_thickness)))
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: half thickness %g: it must be positive and finite", mesh_id, half_thickness);
+    if (ctx->mesh_role[mesh_id].side_reach > 0.0 && half_thickness > ctx->mesh_role[mesh_id].side_reach)
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: half thickness %g exceeds the reach %g of its side memory", mesh_id, half_thickness, ctx->mesh_role[mesh_id].side_reach);
     ctx->meshes[mesh_id].thickness = half_thickness;
     if (ctx->finalized && ctx->device_id >= 0) {
         HIPCHK(hipSetDevice(ctx->device_id));
         HIPCHK(hipMemcpyAsync(ctx->d_mesh_thick + mesh_id, &ctx->meshes[mesh_id].thickness, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
+    return ADMM_OK;
+}
+
+// extension, no reference counterpart (include/admm_hip.h): side memory for an open mesh (mesh_query.hpp); before finalize, which
+// allocates one row of sides per such mesh
+int admm_hip_set_collision_mesh_side_memory(admm_hip_ctx *ctx, int mesh_id, double reach) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "side memory must be set before finalize");
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    const double r = ctx->meshes[mesh_id].thickness;
+    if (!(r > 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed mesh: it has an inside and needs no side memory", mesh_id);
+    if (!std::isfinite(reach)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: reach %g is not finite", mesh_id, reach);
+    if (reach != 0.0 && !(reach >= r)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: reach %g is below its half thickness %g", mesh_id, reach, r);
+    if (reach != 0.0) {      // (the current list may already name it twice)
+        const double before = ctx->mesh_role[mesh_id].side_reach;
+        ctx->mesh_role[mesh_id].side_reach = reach;
+        const int rc = check_side_entries(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]);
+        if (rc) { ctx->mesh_role[mesh_id].side_reach = before; return rc; }
+    }
+    ctx->mesh_role[mesh_id].side_reach = reach;
     return ADMM_OK;
 }
 
@@ -698,6 +734,10 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     for (int j = 0; j < ctx->shapes.n; ++j)
         if (!(ctx->shapes.mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, ctx->shapes.mu[j]);
     TRY(check_sheet_self_collision(ctx));
+    TRY(check_side_entries(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
+    ctx->side_slot.assign(ctx->meshes.size(), -1); ctx->n_side_slots = 0;      // side memory: one row of sides per mesh with a reach
+    for (size_t i = 0; i < ctx->meshes.size(); ++i) if (ctx->mesh_role[i].side_reach > 0.0) ctx->side_slot[i] = ctx->n_side_slots++;
+    if (ctx->device_id < 0) ctx->h_side.assign((size_t)ctx->n_side_slots * (size_t)ctx->n_nodes, 0);
     TRY(host_assemble(ctx, false));
     TRY(host_factor(ctx, false));
     ctx->info.rank = ctx->rank; ctx->info.world = ctx->world;

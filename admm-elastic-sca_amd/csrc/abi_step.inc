@@ -93,6 +93,7 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     ctx->ev_used = 0; ctx->ev_iters = admm_iters; ctx->ev_timed = 0; ctx->ev_pending = ctx->timing;
     TRY(mark(ctx));
     if (ctx->d_body_tag) TRY(update_bodies(ctx));      // body surfaces from the frame-start x, before the explicit forces (eager, outside the graphs)
+    if (ctx->d_side) TRY(latch_sides(ctx));            // side memory: every node's side from the frame-start x (eager, outside the graphs)
     if (ctx->frames++ > 0)      // the blocks of the large tet batches by what they cost in the frame before
         for (const Batch &b : ctx->batches) if (b.n_blocks_ordered)
             hipLaunchKernelGGL(order_by_cost_kernel, dim3(1), dim3(1024), 0, ctx->stream, b.n_blocks_ordered, b.d_cost, b.d_order);
@@ -229,6 +230,67 @@ int admm_hip_debug_graph_state(admm_hip_ctx *ctx, int *iter_graph, int *frame_gr
 int admm_hip_debug_collision_form(admm_hip_ctx *ctx, int *form) {
     if (!ctx || !form) return ADMM_ERR_ARG;
     *form = collision_form(ctx);
+    return ADMM_OK;
+}
+
+// side memory (include/admm_hip.h): the sides of one mesh with memory, n_nodes values in the caller's node order (the device holds them in
+// factor order; a host-only context keeps them on the host)
+static int side_row(admm_hip_ctx *ctx, int mesh_id, int *row) {
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    if (!(ctx->mesh_role[mesh_id].side_reach > 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d has no side memory", mesh_id);
+    if (!ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision sides exist from finalize on");
+    *row = ctx->side_slot[mesh_id];
+    return ADMM_OK;
+}
+int admm_hip_get_collision_sides(admm_hip_ctx *ctx, int mesh_id, int32_t *side) {
+    if (!ctx || !side) return ADMM_ERR_ARG;
+    int row = -1;
+    TRY(side_row(ctx, mesh_id, &row));
+    const size_t n = (size_t)ctx->n_nodes;
+    if (ctx->device_id < 0) { std::copy(ctx->h_side.begin() + row * n, ctx->h_side.begin() + (row + 1) * n, side); return ADMM_OK; }
+    HIPCHK(hipSetDevice(ctx->device_id));
+    std::vector<int32_t> tmp(n);
+    HIPCHK(hipMemcpyAsync(tmp.data(), ctx->d_side + row * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const std::vector<int> &perm = ctx->F.perm;
+    for (size_t i = 0; i < n; ++i) side[perm[i]] = tmp[i];
+    return ADMM_OK;
+}
+int admm_hip_set_collision_sides(admm_hip_ctx *ctx, int mesh_id, const int32_t *side) {
+    if (!ctx || !side) return ADMM_ERR_ARG;
+    int row = -1;
+    TRY(side_row(ctx, mesh_id, &row));
+    const size_t n = (size_t)ctx->n_nodes;
+    for (size_t i = 0; i < n; ++i)
+        if (side[i] < -1 || side[i] > 1) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: the side of node %d is %d: it must be -1, 0 or 1", mesh_id, (int)i, (int)side[i]);
+    if (ctx->device_id < 0) { std::copy(side, side + n, ctx->h_side.begin() + row * n); return ADMM_OK; }
+    HIPCHK(hipSetDevice(ctx->device_id));
+    std::vector<int32_t> tmp(n);
+    const std::vector<int> &perm = ctx->F.perm;
+    for (size_t i = 0; i < n; ++i) tmp[i] = side[perm[i]];
+    HIPCHK(hipMemcpyAsync(ctx->d_side + row * n, tmp.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ADMM_OK;
+}
+// exactly the launches admm_hip_step begins with (body surfaces, then the latch) from the current x, synchronised
+int admm_hip_latch_collision_sides(admm_hip_ctx *ctx) {
+    TRY(require_device(ctx));
+    HIPCHK(hipSetDevice(ctx->device_id));
+    if (ctx->d_body_tag) TRY(update_bodies(ctx));
+    if (ctx->d_side) TRY(latch_sides(ctx));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ADMM_OK;
+}
+int admm_hip_reset_collision_sides(admm_hip_ctx *ctx) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (!ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision sides exist from finalize on");
+    std::fill(ctx->h_side.begin(), ctx->h_side.end(), 0);
+    if (ctx->device_id >= 0 && ctx->d_side) {
+        HIPCHK(hipSetDevice(ctx->device_id));
+        HIPCHK(hipMemsetAsync(ctx->d_side, 0, sizeof(int32_t) * (size_t)ctx->n_side_slots * (size_t)ctx->n_nodes, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
     return ADMM_OK;
 }
 

@@ -138,7 +138,8 @@ struct admm_hip_ctx {
     // elements skip it (own_count 0: none; admm_hip_set_collision_mesh_owner), and for a body surface (admm_hip_add_body_surface) the
     // node behind every vertex, ascending -- the device rebuilds it from them at every step (launch.inc: update_bodies)
     // self_collision (a sheet surface only, admm_hip_set_sheet_self_collision): its own nodes meet it outside their 1-ring instead of skipping it
-    struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; bool self_collision = false; };
+    // side_reach (an open mesh only, admm_hip_set_collision_mesh_side_memory): > 0: the mesh has side memory with this reach, 0: none
+    struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; bool self_collision = false; double side_reach = 0.0; };
     std::vector<MeshRole> mesh_role;
     // obstacles that move (admm_hip_set_collision_motion: shapes.motion; admm_hip_set_collision_mesh_velocity, admm_hip_set_body_surface_friction):
     // per mesh, parallel to `meshes`, the host's record and the device table the moving friction kernel reads.  d_vel: an obstacle's
@@ -152,6 +153,13 @@ struct admm_hip_ctx {
     // contexts where some sheet collides with itself (else both null): the flag of every mesh, parallel to d_meshes, and for every node in
     // device order its vertex id on the self-colliding sheet that owns it (-1: none); project_collision_self_kernel alone reads them
     int *d_mesh_self = nullptr, *d_self_vid = nullptr;
+    // contexts where some open mesh has side memory (mesh_query.hpp; else all null / empty): per mesh, parallel to d_meshes, its reach (0:
+    // none), its row in d_side (-1: none) and its boundary table (null: none); d_side [n_side_slots][n_nodes] in device node order, one
+    // int32 side per node and mesh with memory.  collision_side_kernel writes d_side at the start of every step,
+    // project_collision_sided_kernel reads all four.  side_slot: the host's copy of the rows; h_side: the sides of a host-only context
+    // (caller's node order).
+    double *d_mesh_reach = nullptr; int *d_mesh_side_slot = nullptr; const int **d_mesh_bnd = nullptr; int32_t *d_side = nullptr;
+    int n_side_slots = 0; std::vector<int> side_slot; std::vector<int32_t> h_side;
     int *d_body_tag = nullptr;      // contexts with an owner: the owner group of every node in device order (-1: none), for MeshDev::owner
     SymCSC A;
     Factor F;

@@ -67,9 +67,20 @@ bool self_on(const admm_hip_ctx *ctx) {
     }
     return false;
 }
+// ... and does an entry of the current list name an open mesh with side memory (admm_hip_set_collision_mesh_side_memory: reach > 0)?  Then
+// the collision batches run project_collision_sided_kernel, the self-collision form plus the remembered side, in a launch of their own in
+// both launch modes, and every step begins with the latch (latch_sides).  A context without such a mesh launches exactly what it did.
+bool sided_on(const admm_hip_ctx *ctx) {
+    for (int q = 0; q < ctx->shapes.n; ++q) {
+        if (ctx->shapes.type[q] != ADMM_SHAPE_MESH) continue;
+        const int id = (int)ctx->shapes.par[q][3];
+        if (id >= 0 && id < (int)ctx->mesh_role.size() && ctx->mesh_role[id].side_reach > 0.0) return true;
+    }
+    return false;
+}
 // which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form, 3 the framed form, 4 the
-// shell form, 5 the self-collision form
-int collision_form(const admm_hip_ctx *ctx) { return self_on(ctx) ? 5 : shell_on(ctx) ? 4 : framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
+// shell form, 5 the self-collision form, 6 the side-memory form
+int collision_form(const admm_hip_ctx *ctx) { return sided_on(ctx) ? 6 : self_on(ctx) ? 5 : shell_on(ctx) ? 4 : framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
 // ... in a launch of their own (launch_collision_mesh) instead of a segment of project_multi_kernel or project_collision_kernel
 bool collision_own_launch(const admm_hip_ctx *ctx) { return !ctx->meshes.empty() || friction_on(ctx) || framed_on(ctx); }
 
@@ -185,12 +196,32 @@ int update_bodies(admm_hip_ctx *ctx) {
     return ADMM_OK;
 }
 
+// the latch of side memory (kernels_local.hpp collision_side_kernel): every node's side on every mesh with memory that the current list
+// names, from the frame-start x; eager on ctx->stream right after update_bodies (outside the iteration and frame graphs).  Every address
+// was fixed at finalize.  Every rank holds the full frame-start x, so every rank latches every node from the same bits.
+int latch_sides(admm_hip_ctx *ctx) {
+    using namespace admm_dev;
+    if (!ctx->d_side || !sided_on(ctx)) return ADMM_OK;
+    const int n = ctx->n_nodes;
+    hipLaunchKernelGGL(collision_side_kernel, dim3((unsigned)((n + LOCAL_BLOCK - 1) / LOCAL_BLOCK)), dim3(LOCAL_BLOCK), 0, ctx->stream, n, (const double *)ctx->d_x,
+                       (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag,
+                       (const double *)ctx->d_mesh_reach, (const int *)ctx->d_mesh_side_slot, (const int *const *)ctx->d_mesh_bnd, ctx->d_side);
+    HIPCHK(hipGetLastError());
+    return ADMM_OK;
+}
+
 // a collision batch of a context with mesh obstacles, friction, framed entries or boxes
 void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
-    if (self_on(ctx)) {      // (implies shell_on; d_mesh_self and d_self_vid were uploaded at finalize: the flag is set before it)
+    if (sided_on(ctx)) {      // (implies shell_on; the side tables were uploaded at finalize: the reach is set before it.  d_mesh_self, d_self_vid: null without a self-colliding sheet)
+        hipLaunchKernelGGL(project_collision_sided_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
+                           (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, (const int *)ctx->d_mesh_self, (const int *)ctx->d_self_vid,
+                           (const double *)ctx->d_mesh_reach, (const int *)ctx->d_mesh_side_slot, (const int *const *)ctx->d_mesh_bnd, (const int *)ctx->d_side,
+                           ctx->n_nodes, ctx->dt);
+    } else if (self_on(ctx)) {      // (implies shell_on; d_mesh_self and d_self_vid were uploaded at finalize: the flag is set before it)
         hipLaunchKernelGGL(project_collision_self_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
                            (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
                            (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, (const int *)ctx->d_mesh_self, (const int *)ctx->d_self_vid, ctx->dt);

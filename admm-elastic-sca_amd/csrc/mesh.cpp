@@ -167,6 +167,22 @@ int mesh_build(int nv, const double *verts, int nt, const int32_t *tris, double 
     for (int i = 0; i < nt; ++i) { M.tris[i] = src[B.ord[i]]; M.nrm[i] = nrm[B.ord[i]]; }
     M.depth = B.depth;
     M.thickness = open ? thickness : 0.0;
+    // side memory's boundary table (mesh_query.hpp): topology and leaf order never change, so it is built once
+    {
+        std::vector<char> vb((size_t)nv, 0);
+        for (int t = 0; t < nt; ++t) for (int k = 0; k < 3; ++k)
+            if (adj[3 * (size_t)t + k] < 0) vb[cid[3 * (size_t)t + k]] = vb[cid[3 * (size_t)t + (k + 1) % 3]] = 1;
+        M.bnd.assign((size_t)nt, 0);
+        for (int i = 0; i < nt; ++i) {
+            const int t = M.tris[i].orig;
+            int bits = 0;
+            for (int k = 0; k < 3; ++k) {
+                if (adj[3 * (size_t)t + k] < 0) bits |= 1 << (R_EAB + k);
+                if (vb[cid[3 * (size_t)t + k]]) bits |= 1 << (R_VA + k);
+            }
+            M.bnd[i] = bits;
+        }
+    }
     // the topology admm_hip_mesh_set_vertices recomputes the arrays from: corners, adjacency, each vertex's incidences in ascending
     // (triangle, corner) order -- the order of the vertex-normal sum above --, the nodes by depth (children follow their parent)
     M.nv = nv;
@@ -483,6 +499,83 @@ int admm_hip_mesh_velocity_query_excluding(const admm_hip_mesh *mesh, int64_t n,
         if (weights) for (int k = 0; k < 3; ++k) weights[3 * i + k] = b[k];
         if (corner_ids) for (int k = 0; k < 3; ++k) corner_ids[3 * i + k] = c[k];
         if (out) tri_interpolate(b, vel + 3 * (size_t)c[0], vel + 3 * (size_t)c[1], vel + 3 * (size_t)c[2], out + 3 * i);
+    }
+    return ADMM_OK;
+}
+
+// side memory (mesh_query.hpp), context-free host evaluations with the device's bits.  The latch of collision_side_kernel: the new side of
+// every point from its previous one (prev NULL: all 0) for an instance of an open mesh with reach R >= r, translated by t under a frame
+int admm_hip_mesh_side_latch(const admm_hip_mesh *mesh, int64_t n_pts, const double *pts, const int32_t *prev, double reach, const double t[3], const double *frame,
+                             int32_t *side_out) {
+    if (!mesh || !t || n_pts < 0 || (n_pts && (!pts || !side_out))) return ADMM_ERR_ARG;
+    const double r = mesh->thickness;
+    if (!(r > 0.0) || !std::isfinite(reach) || !(reach >= r)) return ADMM_ERR_ARG;
+    int which; double by;
+    if (frame && admm_frame::check(frame, &which, &by)) return ADMM_ERR_ARG;
+    if (prev) for (int64_t i = 0; i < n_pts; ++i) if (prev[i] < -1 || prev[i] > 1) return ADMM_ERR_ARG;
+    const bool framed = frame && !admm_frame::identity(frame);
+    for (int64_t i = 0; i < n_pts; ++i) {
+        double l[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        if (framed) admm_frame::to_local(frame, pts + 3 * i, l);
+        const double q[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
+        HostStack stk;
+        side_out[i] = side_latch(mesh->nodes.data(), mesh->tris.data(), mesh->nrm.data(), mesh->bnd.data(), q, prev ? prev[i] : 0, r, reach, stk);
+    }
+    return ADMM_OK;
+}
+
+// ... and the projection of project_collision_sided_kernel for one entry: a point with side 0 runs the shell rule (the bits of
+// admm_hip_mesh_query_framed), one with side +-1 sided_project.  sdist = r - d for an unsigned push, r + d for a crossed one, -inf for
+// none; tri: the winning original triangle of a push (-1: none); crossed: 1 where step 4 ran
+int admm_hip_mesh_query_sided(const admm_hip_mesh *mesh, int64_t n_pts, const double *pts, const int32_t *side, double reach, const double t[3], const double *frame,
+                              double *proj, double *sdist, int32_t *tri, int32_t *crossed) {
+    if (!mesh || !t || n_pts < 0 || (n_pts && !pts)) return ADMM_ERR_ARG;
+    const double r = mesh->thickness;
+    if (!(r > 0.0) || !std::isfinite(reach) || !(reach >= r)) return ADMM_ERR_ARG;
+    int which; double by;
+    if (frame && admm_frame::check(frame, &which, &by)) return ADMM_ERR_ARG;
+    if (side) for (int64_t i = 0; i < n_pts; ++i) if (side[i] < -1 || side[i] > 1) return ADMM_ERR_ARG;
+    const bool framed = frame && !admm_frame::identity(frame);
+    for (int64_t i = 0; i < n_pts; ++i) {
+        double l[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        if (framed) admm_frame::to_local(frame, pts + 3 * i, l);
+        const double q[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
+        const int s = side ? side[i] : 0;
+        double o[3] = {0.0, 0.0, 0.0}, sd = -INFINITY; int ti = -1; bool hit, cr = false;
+        if (s == 0) {
+            hit = shell_query_excluding(*mesh, q, -1, o, &sd, &ti);
+            if (!hit) { sd = -INFINITY; ti = -1; }
+        } else {
+            HostStack stk; Hit h;
+            hit = sided_project(mesh->nodes.data(), mesh->tris.data(), mesh->nrm.data(), mesh->bnd.data(), q, s, r, reach, stk, h, o, cr);
+            if (hit) { const double d = std::sqrt(h.d2); sd = cr ? r + d : r - d; ti = mesh->tris[h.slot].orig; }
+        }
+        if (proj) {
+            const double c[3] = {t[0] + o[0], t[1] + o[1], t[2] + o[2]};
+            if (hit && framed) admm_frame::to_world(frame, c, proj + 3 * i);
+            else for (int j = 0; j < 3; ++j) proj[3 * i + j] = hit ? c[j] : pts[3 * i + j];
+        }
+        if (sdist) sdist[i] = sd;
+        if (tri) tri[i] = ti;
+        if (crossed) crossed[i] = cr ? 1 : 0;
+    }
+    return ADMM_OK;
+}
+
+// the boundary table of a mesh as built (for tests): one int32 per leaf slot, with the slot's original triangle
+int admm_hip_mesh_boundary_table(const admm_hip_mesh *mesh, int32_t *bits, int32_t *orig) {
+    if (!mesh) return ADMM_ERR_ARG;
+    for (size_t i = 0; i < mesh->bnd.size(); ++i) { if (bits) bits[i] = mesh->bnd[i]; if (orig) orig[i] = mesh->tris[i].orig; }
+    return ADMM_OK;
+}
+
+// ... and the pseudo-normal feature_normal(nrm[slot], reg) of n (slot, reg) pairs as stored (for tests: the n of side_g)
+int admm_hip_mesh_feature_normal(const admm_hip_mesh *mesh, int64_t n, const int32_t *slot, const int32_t *reg, double *out) {
+    if (!mesh || n < 0 || (n && (!slot || !reg || !out))) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        if (slot[i] < 0 || slot[i] >= (int)mesh->nrm.size() || reg[i] < 0 || reg[i] > 6) return ADMM_ERR_ARG;
+        const double *v = feature_normal(mesh->nrm[slot[i]], reg[i]);
+        for (int j = 0; j < 3; ++j) out[3 * i + j] = v[j];
     }
     return ADMM_OK;
 }

@@ -17,6 +17,9 @@ struct admm_hip_mesh {
     std::vector<int> adj;                   // [nt][3] the triangle across edge k (corners k, k + 1) of original triangle t
     std::vector<int> inc_ptr, inc;          // vertex -> its incidences 3 t + k, ascending
     std::vector<int> lvl_ptr, lvl_nodes;    // BVH nodes grouped by depth: level d = lvl_nodes[lvl_ptr[d], lvl_ptr[d + 1])
+    // side memory (mesh_query.hpp): per leaf slot, bit reg (1..6) set where that feature is a boundary edge or a vertex incident to one,
+    // in the slot's rotated corner order; all zero for a closed mesh
+    std::vector<int> bnd;
 };
 
 namespace admm_mesh {

@@ -20,8 +20,28 @@
 //   4. push       e_j = q_j - c_j,  d = sqrt(h.d2);   d > 0:  s = r / d,  p'_j = c_j + s * e_j;
 //                 d == 0:  p'_j = c_j + r * n_j,  n = the unit face normal of the winning triangle (Nrm::n[0])          (shell_push)
 //   5. world      p_j = t_j + p'_j, then under a frame to_world -- only for a point that was moved
-// The rule does not know on which side a node started the frame: a node that crosses the mid-surface within one frame leaves on the far
-// side.  Callers keep r above closing speed x dt.
+// Without side memory the rule does not know on which side a node started the frame: a node that crosses the mid-surface within one
+// frame leaves on the far side, so callers keep r above closing speed x dt.
+//
+// Side memory (admm_hip_set_collision_mesh_side_memory: an open mesh with a reach R, finite, R >= r > 0).  The context keeps one int32
+// side s per node and such mesh: +1 the side the surface's normals point to, -1 the other one, 0 none.  For a hit h of q:
+//   g = (q0 - c0) n0 + (q1 - c1) n1 + (q2 - c2) n2,  n = feature_normal(nrm[h.slot], h.reg)   (the expression `inside` evaluates; side_g)
+//   side_of = +1 for g > 0, -1 for g < 0, else 0
+//   a boundary hit: h's feature is a boundary edge (adj = -1) or a vertex incident to one -- bit h.reg (1..6) of bnd[h.slot], a table of
+//   one int32 per leaf slot in the slot's rotated corner order, built once from the topology (boundary_table)
+// Latch (side_latch), once per frame from the frame-start position q with the previous side s; the first step whose condition holds decides:
+//   1. in_shell_box(q, root, R) fails: s' = 0        2. h = closest_within(q, R * R) finds nothing: s' = 0
+//   3. h is a boundary hit: s' = 0 (a node that goes round the rim forgets)       4. s != 0: s' = s (sticky)
+//   5. s == 0: s' = side_of(q, h) when h.d2 >= r * r, else 0 (never learned from inside the shell)
+// Projection (sided_project), per iteration, for a node with s != 0 (s == 0: steps 1 to 5 of the shell rule above, the same code and bits):
+//   1. in_shell_box(q, root, R) fails: the point keeps its bits      2. h = closest_within(q, R * R) finds nothing: it keeps its bits
+//   3. a boundary hit, or side_of(q, h) * s >= 0 (or h.d2 == 0): the unsigned rule on this hit -- collides iff h.d2 < r * r, shell_push
+//   4. otherwise the node has crossed: d = sqrt(h.d2) (> 0), sc = r / d, e_j = q_j - c_j, p'_j = c_j - sc * e_j: the point mirrored
+//      through the closest point to distance r on the remembered side
+//   5. p_j = t_j + p'_j, then under a frame to_world -- only for a point that was moved
+// With memory callers keep R above closing speed x dt + r, at the cost of a traversal bounded by R instead of r.  A self-colliding sheet's
+// own nodes keep the unsigned rule (their side stays 0): in the flat parts of a cloth the nearest triangle outside the 1-ring lies in the
+// node's own plane, so the sign there is noise.
 //
 // Self-collision of a sheet (admm_hip_set_sheet_self_collision): a node that is vertex vi of the surface runs steps 1 to 5 with one change
 // in step 2 -- closest_within_excluding leaves out every triangle that has vi as a corner (the node's 1-ring: cid[3 orig + k] == vi for
@@ -314,6 +334,53 @@ ADMM_HD bool inside(const Node &root, const Nrm *nrm, const double *q, const Hit
     const double *n = feature_normal(nrm[h.slot], h.reg);
     const double s = (q[0] - h.c[0]) * n[0] + (q[1] - h.c[1]) * n[1] + (q[2] - h.c[2]) * n[2];
     return s < 0.0;
+}
+
+// ---- side memory (the rule at the top of this file) --------------------------------------------------------------------------------
+// the expression `inside` evaluates, for a hit with slot >= 0
+ADMM_HD double side_g(const Nrm *__restrict__ nrm, const double *q, const Hit &h) {
+    const double *n = feature_normal(nrm[h.slot], h.reg);
+    return (q[0] - h.c[0]) * n[0] + (q[1] - h.c[1]) * n[1] + (q[2] - h.c[2]) * n[2];
+}
+ADMM_HD int side_of(const Nrm *__restrict__ nrm, const double *q, const Hit &h) {
+    const double g = side_g(nrm, q, h);
+    return g > 0.0 ? 1 : (g < 0.0 ? -1 : 0);
+}
+// the hit's feature is a boundary edge or a vertex incident to one (the face region, reg 0, never is)
+ADMM_HD bool boundary_hit(const int *__restrict__ bnd, const Hit &h) { return ((bnd[h.slot] >> h.reg) & 1) != 0; }
+// the latch: the new side of a node at q (relative to the instance) whose previous side is s
+template <class Stack>
+ADMM_HD int side_latch(const Node *__restrict__ nodes, const Tri *__restrict__ tris, const Nrm *__restrict__ nrm, const int *__restrict__ bnd, const double *q,
+                       const int s, const double r, const double R, Stack &stk) {
+    if (!in_shell_box(q, nodes[0], R)) return 0;
+    Hit h;
+    closest_within(nodes, tris, q, R * R, stk, h);
+    if (h.slot < 0) return 0;
+    if (boundary_hit(bnd, h)) return 0;
+    if (s != 0) return s;
+    return h.d2 >= r * r ? side_of(nrm, q, h) : 0;
+}
+// the projection of a node with side s != 0: true when q moves, o = p' then (relative to the instance, like q and h.c); h: the hit
+// (slot -1: none within R, or the box test failed); crossed: step 4 ran
+template <class Stack>
+ADMM_HD bool sided_project(const Node *__restrict__ nodes, const Tri *__restrict__ tris, const Nrm *__restrict__ nrm, const int *__restrict__ bnd, const double *q,
+                           const int s, const double r, const double R, Stack &stk, Hit &h, double *o, bool &crossed) {
+    crossed = false;
+    h.slot = -1; h.d2 = INFINITY; h.reg = 0;
+    if (!in_shell_box(q, nodes[0], R)) return false;
+    closest_within(nodes, tris, q, R * R, stk, h);
+    if (h.slot < 0) return false;
+    if (boundary_hit(bnd, h) || side_of(nrm, q, h) * s >= 0 || !(h.d2 > 0.0)) {
+        if (!shell_collides(h, r)) return false;
+        shell_push(q, h, nrm, r, o);
+        return true;
+    }
+    crossed = true;
+    const double d = sqrt(h.d2);
+    const double sc = r / d;
+    const double e0 = q[0] - h.c[0], e1 = q[1] - h.c[1], e2 = q[2] - h.c[2];
+    o[0] = h.c[0] - sc * e0; o[1] = h.c[1] - sc * e1; o[2] = h.c[2] - sc * e2;
+    return true;
 }
 
 // ---- in-place deformation (admm_hip_mesh_set_vertices on the host, kernels_mesh.hpp on the device) --------------------------------

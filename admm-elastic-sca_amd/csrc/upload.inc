@@ -615,6 +615,23 @@ int upload_all(admm_hip_ctx *ctx) {
         TRY(upload(ctx, &ctx->d_mesh_thick, thick));
         TRY(upload(ctx, &ctx->d_meshes, md));
         TRY(dalloc(ctx, &ctx->d_mesh_chk, 1));
+        // side memory: the reach, the row of sides and the boundary table of every mesh, and the sides themselves (zero) -- allocated only
+        // when a mesh has memory (side_slot and n_side_slots were set by finalize), so that other contexts hold and launch what they did
+        ctx->d_mesh_reach = nullptr; ctx->d_mesh_side_slot = nullptr; ctx->d_mesh_bnd = nullptr; ctx->d_side = nullptr;
+        if (ctx->n_side_slots > 0) {
+            std::vector<double> reach(ctx->meshes.size(), 0.0);
+            std::vector<const int *> bnd(ctx->meshes.size(), nullptr);
+            for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) {
+                if (ctx->side_slot[mi] < 0) continue;
+                reach[mi] = ctx->mesh_role[mi].side_reach;
+                int *b = nullptr;
+                TRY(upload(ctx, &b, ctx->meshes[mi].bnd));
+                bnd[mi] = b;
+            }
+            TRY(upload(ctx, &ctx->d_mesh_reach, reach)); TRY(upload(ctx, &ctx->d_mesh_side_slot, ctx->side_slot)); TRY(upload(ctx, &ctx->d_mesh_bnd, bnd));
+            TRY(dalloc(ctx, &ctx->d_side, (size_t)ctx->n_side_slots * (size_t)n));
+            HIPCHK(hipMemset(ctx->d_side, 0, sizeof(int32_t) * (size_t)ctx->n_side_slots * (size_t)n));
+        }
     }
     for (Explicit &E : ctx->explicits) {
         std::vector<int> pidx(E.idx.size());

@@ -344,6 +344,10 @@ public:
     std::vector<double> velocities;        // the vertices' velocities (empty: none)
     long vel_version = 0;                  // set_vertex_velocities calls so far
     double half_thickness = 0.0;           // 0: a closed mesh; > 0: an open surface, a shell of this half thickness (the host query uses the value at construction)
+    // an open mesh only: > 0: side memory with this reach (admm_hip_set_collision_mesh_side_memory: every node remembers the side of the
+    // surface it is on and is put back there when it crosses within a frame); read at System::initialize, where a force that projects on
+    // the host refuses it (the sides live in the context)
+    double side_reach = 0.0;
 private:
     void query(const Vector3d &p, double *pr, double &sd) const {
         const double t[3] = {center[0], center[1], center[2]}, q[3] = {p[0], p[1], p[2]};
@@ -378,6 +382,7 @@ public:
     int shape_type() const { return typeid(*this) == typeid(CollisionSheet) ? ADMM_SHAPE_MESH : -1; }
     double half_thickness;
     bool self_collision = false;      // the sheet's own nodes meet it outside their 1-ring (admm_hip_set_sheet_self_collision); read at System::initialize
+    double side_reach = 0.0;          // > 0: side memory with this reach for the nodes that do not own the sheet (admm_hip_set_collision_mesh_side_memory); read at System::initialize
 };
 
 // One force over ALL nodes (CollisionForce.hpp:31-46).  With analytic shapes only: a device batch with one element per

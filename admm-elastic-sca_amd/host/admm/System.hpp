@@ -177,6 +177,14 @@ public:
                             return false;
                         }
                     }
+                if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))      // side memory lives in the context: the device form only, like an orientation
+                    for (size_t q = 0; q < cf->collisionShapes.size(); ++q) {
+                        const CollisionMesh *cm = dynamic_cast<const CollisionMesh *>(cf->collisionShapes[q].get());
+                        if (cm && cm->side_reach != 0.0) {
+                            std::cerr << "\n**Solver Error: force " << i << ", shape " << q << ": side memory (side_reach " << cm->side_reach << ") on a force that projects on the host (a user-written shape in its list); it needs the device form of every shape" << std::endl;
+                            return false;
+                        }
+                    }
                 if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))
                     for (size_t q = 0; q < cf->collisionShapes.size(); ++q) if (dynamic_cast<const CollisionBody *>(cf->collisionShapes[q].get())) {
                         std::cerr << "\n**Solver Error: force " << i << " projects on the host (a user-written shape in its list), where a CollisionBody has no evaluation" << std::endl;
@@ -469,6 +477,7 @@ protected:
                     if (!check(cs ? admm_hip_add_sheet_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), cs->half_thickness, &id)
                                   : admm_hip_add_body_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), &id))) return false;
                     if (cs && cs->self_collision && !check(admm_hip_set_sheet_self_collision(gpu, id, 1))) return false;
+                    if (cs && cs->side_reach != 0.0 && !check(admm_hip_set_collision_mesh_side_memory(gpu, id, cs->side_reach))) return false;
                     body_ids.push_back(std::make_pair(&cb, id));
                     body_mu.push_back(0.0);
                 }
@@ -485,6 +494,7 @@ protected:
                 if (k == mesh_ids.size()) {
                     int id = -1;
                     if (!check(admm_hip_add_collision_mesh(gpu, m, &id))) return false;
+                    if (cm.side_reach != 0.0 && !check(admm_hip_set_collision_mesh_side_memory(gpu, id, cm.side_reach))) return false;
                     mesh_ids.push_back(std::make_pair(m, id));
                     mesh_versions.push_back(cm.version);
                     mesh_vel_versions.push_back(0);

@@ -308,8 +308,9 @@ int  admm_hip_mesh_query_framed(const admm_hip_mesh *mesh, const double t[3], co
  *        normal of the winning triangle;
  *     5. p_j = t_j + p'_j, then under a frame to_world -- only for a point that was moved.
  * Everything after the push is what a closed mesh's entry does on the world-space points: the coefficient, the vertex velocities
- * interpolated at the hit, the rigid motion, the friction rule.  The rule has no memory of the side a node started the frame on: a node
- * that crosses the mid-surface within one frame leaves on the far side, so keep r above closing speed x dt.  Edge-edge contact, continuous detection, a thickness on closed meshes and reactions on a sheet's own nodes are out of scope.
+ * interpolated at the hit, the rigid motion, the friction rule.  Without side memory (the section after the next) the rule does not know
+ * the side a node started the frame on: a node that crosses the mid-surface within one frame leaves on the far side, so keep r above
+ * closing speed x dt; with it keep the reach R above closing speed x dt + r.  Edge-edge contact, continuous detection, a thickness on closed meshes and reactions on a sheet's own nodes are out of scope.
  *   admm_hip_mesh_create_open   like admm_hip_mesh_create for a surface that may have boundary edges: every directed edge at most once
  *                           (edge-manifold, consistently oriented where two faces meet), no degenerate triangle, half_thickness finite
  *                           and > 0; at least one triangle.  A closed input is accepted and simply is a shell.  ADMM_ERR_ARG with the
@@ -355,7 +356,7 @@ int  admm_hip_add_sheet_surface(admm_hip_ctx *ctx, int node_first, int node_coun
  * (admm_hip_set_body_surface_friction), the frame-start v of the winning triangle's nodes interpolated at the hit, the friction rule.
  * Nodes that do not belong to the sheet meet it exactly as before.  The surface is frozen at the frame-start x for the frame's
  * iterations: a node meets where the rest of the cloth was at the start of the frame.  Contact is vertex-triangle outside a node's
- * 1-ring only: edge-edge contact, side memory, continuous detection and self-collision of a closed body surface are out of scope, and
+ * 1-ring only: edge-edge contact, side memory for the sheet's own nodes, continuous detection and self-collision of a closed body surface are out of scope, and
  * the push is one-sided (the winning triangle's nodes feel no reaction).
  *   admm_hip_set_sheet_self_collision  before finalize (ADMM_ERR_STATE after it); on != 0 switches it on for the sheet surface mesh_id.
  *                           ADMM_ERR_ARG, naming the mesh, for an obstacle mesh or a closed body surface.  The collision batches of a
@@ -377,6 +378,63 @@ int  admm_hip_mesh_query_excluding(const admm_hip_mesh *mesh, int64_t n_pts, con
                                    double *proj, double *sdist, int32_t *tri);
 int  admm_hip_mesh_velocity_query_excluding(const admm_hip_mesh *mesh, int64_t n, const double *q, const int32_t *skip_vertex, const double t[3], const double *vel,
                                             double *out, double *weights, int32_t *corner_ids);
+
+/* ---- side memory for thick shells: fast nodes do not tunnel ---------------------------------------------------------------------------
+ * Extension, no reference counterpart.  An open mesh may be given a reach R, finite, R >= r > 0; it then has side memory: for every node
+ * and every such mesh the context keeps one int32 side s: +1 the side the surface's normals point to, -1 the other one, 0 none.  For a
+ * hit h of a point q (relative to the entry's translation, in local coordinates under a frame), every product and sum rounded, no fused
+ * multiply-adds:
+ *     g = (q0 - c0) n0 + (q1 - c1) n1 + (q2 - c2) n2,  n the pseudo-normal of the hit's feature;  side_of = +1 for g > 0, -1 for g < 0, else 0;
+ *     a boundary hit: the hit's feature is a boundary edge or a vertex incident to one.
+ * Latch, once per frame from the frame-start position, first in admm_hip_step (after the body surfaces' update, before the explicit
+ * forces).  A node whose body owns the mesh is skipped (its side stays 0).  Any other node, previous side s; the first step whose
+ * condition holds decides:
+ *     1. the box test of the shell rule with R in place of r fails: s' = 0;
+ *     2. the search bounded by R * R finds nothing: s' = 0;
+ *     3. a boundary hit: s' = 0 (a node that goes round the rim forgets);
+ *     4. s != 0: s' = s (sticky: a frame that ended on the wrong side does not relearn it);
+ *     5. s == 0: s' = side_of(q, h) when d2 >= r * r, else 0 (never learned from inside the shell).
+ * Projection, per iteration, for an entry that names such a mesh.  A node with s == 0 runs the shell rule as it stands (a self-colliding
+ * sheet's own node with its 1-ring left out).  A node with s != 0:
+ *     1. the box test with R fails: the point keeps its bits;       2. the search bounded by R * R finds nothing: it keeps its bits;
+ *     3. a boundary hit, or side_of(q, h) * s >= 0 (or d2 == 0): the unsigned rule on this hit -- it collides iff d2 < r * r, step 4 of the shell rule;
+ *     4. otherwise the node has crossed: d = sqrt(d2), sc = r / d, e_j = q_j - c_j, p'_j = c_j - sc * e_j (mirrored through the closest
+ *        point to distance r on the remembered side);
+ *     5. p_j = t_j + p'_j, then under a frame to_world -- only for a point that was moved.
+ * Everything after the push is unchanged.  Keep R above closing speed x dt + r; the traversal is bounded by R instead of r.  A
+ * self-colliding sheet's own nodes keep the unsigned rule: in the flat parts of a cloth the nearest triangle outside the 1-ring lies in
+ * the node's own plane, so the sign there would be noise.  Both shard modes hold the full frame-start x on every rank, so every rank
+ * latches every node from the same bits and nothing new crosses a collective.
+ *   admm_hip_set_collision_mesh_side_memory  before finalize (ADMM_ERR_STATE after it); reach = 0 switches memory off.  ADMM_ERR_ARG,
+ *                           naming the mesh, for a closed mesh, a non-finite reach or one below the mesh's half thickness.
+ *                           admm_hip_set_collision_mesh_thickness then refuses r > reach; finalize and admm_hip_set_collision_shapes
+ *                           refuse a list that names such a mesh in two entries (a node has one side per mesh).  A list that names one
+ *                           launches project_collision_sided_kernel (collision form 6); a context without one uploads and launches
+ *                           exactly what it did.
+ *   admm_hip_get_collision_sides / admm_hip_set_collision_sides  after finalize: n_nodes values in the caller's node order for one mesh with
+ *                           memory; values outside {-1, 0, 1} are refused.  The sides are part of a checkpoint beside x, v and u.
+ *   admm_hip_latch_collision_sides  exactly the launches admm_hip_step begins with (body surfaces, then the latch) from the current x,
+ *                           synchronised: for callers that teleport nodes with admm_hip_set_x, and for tests.
+ *   admm_hip_reset_collision_sides  zeroes all sides.  admm_hip_set_x and admm_hip_set_collision_shapes leave them alone (a translation
+ *                           changed between frames is the moving-obstacle case).
+ *   admm_hip_mesh_side_latch, admm_hip_mesh_query_sided  the context-free host evaluations, the device's bits (prev / side NULL: all 0;
+ *                           frame NULL: the identity).  query_sided: sdist = r - d for an unsigned push, r + d for a crossed one, -inf for
+ *                           none; tri = the winning original triangle of a push; crossed = 1 where step 4 ran; with side all zero the
+ *                           bits of admm_hip_mesh_query_framed.  ADMM_ERR_ARG on a closed mesh, a reach not finite or below r, a side
+ *                           outside {-1, 0, 1}.  admm_hip_mesh_velocity_query at the hit needs no sibling: the hit is the unbounded search's.
+ *   admm_hip_mesh_boundary_table  for tests: per leaf slot the bits (bit reg, 1..6, set for a boundary feature) and the original triangle.
+ *   admm_hip_mesh_feature_normal  for tests: the stored pseudo-normal [n][3] of n (slot, reg) pairs of admm_hip_mesh_closest: the n of g.      */
+int  admm_hip_set_collision_mesh_side_memory(admm_hip_ctx *ctx, int mesh_id, double reach);
+int  admm_hip_get_collision_sides(admm_hip_ctx *ctx, int mesh_id, int32_t *side);
+int  admm_hip_set_collision_sides(admm_hip_ctx *ctx, int mesh_id, const int32_t *side);
+int  admm_hip_latch_collision_sides(admm_hip_ctx *ctx);
+int  admm_hip_reset_collision_sides(admm_hip_ctx *ctx);
+int  admm_hip_mesh_side_latch(const admm_hip_mesh *mesh, int64_t n_pts, const double *pts, const int32_t *prev, double reach, const double t[3], const double *frame,
+                              int32_t *side_out);
+int  admm_hip_mesh_query_sided(const admm_hip_mesh *mesh, int64_t n_pts, const double *pts, const int32_t *side, double reach, const double t[3], const double *frame,
+                               double *proj, double *sdist, int32_t *tri, int32_t *crossed);
+int  admm_hip_mesh_boundary_table(const admm_hip_mesh *mesh, int32_t *bits, int32_t *orig);
+int  admm_hip_mesh_feature_normal(const admm_hip_mesh *mesh, int64_t n, const int32_t *slot, const int32_t *reg, double *out);
 
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
