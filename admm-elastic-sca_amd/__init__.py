@@ -186,6 +186,9 @@ def lib():
         L.admm_hip_mesh_query_sided.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, C.c_double, _dp, _dp, _dp, _dp, _ip, _ip]
         L.admm_hip_mesh_boundary_table.argtypes = [C.c_void_p, _ip, _ip]
         L.admm_hip_mesh_feature_normal.argtypes = [C.c_void_p, C.c_int64, _ip, _ip, _dp]
+        L.admm_hip_set_body_self_collision.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]
+        L.admm_hip_mesh_query_self.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, _dp, C.c_double, C.c_double, C.c_double, _dp, _dp, _ip, _ip]
+        L.admm_hip_mesh_velocity_query_self.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _ip]
         _lib = L
     return _lib
 
@@ -319,6 +322,36 @@ class Mesh:
         if rc != 0:
             raise AdmmHipError("admm_hip_mesh_query_sided error %d" % rc)
         return proj, sd, tri, cr
+
+    def query_self(self, pts, vertex_id, rest_verts, r, reach, rest_radius):
+        """self-collision of a closed body surface (admm_hip_mesh_query_self) -> (proj [n][3], sdist [n], tri [n], crossed [n]): point i
+        is vertex vertex_id[i] of this closed mesh (-1: an interior node, left alone) and meets the triangles within the reach that are
+        not within rest_radius of that vertex in the rest shape rest_verts [nv][3]: pushed to distance r when nearer outside, mirrored
+        to distance r outside when it has crossed the skin; sdist = r - d for a hit on the outside (> 0: pushed), r + d for a crossed
+        point, -inf for no hit; tri: the winning triangle of a hit, -1 for none"""
+        p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        vid = np.ascontiguousarray(np.broadcast_to(np.asarray(vertex_id, dtype=np.int32), (p.shape[0],)))
+        X = np.ascontiguousarray(rest_verts, dtype=np.float64).reshape(-1, 3)
+        proj = np.empty_like(p); sd = np.empty(p.shape[0]); tri = np.empty(p.shape[0], np.int32); cr = np.empty(p.shape[0], np.int32)
+        rc = self.L.admm_hip_mesh_query_self(self.h, p.shape[0], _d(p), _i(vid), _d(X), float(r), float(reach), float(rest_radius), _d(proj), _d(sd), _i(tri), _i(cr))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_query_self error %d" % rc)
+        return proj, sd, tri, cr
+
+    def velocity_query_self(self, pts, vertex_id, rest_verts, reach, rest_radius, vel):
+        """mesh_velocity_query at the hit of query_self's search (admm_hip_mesh_velocity_query_self) -> (out, weights, corner_ids);
+        a point without a hit within the reach gets zeros and ids -1"""
+        p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        vid = np.ascontiguousarray(np.broadcast_to(np.asarray(vertex_id, dtype=np.int32), (p.shape[0],)))
+        X = np.ascontiguousarray(rest_verts, dtype=np.float64).reshape(-1, 3)
+        v = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+        if v.shape != X.shape:
+            raise AdmmHipError("velocity_query_self: %d velocities given, the rest shape has %d vertices" % (v.shape[0], X.shape[0]))
+        out = np.empty_like(p); wts = np.empty_like(p); ids = np.empty((p.shape[0], 3), np.int32)
+        rc = self.L.admm_hip_mesh_velocity_query_self(self.h, p.shape[0], _d(p), _i(vid), _d(X), float(reach), float(rest_radius), _d(v), _d(out), _d(wts), _i(ids))
+        if rc != 0:
+            raise AdmmHipError("admm_hip_mesh_velocity_query_self error %d" % rc)
+        return out, wts, ids
 
     def boundary_table(self):
         """-> (bits [nt], orig [nt]) per leaf slot (admm_hip_mesh_boundary_table): bit reg (1..6) set where that feature of the slot's
@@ -578,7 +611,7 @@ class System:
 
     def collision_form(self):
         """which kernels the collision batches launch for the current list (admm_hip_debug_collision_form): 0 frictionless, 1 friction,
-        2 moving friction, 3 framed, 4 shell, 5 sheet self-collision, 6 side memory"""
+        2 moving friction, 3 framed, 4 shell, 5 sheet self-collision, 6 side memory, 7 body self-collision"""
         f = C.c_int()
         self._chk(self.L.admm_hip_debug_collision_form(self.h, C.byref(f)))
         return f.value
@@ -675,13 +708,24 @@ class System:
         refuses a sheet with a vertex nearer than the half thickness to a triangle it is not a corner of)"""
         self._chk(self.L.admm_hip_set_sheet_self_collision(self.h, int(mesh_id), 1 if on else 0))
 
-    def add_body_surface(self, node_first, node_count, tris):
+    def add_body_surface(self, node_first, node_count, tris, self_collision=None):
         """registers a body surface (before initialize): a closed mesh of simulated nodes, tris [nt][3] global node ids inside
-        [node_first, node_first + node_count), rebuilt from x at every step and ignored by its own nodes -> its mesh_id"""
+        [node_first, node_first + node_count), rebuilt from x at every step and ignored by its own nodes -> its mesh_id.
+        self_collision = (r, reach, rest_radius): its surface nodes meet it too (set_body_self_collision)."""
         t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
         mid = C.c_int()
         self._chk(self.L.admm_hip_add_body_surface(self.h, int(node_first), int(node_count), t.shape[0], _i(t), C.byref(mid)))
+        if self_collision is not None:
+            self.set_body_self_collision(mid.value, *self_collision)
         return mid.value
+
+    def set_body_self_collision(self, mesh_id, r, reach, rest_radius):
+        """a closed body surface's own surface nodes collide with it (admm_hip_set_body_self_collision; before initialize, which refuses
+        a body that the rule would already move where it stands): a node meets the triangles within the reach that are farther than
+        rest_radius from it in the rest shape (the positions at add_body_surface), is pushed to distance r outside them, and mirrored
+        back out when it has crossed the skin.  r = 0 switches it off.  Keep reach above closing speed x dt + r, rest_radius above the
+        reach by the compression the body will see and below the body's thinnest part."""
+        self._chk(self.L.admm_hip_set_body_self_collision(self.h, int(mesh_id), float(r), float(reach), float(rest_radius)))
 
     def set_collision_mesh_owner(self, mesh_id, node_first, node_count):
         """the nodes [node_first, node_first + node_count) skip mesh mesh_id (before initialize; node_count 0 clears the owner)"""

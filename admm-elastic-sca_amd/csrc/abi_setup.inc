@@ -479,6 +479,7 @@ static int add_node_surface(admm_hip_ctx *ctx, int node_first, int node_count, i
     admm_hip_mesh_destroy(M);
     admm_hip_ctx::MeshRole R;
     R.own_first = node_first; R.own_count = node_count; R.body_nodes = std::move(nodes);
+    if (!(half_thickness > 0.0)) R.rest = verts;      // a closed body surface keeps its rest shape (admm_hip_set_body_self_collision)
     ctx->mesh_role.push_back(std::move(R));
     ctx->mesh_move.emplace_back();
     if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
@@ -507,6 +508,57 @@ int admm_hip_set_sheet_self_collision(admm_hip_ctx *ctx, int mesh_id, int on) {
     if (!(ctx->meshes[mesh_id].thickness > 0.0))
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed body surface, not a sheet surface: self-collision of a closed surface is not supported", mesh_id);
     ctx->mesh_role[mesh_id].self_collision = on != 0;
+    return ADMM_OK;
+}
+
+// extension, no reference counterpart (include/admm_hip.h): a closed body surface whose surface nodes meet it outside what is near them in
+// the rest shape (project_collision_bodyself_kernel, mesh_query.hpp); before finalize, which checks the finalize positions against the rule
+int admm_hip_set_body_self_collision(admm_hip_ctx *ctx, int mesh_id, double r, double reach, double rest_radius) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "body self-collision must be set before finalize");
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
+        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    admm_hip_ctx::MeshRole &R = ctx->mesh_role[mesh_id];
+    if (R.body_nodes.empty())
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is an obstacle mesh, not a body surface: it has no nodes to collide with itself", mesh_id);
+    if (ctx->meshes[mesh_id].thickness > 0.0)
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a sheet surface, not a closed body surface: use admm_hip_set_sheet_self_collision", mesh_id);
+    if (!std::isfinite(r) || !std::isfinite(reach) || !std::isfinite(rest_radius))
+        return fail(ctx, ADMM_ERR_ARG, "body surface %d: self-collision lengths r %g, reach %g, rest radius %g: a value is not finite", mesh_id, r, reach, rest_radius);
+    if (r == 0.0) { R.body_self[0] = R.body_self[1] = R.body_self[2] = 0.0; return ADMM_OK; }
+    if (!(r > 0.0)) return fail(ctx, ADMM_ERR_ARG, "body surface %d: half gap %g is negative", mesh_id, r);
+    if (!(reach >= r)) return fail(ctx, ADMM_ERR_ARG, "body surface %d: reach %g is below the half gap %g", mesh_id, reach, r);
+    if (!(rest_radius >= reach)) return fail(ctx, ADMM_ERR_ARG, "body surface %d: rest radius %g is below the reach %g", mesh_id, rest_radius, reach);
+    R.body_self[0] = r; R.body_self[1] = reach; R.body_self[2] = rest_radius;
+    return ADMM_OK;
+}
+
+// finalize: a body surface that collides with itself must be left alone by the rule where it stands (the positions finalize sees), or
+// its nodes would be pushed from the first frame; and a node takes its vertex id from one self-colliding surface only, sheet or body
+static int check_body_self_collision(admm_hip_ctx *ctx) {
+    for (size_t i = 0; i < ctx->meshes.size(); ++i) {
+        const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+        if (!(R.body_self[0] > 0.0)) continue;
+        for (size_t k = 0; k < ctx->meshes.size(); ++k) {      // (owner ranges overlap only when they are equal)
+            const admm_hip_ctx::MeshRole &Q = ctx->mesh_role[k];
+            if (k == i || Q.own_first != R.own_first || Q.own_count != R.own_count) continue;
+            if (Q.self_collision || (k < i && Q.body_self[0] > 0.0))
+                return fail(ctx, ADMM_ERR_ARG, "surfaces %d and %d both collide with themselves and share the node range [%d, %d): a node takes its vertex id from one such surface",
+                            (int)std::min(i, k), (int)std::max(i, k), R.own_first, R.own_first + R.own_count);
+        }
+        admm_hip_mesh cur = ctx->meshes[i];
+        std::vector<double> verts(3 * R.body_nodes.size());
+        for (size_t k = 0; k < R.body_nodes.size(); ++k) for (int j = 0; j < 3; ++j) verts[3 * k + j] = ctx->x[3 * (size_t)R.body_nodes[k] + j];
+        char msg[512];
+        if (const int rc = admm_mesh::mesh_set_vertices(cur, cur.nv, verts.data(), msg, (int)sizeof msg)) return fail(ctx, rc, "body surface %d: %s", (int)i, msg);
+        int v = -1, t = -1; double d = 0.0;
+        if (admm_mesh::body_rest_violation(cur, R.rest.data(), R.body_self[0], R.body_self[1], R.body_self[2], &v, &t, &d)) {
+            const int *c = cur.cid.data() + 3 * (size_t)t;
+            return fail(ctx, ADMM_ERR_ARG, "body surface %d: vertex %d (node %d) lies at distance %g from triangle %d (%d, %d, %d), which is not near it in the rest shape (rest radius %g): "
+                        "the rule (half gap %g, reach %g) would move it, the body would collide with itself where it stands", (int)i, v, R.body_nodes[v], d, t, c[0], c[1], c[2],
+                        R.body_self[2], R.body_self[0], R.body_self[1]);
+        }
+    }
     return ADMM_OK;
 }
 
@@ -734,6 +786,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     for (int j = 0; j < ctx->shapes.n; ++j)
         if (!(ctx->shapes.mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, ctx->shapes.mu[j]);
     TRY(check_sheet_self_collision(ctx));
+    TRY(check_body_self_collision(ctx));
     TRY(check_side_entries(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
     ctx->side_slot.assign(ctx->meshes.size(), -1); ctx->n_side_slots = 0;      // side memory: one row of sides per mesh with a reach
     for (size_t i = 0; i < ctx->meshes.size(); ++i) if (ctx->mesh_role[i].side_reach > 0.0) ctx->side_slot[i] = ctx->n_side_slots++;

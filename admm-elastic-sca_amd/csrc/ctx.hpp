@@ -139,7 +139,10 @@ struct admm_hip_ctx {
     // node behind every vertex, ascending -- the device rebuilds it from them at every step (launch.inc: update_bodies)
     // self_collision (a sheet surface only, admm_hip_set_sheet_self_collision): its own nodes meet it outside their 1-ring instead of skipping it
     // side_reach (an open mesh only, admm_hip_set_collision_mesh_side_memory): > 0: the mesh has side memory with this reach, 0: none
-    struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; bool self_collision = false; double side_reach = 0.0; };
+    // body_self (a closed body surface only, admm_hip_set_body_self_collision): {r, R, rho}, r > 0: its surface nodes meet it outside what is
+    // near them in the rest shape; rest: the vertices [nv][3] as admm_hip_add_body_surface registered them
+    struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; bool self_collision = false; double side_reach = 0.0;
+                      double body_self[3] = {0.0, 0.0, 0.0}; std::vector<double> rest; };
     std::vector<MeshRole> mesh_role;
     // obstacles that move (admm_hip_set_collision_motion: shapes.motion; admm_hip_set_collision_mesh_velocity, admm_hip_set_body_surface_friction):
     // per mesh, parallel to `meshes`, the host's record and the device table the moving friction kernel reads.  d_vel: an obstacle's
@@ -150,8 +153,9 @@ struct admm_hip_ctx {
     // open meshes (thick shells, admm_hip_mesh::thickness > 0): the half thickness of every mesh, parallel to d_meshes (0: a closed mesh), a
     // table of its own that project_collision_shell_kernel alone reads; admm_hip_set_collision_mesh_thickness writes one entry
     double *d_mesh_thick = nullptr;
-    // contexts where some sheet collides with itself (else both null): the flag of every mesh, parallel to d_meshes, and for every node in
-    // device order its vertex id on the self-colliding sheet that owns it (-1: none); project_collision_self_kernel alone reads them
+    // contexts where some sheet collides with itself (else null): the flag of every mesh, parallel to d_meshes; contexts where a sheet or a
+    // body surface collides with itself (else null): for every node in device order its vertex id on the self-colliding surface that owns
+    // it (-1: none); the self, sided and bodyself collision kernels read them
     int *d_mesh_self = nullptr, *d_self_vid = nullptr;
     // contexts where some open mesh has side memory (mesh_query.hpp; else all null / empty): per mesh, parallel to d_meshes, its reach (0:
     // none), its row in d_side (-1: none) and its boundary table (null: none); d_side [n_side_slots][n_nodes] in device node order, one
@@ -160,6 +164,10 @@ struct admm_hip_ctx {
     // (caller's node order).
     double *d_mesh_reach = nullptr; int *d_mesh_side_slot = nullptr; const int **d_mesh_bnd = nullptr; int32_t *d_side = nullptr;
     int n_side_slots = 0; std::vector<int> side_slot; std::vector<int32_t> h_side;
+    // contexts where some body surface collides with itself (mesh_query.hpp; else both null): per mesh, parallel to d_meshes, the three
+    // lengths {r, R, rho} (zeros: off) and the rest vertices [nv][3] (null: none); project_collision_bodyself_kernel alone reads them, with
+    // d_self_vid for the nodes' vertex ids
+    double *d_mesh_bself = nullptr; const double **d_mesh_rest = nullptr;
     int *d_body_tag = nullptr;      // contexts with an owner: the owner group of every node in device order (-1: none), for MeshDev::owner
     SymCSC A;
     Factor F;

@@ -967,6 +967,118 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_sided_kernel(Ba
     }
 }
 
+// ... with a closed body surface that collides with itself (admm_hip_set_body_self_collision, mesh_query.hpp; a context where bodyself_on
+// holds, launch.inc, launches this form for its collision batches; every kernel above stays as it is).  A sibling of
+// project_collision_sided_kernel: the same lane per node, LDS stack column, owner skip, frames, box, coefficients, motions, vertex
+// velocities, self-collision and side-memory branches (reach, side_slot, bnd, side: null where no mesh has memory).  The one difference:
+// an entry that names a mesh the node's body owns and whose lengths bself[3 mi..] = {r, R, rho} have r > 0.  A surface node (vid >= 0)
+// runs body_self_project against the rest vertices rest[mi] -- the search bounded by R that passes over what is near the node in the
+// rest shape, the unsigned rule outside, the mirror push for a node that has crossed the skin --, an interior node skips the entry as
+// before.  Everything after the push is unchanged.
+__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_bodyself_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
+                                                                               const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
+                                                                               const admm_mesh::MeshMotion *__restrict__ mm, const double *__restrict__ thick, const int *__restrict__ tag,
+                                                                               const int *__restrict__ self, const int *__restrict__ vid,
+                                                                               const double *__restrict__ reach, const int *__restrict__ side_slot, const int *const *__restrict__ bnd,
+                                                                               const int *__restrict__ side, const int side_stride,
+                                                                               const double *__restrict__ bself, const double *const *__restrict__ rest, const double dt) {
+    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
+    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
+    const int n = b.n;
+    if (e >= b.e1) return;
+    const int id = b.idx[e];
+    const int ds = b.dst[e];
+    const double s = b.w2h2[e];
+    double dx[3], u[3], p[3], x0[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
+        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
+        x0[j] = xs[3 * (size_t)id + j];
+        u[j] = b.u[(size_t)j * n + e];
+        p[j] = dx[j] + u[j];
+    }
+    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
+    const int own = tag ? tag[id] : -1;
+    const int vi_own = vid ? vid[id] : -1;      // the node's vertex id on the self-colliding surface that owns it (-1: none)
+    const int ns = shapes->n;
+    for (int q = 0; q < ns; ++q) {
+        const double before[3] = {p[0], p[1], p[2]};
+        const double *f = shapes->frame[q];
+        const bool framed = shapes->framed[q] != 0;
+        const int ty = shapes->type[q];
+        double mu = shapes->mu[q];
+        double vi[3] = {0.0, 0.0, 0.0};      // the mesh's vertex velocities at the hit, world axes
+        bool vhit = false;
+        if (ty != ADMM_SHAPE_MESH) {
+            if (!admm_frame::collide_entry(ty, shapes->par[q], f, framed, p)) continue;
+        } else {
+            const int mi = (int)shapes->par[q][3];
+            const admm_mesh::MeshDev m = meshes[mi];
+            const bool mine = own >= 0 && m.owner == own;
+            const bool bs = mine && bself[3 * mi] > 0.0;      // the node's body owns the mesh and its surface collides with itself (uniform per entry and body)
+            if (mine && !bs && !(self && self[mi])) continue;
+            if (bs && vi_own < 0) continue;                    // an interior node
+            double l[3] = {p[0], p[1], p[2]};
+            if (framed) admm_frame::to_local(f, p, l);
+            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
+            const double qq[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
+            const double r = thick[mi];
+            admm_mesh::Hit h;
+            if (bs) {           // mesh_query.hpp, self-collision of a closed body surface (no translation, no frame: refused on a body surface)
+                double o[3]; bool crossed;
+                if (!admm_mesh::body_self_project(m.nodes, m.tris, m.nrm, mm[mi].cid, rest[mi], vi_own, qq, bself[3 * mi], bself[3 * mi + 1], bself[3 * mi + 2], stk, h, o,
+                                                  crossed)) continue;
+                l[0] = o[0]; l[1] = o[1]; l[2] = o[2];
+            } else if (r > 0.0) {
+                const double R = reach ? reach[mi] : 0.0;
+                const int sd = (R > 0.0 && !mine) ? side[(size_t)side_slot[mi] * (size_t)side_stride + id] : 0;      // (an owner's node: the unsigned rule)
+                double o[3];
+                if (sd != 0) {      // a remembered side: mesh_query.hpp, projection steps 1 to 4
+                    bool crossed;
+                    if (!admm_mesh::sided_project(m.nodes, m.tris, m.nrm, bnd[mi], qq, sd, r, R, stk, h, o, crossed)) continue;
+                } else {            // the self kernel's shell branch
+                    if (!admm_mesh::in_shell_box(qq, m.nodes[0], r)) continue;
+                    admm_mesh::closest_within_excluding(m.nodes, m.tris, mm[mi].cid, mine ? vi_own : -1, qq, r * r, stk, h);
+                    if (!admm_mesh::shell_collides(h, r)) continue;
+                    admm_mesh::shell_push(qq, h, m.nrm, r, o);
+                }
+                l[0] = t[0] + o[0]; l[1] = t[1] + o[1]; l[2] = t[2] + o[2];
+            } else {
+                if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
+                admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
+                if (!(admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0)) continue;
+                l[0] = t[0] + h.c[0]; l[1] = t[1] + h.c[1]; l[2] = t[2] + h.c[2];
+            }
+            if (framed) admm_frame::to_world(f, l, p); else { p[0] = l[0]; p[1] = l[1]; p[2] = l[2]; }
+            const admm_mesh::MeshMotion mo = mm[mi];
+            if (mo.body) mu = mo.mu;
+            if (mo.vel && mu > 0.0) {
+                const admm_mesh::Tri &tr = m.tris[h.slot];
+                const int *c = mo.cid + 3 * (size_t)tr.orig;
+                const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
+                const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
+                double bw[3];
+                admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
+                vi[0] = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi[1] = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi[2] = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
+                if (framed) admm_frame::rotate(f, vi, vi);
+                vhit = true;
+            }
+        }
+        if (!(mu > 0.0)) continue;
+        double w[3];
+        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
+        if (vhit) { w[0] = w[0] + dt * vi[0]; w[1] = w[1] + dt * vi[1]; w[2] = w[2] + dt * vi[2]; }
+        admm_friction::apply_moving(before, p, x0, w, mu);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double un = u[j] + (dx[j] - p[j]);
+        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
+        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
+    }
+}
+
 // the latch of side memory (mesh_query.hpp side_latch), once per frame from the frame-start x, eager at the start of admm_hip_step
 // (launch.inc: latch_sides): one lane per node in device order, the traversal stack in the lane's LDS column.  For every entry of the
 // current list that names a mesh with memory (slot >= 0; a list names such a mesh once): a node whose body owns the mesh is skipped,

@@ -78,9 +78,20 @@ bool sided_on(const admm_hip_ctx *ctx) {
     }
     return false;
 }
+// ... and does an entry of the current list name a closed body surface that collides with itself (admm_hip_set_body_self_collision: r > 0)?
+// Then the collision batches run project_collision_bodyself_kernel, the side-memory form plus the rest-excluding search for the body's own
+// surface nodes, in a launch of their own in both launch modes.  A context where no body self-collides launches exactly what it did.
+bool bodyself_on(const admm_hip_ctx *ctx) {
+    for (int q = 0; q < ctx->shapes.n; ++q) {
+        if (ctx->shapes.type[q] != ADMM_SHAPE_MESH) continue;
+        const int id = (int)ctx->shapes.par[q][3];
+        if (id >= 0 && id < (int)ctx->mesh_role.size() && ctx->mesh_role[id].body_self[0] > 0.0) return true;
+    }
+    return false;
+}
 // which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form, 3 the framed form, 4 the
-// shell form, 5 the self-collision form, 6 the side-memory form
-int collision_form(const admm_hip_ctx *ctx) { return sided_on(ctx) ? 6 : self_on(ctx) ? 5 : shell_on(ctx) ? 4 : framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
+// shell form, 5 the self-collision form, 6 the side-memory form, 7 the body self-collision form
+int collision_form(const admm_hip_ctx *ctx) { return bodyself_on(ctx) ? 7 : sided_on(ctx) ? 6 : self_on(ctx) ? 5 : shell_on(ctx) ? 4 : framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
 // ... in a launch of their own (launch_collision_mesh) instead of a segment of project_multi_kernel or project_collision_kernel
 bool collision_own_launch(const admm_hip_ctx *ctx) { return !ctx->meshes.empty() || friction_on(ctx) || framed_on(ctx); }
 
@@ -215,7 +226,13 @@ void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
-    if (sided_on(ctx)) {      // (implies shell_on; the side tables were uploaded at finalize: the reach is set before it.  d_mesh_self, d_self_vid: null without a self-colliding sheet)
+    if (bodyself_on(ctx)) {      // (d_mesh_bself, d_mesh_rest and d_self_vid were uploaded at finalize: the lengths are set before it; the side and sheet tables: null where there is none)
+        hipLaunchKernelGGL(project_collision_bodyself_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
+                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
+                           (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, (const int *)ctx->d_mesh_self, (const int *)ctx->d_self_vid,
+                           (const double *)ctx->d_mesh_reach, (const int *)ctx->d_mesh_side_slot, (const int *const *)ctx->d_mesh_bnd, (const int *)ctx->d_side,
+                           ctx->n_nodes, (const double *)ctx->d_mesh_bself, (const double *const *)ctx->d_mesh_rest, ctx->dt);
+    } else if (sided_on(ctx)) {      // (implies shell_on; the side tables were uploaded at finalize: the reach is set before it.  d_mesh_self, d_self_vid: null without a self-colliding sheet)
         hipLaunchKernelGGL(project_collision_sided_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
                            (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
                            (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, (const int *)ctx->d_mesh_self, (const int *)ctx->d_self_vid,

@@ -303,6 +303,23 @@ bool sheet_rest_violation(const admm_hip_mesh &M, int *vtx, int *tri, double *di
     return false;
 }
 
+// the rest-pose condition of a body surface that collides with itself (admm_hip_set_body_self_collision): the lowest vertex that the rule
+// (body_self_project, mesh_query.hpp) would move where the surface M stands, with rest shape `rest` [nv][3] -> true, with the winning
+// triangle and the distance; false: none
+bool body_rest_violation(const admm_hip_mesh &M, const double *rest, double r, double R, double rho, int *vtx, int *tri, double *dist) {
+    std::vector<double> verts(3 * (size_t)M.nv, 0.0);
+    for (size_t s = 0; s < M.tris.size(); ++s)
+        for (int k = 0; k < 3; ++k) for (int j = 0; j < 3; ++j) verts[3 * (size_t)M.cid[3 * (size_t)M.tris[s].orig + k] + j] = M.tris[s].v[3 * k + j];
+    for (int v = 0; v < M.nv; ++v) {
+        if (M.inc_ptr[v] == M.inc_ptr[v + 1]) continue;
+        HostStack stk; Hit h; double o[3]; bool crossed;
+        if (body_self_project(M.nodes.data(), M.tris.data(), M.nrm.data(), M.cid.data(), rest, v, &verts[3 * (size_t)v], r, R, rho, stk, h, o, crossed)) {
+            *vtx = v; *tri = M.tris[h.slot].orig; *dist = std::sqrt(h.d2); return true;
+        }
+    }
+    return false;
+}
+
 } // namespace admm_mesh
 
 extern "C" {
@@ -558,6 +575,63 @@ int admm_hip_mesh_query_sided(const admm_hip_mesh *mesh, int64_t n_pts, const do
         if (sdist) sdist[i] = sd;
         if (tri) tri[i] = ti;
         if (crossed) crossed[i] = cr ? 1 : 0;
+    }
+    return ADMM_OK;
+}
+
+// self-collision of a closed body surface (mesh_query.hpp), the context-free host evaluation of what project_collision_bodyself_kernel
+// runs for a node of the body that owns the surface: point i is vertex vertex_id[i] of the mesh (-1: an interior node, skipped: proj
+// is the point, tri -1), rest_verts [nv][3] the rest shape.  No translation, no frame: a body surface has neither.  sdist = r - d for
+// a hit on the outside (> 0: pushed; <= 0: a hit within the reach that leaves the point alone), r + d for a crossed one, -inf for no
+// hit; tri: the winning original triangle of a hit (-1: none); crossed: 1 where the mirror ran
+static bool self_lengths_ok(double r, double reach, double rest_radius) {
+    return std::isfinite(r) && std::isfinite(reach) && std::isfinite(rest_radius) && r > 0.0 && reach >= r && rest_radius >= reach;
+}
+int admm_hip_mesh_query_self(const admm_hip_mesh *mesh, int64_t n_pts, const double *pts, const int32_t *vertex_id, const double *rest_verts, double r, double reach,
+                             double rest_radius, double *proj, double *sdist, int32_t *tri, int32_t *crossed) {
+    if (!mesh || n_pts < 0 || (n_pts && (!pts || !vertex_id)) || !rest_verts) return ADMM_ERR_ARG;
+    if (mesh->thickness > 0.0 || !self_lengths_ok(r, reach, rest_radius)) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n_pts; ++i) if (vertex_id[i] < -1 || vertex_id[i] >= mesh->nv) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n_pts; ++i) {
+        const double *q = pts + 3 * i;
+        double o[3] = {0.0, 0.0, 0.0}, sd = -INFINITY; int ti = -1; bool hit = false, cr = false;
+        if (vertex_id[i] >= 0) {
+            HostStack stk; Hit h;
+            hit = body_self_project(mesh->nodes.data(), mesh->tris.data(), mesh->nrm.data(), mesh->cid.data(), rest_verts, vertex_id[i], q, r, reach, rest_radius, stk, h, o, cr);
+            if (h.slot >= 0) { const double d = std::sqrt(h.d2); sd = cr ? r + d : r - d; ti = mesh->tris[h.slot].orig; }
+        }
+        if (proj) for (int j = 0; j < 3; ++j) proj[3 * i + j] = hit ? o[j] : q[j];
+        if (sdist) sdist[i] = sd;
+        if (tri) tri[i] = ti;
+        if (crossed) crossed[i] = cr ? 1 : 0;
+    }
+    return ADMM_OK;
+}
+
+// admm_hip_mesh_velocity_query at the hit of that search (no existing call evaluates at a given triangle): the winning triangle among
+// those that are not rest-near vertex_id[i] and lie within the reach; a point without one (or with id -1) gets zeros and corner ids -1
+int admm_hip_mesh_velocity_query_self(const admm_hip_mesh *mesh, int64_t n, const double *q, const int32_t *vertex_id, const double *rest_verts, double reach,
+                                      double rest_radius, const double *vel, double *out, double *weights, int32_t *corner_ids) {
+    if (!mesh || n < 0 || (n && (!q || !vertex_id)) || !rest_verts || (out && !vel)) return ADMM_ERR_ARG;
+    if (mesh->thickness > 0.0 || !self_lengths_ok(reach, reach, rest_radius)) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) if (vertex_id[i] < -1 || vertex_id[i] >= mesh->nv) return ADMM_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        const double *qq = q + 3 * i;
+        HostStack stk; Hit h;
+        h.slot = -1;
+        if (vertex_id[i] >= 0 && in_shell_box(qq, mesh->nodes[0], reach))
+            closest_within_rest_excluding(mesh->nodes.data(), mesh->tris.data(), mesh->cid.data(), rest_verts, vertex_id[i], rest_radius * rest_radius, qq, reach * reach, stk, h);
+        if (h.slot < 0) {
+            for (int k = 0; k < 3; ++k) { if (weights) weights[3 * i + k] = 0.0; if (corner_ids) corner_ids[3 * i + k] = -1; if (out) out[3 * i + k] = 0.0; }
+            continue;
+        }
+        const Tri &tr = mesh->tris[h.slot];
+        const int *c = mesh->cid.data() + 3 * (size_t)tr.orig;
+        double b[3];
+        tri_weights(qq, tr.v, h.reg, b);
+        if (weights) for (int k = 0; k < 3; ++k) weights[3 * i + k] = b[k];
+        if (corner_ids) for (int k = 0; k < 3; ++k) corner_ids[3 * i + k] = c[k];
+        if (out) tri_interpolate(b, vel + 3 * (size_t)c[0], vel + 3 * (size_t)c[1], vel + 3 * (size_t)c[2], out + 3 * i);
     }
     return ADMM_OK;
 }

@@ -30,4 +30,7 @@ int mesh_refusal(const admm_hip_mesh &M, const double *verts, const UpdateCheck 
 // a sheet that collides with itself (admm_hip_set_sheet_self_collision): does a vertex lie nearer than the half thickness to a triangle it
 // is not a corner of?  The lowest such vertex, its triangle and the distance
 bool sheet_rest_violation(const admm_hip_mesh &M, int *vtx, int *tri, double *dist);
+// a body surface that collides with itself (admm_hip_set_body_self_collision): would the rule move one of M's own vertices where M stands,
+// with the rest shape rest [nv][3]?  The lowest such vertex, the winning triangle and the distance
+bool body_rest_violation(const admm_hip_mesh &M, const double *rest, double r, double R, double rho, int *vtx, int *tri, double *dist);
 }

@@ -46,6 +46,24 @@
 // Self-collision of a sheet (admm_hip_set_sheet_self_collision): a node that is vertex vi of the surface runs steps 1 to 5 with one change
 // in step 2 -- closest_within_excluding leaves out every triangle that has vi as a corner (the node's 1-ring: cid[3 orig + k] == vi for
 // k = 0, 1, 2); among the others the winner is the minimum of (d2, original triangle index) with d2 < r * r, as before.
+//
+// Self-collision of a closed body surface (admm_hip_set_body_self_collision: a body surface S with a half gap r > 0, a reach R >= r and a
+// rest radius rho >= R).  X: the surface's vertices as admm_hip_add_body_surface registered them, the rest shape; later updates do not
+// change it.  A body surface has no translation and no frame.  An interior node of the body (no vertex of S) skips S as before.  A
+// surface node, vertex vi of S, with candidate q (body_self_project), every product and sum rounded, in this order:
+//   1. box test   in_shell_box(q, root, R) fails: the point keeps its bits
+//   2. search     closest_within_rest_excluding: the minimum of (d2, original triangle index), d2 < R * R, over the triangles that are
+//                 not rest-near vi.  Triangle T with corners a, b, c = cid[3 orig + 0..2], in that order, is rest-near when
+//                 closest_on_tri(X[vi], {X[a], X[b], X[c]}) gives e0 * e0 + e1 * e1 + e2 * e2 < rho * rho (rest_near; the 1-ring has
+//                 e = 0).  A left-out triangle never tightens the bound; the boxes only prune (box_open), so the result does not depend
+//                 on the tree.  The test is evaluated lazily, only for a triangle whose d2 would make it the new best: the winner and its
+//                 bits are the definition's.  No hit: the point keeps its bits
+//   3. push       g = side_g(q, h).  g >= 0 (or not a number) or d2 == 0: the unsigned rule on this hit -- collides iff d2 < r * r,
+//                 shell_push.  g < 0: the node has crossed the skin and is mirrored to distance r outside: d = sqrt(d2), sc = r / d,
+//                 e_j = q_j - c_j, p'_j = c_j - sc * e_j   (steps 3 and 4 of the side-memory projection with s = +1, no boundary hits)
+// Everything after the push is what every mesh entry does.  Nodes of other bodies meet S by the closed-mesh rule.  Callers keep R above
+// closing speed x dt + r, rho above R by the compression the body is expected to see, and rho below the body's thinnest part (or the
+// two faces of a thin plate never see each other).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -514,6 +532,82 @@ ADMM_HD void refit_node(Node *nodes, const Tri *tris, int ni) {
         for (int j = 0; j < 3; ++j) { lo[j] = min_d(l.lo[j], r.lo[j]); hi[j] = max_d(l.hi[j], r.hi[j]); }
     }
     for (int j = 0; j < 3; ++j) { n.lo[j] = lo[j]; n.hi[j] = hi[j]; }
+}
+
+// ---- self-collision of a closed body surface (the rule at the top of this file) ---------------------------------------------------
+// original triangle oi is rest-near vertex vi: its distance to X[vi] in the rest shape X [nv][3] is below rho (rho2 = rho * rho)
+ADMM_HD bool rest_near(const double *__restrict__ rest, const int *__restrict__ cid, const int oi, const int vi, const double rho2) {
+    double v[9], o[3]; int reg;
+    gather_tri(rest, cid, oi, v);
+    const double *p = rest + 3 * (size_t)vi;
+    closest_on_tri(p, v, o, reg);
+    const double e0 = p[0] - o[0], e1 = p[1] - o[1], e2 = p[2] - o[2];
+    return e0 * e0 + e1 * e1 + e2 * e2 < rho2;
+}
+// `closest_within` over the triangles that are not rest-near vertex vi: the minimum of (d2, original triangle index), d2 < r2.  The rest
+// test runs only for a triangle that would become the new best (the gathers of the rest shape stay off every other triangle); one that
+// fails it is passed over and never tightens the bound, so the winner is the one an eager test before the distance gives.
+template <class Stack>
+ADMM_HD void closest_within_rest_excluding(const Node *__restrict__ nodes, const Tri *__restrict__ tris, const int *__restrict__ cid, const double *__restrict__ rest,
+                                           const int vi, const double rho2, const double *q, const double r2, Stack &stk, Hit &h) {
+    h.d2 = r2; h.slot = -1; h.reg = 0; h.c[0] = h.c[1] = h.c[2] = 0.0;
+    int best_i = NO_TRI;
+    int sp = 0, cur = 0;
+    for (;;) {
+        const Node &n = nodes[cur];
+        int next = -1;
+        if (n.cnt > 0) {
+            for (int t = n.a; t < n.a + n.cnt; ++t) {
+                double o[3]; int reg;
+                closest_on_tri(q, tris[t].v, o, reg);
+                const double e0 = q[0] - o[0], e1 = q[1] - o[1], e2 = q[2] - o[2];
+                const double d2 = e0 * e0 + e1 * e1 + e2 * e2;
+                const int oi = tris[t].orig;
+                if (d2 < r2 && closer(d2, oi, h.d2, best_i) && !rest_near(rest, cid, oi, vi, rho2)) {
+                    h.d2 = d2; best_i = oi; h.slot = t; h.reg = reg; h.c[0] = o[0]; h.c[1] = o[1]; h.c[2] = o[2];
+                }
+            }
+        } else {
+            const int l = n.a, r = n.a + 1;
+            const double dl = box_d2(q, nodes[l]), dr = box_d2(q, nodes[r]);
+            const bool rf = dr < dl || (dr == dl && centre_d2(q, nodes[r]) < centre_d2(q, nodes[l]));
+            const int near = rf ? r : l, far = rf ? l : r;
+            const double dn = rf ? dr : dl, df = rf ? dl : dr;
+            if (box_open(df, h.d2) && sp < MAX_DEPTH) { stk[sp] = far; ++sp; }
+            if (box_open(dn, h.d2)) next = near;
+        }
+        while (next < 0 && sp > 0) {
+            --sp;
+            const int cand = stk[sp];
+            if (box_open(box_d2(q, nodes[cand]), h.d2)) next = cand;
+        }
+        if (next < 0) break;
+        cur = next;
+    }
+    if (h.slot < 0) h.d2 = INFINITY;
+}
+// the projection of a surface node, vertex vi: true when q moves, o = p' then; h: the hit (slot -1: none within R, or the box test
+// failed); crossed: the mirror push ran
+template <class Stack>
+ADMM_HD bool body_self_project(const Node *__restrict__ nodes, const Tri *__restrict__ tris, const Nrm *__restrict__ nrm, const int *__restrict__ cid,
+                               const double *__restrict__ rest, const int vi, const double *q, const double r, const double R, const double rho, Stack &stk,
+                               Hit &h, double *o, bool &crossed) {
+    crossed = false;
+    h.slot = -1; h.d2 = INFINITY; h.reg = 0;
+    if (!in_shell_box(q, nodes[0], R)) return false;
+    closest_within_rest_excluding(nodes, tris, cid, rest, vi, rho * rho, q, R * R, stk, h);
+    if (h.slot < 0) return false;
+    if (!(side_g(nrm, q, h) < 0.0) || !(h.d2 > 0.0)) {
+        if (!shell_collides(h, r)) return false;
+        shell_push(q, h, nrm, r, o);
+        return true;
+    }
+    crossed = true;
+    const double d = sqrt(h.d2);
+    const double sc = r / d;
+    const double e0 = q[0] - h.c[0], e1 = q[1] - h.c[1], e2 = q[2] - h.c[2];
+    o[0] = h.c[0] - sc * e0; o[1] = h.c[1] - sc * e1; o[2] = h.c[2] - sc * e2;
+    return true;
 }
 
 } // namespace admm_mesh

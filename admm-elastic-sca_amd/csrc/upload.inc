@@ -561,14 +561,31 @@ int upload_all(admm_hip_ctx *ctx) {
         ctx->d_mesh_self = nullptr; ctx->d_self_vid = nullptr;
         {
             std::vector<int> flag(ctx->meshes.size(), 0), vid((size_t)n, -1);
-            bool any = false;
+            bool any = false, any_body = false;
             for (size_t i = 0; i < ctx->meshes.size(); ++i) {
                 const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
-                if (!R.self_collision) continue;
-                any = true; flag[i] = 1;
+                const bool bs = R.body_self[0] > 0.0;      // a body surface that collides with itself: the same vertex ids (finalize: one such surface per node range)
+                if (!R.self_collision && !bs) continue;
+                if (R.self_collision) { any = true; flag[i] = 1; } else any_body = true;
                 for (size_t k = 0; k < R.body_nodes.size(); ++k) vid[F.iperm[R.body_nodes[k]]] = (int)k;
             }
-            if (any) { TRY(upload(ctx, &ctx->d_mesh_self, flag)); TRY(upload(ctx, &ctx->d_self_vid, vid)); }
+            if (any) TRY(upload(ctx, &ctx->d_mesh_self, flag));
+            if (any || any_body) TRY(upload(ctx, &ctx->d_self_vid, vid));
+            // ... and the lengths and rest vertices of the body surfaces among them, only where there is one
+            ctx->d_mesh_bself = nullptr; ctx->d_mesh_rest = nullptr;
+            if (any_body) {
+                std::vector<double> len(3 * ctx->meshes.size(), 0.0);
+                std::vector<const double *> rest(ctx->meshes.size(), nullptr);
+                for (size_t i = 0; i < ctx->meshes.size(); ++i) {
+                    const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+                    if (!(R.body_self[0] > 0.0)) continue;
+                    for (int j = 0; j < 3; ++j) len[3 * i + j] = R.body_self[j];
+                    double *rv = nullptr;
+                    TRY(upload(ctx, &rv, R.rest));
+                    rest[i] = rv;
+                }
+                TRY(upload(ctx, &ctx->d_mesh_bself, len)); TRY(upload(ctx, &ctx->d_mesh_rest, rest));
+            }
         }
         for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) {
             const admm_hip_mesh &M = ctx->meshes[mi];

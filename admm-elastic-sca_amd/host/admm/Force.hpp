@@ -371,6 +371,10 @@ public:
     // the Coulomb coefficient of contacts with this surface (admm_hip_set_body_surface_friction): a property of the body, whatever list
     // names it; the surface's velocity at a contact is its nodes'.  `friction` (the per-entry coefficient) stays refused on a CollisionBody.
     double surface_friction = 0.0;
+    // {r, reach, rest_radius}, r > 0: the body's surface nodes meet this surface too, outside what is near them in the rest shape
+    // (admm_hip_set_body_self_collision); read at System::initialize, where a force that projects on the host refuses it.  (A
+    // CollisionSheet has a flag of the same name instead: admm_hip_set_sheet_self_collision.)
+    double self_collision[3] = {0.0, 0.0, 0.0};
 };
 
 // Extension, no reference counterpart: CollisionBody for an open surface of simulated nodes such as a cloth (admm_hip_add_sheet_surface):

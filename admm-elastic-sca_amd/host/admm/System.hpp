@@ -185,6 +185,14 @@ public:
                             return false;
                         }
                     }
+                if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))      // body self-collision runs in the device form only, like an orientation
+                    for (size_t q = 0; q < cf->collisionShapes.size(); ++q) {
+                        const CollisionBody *cb = dynamic_cast<const CollisionBody *>(cf->collisionShapes[q].get());
+                        if (cb && !dynamic_cast<const CollisionSheet *>(cb) && cb->self_collision[0] != 0.0) {
+                            std::cerr << "\n**Solver Error: force " << i << ", shape " << q << ": body self-collision (r " << cb->self_collision[0] << ") on a force that projects on the host (a user-written shape in its list); it needs the device form of every shape" << std::endl;
+                            return false;
+                        }
+                    }
                 if (const CollisionForce *cf = dynamic_cast<const CollisionForce *>(&f))
                     for (size_t q = 0; q < cf->collisionShapes.size(); ++q) if (dynamic_cast<const CollisionBody *>(cf->collisionShapes[q].get())) {
                         std::cerr << "\n**Solver Error: force " << i << " projects on the host (a user-written shape in its list), where a CollisionBody has no evaluation" << std::endl;
@@ -477,6 +485,7 @@ protected:
                     if (!check(cs ? admm_hip_add_sheet_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), cs->half_thickness, &id)
                                   : admm_hip_add_body_surface(gpu, cb.node_first, cb.node_count, (int)(t.size() / 3), t.data(), &id))) return false;
                     if (cs && cs->self_collision && !check(admm_hip_set_sheet_self_collision(gpu, id, 1))) return false;
+                    if (!cs && cb.self_collision[0] != 0.0 && !check(admm_hip_set_body_self_collision(gpu, id, cb.self_collision[0], cb.self_collision[1], cb.self_collision[2]))) return false;
                     if (cs && cs->side_reach != 0.0 && !check(admm_hip_set_collision_mesh_side_memory(gpu, id, cs->side_reach))) return false;
                     body_ids.push_back(std::make_pair(&cb, id));
                     body_mu.push_back(0.0);

@@ -41,6 +41,16 @@ def bar(nx, ny, nz, h=0.05):
     return x, tets.astype(np.int32)
 
 
+def slotted_bar(nx, ny, nz, slot_from, h=0.05):
+    """bar(nx, ny, nz, h) without the cubes whose j == ny // 2 and k >= slot_from: two arms one cell apart, joined by a spine (a
+    gripper, a tuning fork) -> (x, tets): the positions of bar (nodes inside the slot that no tet uses included) and the kept tets in
+    bar's order."""
+    x, tets = bar(nx, ny, nz, h)
+    ck, cj, _ = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    cut = ((cj.ravel() == ny // 2) & (ck.ravel() >= slot_from))      # cube-major, i fastest, six tets a cube: bar's order
+    return x, np.ascontiguousarray(tets[~np.repeat(cut, 6)])
+
+
 def lumped_tet_mass(x, tets, density):
     """rho * vol / 4 to each corner (ForceBuilder density-weighted mass,
     reference src/ForceBuilder.hpp:191-303); returns [n] per-node mass."""

@@ -163,7 +163,7 @@ int  admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, cons
  *     ADMM iterations.  No read-back: a frame whose positions the update would refuse (non-finite vertex, zero-area triangle,
  *     non-positive volume) keeps the last good surface, is counted, and the step returns ADMM_OK;
  *   - has an owner, its node range: the collision elements of those nodes skip the mesh (every interior node is inside its own body).
- * Self-collision within one body and edge-edge contact are out of scope (open surfaces: the thick-shell section below).  Friction against a body surface:
+ * Edge-edge contact is out of scope (open surfaces: the thick-shell section below; self-collision within one body: admm_hip_set_body_self_collision, further below).  Friction against a body surface:
  * admm_hip_set_body_surface_friction below; it acts on the node in contact only, the surface's own nodes feel no reaction from it.
  *   admm_hip_add_body_surface  before finalize; tris [n_tris][3] are global node ids, all inside [node_first, node_first + node_count).
  *                           Vertices: the distinct referenced nodes in ascending id order, at their current positions (admm_hip_add_nodes
@@ -356,10 +356,10 @@ int  admm_hip_add_sheet_surface(admm_hip_ctx *ctx, int node_first, int node_coun
  * (admm_hip_set_body_surface_friction), the frame-start v of the winning triangle's nodes interpolated at the hit, the friction rule.
  * Nodes that do not belong to the sheet meet it exactly as before.  The surface is frozen at the frame-start x for the frame's
  * iterations: a node meets where the rest of the cloth was at the start of the frame.  Contact is vertex-triangle outside a node's
- * 1-ring only: edge-edge contact, side memory for the sheet's own nodes, continuous detection and self-collision of a closed body surface are out of scope, and
+ * 1-ring only: edge-edge contact, side memory for the sheet's own nodes and continuous detection are out of scope (a closed body surface: the section after the next), and
  * the push is one-sided (the winning triangle's nodes feel no reaction).
  *   admm_hip_set_sheet_self_collision  before finalize (ADMM_ERR_STATE after it); on != 0 switches it on for the sheet surface mesh_id.
- *                           ADMM_ERR_ARG, naming the mesh, for an obstacle mesh or a closed body surface.  The collision batches of a
+ *                           ADMM_ERR_ARG, naming the mesh, for an obstacle mesh or a closed body surface (admm_hip_set_body_self_collision is its call).  The collision batches of a
  *                           list that names such a sheet launch project_collision_self_kernel; a context where no sheet self-collides
  *                           launches exactly what it launched before.
  *   admm_hip_finalize       refuses (ADMM_ERR_ARG, naming the vertex, the triangle and the distance) a self-colliding sheet in whose
@@ -435,6 +435,48 @@ int  admm_hip_mesh_query_sided(const admm_hip_mesh *mesh, int64_t n_pts, const d
                                double *proj, double *sdist, int32_t *tri, int32_t *crossed);
 int  admm_hip_mesh_boundary_table(const admm_hip_mesh *mesh, int32_t *bits, int32_t *orig);
 int  admm_hip_mesh_feature_normal(const admm_hip_mesh *mesh, int64_t n, const int32_t *slot, const int32_t *reg, double *out);
+
+/* ---- self-collision of a closed body surface: a tet body meets its own skin ---------------------------------------------------------------
+ * Extension, no reference counterpart.  A body surface's own nodes skip it, which is right for interior nodes and wrong for surface
+ * nodes: a bar bent back on itself, the jaws of a gripper, an arm and its torso pass through each other.  A body surface S
+ * (admm_hip_add_body_surface) may be given three lengths: a half gap r > 0, a reach R >= r, a rest radius rho >= R.  X are the surface's
+ * vertices as admm_hip_add_body_surface registered them, the rest shape; the context keeps a copy and later updates do not change it.
+ * Node i of the body has a candidate q; a body surface has no translation and no frame.  An interior node (no vertex of S) skips S as
+ * before.  A surface node, vertex vi of S, every product and sum rounded, no fused multiply-adds:
+ *     1. the box test of the shell rule with R (lo_j - R < q_j < hi_j + R strictly, the root box) fails: the point keeps its bits;
+ *     2. the winner is the minimum of (d2, original triangle index), d2 < R * R, over the triangles that are not rest-near vi.  Triangle
+ *        T with corners a, b, c = cid[3 orig + 0..2], in that order, is rest-near when the closest point of {X[a], X[b], X[c]} to X[vi]
+ *        gives e0 * e0 + e1 * e1 + e2 * e2 < rho * rho; the 1-ring is rest-near by construction.  A left-out triangle never tightens
+ *        the bound and the boxes only prune with the usual margin, so the result does not depend on the tree.  The test is evaluated
+ *        lazily, for a triangle whose d2 would make it the new best; the winner and its bits are the definition's.  No hit: the point
+ *        keeps its bits;
+ *     3. g = (q0 - c0) n0 + (q1 - c1) n1 + (q2 - c2) n2, n the pseudo-normal of the hit's feature.  g >= 0 or d2 == 0: the unsigned rule
+ *        on this hit -- it collides iff d2 < r * r, then step 4 of the shell rule.  g < 0: the node has crossed the skin and is mirrored
+ *        to distance r outside, d = sqrt(d2), p'_j = c_j - (r / d)(q_j - c_j);
+ *     4. everything after the push is unchanged: the surface's own coefficient (admm_hip_set_body_surface_friction), the frame-start v
+ *        of the winning triangle's nodes interpolated at the hit, the rigid displacement, the friction rule.
+ * Nodes of other bodies meet S by the closed-mesh rule, exactly as before.  The surface is frozen at the frame-start x; contact is
+ * one-sided and vertex-triangle, like every surface here.  Keep R above closing speed x dt + r, rho above R by the compression the body
+ * is expected to see, and rho below the body's thinnest part, or the two faces of a thin plate never see each other.  Both shard modes
+ * hold the full frame-start x on every rank; nothing new crosses a collective.
+ *   admm_hip_set_body_self_collision  before finalize (ADMM_ERR_STATE after it); r = 0 switches it off.  ADMM_ERR_ARG, naming the mesh,
+ *                           for an obstacle mesh, a sheet surface, a non-finite value, reach < r, rest_radius < reach.  Finalize refuses
+ *                           (ADMM_ERR_ARG naming vertex, triangle and distance) a body in whose finalize positions the rule would already
+ *                           move one of its own vertices, and two self-colliding surfaces (sheets or bodies) over one node range: a
+ *                           node has one vertex id.  A list that names such a surface launches project_collision_bodyself_kernel
+ *                           (collision form 7); a context where no body self-collides uploads and launches exactly what it did.
+ *   admm_hip_mesh_query_self  the context-free host evaluation, the device's bits: point i is vertex vertex_id[i] of the closed mesh
+ *                           (-1: skipped, proj = the point, tri = -1), rest_verts [nv][3] the rest shape.  sdist = r - d for a hit on the
+ *                           outside (> 0: pushed; <= 0: a hit within the reach that leaves the point alone), r + d for a crossed one,
+ *                           -inf for no hit; tri = the winning original triangle of a hit (-1: none); crossed = 1 where the mirror ran.  ADMM_ERR_ARG on an open mesh, for an id outside [-1, nv) and for lengths the setter
+ *                           refuses (r = 0 included).
+ *   admm_hip_mesh_velocity_query_self  admm_hip_mesh_velocity_query at the hit of that search (no other call evaluates at a given
+ *                           triangle); a point without a hit within the reach gets zeros and corner ids -1.                            */
+int  admm_hip_set_body_self_collision(admm_hip_ctx *ctx, int mesh_id, double r, double reach, double rest_radius);
+int  admm_hip_mesh_query_self(const admm_hip_mesh *mesh, int64_t n_pts, const double *pts, const int32_t *vertex_id, const double *rest_verts, double r, double reach,
+                              double rest_radius, double *proj, double *sdist, int32_t *tri, int32_t *crossed);
+int  admm_hip_mesh_velocity_query_self(const admm_hip_mesh *mesh, int64_t n, const double *q, const int32_t *vertex_id, const double *rest_verts, double reach,
+                                       double rest_radius, const double *vel, double *out, double *weights, int32_t *corner_ids);
 
 /* ---- multi-GPU ------------------------------------------------------------
  * Elements shard across ranks (see admm_hip_set_shard_mode); must be called before finalize.  The hook must sum `count`
