@@ -115,7 +115,7 @@ def lib():
         L.admm_hip_update_anchors.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
         L.admm_hip_step.argtypes = [C.c_void_p, C.c_int]
         L.admm_hip_sync.argtypes = [C.c_void_p]
-        for n in ("get_x", "get_v"):
+        for n in ("get_x", "get_v", "debug_rhs"):
             getattr(L, "admm_hip_" + n).argtypes = [C.c_void_p, _dp]
         for n in ("set_x", "set_v", "local_step_only"):
             getattr(L, "admm_hip_" + n).argtypes = [C.c_void_p, _dp]
@@ -892,6 +892,10 @@ class System:
     def local_step_only(self, x_cur):
         x_cur = np.ascontiguousarray(x_cur, dtype=np.float64).ravel()
         self._chk(self.L.admm_hip_local_step_only(self.h, _d(x_cur)))
+
+    def debug_rhs(self):
+        """the right-hand side b = M x_bar + dt^2 D^T W^2 (z - u) the last local step assembled (this rank's, before any all-reduce)"""
+        return self._getn(self.L.admm_hip_debug_rhs)
 
     def local_step_dx(self, batch, dx):
         dx = np.ascontiguousarray(dx, dtype=np.float64)

@@ -93,6 +93,14 @@ int admm_hip_local_step_only(admm_hip_ctx *ctx, const double *x_cur) {
     return ADMM_OK;
 }
 
+// Parity-test hook: the right-hand side the last launch_rhs left in d_y, in the caller's node order -- after admm_hip_local_step_only
+// exactly what the sweeps would be handed (this rank's vector, before any all-reduce).  NOT used by admm_hip_step or any product path.
+int admm_hip_debug_rhs(admm_hip_ctx *ctx, double *y) {
+    TRY(require_factor(ctx));
+    if (!y) return ADMM_ERR_ARG;
+    return get_nodes(ctx, ctx->d_y, y);
+}
+
 // Parity-test hook: one project() of every local element of `batch` on
 // caller-supplied D_i x rows (element-major [n_local][rows]) instead of the
 // gather from x -- replays the reference's recorded (Dx,u,state)->(u,z,state) tuples.

@@ -384,6 +384,9 @@ int upload_all(admm_hip_ctx *ctx) {
     // (r ascending = batch, element, corner), so the results are bitwise the same.  It pads every node to the largest incidence
     // count: used unless that more than doubles the array (meshes with a few very high-valence nodes).
     ctx->slot_stride = (maxdeg * n <= 2 * inc_ptr[n] + 1024 && getenv("ADMM_HIP_SLOTS_NODE_SORTED") == nullptr) ? n : 0;
+    if (getenv("ADMM_HIP_VERBOSE"))      // the layout this context's right-hand side is assembled in (tests/test_rhs_reference.py asserts it)
+        fprintf(stderr, "admm_hip: plan rhs: slots %lld maxdeg %lld layout %s prered %d\n", (long long)inc_ptr[n], (long long)maxdeg,
+                ctx->slot_stride ? "rank-major" : "node-sorted", ctx->tet_prered ? 1 : 0);
     // pass 2: device arrays; every corner gets the next slot of its node (fixed order: batch, element, corner)
     for (Batch &b : ctx->batches) {
         if (b.kind == ADMM_KIND_GENERIC) {

@@ -619,6 +619,11 @@ int admm_hip_read_rest(admm_hip_ctx *ctx, int batch, double *weight, double *res
 /* one local step on caller-supplied positions (no global step): runs the batch
  * kernels on x_cur = x and returns; used by the per-project parity tests.     */
 int admm_hip_local_step_only(admm_hip_ctx *ctx, const double *x_cur);
+/* the assembled right-hand side b = M x_bar + dt^2 D^T W^2 (z - u) as the last local step left it on the device, y [n_nodes][3] in
+ * the caller's node order.  admm_hip_local_step_only ends with the assembly and runs no solve, so local_step_only + debug_rhs observes
+ * exactly what the sweeps would be handed (M x_bar: of the last admm_hip_step's prologue).  In a sharded context: this rank's vector
+ * before any all-reduce (the ranks' vectors sum to b).  Parity tests only; no product path calls it.                              */
+int admm_hip_debug_rhs(admm_hip_ctx *ctx, double *y);
 /* one project() of every local element of `batch` on caller-supplied D_i x rows
  * (element-major [n_local][rows]) instead of the gather: replays the per-project
  * golden tuples captured from the reference (tests/golden/project_*.npz).       */

@@ -88,6 +88,7 @@ class _Sys:
     def add_nodes(self, x, m):
         x = np.ascontiguousarray(x, dtype=np.float64).ravel()
         m = np.ascontiguousarray(m, dtype=np.float64).ravel()
+        self.m3 = np.concatenate([getattr(self, "m3", np.zeros(0)), m])      # the masses this system was given (RhsReference)
         return self._f("add_nodes")(self.h, x.size, _d(x), _d(m))
 
     def add_forces(self, kind, idx, params):
@@ -887,3 +888,168 @@ class ResidualReference:
         if x_start is not None:
             b = b + gamma(self.nnz_row) * self._norm(self._DT(w2 * self._D(x_start, absolute=True), absolute=True))
         return float(b + c_s * EPS * self.s(z1, zprev))
+
+
+# ---- the assembled right-hand side recomputed from captured states (tests/test_rhs_reference.py) ----
+class RhsReference(ResidualReference):
+    """The right-hand side of the global step, b = M x_bar + dt^2 D^T W^2 (z - u), recomputed in np.longdouble from the u and z a local step
+    left behind (the states AFTER it, in the oracle's row order; rows_of() maps a batch's per-element arrays there).  D (compact rows), W and
+    the masses are the ORACLE's (D_triplets, wdiag, the m3 it was given); nothing here calls the library under test.
+
+    A `corner` is one (force, node) pair: the node's share of one element, dt^2 sum_r D[r, 3 node + j] w_r^2 (z - u)_r for j = 0..2.
+    corner_force / corner_node name them, degree[node] counts the corners on a node, b(drop=...) leaves corners out (the sensitivity
+    condition: one share dropped moves b by exactly that share).
+
+    bound(): |b_dev - b_ref| <= gamma_k (|m x_bar| + dt^2 |D^T| W^2 |z - u|) per dof, k from the kernels' operation counts (EPS = 2^-53,
+    gamma_k = k EPS / (1 - k EPS)); nothing measured goes into it:
+      * q = fl(z - u_new): the device's u_new and z are the very doubles the reference reads back, so this is ONE rounding              1
+      * the factor dt^2 w^2 = fl(fl(dt dt) fl(w w)) (w2h2 of upload.inc)                                                                3
+      * the product with the selector entry and the product with that factor -- s (B q) in the tet and triangle kernels, s q alone
+        where the entry is +-1 (anchors, collisions, springs, hinges): at most                                                          2
+      * the additions of one corner's terms, T - 1 with T = the most entries one element has in one column of D (3 for tets, 2 for
+        triangles, 1 otherwise; the hinge's minus-all corner adds 2: its three terms count as T = 3 there)                             T - 1
+      * the corners of a node meet in at most (corners on the node - 1) additions whichever layout and block cut is used: the run in the
+        block's LDS staging plus the node's slots in the gather never exceed it                                                  degree - 1
+      * the addition of fl(m x_bar) (its own product rounding and this addition stay below the count of the other terms)                1
+    k(node) = 7 + (T - 1) + (degree(node) - 1).  The ranks' vectors of a sharded context are summed in np.longdouble by the test: every rank
+    adds fewer corners than the node has, M x_bar enters on one rank, and the same bound holds.
+    The longdouble arithmetic (eps <= 2^-63, asserted) contributes errors 1000 times below this and is not counted."""
+
+    def __init__(self, oracle, dt=0.04):
+        super().__init__(oracle)
+        ld = np.longdouble
+        self.dt = float(dt)
+        self.m3 = np.asarray(oracle.m3, dtype=np.float64)
+        assert self.m3.size == self.n
+        force, node = self.row_force[self.rr], self.cc // 3
+        key, self.entry_corner = np.unique(force * (self.n // 3) + node, return_inverse=True)
+        self.corner_force, self.corner_node = key // (self.n // 3), key % (self.n // 3)
+        self.n_corners = key.size
+        self.degree = np.bincount(self.corner_node, minlength=self.n // 3)
+        T = int(np.bincount(self.entry_corner * 3 + self.cc % 3).max())
+        if (self.kinds == KIND["BEND"]).any():
+            T = max(T, 3)
+        self.T = T
+        self.k_dof = np.repeat(7 + (T - 1) + np.maximum(self.degree - 1, 0), 3)
+        self._coef = ld(self.dt) * ld(self.dt) * self.vv * (self.W * self.W)[self.rr]      # dt^2 D[r, c] w_r^2 per entry
+
+    def shares(self, u, z, absolute=False):
+        """[corners][3]: every corner's share of b (absolute: of |D^T| W^2 |z - u|)"""
+        ld = np.longdouble
+        q = np.asarray(z, dtype=ld) - np.asarray(u, dtype=ld)
+        t = self._coef * q[self.rr]
+        out = np.zeros(3 * self.n_corners, ld)
+        np.add.at(out, self.entry_corner * 3 + self.cc % 3, np.abs(t) if absolute else t)
+        return out.reshape(-1, 3)
+
+    def _scatter(self, sh, drop=None):
+        out = np.zeros(self.n, np.longdouble)
+        keep = np.ones(self.n_corners, bool) if drop is None else ~np.asarray(drop, bool)
+        dof = (3 * self.corner_node[keep])[:, None] + np.arange(3)[None, :]
+        np.add.at(out, dof.ravel(), sh[keep].ravel())
+        return out
+
+    def b(self, xbar, u, z, drop=None):
+        """drop: a boolean mask over the corners left out"""
+        ld = np.longdouble
+        return self.m3.astype(ld) * np.asarray(xbar, dtype=ld) + self._scatter(self.shares(u, z), drop)
+
+    def bound(self, xbar, u, z):
+        ld = np.longdouble
+        mag = np.abs(self.m3.astype(ld) * np.asarray(xbar, dtype=ld)) + self._scatter(self.shares(u, z, absolute=True))
+        k = self.k_dof.astype(ld)
+        return (k * EPS / (1.0 - k * EPS)) * mag
+
+    def corner_sensitivity(self, xbar, u, z):
+        """per corner: by how many bounds its removal moves b in its most sensitive component"""
+        bd = self.bound(xbar, u, z).reshape(-1, 3)
+        return np.max(np.abs(self.shares(u, z)) / bd[self.corner_node], axis=1).astype(np.float64)
+
+
+# ---- the explicit forces of a frame in np.longdouble (tests/test_explicit_reference.py) ----
+def _explicit(x, v, dt, forces, with_bound):
+    ld = np.longdouble
+    assert np.finfo(ld).eps <= 2.0 ** -63, "np.longdouble has no extended precision here (the tests that use this skip on such hosts)"
+    X = np.asarray(x, dtype=np.float64).reshape(-1, 3).astype(ld)
+    V = np.asarray(v, dtype=np.float64).reshape(-1, 3).astype(ld).copy()
+    n = X.shape[0]
+    h = ld(float(dt))
+    E = np.zeros((n, 3), ld)      # running first-order bound on the device's error in v
+    e = ld(EPS)
+    third, c33, k1000 = ld(3.0), ld(0.33), ld(1000.0)      # the doubles the kernels hold (0.33 is not exact: the same double here)
+    P, Q = [1, 2, 0], [2, 0, 1]
+    for type_, direction, idx in forces:
+        d = np.asarray(direction, dtype=np.float64).astype(ld)
+        if type_ == "const":
+            sel = np.arange(n) if idx is None or len(idx) == 0 else np.asarray(idx, dtype=np.int64)      # an empty list = every node (ExplicitForce.cpp:30-32)
+            inc = h * d
+            for node in (sel if np.unique(sel).size != sel.size else [sel]):      # (a list naming a node twice increments it twice)
+                V[node] += inc
+                if with_bound:
+                    E[node] += e * np.abs(inc) + e * np.abs(V[node])
+            continue
+        assert type_ == "wind"
+        tris = np.asarray(idx, dtype=np.int64).reshape(-1, 3)
+        # the geometry reads x only: all triangles at once
+        a, b = X[tris[:, 1]] - X[tris[:, 0]], X[tris[:, 2]] - X[tris[:, 0]]
+        nv = a[:, P] * b[:, Q] - a[:, Q] * b[:, P]
+        nn = np.sqrt(nv[:, 0] * nv[:, 0] + (nv[:, 1] * nv[:, 1] + nv[:, 2] * nv[:, 2]))
+        nm = nv / nn[:, None]
+        area = ld(0.5) * nn
+        if with_bound:
+            dn = 4 * e * (np.abs(a[:, P] * b[:, Q]) + np.abs(a[:, Q] * b[:, P]))
+            dnn = (np.abs(nv) * dn).sum(axis=1) / nn + 3 * e * nn
+            dnm = dn / nn[:, None] + np.abs(nm) * (dnn / nn)[:, None] + e * np.abs(nm)
+            darea = ld(0.5) * dnn
+        for t in range(tris.shape[0]):      # serial triangle order: each triangle sees the velocities the earlier ones left
+            i = tris[t]
+            vv = V[i]
+            vr = (vv[0] + vv[1] + vv[2]) / third - d
+            vn = (nm[t] * vr).sum()
+            c = -k1000 * area[t] * vn * abs(vn)
+            f = c * nm[t] * c33 * h
+            if with_bound:
+                dvr = E[i].sum(axis=0) / 3 + e * (np.abs(vv).sum(axis=0) + np.abs(vr))
+                dvn = (dnm[t] * np.abs(vr) + np.abs(nm[t]) * dvr).sum() + 3 * e * np.abs(nm[t] * vr).sum()
+                dc = k1000 * (darea[t] * vn * vn + 2 * area[t] * abs(vn) * dvn) + 3 * e * abs(c)
+                df = c33 * h * (dc * np.abs(nm[t]) + abs(c) * dnm[t]) + 3 * e * np.abs(f)
+            for q in range(3):      # corner by corner: a triangle naming one node twice increments it twice
+                V[i[q]] += f
+                if with_bound:
+                    E[i[q]] += df + e * np.abs(V[i[q]])
+    xbar = X + h * V
+    vout = (xbar - X) * (ld(1.0) / h)
+    out = (xbar.ravel(), vout.ravel(), V.ravel())
+    if not with_bound:
+        return out
+    bx = h * E + e * np.abs(h * V) + e * np.abs(xbar)
+    bvout = bx / h + 3 * e * np.abs(vout)
+    second = ld(1.0) + ld(2.0) ** -10      # the neglected products of two errors, each below 1e-13 of a first-order term
+    return out, (second * bx.ravel(), second * bvout.ravel(), second * E.ravel())
+
+
+def explicit_reference(x, v, dt, forces):
+    """The explicit part of a frame (System.cpp:37-48, 70-71 with no ADMM iteration in between) in np.longdouble, the forces in LIST ORDER.
+    forces: [("const", g, idx or None), ("wind", direction, tris)].  A constant force adds dt g on all nodes (idx None or empty:
+    ExplicitForce.cpp:30-32) or on a subset.  The wind (ExplicitForce.cpp:42-98 as wind_serial_kernel's comment states it) runs in SERIAL
+    triangle order: each triangle sees the velocities the earlier ones left, v_r = (v_0 + v_1 + v_2) / 3 - direction, n = a x b with
+    a = x_1 - x_0, b = x_2 - x_0, normal = n / |n|, area = |n| / 2, v_n = normal . v_r, force = -1000 area v_n |v_n| normal, times 0.33, times dt,
+    added to each of the triangle's three corners in turn.  Then x_bar = x + dt v' and v_out = (x_bar - x) (1 / dt).  -> (x_bar, v_out, v')."""
+    return _explicit(x, v, dt, forces, False)
+
+
+def explicit_bound(x, v, dt, forces):
+    """-> ((x_bar, v_out, v'), (bound on the device's x_bar, on its v_out, on its v')): a running first-order bound of the device's rounding
+    errors against explicit_reference, from the kernels' operations (EPS = 2^-53 each; nothing measured goes into it):
+      * a constant force, v = fl(v + fl(dt g)): TWO roundings per force on the node, EPS |dt g| + EPS |v|;
+      * the wind, per triangle: a, b one rounding each; every component of a x b two products and a subtraction on them, 4 EPS (|a_p b_q| +
+        |a_q b_p|); |n| its squares, two additions and the root, 3 EPS |n| on top of what n carries; normal = n / |n| one more; v_r two
+        additions, a division and a subtraction, EPS (|v_0| + |v_1| + |v_2| + |v_r|) on top of a third of the three nodes' carried bounds
+        (this is how the serial chain through a node propagates); v_n three products and two additions, 3 EPS sum |normal_j v_r,j|; the
+        coefficient -1000 area v_n |v_n| three products; the force three more (normal, 0.33, dt); and each of the three increments one
+        rounding, EPS |v| -- once per triangle on the node;
+      * x_bar = fl(x + fl(dt v')): TWO more, dt bound(v') + EPS |dt v'| + EPS |x_bar|;
+      * v_out = fl(fl(x_bar - x) fl(1 / dt)): the subtraction, the reciprocal and the product, bound(x_bar) / dt + 3 EPS |v_out| -- the
+        EPS |x_bar| / dt inside the first term dominates everything else.
+    The products of two errors are covered by a factor 1 + 2^-10."""
+    return _explicit(x, v, dt, forces, True)
