@@ -538,6 +538,73 @@ def extreme_matrices(rng, n):
     return np.array(M[:n]).reshape(n, 9)
 
 
+def edge_rows(Dx, rows):
+    """Dx [n][rows] (extreme_matrices cut to a kind's row count) with the rows the closed-form kinds branch on made sure of: all zero
+    (Spring's nrm <= 0), all denormal, around 1e+160 and 1e-160 (the squares of a norm overflow / underflow), one and all entries
+    infinite, one and all NaN -- written over the tail (the generic fill) where missing.  -> (Dx, dict name -> row index of one)."""
+    Dx = np.array(Dx[:, :rows], dtype=np.float64)
+    a = np.abs(Dx)
+    fin = np.isfinite(Dx).all(axis=1)
+    tests = dict(zero=lambda: (Dx == 0).all(axis=1),
+                 denormal=lambda: ((a > 0) & (a < np.finfo(np.float64).tiny)).all(axis=1),
+                 huge=lambda: fin & (a.max(axis=1) > 1e155) & (a.max(axis=1) < 1e165),
+                 tiny=lambda: (a.max(axis=1) < 1e-155) & (a.max(axis=1) > 1e-165),
+                 inf=lambda: np.isinf(Dx).any(axis=1) & ~np.isnan(Dx).any(axis=1),
+                 all_inf=lambda: np.isinf(Dx).all(axis=1),
+                 nan=lambda: np.isnan(Dx).any(axis=1),
+                 all_nan=lambda: np.isnan(Dx).all(axis=1))
+    ramp = 1.0 + 0.25 * np.arange(rows)
+    fill = dict(zero=0.0 * ramp, denormal=3e-310 * ramp, huge=-1.1e160 * ramp, tiny=1.3e-160 * ramp, inf=np.where(np.arange(rows) == 1, np.inf, ramp),
+                all_inf=np.where(np.arange(rows) % 2 == 0, np.inf, -np.inf), nan=np.where(np.arange(rows) == rows - 1, np.nan, ramp), all_nan=np.nan * ramp)
+    where, tail = {}, Dx.shape[0] - 1
+    for name, test in tests.items():
+        hit = np.flatnonzero(test())
+        if hit.size == 0:
+            Dx[tail] = fill[name]; a = np.abs(Dx); fin = np.isfinite(Dx).all(axis=1)
+            hit = np.array([tail]); tail -= 1
+        where[name] = int(hit[0])
+    for name, test in tests.items():      # (a later fill never lands on an earlier find: the tail is generic rows only)
+        assert test()[where[name]], name
+    return Dx, where
+
+
+HYPER_CAPS, HYPER_CAPS_WIDE = (1, 3, 5), (1, 3, 5, 7, 10, 12)
+
+
+def het_params(kind, n, rng, caps=HYPER_CAPS):
+    """[n][KIND_PARAMS[kind]] constructor parameters that differ from element to element, drawn (never sorted: nothing follows the
+    element order): stiffness-like entries log-uniform over 2.5 decades (mu, lambda: four); TET_VOLUME limits in [0.7, 1] / [1, 1.3]; TRI_STRAIN limits in
+    [0.8, 1] / [1, 1.2] and the strain-limiting flag from {0, 1}; TRI_AREA 1..6 iterations; TRI_FUNG mu in [5, 500] with the limits of
+    test_local_step_fung; about 30 % of the ANCHORs with use_weight <= 0 (-1 or 0: the 1000.f default); the hyperelastic kinds'
+    max_iterations from `caps`."""
+    name = {v: k for k, v in KIND.items()}[kind]
+    stiff = lambda lo, hi: 10.0 ** rng.uniform(np.log10(lo), np.log10(hi), size=n)      # noqa: E731
+    if name == "ANCHOR":
+        w = stiff(10.0, 3000.0)
+        off = rng.random(n) < 0.3
+        w[off] = rng.choice([-1.0, 0.0], size=int(off.sum()))
+        cols = [w, np.ones(n)]
+    elif name in ("SPRING", "TET_LINEAR", "BEND", "COLLISION"):
+        cols = [stiff(3.0, 1000.0)]
+    elif name == "TET_VOLUME":
+        cols = [stiff(3.0, 1000.0), rng.uniform(0.7, 1.0, size=n), rng.uniform(1.0, 1.3, size=n)]
+    elif name in ("TET_NH", "TET_STVK"):
+        # four decades, mu and lambda drawn apart: the L-BFGS count grows with lambda / mu and with the stiffness itself (its gradient
+        # tolerance is absolute), and the caps of 10 and 12 only bind on the slow tail (test_batch_parameters.cap_condition)
+        cols = [stiff(1e2, 1e6), stiff(1e2, 1e6), rng.choice(np.asarray(caps, dtype=np.float64), size=n)]
+    elif name == "TRI_STRAIN":
+        cols = [stiff(3.0, 1000.0), rng.uniform(0.8, 1.0, size=n), rng.uniform(1.0, 1.2, size=n), rng.integers(0, 2, size=n).astype(np.float64)]
+    elif name == "TRI_AREA":
+        cols = [stiff(3.0, 1000.0), rng.integers(1, 7, size=n).astype(np.float64), rng.uniform(0.8, 1.0, size=n), rng.uniform(1.0, 1.2, size=n)]
+    elif name == "TRI_FUNG":
+        cols = [stiff(5.0, 500.0), np.full(n, 0.5), np.full(n, 2.0)]
+    else:
+        raise ValueError(name)
+    P = np.ascontiguousarray(np.stack(cols, axis=1))
+    assert P.shape == (n, KIND_PARAMS[kind])
+    return P
+
+
 class SparseReference:
     """An independent, extended-precision solve of the global system A = M + dt^2 D^T W^2 D, assembled as a scipy.sparse matrix from the
     ORACLE's selector D (D_triplets), its weight diagonal and the masses -- not from the library's assembly (apply_A).  splu (SuperLU)

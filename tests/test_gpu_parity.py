@@ -19,7 +19,7 @@ import os
 import numpy as np
 import pytest
 
-from checkers import KIND, KIND_NODES, KIND_ROWS, Oracle, extreme_matrices
+from checkers import KIND, KIND_NODES, KIND_ROWS, Oracle, edge_rows, extreme_matrices
 from conftest import golden
 from test_host_math import hm  # noqa: F401  (fixture: the host build of local_math.hpp + this host's libm)
 from test_oracle_golden import tol
@@ -36,7 +36,7 @@ def rand_tets(rng, n):
     return np.array(xs)
 
 
-def build_disjoint(pkg, name, params, n, seed, shuffle=True):
+def disjoint_layout(name, n, seed, shuffle=True):
     """n elements of one kind on their own nodes (4 nodes each); node ids of an
     element are shuffled so that the corner sorting of the device layout is exercised."""
     kind = KIND[name]
@@ -46,13 +46,26 @@ def build_disjoint(pkg, name, params, n, seed, shuffle=True):
     perm = rng.permutation(4 * n) if shuffle else np.arange(4 * n)
     Xp = np.zeros_like(X); Xp[perm] = X            # node q of the element lives at id perm[q]
     idx = perm.reshape(n, 4)[:, :nn].astype(np.int32)
-    s = pkg.System(device_id=0); s.set_timestep(0.04)
+    return Xp, idx, rng
+
+
+def disjoint_oracle(name, params, Xp, idx):
+    """the oracle of a disjoint_layout; params one row for all elements or one per element"""
     o = Oracle(); o.settings(0.04, 1)
-    m = np.ones(3 * 4 * n)
-    s.add_nodes(Xp.ravel(), m); o.add_nodes(Xp.ravel(), m)
-    s.add_forces(kind, idx, params); o.add_forces(kind, idx, params)
-    s.initialize(); assert o.initialize()
-    return s, o, Xp, idx, rng
+    o.add_nodes(Xp.ravel(), np.ones(Xp.size))
+    o.add_forces(KIND[name], idx, params)
+    assert o.initialize()
+    return o
+
+
+def build_disjoint(pkg, name, params, n, seed, shuffle=True):
+    """the library's system and the oracle of a disjoint_layout"""
+    Xp, idx, rng = disjoint_layout(name, n, seed, shuffle)
+    s = pkg.System(device_id=0); s.set_timestep(0.04)
+    s.add_nodes(Xp.ravel(), np.ones(3 * 4 * n))
+    s.add_forces(KIND[name], idx, params)
+    s.initialize()
+    return s, disjoint_oracle(name, params, Xp, idx), Xp, idx, rng
 
 
 def oracle_local_step(o, xcur, n, rows):
@@ -230,24 +243,39 @@ def test_golden_project_tuples(pkg, name):
 
 
 @pytest.mark.parametrize("name,params", [("TET_LINEAR", [10.0]), ("TET_VOLUME", [100.0, 0.9, 1.1]), ("TET_NH", [100.0, 150.0, 5]), ("TET_STVK", [3e3, 1e3, 9]),
-                                         ("TRI_STRAIN", [100.0, 0.95, 1.05, 1.0]), ("TRI_AREA", [100.0, 4, 0.9, 1.1]), ("TRI_FUNG", [50.0, 0.5, 2.0])])
+                                         ("TRI_STRAIN", [100.0, 0.95, 1.05, 1.0]), ("TRI_AREA", [100.0, 4, 0.9, 1.1]), ("TRI_FUNG", [50.0, 0.5, 2.0]),
+                                         ("SPRING", [50.0]), ("BEND", [20.0]), ("ANCHOR", [-1.0, 1.0]), ("COLLISION", [32.0])])
 def test_svd_and_prox_corner_cases_bit_exact(pkg, name, params):
     """The Jacobi SVD and the proxes on inputs at the edges of the format (checkers.extreme_matrices) fed straight into the kernels
     (admm_hip_local_step_dx): u, z, warm start and iteration counts bit for bit the oracle's -- the round-4 kernels use the
     compiler's sqrt / reciprocal expansions WITHOUT their rescaling and special-case wrappers where the argument's range is
-    known; this is where a wrong range assumption would show."""
+    known; this is where a wrong range assumption would show.  The closed-form kinds (spring: a division by a norm whose squares
+    overflow, and the nrm <= 0 branch; hinge; static anchor; collision with a floor, a sphere and a cylinder in the list) get the same
+    matrices cut to their rows, with a zero, a denormal, a 1e+-160, an infinite and a NaN row made sure of (checkers.edge_rows)."""
     import warnings
     kind = KIND[name]
     n = 256
     rng = np.random.default_rng(77 + kind)
     rows = KIND_ROWS[kind]; nn = KIND_NODES[kind]
     Dx = np.ascontiguousarray(extreme_matrices(rng, n)[:, :rows])      # (triangles: the first two columns, a 3x2 matrix)
+    closed_form = name in ("SPRING", "BEND", "ANCHOR", "COLLISION")
+    if closed_form:
+        Dx, where = edge_rows(Dx, rows)
+        assert sorted(where) == ["all_inf", "all_nan", "denormal", "huge", "inf", "nan", "tiny", "zero"] and len(set(where.values())) == 8
+        assert not Dx[where["zero"]].any() and np.isnan(Dx[where["nan"]]).any() and np.isinf(Dx[where["inf"]]).any()
+        assert 0 < np.abs(Dx[where["denormal"]]).max() < np.finfo(np.float64).tiny
+        with np.errstate(over="ignore", under="ignore"):      # the squares overflow / underflow (below the smallest normal number)
+            assert np.isinf(np.square(Dx[where["huge"]])).any() and (np.square(Dx[where["tiny"]]) < np.finfo(np.float64).tiny).all()
     x_rest = np.array([0.0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1])
     X = np.tile(x_rest.reshape(4, 3), (n, 1)) + np.repeat(np.arange(n), 4)[:, None] * np.array([3.0, 0, 0])
     idx = np.arange(4 * n, dtype=np.int32).reshape(n, 4)[:, :nn]
     s = pkg.System(device_id=0); s.set_timestep(0.04)
     s.add_nodes(X.ravel(), np.ones(3 * 4 * n))
     s.add_forces(kind, idx, params)
+    if name == "COLLISION":      # the origin lies inside the sphere: the zero, denormal and 1e-160 rows take its branch; the cylinder's axis is off it
+        shapes = ([pkg.SHAPE["FLOOR"], pkg.SHAPE["SPHERE"], pkg.SHAPE["CYLINDER"]], [[0.0, -1.0, 0.0, 0.0], [0.5, 0.5, 0.5, 1.0], [3.0, 0.25, 0.0, 0.7]])
+        s.set_collision_shapes(*shapes)
+        Oracle().set_collision_shapes(*shapes)      # (the oracle's shape list is one per process: project_single below reads it)
     s.initialize()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
