@@ -476,7 +476,7 @@ class System:
         self.n_nodes = 0
         self._cb = None
         if stream is not None:
-            self._chk(self.L.admm_hip_set_stream(self.h, C.c_void_p(stream)))
+            self.set_stream(stream)
 
     def __del__(self):
         try:
@@ -489,6 +489,11 @@ class System:
     def _chk(self, rc):
         if rc != 0:
             raise AdmmHipError("admm_hip error %d: %s" % (rc, self.L.admm_hip_last_error(self.h).decode()))
+
+    def set_stream(self, stream):
+        """run on the caller's hipStream_t from now on (admm_hip_set_stream; e.g. torch.cuda.current_stream().cuda_stream), None: on a
+        stream of the library's own again.  The caller keeps its stream: the library never destroys it."""
+        self._chk(self.L.admm_hip_set_stream(self.h, C.c_void_p(stream) if stream else None))
 
     # ---- setup (System.hpp:36-63) ----
     def set_timestep(self, dt):

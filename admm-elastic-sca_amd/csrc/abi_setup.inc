@@ -91,7 +91,10 @@ const char *admm_hip_last_error(const admm_hip_ctx *ctx) { return ctx ? ctx->err
 
 int admm_hip_set_stream(admm_hip_ctx *ctx, void *s) {
     if (!ctx || ctx->device_id < 0) return ADMM_ERR_ARG;
-    if (ctx->own_stream && ctx->stream) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamDestroy(ctx->stream); }
+    // the outgoing stream's work is finished first, a caller's stream too: nothing orders the next stream behind it (two non-blocking
+    // streams, or a non-blocking and a blocking one, run side by side), and the frames queued there write what the next frame reads
+    if (ctx->stream) { HIPCHK(hipSetDevice(ctx->device_id)); (void)hipStreamSynchronize(ctx->stream); }
+    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     ctx->own_stream = false;
     ctx->stream = (hipStream_t)s;
     if (!s) { HIPCHK(hipStreamCreate(&ctx->stream)); ctx->own_stream = true; }

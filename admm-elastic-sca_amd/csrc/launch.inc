@@ -496,7 +496,7 @@ int ensure_residual_buffers(admm_hip_ctx *ctx, int iters) {
             if (b.res_fused) {      // the tet kernels produce their residuals themselves: no snapshots, one partial per 64-tet block
                 const int nblk = std::max(batch_blocks(b), 1);
                 TRY(dalloc(ctx, &b.d_res_partial, (size_t)nblk));
-                HIPCHK(hipMemset(b.d_res_partial, 0, sizeof(double) * (size_t)nblk));
+                HIPCHK(hipMemsetAsync(b.d_res_partial, 0, sizeof(double) * (size_t)nblk, ctx->stream));      // (stream-ordered: on a caller's non-blocking stream the default stream orders nothing)
             } else { TRY(dalloc(ctx, &b.d_u_prev, (size_t)rows * nl)); TRY(dalloc(ctx, &b.d_z_prev, (size_t)rows * nl)); }
             TRY(upload(ctx, &b.d_G, b.G));
             slots += (int64_t)b.n_local * ADMM_KIND_NODES[b.kind]; maxn = std::max(maxn, b.n_local);
@@ -507,7 +507,7 @@ int ensure_residual_buffers(admm_hip_ctx *ctx, int iters) {
         }
         slots = std::max<int64_t>(slots, ctx->n_fslots);      // same layout as the RHS slots
         TRY(dalloc(ctx, &ctx->d_res_slots, 3 * (size_t)std::max<int64_t>(slots, 1)));
-        HIPCHK(hipMemset(ctx->d_res_slots, 0, sizeof(double) * 3 * (size_t)std::max<int64_t>(slots, 1)));
+        HIPCHK(hipMemsetAsync(ctx->d_res_slots, 0, sizeof(double) * 3 * (size_t)std::max<int64_t>(slots, 1), ctx->stream));
         TRY(dalloc(ctx, &ctx->d_res_s, 3 * (size_t)ctx->n_nodes));
         ctx->res_partial_n = std::max((maxn + admm_dev::RES_BLOCK - 1) / admm_dev::RES_BLOCK, (3 * ctx->n_nodes + admm_dev::RES_BLOCK - 1) / admm_dev::RES_BLOCK);
         TRY(dalloc(ctx, &ctx->d_res_partial, (size_t)std::max(ctx->res_partial_n, 1)));

@@ -44,7 +44,9 @@ enum admm_hip_err {
 int  admm_hip_create(admm_hip_ctx **out, int device_id);
 void admm_hip_destroy(admm_hip_ctx *ctx);
 const char *admm_hip_last_error(const admm_hip_ctx *ctx);
-/* run on an existing hipStream_t (e.g. torch's current stream); NULL = own stream */
+/* run on an existing hipStream_t (e.g. torch's current stream); NULL = own stream.  Waits for the work already queued on the
+ * stream it leaves (the library's or the caller's); a caller's stream is never destroyed.  Results on a caller's non-blocking
+ * stream are bitwise those on the library's own: no call relies on the legacy default stream for ordering. */
 int  admm_hip_set_stream(admm_hip_ctx *ctx, void *hip_stream);
 
 /* ---- settings -------------------------------------------------------------

@@ -1120,3 +1120,198 @@ def explicit_bound(x, v, dt, forces):
         EPS |x_bar| / dt inside the first term dominates everything else.
     The products of two errors are covered by a factor 1 + 2^-10."""
     return _explicit(x, v, dt, forces, True)
+
+
+# ---- a caller's non-blocking stream with skewed queues (tests/test_caller_stream.py) ------------------------------------------------
+HIP_STREAM_NON_BLOCKING = 0x01
+
+
+def hip_runtime():
+    """The HIP runtime this process already has loaded (torch's copy, which libadmm_hip.so binds to as well), as a ctypes handle: the
+    path comes from the process's own mappings, and opening a path that is already mapped returns the loaded image -- no second runtime."""
+    import torch
+    torch.cuda.init()
+    with open("/proc/self/maps") as f:
+        paths = sorted({line.split()[-1] for line in f if "libamdhip64" in line and "r-xp" in line})
+    assert len(paths) == 1, "expected exactly one HIP runtime in this process: %r" % (paths,)
+    rt = C.CDLL(paths[0])
+    rt.hipStreamGetFlags.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
+    rt.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+    return rt
+
+
+def stream_flags(stream):
+    """hipStreamGetFlags of a torch stream"""
+    fl = C.c_uint(0xFFFF)
+    rc = hip_runtime().hipStreamGetFlags(C.c_void_p(stream.cuda_stream), C.byref(fl))
+    assert rc == 0, "hipStreamGetFlags failed (%d)" % rc
+    return fl.value
+
+
+def nonblocking_stream():
+    """-> (a torch stream that has no implicit ordering with the legacy default stream, its flags as read back).  torch's pool
+    streams are created non-blocking; should a build hand out a blocking one, a stream is created with hipStreamNonBlocking through
+    the same runtime and wrapped (it lives as long as the process: the tests' streams are module fixtures)."""
+    import torch
+    st = torch.cuda.Stream()
+    if not stream_flags(st) & HIP_STREAM_NON_BLOCKING:
+        h = C.c_void_p()
+        rc = hip_runtime().hipStreamCreateWithFlags(C.byref(h), HIP_STREAM_NON_BLOCKING)
+        assert rc == 0 and h.value, "hipStreamCreateWithFlags failed (%d)" % rc
+        st = torch.cuda.ExternalStream(h.value)
+    fl = stream_flags(st)
+    assert st.cuda_stream != 0 and fl & HIP_STREAM_NON_BLOCKING, (st.cuda_stream, fl)
+    return st, fl
+
+
+class Delay:
+    """A kernel that keeps a queue busy for 5 to 20 ms: torch.cuda._sleep, or a fixed stack of matrix products should that not land in
+    the window; its length is calibrated once with events (aim: 8 ms) and measured again -- .ms is that last measurement."""
+    LO_MS, HI_MS, AIM_MS = 5.0, 20.0, 8.0
+
+    def __init__(self):
+        import torch
+        self.torch = torch
+        self.a = None
+        for kind in ("sleep", "matmul"):
+            self.kind = kind
+            if kind == "matmul":
+                self.a = torch.randn(1024, 1024, device="cuda")
+            self.n = 2_000_000 if kind == "sleep" else 8
+            self._measure(); first = self._measure()                 # (the first launch pays for loading the kernel)
+            self.ms = first
+            for _ in range(3):                                        # (a second and third scaling only if a measurement was disturbed)
+                self.n = max(1, int(round(self.n * self.AIM_MS / max(self.ms, 1e-3))))
+                self.ms = self._measure()
+                if self.LO_MS + 1.0 <= self.ms <= self.HI_MS - 5.0:
+                    break
+            if self.LO_MS <= self.ms <= self.HI_MS:
+                break
+        assert self.LO_MS <= self.ms <= self.HI_MS, "no delay kernel between %g and %g ms (%s: %.2f ms)" % (self.LO_MS, self.HI_MS, self.kind, self.ms)
+
+    def _measure(self):
+        t = self.torch
+        st = t.cuda.current_stream()
+        e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+        t.cuda.synchronize()
+        e0.record(st); self(st); e1.record(st)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def __call__(self, stream):
+        t = self.torch
+        with t.cuda.stream(stream):
+            if self.kind == "sleep":
+                t.cuda._sleep(self.n)
+            else:
+                b = self.a
+                for _ in range(self.n):
+                    b = b @ self.a * (1.0 / 32.0)
+
+
+class Skew:
+    """Keeps one queue busy in front of every library call.  mode None: nothing; "A": the delay goes on the caller's stream (the call's
+    own work queues behind it: a host read, overwrite or free that does not wait for the context's stream sees the state before the
+    call); "B": on the legacy default stream (work the library leaves there runs late, unordered against the context's stream).
+    Armed after set-up.  before() asserts that the delay is still running when the call begins and counts the call."""
+
+    def __init__(self, mode, stream, delay):
+        import torch
+        assert mode in (None, "A", "B")
+        self.torch, self.mode, self.delay, self.armed, self.calls = torch, mode, delay, False, 0
+        self.queue = None if mode is None else (stream if mode == "A" else torch.cuda.default_stream())
+
+    def arm(self):
+        self.armed = True
+
+    def before(self, name=""):
+        if self.mode is None or not self.armed:
+            return
+        self.delay(self.queue)
+        ev = self.torch.cuda.Event()
+        ev.record(self.queue)
+        assert not ev.query(), "skew %s: call %d (%s) began on an idle queue" % (self.mode, self.calls, name)
+        self.calls += 1
+
+
+class Skewed:
+    """A System whose calls that reach the device are each preceded by skew.before(); attributes and host-only calls pass through."""
+    HOST_ONLY = frozenset(("graph_state", "info", "collision_form", "read_rest", "local_elements", "local_range", "apply_A", "n_collision_shapes",
+                           "node_owner", "node_supernode"))
+
+    def __init__(self, system, skew):
+        object.__setattr__(self, "raw", system)
+        object.__setattr__(self, "skew", skew)
+
+    def __getattr__(self, name):
+        s, skew = self.raw, self.skew
+        if isinstance(getattr(type(s), name, None), property):
+            skew.before(name)
+            return getattr(s, name)
+        v = getattr(s, name)
+        if not callable(v) or name in self.HOST_ONLY:
+            return v
+
+        def call(*a, **k):
+            skew.before(name)
+            return v(*a, **k)
+        return call
+
+    def __setattr__(self, name, val):
+        if isinstance(getattr(type(self.raw), name, None), property):
+            self.skew.before(name + " =")
+        setattr(self.raw, name, val)
+
+
+def same_bits(a, b):
+    """np.array_equal through lists, tuples and dicts (NaNs equal: a NaN is a value here); anything else by =="""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(same_bits(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return isinstance(b, (list, tuple)) and len(a) == len(b) and all(same_bits(p, q) for p, q in zip(a, b))
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        a, b = np.asarray(a), np.asarray(b)
+        return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
+    return a == b
+
+
+def stream_ordered_allreduce_hooks(world):
+    """all-reduce between `world` contexts in ONE process on ONE GPU that never synchronises the device: every rank records a "ready"
+    event on the stream it is handed; rank 0's stream waits for all of them, sums (rank order, like the synchronising test hooks) and
+    writes every rank's buffer, then records "done", which the other ranks' streams wait for.  The host threads meet at two barriers.
+    -> (hooks, calls: how often every rank's hook has run)"""
+    import threading
+    import torch
+    bar = threading.Barrier(world)
+    bufs, ready, done, calls = {}, {}, {}, [0] * world
+
+    class _Ptr:
+        def __init__(self, ptr, count):
+            self.__cuda_array_interface__ = {"shape": (count,), "typestr": "<f8", "data": (ptr, False), "version": 2}
+
+    def make_hook(r):
+        def hook(ptr, count, stream):
+            assert stream, "the hook was handed the legacy default stream"
+            st = torch.cuda.ExternalStream(stream)
+            bufs[r] = torch.as_tensor(_Ptr(ptr, count), device="cuda:0")
+            ready[r] = torch.cuda.Event()
+            ready[r].record(st)
+            bar.wait(timeout=120)
+            if r == 0:
+                for q in range(world):
+                    st.wait_event(ready[q])
+                with torch.cuda.stream(st):
+                    tot = bufs[0].clone()
+                    for q in range(1, world):
+                        tot += bufs[q]
+                    for q in range(world):
+                        bufs[q].copy_(tot)
+                done[0] = torch.cuda.Event()
+                done[0].record(st)
+            bar.wait(timeout=120)
+            if r != 0:
+                st.wait_event(done[0])
+            calls[r] += 1
+            return 0
+        return hook
+    return [make_hook(r) for r in range(world)], calls
