@@ -609,7 +609,10 @@ class SparseReference:
     """An independent, extended-precision solve of the global system A = M + dt^2 D^T W^2 D, assembled as a scipy.sparse matrix from the
     ORACLE's selector D (D_triplets), its weight diagonal and the masses -- not from the library's assembly (apply_A).  splu (SuperLU)
     factors it once; every solution is refined with residuals evaluated in np.longdouble until the correction is below 1e-16 of the
-    solution.  kappa1 estimates the 1-norm condition number: onenormest of A times onenormest of A^-1 applied through the LU.
+    solution (solve), or below the floor that the longdouble residual itself sets on an ill-conditioned system (solve_ill).  kappa1
+    estimates the 1-norm condition number: onenormest of A times onenormest of A^-1 applied through the LU; kappa1_eq (lazy) is the
+    same estimate for the equilibrated matrix D^-1/2 A D^-1/2, D = diag(A) -- what is left of kappa1 once bad scaling, which
+    Cholesky does not feel, is taken out.
 
     with_weights(w) rebuilds the reference for new per-force weights (System::recompute_weights with edited Force::weight members): the
     rows of force i are [global_idx_i, global_idx_i + rows of its kind) of W, the layout the constructor checks against the oracle's W."""
@@ -675,7 +678,7 @@ class SparseReference:
 
     def with_weights(self, w):
         ref = SparseReference.__new__(SparseReference)
-        ref.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("A", "norm_inf", "_Al", "lu", "kappa1")})
+        ref.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("A", "norm_inf", "_Al", "lu", "kappa1", "_kappa1_eq")})
         ref._factor(ref._wdiag(np.asarray(w, dtype=np.float64)))
         return ref
 
@@ -689,19 +692,48 @@ class SparseReference:
         """normwise backward error |b - A x|_inf / (|A|_inf |x|_inf + |b|_inf), the residual in longdouble"""
         return float(np.abs(self.residual(x, b)).max()) / (self.norm_inf * float(np.abs(x).max()) + float(np.abs(b).max()))
 
-    def solve(self, b, max_steps=10):
-        """-> (x_ref, the longdouble residual of x_ref, the refinement steps taken)"""
+    @property
+    def kappa1_eq(self):
+        """kappa1 of D^-1/2 A D^-1/2, D = diag(A): the same onenormest pair, the inverse applied as D^1/2 A^-1 D^1/2 through the LU"""
+        if getattr(self, "_kappa1_eq", None) is None:
+            import scipy.sparse as sp
+            import scipy.sparse.linalg as sla
+            d = np.sqrt(self.A.diagonal())
+            S = sp.diags(1.0 / d)
+            inv = sla.LinearOperator(self.A.shape, matvec=lambda v: d * self.lu.solve(d * np.ravel(v)), rmatvec=lambda v: d * self.lu.solve(d * np.ravel(v)), dtype=np.float64)
+            self._kappa1_eq = float(sla.onenormest((S @ self.A @ S).tocsr()) * sla.onenormest(inv))
+        return self._kappa1_eq
+
+    def _refine(self, b, max_steps, floor):
+        """iterative refinement, x carried in longdouble: stops when the correction is <= max(1e-16, floor) |x|_inf, or -- with a floor --
+        when two successive corrections lie within a factor 2 (it has stopped shrinking).  -> (x, steps, last correction / |x|_inf)"""
         x = self.lu.solve(np.asarray(b, dtype=np.float64)).astype(np.longdouble)
+        prev = np.inf
         for step in range(1, max_steps + 1):
             r = self.residual(x, b)
             dx = self.lu.solve(r.astype(np.float64))
             x = x + dx
-            if np.abs(dx).max() <= 1e-16 * float(np.abs(x).max()):
-                break
-        else:
-            raise AssertionError("iterative refinement did not converge in %d steps" % max_steps)
+            corr = float(np.abs(dx).max()) / float(np.abs(x).max())
+            if corr <= max(1e-16, floor) or (floor > 0.0 and corr >= 0.5 * prev):
+                return x, step, corr
+            prev = corr
+        raise AssertionError("iterative refinement did not converge in %d steps (last correction %.3g |x|)" % (max_steps, corr))
+
+    def solve(self, b, max_steps=10):
+        """-> (x_ref, the longdouble residual of x_ref, the refinement steps taken); the correction falls below 1e-16 |x| (two steps on
+        the well-conditioned systems this is for; solve_ill beyond kappa1 ~ 1e5)"""
+        x, step, _ = self._refine(b, max_steps, 0.0)
         xr = x.astype(np.float64)
         return xr, self.residual(xr, b), step
+
+    def solve_ill(self, b, max_steps=40):
+        """solve for an ill-conditioned system -> (x_ref, its longdouble residual, steps, the last correction relative to |x|_inf).  The
+        residual is evaluated in longdouble (eps 2^-64), so a correction cannot fall below about 2^-64 kappa1 |x|: refinement stops
+        at max(1e-16, 8 * 2^-64 * kappa1) |x|, or when the correction has stopped shrinking.  The last correction bounds what is
+        left of the error, up to the contraction factor (~ 2^-53 kappa1 << 1) of one more step."""
+        x, step, corr = self._refine(b, max_steps, 8.0 * 2.0 ** -64 * self.kappa1)
+        xr = x.astype(np.float64)
+        return xr, self.residual(xr, b), step, corr
 
 
 def selector_rows(oracle, f0, f1, rng=None, split=0.0):
