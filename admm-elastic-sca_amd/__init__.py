@@ -60,6 +60,13 @@ class Timing(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class EnergyTotals(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("kinetic", "gravity", "elastic", "anchor")] + [(n, C.c_int64) for n in ("n_infinite", "batches_skipped")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class AdmmHipError(RuntimeError):
     pass
 
@@ -100,6 +107,13 @@ def lib():
         L.admm_hip_enable_residuals.argtypes = [C.c_void_p, C.c_int]
         L.admm_hip_set_tolerance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int]
         L.admm_hip_get_residuals.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
+        L.admm_hip_energy.argtypes = [C.c_void_p, C.POINTER(EnergyTotals)]
+        L.admm_hip_batch_energy.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]
+        L.admm_hip_batch_energy_dx.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        L.admm_hip_read_energy_scale.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.admm_hip_energy_query.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _dp, _dp]
+        L.admm_hip_enable_objective.argtypes = [C.c_void_p, C.c_int]
+        L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
         L.admm_hip_add_nodes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
         L.admm_hip_add_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, C.POINTER(C.c_int)]
@@ -443,6 +457,26 @@ def friction_query_moving(p, p_out, x0, w, mu):
     return res, mode
 
 
+def energy_query(kind, dx, params, rest, scale):
+    """the elements' energies on the host (admm_hip_energy_query; csrc/energy.hpp, the device's bits; needs no GPU): dx [n][rows] = D_i x,
+    params [n][KIND_PARAMS] (or one row for all), rest [n][12] as read_rest lays it out (or None: zeros), scale [n] (or a scalar)
+    -> energy [n]; +inf where the kind's energy is infinite"""
+    kind = KIND[kind] if isinstance(kind, str) else int(kind)
+    if not 0 <= kind < len(KIND_ROWS):
+        rc = lib().admm_hip_energy_query(kind, 0, None, None, None, None, None)
+        raise AdmmHipError("admm_hip_energy_query error %d" % rc)
+    dx = np.ascontiguousarray(dx, dtype=np.float64).reshape(-1, KIND_ROWS[kind])
+    n = dx.shape[0]
+    par = np.ascontiguousarray(np.broadcast_to(np.asarray(params, dtype=np.float64).reshape(-1, KIND_PARAMS[kind]), (n, KIND_PARAMS[kind])))
+    rs = np.zeros((n, 12)) if rest is None else np.ascontiguousarray(np.broadcast_to(np.asarray(rest, dtype=np.float64).reshape(-1, 12), (n, 12)))
+    sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (n,)))
+    out = np.zeros(n)
+    rc = lib().admm_hip_energy_query(kind, n, _d(dx), _d(par), _d(rs), _d(sc), _d(out))
+    if rc:
+        raise AdmmHipError("admm_hip_energy_query error %d" % rc)
+    return out
+
+
 def mesh_velocity_query(verts, tris, pts, vel, t=(0.0, 0.0, 0.0)):
     """the vertex field vel [nv][3] of the closed mesh (verts, tris; a Mesh for verts: tris ignored) translated by t, interpolated at the
     closest point to each of pts (admm_hip_mesh_velocity_query) -> (out [n][3], weights [n][3], corner_ids [n][3]): the barycentric
@@ -766,6 +800,42 @@ class System:
         self._chk(self.L.admm_hip_get_residuals(self.h, _d(r), _d(s), capacity, C.byref(n)))
         k = min(n.value, capacity)
         return r[:k], s[:k], n.value
+
+    # ---- energies and the per-iteration objective (extension; include/admm_hip.h) ----
+    def energy(self):
+        """-> dict(kinetic, gravity, elastic, anchor, n_infinite, batches_skipped) of the state as it stands"""
+        t = EnergyTotals()
+        self._chk(self.L.admm_hip_energy(self.h, C.byref(t)))
+        return t.as_dict()
+
+    def batch_energy(self, batch):
+        """-> (total, per_elem [n_local] in read_local's order, n_infinite) of one batch"""
+        n = self.local_elements(batch).size
+        tot = C.c_double(0.0); ninf = C.c_int64(0); per = np.zeros(n)
+        self._chk(self.L.admm_hip_batch_energy(self.h, batch, C.byref(tot), _d(per), C.byref(ninf)))
+        return tot.value, per, ninf.value
+
+    def batch_energy_dx(self, batch, dx, out=None):
+        """the batch's energy kernel on caller-supplied rows dx [n_local][rows] -> per_elem (written into `out` when given)"""
+        dx = np.ascontiguousarray(dx, dtype=np.float64)
+        per = np.zeros(self.local_elements(batch).size) if out is None else out
+        self._chk(self.L.admm_hip_batch_energy_dx(self.h, batch, _d(dx), _d(per)))
+        return per
+
+    def energy_scale(self, batch):
+        s = np.zeros(self.local_elements(batch).size)
+        self._chk(self.L.admm_hip_read_energy_scale(self.h, batch, _d(s)))
+        return s
+
+    def enable_objective(self, on=True):
+        self._chk(self.L.admm_hip_enable_objective(self.h, 1 if on else 0))
+
+    def objective(self, capacity=256):
+        """-> (inertia, elastic, n_iters) of the last step's ADMM iterations; the objective is inertia + elastic"""
+        a = np.zeros(capacity); e = np.zeros(capacity); n = C.c_int(0)
+        self._chk(self.L.admm_hip_get_objective(self.h, _d(a), _d(e), capacity, C.byref(n)))
+        k = min(n.value, capacity)
+        return a[:k], e[:k], n.value
 
     def set_allreduce(self, pyfunc):
         """pyfunc(dev_ptr:int, count:int, stream:int) -> 0 on success."""

@@ -114,6 +114,11 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     const bool track = ctx->res_on || ctx->tol_r > 0.0;
     if (track) TRY(ensure_residual_buffers(ctx, admm_iters));
     ctx->keep_z = ctx->keep_z_user || track;
+    // the per-iteration objective (admm_hip_enable_objective): its buffers exist before the loop, which then runs eagerly like a tracked one
+    const bool objective = ctx->obj_on;
+    if (objective && ctx->world > 1) return fail(ctx, ADMM_ERR_UNSUPPORTED, "the per-iteration objective is not available in a sharded context (world = %d)", ctx->world);
+    if (objective) TRY(ensure_energy_buffers(ctx, admm_iters));
+    ctx->obj_n = 0;
     if (ctx->n_gen_rows) {      // user-defined forces: curr_z = D * m_x before the loop (System.cpp:43)
         TRY(generic_begin(ctx, ctx->d_x));
         HIPCHK(hipEventSynchronize(ctx->gen_ev));
@@ -122,7 +127,7 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     // world > 1: the iteration contains an all-reduce.  A host hook cannot be captured; ncclAllReduce can (RCCL collectives are
     // stream-ordered device work), so with the communicator inside the library the multi-GPU iteration is one graph launch too.
     const bool comm_capturable = ctx->world == 1 || (ctx->rccl_comm != nullptr && ctx->graph_comm);
-    const bool use_graph = ctx->graph_enabled && (ctx->graph_forced || ctx->n_nodes < 100000) && comm_capturable && !(ctx->timing && ctx->timing_stride <= 1) && !track && admm_iters > 0 && !ctx->n_gen_rows;
+    const bool use_graph = ctx->graph_enabled && (ctx->graph_forced || ctx->n_nodes < 100000) && comm_capturable && !(ctx->timing && ctx->timing_stride <= 1) && !track && !objective && admm_iters > 0 && !ctx->n_gen_rows;
     if (use_graph && !ctx->iter_exec) {   // capture one iteration; every kernel argument is a fixed device address
         // a stream that cannot be captured (caller-supplied, already capturing ...) is not an error: launch eagerly instead
         const hipError_t be = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
@@ -199,6 +204,7 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
         }
         TRY(launch_solve(ctx, mid, ex0, ex1, ex2, ex3));
         TRY(mark(ctx, timed));
+        if (objective) { TRY(launch_objective(ctx, it)); ctx->obj_n = it + 1; }      // inertia(x_k), elastic(x_k) of the x the global step just left
         iters_done = it + 1;
         if (ctx->tol_r > 0.0 && (it + 1) % ctx->check_every == 0 && it + 1 < admm_iters) {   // convergence test: one round trip
             double rs[2];

@@ -23,6 +23,7 @@
 #include "factor_dev.hpp"
 #include "kernels_local.hpp"
 #include "kernels_mesh.hpp"
+#include "kernels_energy.hpp"
 
 extern "C" int omp_get_max_threads(void);
 
@@ -68,6 +69,7 @@ void free_device(admm_hip_ctx *ctx) {
 extern "C" {
 
 #include "abi_setup.inc"
+#include "abi_energy.inc"
 #include "abi_step.inc"
 #include "abi_parity.inc"
 

@@ -54,6 +54,9 @@ struct Batch {
     int tpb = 64;      // tets per one-wave block (admm_hip_ctx::tet_tpb): 64, or fewer in under-filled launches -- the lanes beyond stay idle
     unsigned int *d_pos4 = nullptr; int *d_bn_ptr = nullptr, *d_bn_dst = nullptr; unsigned short *d_bn_end = nullptr;
     double *d_res_partial = nullptr; bool res_fused = false;           // tets: residuals come out of the projection kernel itself (one |r|^2 partial per 64-tet block)
+    // energies (kernels_energy.hpp): the elements' scale s, uploaded at finalize; the per-element values, one partial and one count of
+    // non-finite elements per 64-element block, allocated by the first call that evaluates an energy (abi_energy.inc)
+    double *d_escale = nullptr, *d_eE = nullptr, *d_epart = nullptr; int *d_ecnt = nullptr;
     std::vector<double> G;                // [12][n_local] selector block per element, corners in device order
     // ---- ADMM_KIND_GENERIC (user-defined forces): selector rows as CSR over the batch's rows
     std::vector<int64_t> g_elem_row;      // [n_total + 1] first batch row of every element
@@ -257,6 +260,12 @@ struct admm_hip_ctx {
     double tol_r = 0.0, tol_s = 0.0; int check_every = 1;
     double *d_res = nullptr; int res_cap = 0, res_n = 0;      // [2 * res_cap]: r^2, s^2 per iteration
     double *d_res_slots = nullptr, *d_res_s = nullptr, *d_res_partial = nullptr; int res_partial_n = 0;
+    // energies and the per-iteration objective (abi_energy.inc; off by default, every buffer created on first use).  d_en_out: { kinetic,
+    // gravity, inertia, one total per batch }, d_en_cnt: one count of non-finite elements per batch; d_en_npart: the node terms' partials
+    // (kinetic / inertia first, then the constant explicit forces' in list order).  d_obj [obj_cap][1 + batches]: per ADMM iteration of
+    // the last step, inertia(x_k) and every batch's total at x_k
+    bool en_ready = false; double *d_en_out = nullptr, *d_en_npart = nullptr; long long *d_en_cnt = nullptr;
+    bool obj_on = false; int obj_cap = 0, obj_n = 0; double *d_obj = nullptr;
 
     // user-defined forces: host round trip per ADMM iteration (see admm_hip_add_generic_batch)
     admm_hip_project_fn project_hook = nullptr; void *project_user = nullptr;

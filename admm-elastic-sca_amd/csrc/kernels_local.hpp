@@ -111,8 +111,8 @@ __device__ __forceinline__ void st_stream(double *p, double v) {
 // Tets: KIND 0 = Neo-Hookean, 1 = StVK (HyperElasticTet, TetForce.cpp:320-364),
 //       2 = LinearTetStrain (:127-153), 3 = TetVolume (:173-210)
 // ---------------------------------------------------------------------------
-// the lane's inputs: B (stored corner order), Dx = D_i x, u
-__device__ __forceinline__ void tet_load(const BatchDev &b, const double *__restrict__ x, int e, int n, double (&B)[12], Mat3 &Dx, Mat3 &u) {
+// the lane's inputs: B (stored corner order) and Dx = D_i x (tet_load_dx: also what the energy kernels evaluate, kernels_energy.hpp), u
+__device__ __forceinline__ void tet_load_dx(const BatchDev &b, const double *__restrict__ x, int e, int n, double (&B)[12], Mat3 &Dx) {
     const int4 id = reinterpret_cast<const int4 *>(b.idx)[e];
     const double *x0 = x + 3 * (size_t)id.x, *x1 = x + 3 * (size_t)id.y, *x2 = x + 3 * (size_t)id.z, *x3 = x + 3 * (size_t)id.w;
     const double p0x = x0[0], p0y = x0[1], p0z = x0[2];
@@ -133,6 +133,9 @@ __device__ __forceinline__ void tet_load(const BatchDev &b, const double *__rest
         Dx.m01 = o[(size_t)3 * n + e]; Dx.m11 = o[(size_t)4 * n + e]; Dx.m21 = o[(size_t)5 * n + e];
         Dx.m02 = o[(size_t)6 * n + e]; Dx.m12 = o[(size_t)7 * n + e]; Dx.m22 = o[(size_t)8 * n + e];
     }
+}
+__device__ __forceinline__ void tet_load(const BatchDev &b, const double *__restrict__ x, int e, int n, double (&B)[12], Mat3 &Dx, Mat3 &u) {
+    tet_load_dx(b, x, e, n, B, Dx);
     u.m00 = ld_stream(&b.u[(size_t)0 * n + e]); u.m10 = ld_stream(&b.u[(size_t)1 * n + e]); u.m20 = ld_stream(&b.u[(size_t)2 * n + e]);
     u.m01 = ld_stream(&b.u[(size_t)3 * n + e]); u.m11 = ld_stream(&b.u[(size_t)4 * n + e]); u.m21 = ld_stream(&b.u[(size_t)5 * n + e]);
     u.m02 = ld_stream(&b.u[(size_t)6 * n + e]); u.m12 = ld_stream(&b.u[(size_t)7 * n + e]); u.m22 = ld_stream(&b.u[(size_t)8 * n + e]);

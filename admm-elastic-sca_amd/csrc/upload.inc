@@ -305,6 +305,20 @@ int upload_factor(admm_hip_ctx *ctx) {
     return ADMM_OK;
 }
 
+// the scale s of an element's energy (energy.hpp): the rest measure of the hyperelastic kinds, stiffness * measure of the blended tets
+// and triangles (the local step's kblend), the stiffness of springs and hinges, weight^2 of an anchor (the anchor kernel reads the live
+// weight^2 instead, which admm_hip_recompute_weights refreshes); 0 for what is not evaluated
+double energy_scale(const Batch &b, int e) {
+    const int np = b.kind < ADMM_KIND_COUNT ? ADMM_KIND_PARAMS[b.kind] : 0;
+    switch (b.kind) {
+    case ADMM_KIND_TET_NH: case ADMM_KIND_TET_STVK: case ADMM_KIND_TRI_FUNG: return b.measure[e];
+    case ADMM_KIND_TET_LINEAR: case ADMM_KIND_TET_VOLUME: case ADMM_KIND_TRI_STRAIN: case ADMM_KIND_TRI_AREA: return b.params[(size_t)e * np] * b.measure[e];
+    case ADMM_KIND_SPRING: case ADMM_KIND_BEND: return b.params[(size_t)e * np];
+    case ADMM_KIND_ANCHOR: return b.weight[e] * b.weight[e];
+    }
+    return 0.0;
+}
+
 int upload_all(admm_hip_ctx *ctx) {
     const double t0 = now_s();
     const int n = ctx->n_nodes;
@@ -433,7 +447,7 @@ int upload_all(admm_hip_ctx *ctx) {
         const int nl = b.n_local;
         std::vector<int> idx((size_t)std::max(nl, 1) * ist, 0), dst((size_t)std::max(nl, 1) * ist, 0);
         b.G.assign((size_t)12 * std::max(nl, 1), 0.0);
-        std::vector<double> rest((size_t)12 * std::max(nl, 1), 0.0), par((size_t)std::max(np, 1) * std::max(nl, 1), 0.0), w2h2(std::max(nl, 1)), kbl(std::max(nl, 1)), w2(std::max(nl, 1));
+        std::vector<double> rest((size_t)12 * std::max(nl, 1), 0.0), par((size_t)std::max(np, 1) * std::max(nl, 1), 0.0), w2h2(std::max(nl, 1)), kbl(std::max(nl, 1)), w2(std::max(nl, 1)), esc(std::max(nl, 1));
         // prered: per block, the corners sorted by (node, lane, corner) -> pos4 (where a corner's share goes in the block's LDS
         // staging, one byte per corner), and per distinct node an entry (slot, end of its run in the staging)
         std::vector<unsigned int> pos4(b.prered ? (size_t)std::max(nl, 1) : 0, 0u);
@@ -485,11 +499,13 @@ int upload_all(admm_hip_ctx *ctx) {
             w2[el] = w * w;
             w2h2[el] = (ctx->dt * ctx->dt) * (w * w);
             kbl[el] = b.params[(size_t)e * np] * b.measure[e];
+            esc[el] = energy_scale(b, e);
         }
         b.d_pos4 = nullptr; b.d_bn_ptr = nullptr; b.d_bn_dst = nullptr; b.d_bn_end = nullptr;
         if (b.prered) { TRY(upload(ctx, &b.d_pos4, pos4)); TRY(upload(ctx, &b.d_bn_ptr, bn_ptr)); TRY(upload(ctx, &b.d_bn_dst, bn_dst)); TRY(upload(ctx, &b.d_bn_end, bn_end)); }
         TRY(upload(ctx, &b.d_idx, idx)); TRY(upload(ctx, &b.d_dst, dst)); TRY(upload(ctx, &b.d_rest, rest)); TRY(upload(ctx, &b.d_par, par));
         TRY(upload(ctx, &b.d_w2h2, w2h2)); TRY(upload(ctx, &b.d_kblend, kbl)); TRY(upload(ctx, &b.d_w2, w2));
+        TRY(upload(ctx, &b.d_escale, esc));
         TRY(dalloc(ctx, &b.d_u, (size_t)rows * std::max(nl, 1))); TRY(dalloc(ctx, &b.d_z, (size_t)rows * std::max(nl, 1)));
         HIPCHK(hipMemset(b.d_u, 0, sizeof(double) * (size_t)rows * std::max(nl, 1)));
         HIPCHK(hipMemset(b.d_z, 0, sizeof(double) * (size_t)rows * std::max(nl, 1)));

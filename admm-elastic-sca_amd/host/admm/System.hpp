@@ -63,7 +63,10 @@ public:
         // residual_check_every iterations; admm_iters stays the upper bound.  0 (default) = the reference's fixed count.
         double residual_tol_primal, residual_tol_dual;
         int residual_check_every;
-        Settings() : timestep_s(0.04), verbose(1), admm_iters(10), residual_tol_primal(0.0), residual_tol_dual(0.0), residual_check_every(1) {}
+        // extension, no reference counterpart: every ADMM iteration of step() records inertia(x_k) and elastic(x_k) of the incremental
+        // potential (System::objective(); admm_hip_enable_objective).  Not available on a sharded system.
+        bool track_objective;
+        Settings() : timestep_s(0.04), verbose(1), admm_iters(10), residual_tol_primal(0.0), residual_tol_dual(0.0), residual_check_every(1), track_objective(false) {}
     } settings;
 
     double elapsed_s;
@@ -323,6 +326,7 @@ public:
         pin_state();
         if (!check(admm_hip_upload_state(gpu, m_x.data(), m_v.data()))) return false;
         if (!check(admm_hip_set_tolerance(gpu, settings.residual_tol_primal, settings.residual_tol_dual, settings.residual_check_every < 1 ? 1 : settings.residual_check_every))) return false;
+        if (!check(admm_hip_enable_objective(gpu, settings.track_objective ? 1 : 0))) return false;
         if (!check(admm_hip_step(gpu, settings.admm_iters))) return false;
         if (!check(admm_hip_download_state(gpu, m_x.data(), m_v.data()))) return false;
         // released MovingAnchors follow their node: point->pos = Dx (AnchorForce.cpp:80-83)
@@ -379,6 +383,29 @@ public:
             if (!check(admm_hip_set_weights(gpu, (int)b, w.data()))) return;
         }
         check(admm_hip_recompute_weights(gpu));
+    }
+
+    // extension, no reference counterpart (admm_hip_energy): the energies of the device state as the last step() left it (m_x / m_v edited
+    // since are not uploaded by this call).  ok = false: the call failed (not initialized, no GPU).
+    struct Energy { double kinetic, gravity, elastic, anchor; long n_infinite, batches_skipped; bool ok; };
+    Energy energy() {
+        Energy e = {0.0, 0.0, 0.0, 0.0, 0, 0, false};
+        admm_hip_energy_totals t;
+        if (!initialized || !check(admm_hip_energy(gpu, &t))) return e;
+        e.kinetic = t.kinetic; e.gravity = t.gravity; e.elastic = t.elastic; e.anchor = t.anchor;
+        e.n_infinite = (long)t.n_infinite; e.batches_skipped = (long)t.batches_skipped; e.ok = true;
+        return e;
+    }
+    // the last step()'s per-iteration histories under settings.track_objective: inertia(x_k), elastic(x_k); their sum is the objective
+    struct Objective { std::vector<double> inertia, elastic; };
+    Objective objective() {
+        Objective o;
+        if (!initialized) return o;
+        int n = 0;
+        if (!check(admm_hip_get_objective(gpu, nullptr, nullptr, 0, &n)) || n <= 0) return o;
+        o.inertia.resize(n); o.elastic.resize(n);
+        if (!check(admm_hip_get_objective(gpu, o.inertia.data(), o.elastic.data(), n, &n))) { o.inertia.clear(); o.elastic.clear(); }
+        return o;
     }
 
     admm_hip_ctx *context() { return gpu; }

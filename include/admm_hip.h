@@ -728,6 +728,59 @@ int admm_hip_enable_residuals(admm_hip_ctx *ctx, int on);
 int admm_hip_get_residuals(admm_hip_ctx *ctx, double *r_norm, double *s_norm, int capacity, int *n_iters);
 int admm_hip_set_tolerance(admm_hip_ctx *ctx, double eps_r, double eps_s, int check_every);
 
+/* ---- energies and the per-iteration ADMM objective ---------------------------------------------------------------------------------
+ * Extension, no reference counterpart (the reference never evaluates what it minimises).  Every frame the solver minimises the incremental
+ * potential of the paper,   Phi(x) = 1 / (2 dt^2) |x - x_bar|^2_M + sum_i E_i(D_i x),   with d = D_i x the element's compact rows exactly
+ * as the local step forms them (the scaled dual variable u plays no part) and s the element's scale:
+ *   TET_NH      s [mu/2 (I1 - L - 3) + lambda/8 L^2],  I1 = |d|^2_F, J = det d, L = log(J J); +inf when J <= 0 or not finite      s = rest volume
+ *   TET_STVK    s [mu |E|^2_F + lambda/2 tr^2 E],  E = (d^T d - I) / 2; finite for inverted elements too                          s = rest volume
+ *   TRI_FUNG    s mu/2 (exp(I1 - 3) - 1),  I1 = |d|^2_F + 1/g, g = det(d^T d); +inf when g <= 0 or the exponential overflows      s = rest area
+ *   TET_LINEAR, TET_VOLUME, TRI_STRAIN, TRI_AREA   s/2 |d - p|^2, p the kind's projection of d (TRI_STRAIN: U(:, :2) V^T; its strain
+ *               limits are a hard clamp and carry no energy)                                                  s = stiffness * rest measure
+ *   SPRING      s/2 |d - L d / |d||^2 (p = 0 where |d| <= 0);   BEND   s/2 |d - p|^2, p the hinge projection                     s = stiffness
+ *   ANCHOR      active: w^2/2 |x - t|^2, released: 0.  A hard constraint in z, zero at convergence: reported as `anchor`, never part of
+ *               `elastic`.                                                                                    s = weight^2
+ *   COLLISION, GENERIC   not evaluated: the value is 0 and the batch is counted in batches_skipped.
+ * One definition, csrc/energy.hpp, compiled without fused multiply-adds for the host and the device: both give the same bits.  An element
+ * whose energy is not finite adds nothing to a sum and is counted instead (n_infinite).  Sums use no atomics and a fixed order that depends
+ * only on the element (node) count (csrc/kernels_energy.hpp documents it): two calls on the same state return the same bits, whatever
+ * ADMM_HIP_TPB, ADMM_HIP_LOCAL_MULTI and ADMM_HIP_PRERED are.  The node terms are summed in the caller's node order.
+ * Every call below reads the device state as it stands (after finalize, between frames), runs on the context's stream and waits for it;
+ * none writes x, v, u, z, the warm starts, the cost counters or the sides, and none drops a captured graph.  Their buffers are created by
+ * the first call that needs them; a context that never calls them launches exactly what it did.  Cost: not measured.
+ *   admm_hip_energy          kinetic = 1/2 sum m v^2,  gravity = -sum m g x over every ADMM_EXPLICIT_CONST entry and its nodes (wind has no
+ *                           potential and is left out),  elastic = the evaluated batches' totals except the anchors', added in batch
+ *                           order,  anchor = the anchor batches' totals,  n_infinite, batches_skipped.
+ *   admm_hip_batch_energy    one batch: its total, per_elem [n_local] in the order of admm_hip_read_local, the count of non-finite
+ *                           elements.  Any pointer may be NULL.  A batch that is not evaluated: zeros.
+ *   admm_hip_batch_energy_dx a parity entry like admm_hip_local_step_dx: the same kernel on caller-supplied rows dx [n_local][rows].
+ *                           ADMM_ERR_UNSUPPORTED for a batch that is not evaluated.
+ *   admm_hip_read_energy_scale  s [n_local] of this rank's elements (an anchor's: the weight^2 of admm_hip_set_weights as it stands).
+ *   admm_hip_energy_query    context-free host evaluation, the device's bits; needs no GPU: dx [n][rows], params [n][ADMM_KIND_PARAMS],
+ *                           rest [n][12] as admm_hip_read_rest lays it out (read for springs and hinges only; an anchor's target in
+ *                           rest[0..2], active = params[1] != 0), scale [n] -> energy [n].  ADMM_ERR_ARG: a kind that is not evaluated,
+ *                           n < 0, a NULL array with n > 0.  n = 0: ADMM_OK, nothing is read.
+ *   admm_hip_enable_objective  on != 0: every ADMM iteration of admm_hip_step appends, after its global step, inertia(x_k) =
+ *                           1 / (2 dt^2) sum m (x_k - x_bar)^2 (x_bar from the prologue's M x_bar) and elastic(x_k); the objective is their
+ *                           sum.  The loop then runs eagerly, as under residual tracking; x and v are bitwise what they are with it off.
+ *                           ADMM_ERR_UNSUPPORTED in a sharded context (world > 1): under subtree shards the full x exists only at the
+ *                           end of the frame.
+ *   admm_hip_get_objective   the two histories of the last step, at most `capacity` entries; *n_iters = the iterations it recorded (an
+ *                           early exit ends the history where the loop ends: the length of admm_hip_get_residuals').
+ * Sharded contexts: elastic, anchor, the counts and admm_hip_batch_energy cover THIS rank's local elements (admm_hip_local_elements); the
+ * ranks' values add up to the one-rank value.  The node terms cover all nodes and are the same, bit for bit, on every rank.           */
+typedef struct admm_hip_energy_totals {
+    double kinetic, gravity, elastic, anchor;
+    int64_t n_infinite, batches_skipped;
+} admm_hip_energy_totals;
+int admm_hip_energy(admm_hip_ctx *ctx, admm_hip_energy_totals *out);
+int admm_hip_batch_energy(admm_hip_ctx *ctx, int batch, double *total, double *per_elem, int64_t *n_infinite);
+int admm_hip_batch_energy_dx(admm_hip_ctx *ctx, int batch, const double *dx, double *per_elem);
+int admm_hip_read_energy_scale(admm_hip_ctx *ctx, int batch, double *s);
+int admm_hip_energy_query(int kind, int64_t n, const double *dx, const double *params, const double *rest, const double *scale, double *energy);
+int admm_hip_enable_objective(admm_hip_ctx *ctx, int on);
+int admm_hip_get_objective(admm_hip_ctx *ctx, double *inertia, double *elastic, int capacity, int *n_iters);
+
 #ifdef __cplusplus
 }
 #endif
