@@ -776,6 +776,7 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_shell_kernel(Ba
 // closest_within_excluding and the node's vertex id vid[node], so that the triangles around the node are left out.  Any other entry runs
 // the shell kernel's code and gives its bits (skip = -1).  The surface is the frame-start one: a node meets where the rest of the cloth
 // was at the start of the frame.  self: the flag of every mesh, parallel to meshes; vid: one id per node in device order (-1: none).
+// tests/test_collision_form_ladder.py holds this kernel to the bits of every form below it, on lists that a far trigger entry moves here.
 __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_self_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
                                                                                const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
                                                                                const admm_mesh::MeshMotion *__restrict__ mm, const double *__restrict__ thick, const int *__restrict__ tag,
@@ -978,6 +979,7 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_sided_kernel(Ba
 // runs body_self_project against the rest vertices rest[mi] -- the search bounded by R that passes over what is near the node in the
 // rest shape, the unsigned rule outside, the mirror push for a node that has crossed the skin --, an interior node skips the entry as
 // before.  Everything after the push is unchanged.
+// tests/test_collision_form_ladder.py holds this kernel to the bits of every form below it, on lists that a far trigger entry moves here.
 __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_bodyself_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
                                                                                const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
                                                                                const admm_mesh::MeshMotion *__restrict__ mm, const double *__restrict__ thick, const int *__restrict__ tag,
