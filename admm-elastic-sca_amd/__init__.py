@@ -67,6 +67,13 @@ class EnergyTotals(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ForceInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_nonfinite", "batches_skipped")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class AdmmHipError(RuntimeError):
     pass
 
@@ -112,6 +119,12 @@ def lib():
         L.admm_hip_batch_energy_dx.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
         L.admm_hip_read_energy_scale.argtypes = [C.c_void_p, C.c_int, _dp]
         L.admm_hip_energy_query.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _dp, _dp]
+        L.admm_hip_batch_gradient.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]
+        L.admm_hip_batch_gradient_dx.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        L.admm_hip_batch_stress.argtypes = [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_int64)]
+        L.admm_hip_node_forces.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(ForceInfo)]
+        L.admm_hip_gradient_query.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _dp, _dp]
+        L.admm_hip_stress_query.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _dp]
         L.admm_hip_enable_objective.argtypes = [C.c_void_p, C.c_int]
         L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
@@ -477,6 +490,44 @@ def energy_query(kind, dx, params, rest, scale):
     return out
 
 
+def gradient_query(kind, dx, params, rest, scale):
+    """the elements' gradients g = dE/dd on the host (admm_hip_gradient_query; csrc/gradient.hpp, the device's bits; needs no GPU), with
+    the arguments of energy_query -> g [n][rows]; NaN rows where the kind's energy is infinite.  TET_VOLUME and TRI_AREA return the
+    projective force s (d - p), which is not the derivative of their stored energy (include/admm_hip.h)"""
+    kind = KIND[kind] if isinstance(kind, str) else int(kind)
+    if not 0 <= kind < len(KIND_ROWS):
+        rc = lib().admm_hip_gradient_query(kind, 0, None, None, None, None, None)
+        raise AdmmHipError("admm_hip_gradient_query error %d" % rc)
+    dx = np.ascontiguousarray(dx, dtype=np.float64).reshape(-1, KIND_ROWS[kind])
+    n = dx.shape[0]
+    par = np.ascontiguousarray(np.broadcast_to(np.asarray(params, dtype=np.float64).reshape(-1, KIND_PARAMS[kind]), (n, KIND_PARAMS[kind])))
+    rs = np.zeros((n, 12)) if rest is None else np.ascontiguousarray(np.broadcast_to(np.asarray(rest, dtype=np.float64).reshape(-1, 12), (n, 12)))
+    sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (n,)))
+    out = np.zeros((n, KIND_ROWS[kind]))
+    rc = lib().admm_hip_gradient_query(kind, n, _d(dx), _d(par), _d(rs), _d(sc), _d(out))
+    if rc:
+        raise AdmmHipError("admm_hip_gradient_query error %d" % rc)
+    return out
+
+
+def stress_query(kind, dx, params, volume):
+    """the tets' Cauchy stress on the host (admm_hip_stress_query; the device's bits; needs no GPU): dx [n][9], params [n][KIND_PARAMS] (or
+    one row for all), volume [n] (or a scalar): the rest volumes -> stress [n][7]: xx, yy, zz, xy, xz, yz, von Mises; NaN where J <= 0"""
+    kind = KIND[kind] if isinstance(kind, str) else int(kind)
+    if kind not in (KIND["TET_LINEAR"], KIND["TET_VOLUME"], KIND["TET_NH"], KIND["TET_STVK"]):
+        rc = lib().admm_hip_stress_query(kind, 0, None, None, None, None)
+        raise AdmmHipError("admm_hip_stress_query error %d" % rc)
+    dx = np.ascontiguousarray(dx, dtype=np.float64).reshape(-1, 9)
+    n = dx.shape[0]
+    par = np.ascontiguousarray(np.broadcast_to(np.asarray(params, dtype=np.float64).reshape(-1, KIND_PARAMS[kind]), (n, KIND_PARAMS[kind])))
+    vol = np.ascontiguousarray(np.broadcast_to(np.asarray(volume, dtype=np.float64), (n,)))
+    out = np.zeros((n, 7))
+    rc = lib().admm_hip_stress_query(kind, n, _d(dx), _d(par), _d(vol), _d(out))
+    if rc:
+        raise AdmmHipError("admm_hip_stress_query error %d" % rc)
+    return out
+
+
 def mesh_velocity_query(verts, tris, pts, vel, t=(0.0, 0.0, 0.0)):
     """the vertex field vel [nv][3] of the closed mesh (verts, tris; a Mesh for verts: tris ignored) translated by t, interpolated at the
     closest point to each of pts (admm_hip_mesh_velocity_query) -> (out [n][3], weights [n][3], corner_ids [n][3]): the barycentric
@@ -826,6 +877,42 @@ class System:
         s = np.zeros(self.local_elements(batch).size)
         self._chk(self.L.admm_hip_read_energy_scale(self.h, batch, _d(s)))
         return s
+
+    # ---- elastic forces and tet stresses: the energies' gradient (extension; include/admm_hip.h) ----
+    def batch_gradient(self, batch):
+        """-> (g [n_local][rows], corner_forces [n_local][nodes][3], n_nonfinite) of one batch, in read_local's order"""
+        kind, _ = self.batches[batch]
+        n = self.local_elements(batch).size
+        if kind == KIND_GENERIC:
+            g = np.zeros((n, 0)); cf = np.zeros((n, 0, 3)); bad = C.c_int64(0)
+            self._chk(self.L.admm_hip_batch_gradient(self.h, batch, None, None, C.byref(bad)))
+            return g, cf, bad.value
+        g = np.zeros((n, KIND_ROWS[kind])); cf = np.zeros((n, KIND_NODES[kind], 3)); bad = C.c_int64(0)
+        self._chk(self.L.admm_hip_batch_gradient(self.h, batch, _d(g), _d(cf), C.byref(bad)))
+        return g, cf, bad.value
+
+    def batch_gradient_dx(self, batch, dx, out=None):
+        """the batch's gradient kernel on caller-supplied rows dx [n_local][rows] -> g (written into `out` when given)"""
+        kind, _ = self.batches[batch]
+        dx = np.ascontiguousarray(dx, dtype=np.float64)
+        g = np.zeros((self.local_elements(batch).size, KIND_ROWS[kind] if kind != KIND_GENERIC else 0)) if out is None else out
+        self._chk(self.L.admm_hip_batch_gradient_dx(self.h, batch, _d(dx), _d(g)))
+        return g
+
+    def batch_stress(self, batch):
+        """-> (stress [n_local][7]: xx, yy, zz, xy, xz, yz, von Mises, n_nonfinite) of a tet batch"""
+        st = np.zeros((self.local_elements(batch).size, 7)); bad = C.c_int64(0)
+        self._chk(self.L.admm_hip_batch_stress(self.h, batch, _d(st), C.byref(bad)))
+        return st, bad.value
+
+    def node_forces(self):
+        """-> dict(elastic [n_nodes][3], anchor [n_nodes][3], n_nonfinite, batches_skipped): the internal forces -sum D_i^T dE_i/dd of the
+        state as it stands, in the caller's node order; a sharded context returns this rank's share"""
+        fe = np.zeros((self.n_nodes, 3)); fa = np.zeros((self.n_nodes, 3)); info = ForceInfo()
+        self._chk(self.L.admm_hip_node_forces(self.h, _d(fe), _d(fa), C.byref(info)))
+        d = info.as_dict()
+        d.update(elastic=fe, anchor=fa)
+        return d
 
     def enable_objective(self, on=True):
         self._chk(self.L.admm_hip_enable_objective(self.h, 1 if on else 0))

@@ -5,7 +5,8 @@
                                            subtree sharding, RCCL / all-reduce hooks -- hipcc as a host compile (HIP runtime API only)
   mesh.cpp                               : mesh obstacles on the host (validation, BVH, the host query of mesh_query.hpp), g++ -O3
                                            -ffp-contract=off (the device's arithmetic)
-  energy_host.cpp                        : the host evaluation of the elements' energies (energy.hpp), g++ -O3 -ffp-contract=off likewise
+  energy_host.cpp, gradient_host.cpp     : the host evaluation of the elements' energies (energy.hpp), their gradients and the tet
+                                           stress (gradient.hpp), g++ -O3 -ffp-contract=off likewise
   admm_hip.hip                           : the device translation unit: kernels (kernels_*.hpp, factor_dev.hpp), device factorization,
                                            upload, launches, step loop, C ABI; hipcc --offload-arch=gfx950, -ffp-contract=off
                                            (operation order = reference's)
@@ -77,6 +78,7 @@ def _jobs(extra_hip_flags, tag):
         ([hipcc] + HIPHOST_FLAGS, "comm.cpp", "comm.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "mesh.cpp", "mesh.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "energy_host.cpp", "energy_host.o"),
+        (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "gradient_host.cpp", "gradient_host.o"),
         ([hipcc] + HIP_FLAGS + list(extra_hip_flags), "admm_hip.hip", "admm_hip%s.o" % tag),
     ]
 

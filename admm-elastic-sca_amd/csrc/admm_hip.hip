@@ -24,6 +24,7 @@
 #include "kernels_local.hpp"
 #include "kernels_mesh.hpp"
 #include "kernels_energy.hpp"
+#include "kernels_gradient.hpp"
 
 extern "C" int omp_get_max_threads(void);
 
@@ -70,6 +71,7 @@ extern "C" {
 
 #include "abi_setup.inc"
 #include "abi_energy.inc"
+#include "abi_gradient.inc"
 #include "abi_step.inc"
 #include "abi_parity.inc"
 

@@ -57,6 +57,10 @@ struct Batch {
     // energies (kernels_energy.hpp): the elements' scale s, uploaded at finalize; the per-element values, one partial and one count of
     // non-finite elements per 64-element block, allocated by the first call that evaluates an energy (abi_energy.inc)
     double *d_escale = nullptr, *d_eE = nullptr, *d_epart = nullptr; int *d_ecnt = nullptr;
+    // gradients (kernels_gradient.hpp), allocated by the first call that evaluates one (abi_gradient.inc): g SoA [rows][n_local], one count
+    // of non-finite elements per 64-element block, the batch's corner forces at gr_cf_off of the context's d_gr_cf; tets, first
+    // admm_hip_batch_stress: the stress SoA [7][n_local] and the rest volumes
+    double *d_gg = nullptr, *d_gstress = nullptr, *d_gvol = nullptr; int *d_gcnt = nullptr; long long gr_cf_off = 0;
     std::vector<double> G;                // [12][n_local] selector block per element, corners in device order
     // ---- ADMM_KIND_GENERIC (user-defined forces): selector rows as CSR over the batch's rows
     std::vector<int64_t> g_elem_row;      // [n_total + 1] first batch row of every element
@@ -266,6 +270,11 @@ struct admm_hip_ctx {
     // the last step, inertia(x_k) and every batch's total at x_k
     bool en_ready = false; double *d_en_out = nullptr, *d_en_npart = nullptr; long long *d_en_cnt = nullptr;
     bool obj_on = false; int obj_cap = 0, obj_n = 0; double *d_obj = nullptr;
+    // gradients and nodal forces (abi_gradient.inc; every buffer created on first use).  d_gr_cf: every evaluated batch's corner forces,
+    // SoA [3 nodes][n_local] per batch; d_gr_out [2][3 n_nodes]: the elastic and the anchor forces in the caller's node order; the two
+    // CSRs of gradient_gather_kernel (0: elastic batches, 1: anchor batches), built by the first admm_hip_node_forces
+    bool gr_ready = false, gr_csr_ready = false; double *d_gr_cf = nullptr, *d_gr_out = nullptr;
+    int *d_gr_ptr[2] = {nullptr, nullptr}, *d_gr_stride[2] = {nullptr, nullptr}; long long *d_gr_off[2] = {nullptr, nullptr};
 
     // user-defined forces: host round trip per ADMM iteration (see admm_hip_add_generic_batch)
     admm_hip_project_fn project_hook = nullptr; void *project_user = nullptr;

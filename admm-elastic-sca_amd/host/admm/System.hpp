@@ -396,6 +396,30 @@ public:
         e.n_infinite = (long)t.n_infinite; e.batches_skipped = (long)t.batches_skipped; e.ok = true;
         return e;
     }
+    // extension, no reference counterpart (admm_hip_node_forces): the internal forces -sum D_i^T dE_i/dd of the device state as the last
+    // step() left it, [n_nodes][3] in m_x's node order; elastic: the built-in elastic forces, anchor: the anchors' (the reaction at a held
+    // node is minus its elastic force).  ok = false: the call failed (not initialized, no GPU).
+    struct NodeForces { std::vector<double> elastic, anchor; long n_nonfinite, batches_skipped; bool ok; };
+    NodeForces node_forces() {
+        NodeForces f; f.n_nonfinite = 0; f.batches_skipped = 0; f.ok = false;
+        if (!initialized) return f;
+        f.elastic.assign((size_t)m_x.size(), 0.0); f.anchor.assign((size_t)m_x.size(), 0.0);
+        admm_hip_force_info info;
+        if (!check(admm_hip_node_forces(gpu, f.elastic.data(), f.anchor.data(), &info))) { f.elastic.clear(); f.anchor.clear(); return f; }
+        f.n_nonfinite = (long)info.n_nonfinite; f.batches_skipped = (long)info.batches_skipped; f.ok = true;
+        return f;
+    }
+    // the Cauchy stress of the tets of device batch `batch` (admm_hip_batch_stress): seven doubles per tet, xx, yy, zz, xy, xz, yz, von
+    // Mises, in the order of admm_hip_read_local; empty when the call failed (not a tet batch, not initialized, no GPU)
+    std::vector<double> batch_stress(int batch) {
+        std::vector<double> s;
+        int n = 0;
+        if (!initialized || !check(admm_hip_local_elements(gpu, batch, nullptr, 0, &n))) return s;
+        s.assign((size_t)7 * (n > 0 ? n : 0), 0.0);
+        std::vector<double> one(7, 0.0);
+        if (!check(admm_hip_batch_stress(gpu, batch, n > 0 ? s.data() : one.data(), nullptr))) s.clear();
+        return s;
+    }
     // the last step()'s per-iteration histories under settings.track_objective: inertia(x_k), elastic(x_k); their sum is the objective
     struct Objective { std::vector<double> inertia, elastic; };
     Objective objective() {

@@ -781,6 +781,53 @@ int admm_hip_energy_query(int kind, int64_t n, const double *dx, const double *p
 int admm_hip_enable_objective(admm_hip_ctx *ctx, int on);
 int admm_hip_get_objective(admm_hip_ctx *ctx, double *inertia, double *elastic, int capacity, int *n_iters);
 
+/* ---- elastic forces and tet stresses: the gradient of the energies above ---------------------------------------------------------------
+ * Extension, no reference counterpart.  g = dE_i/dd in the element's compact rows (the layout of d: 9 / 6 / 3 rows), the nodal internal
+ * force f = -sum_i D_i^T g_i, and the tets' Cauchy stress.  One definition, csrc/gradient.hpp, compiled without fused multiply-adds for the
+ * host and the device: both give the same bits.
+ *   Exact derivatives of the energy:  TET_NH  s [mu d + (lambda L / 2 - mu) cof(d) / J];  TET_STVK  s d (2 mu E + lambda tr(E) I);
+ *     TRI_FUNG by the chain rule through I1;  SPRING, BEND, ANCHOR  s (d - p) (an anchor: w^2 (x - t), released: 0);  TET_LINEAR,
+ *     TRI_STRAIN  s (d - p), p the nearest rotation / isometry.
+ *   PROJECTIVE FORCE ONLY:  TET_VOLUME, TRI_AREA return s (d - p) with the kind's projection p.  That is the force projective dynamics
+ *     applies, NOT the derivative of the stored energy: the projections stop after 4 / `iters` Newton steps, and finite differences of
+ *     the energy differ from it by 2 % to 90 % where the limits are active (both are exactly 0 where they are not).
+ *   Not finite: where the energy is not finite (TET_NH at J <= 0, TRI_FUNG at g <= 0) or an entry overflows, every entry of the element's
+ *     g is NaN; the element adds zeros to every corner force and node sum and is counted in n_nonfinite.
+ *   Stress (TET_* only): Cauchy sigma = (g d^T) / (V J), V the rest volume, off-diagonal pairs symmetrised as (a + b) / 2; seven doubles per
+ *     tet: xx, yy, zz, xy, xz, yz, von Mises.  All seven are NaN where J <= 0.
+ * Every compute call reads the device state as it stands, runs on the context's stream and waits for it; none writes x, v, u, z, the warm
+ * starts, the cost counters or the sides, and none drops a captured graph.  Their buffers are created by the first call that needs them;
+ * a context that never calls them uploads and launches exactly what it did.  Sums use no atomics and a fixed order (csrc/
+ * kernels_gradient.hpp): a node adds its incident corners by a compensated sequential sum (the exact sum rounded once, to second order in
+ * 2^-53) in batch order, then local element order, then the element's corners as the caller listed them -- whatever the elimination order, ADMM_HIP_TPB, ADMM_HIP_LOCAL_MULTI and ADMM_HIP_PRERED are.  Cost: not
+ * measured.
+ *   admm_hip_batch_gradient     one batch: g [n_local][rows] and corner_forces [n_local][nodes][3] (-D_i^T g, the corners as the caller
+ *                              listed them), element-major in the order of admm_hip_read_local, and the count of elements whose g is not
+ *                              finite.  Any pointer may be NULL.  A batch that is not evaluated (COLLISION, GENERIC): zeros.
+ *   admm_hip_batch_gradient_dx  a parity entry like admm_hip_batch_energy_dx: the same kernel on caller-supplied rows dx [n_local][rows]
+ *                              -> g.  ADMM_ERR_UNSUPPORTED for a batch that is not evaluated.
+ *   admm_hip_batch_stress       stress7 [n_local][7] of a tet batch and the count of tets whose stress is not finite.
+ *                              ADMM_ERR_UNSUPPORTED for a batch that is not a tet batch.
+ *   admm_hip_node_forces        f_elastic, f_anchor [n_nodes][3] in the caller's node order (either may be NULL): the internal forces of
+ *                              the evaluated batches except the anchors', and of the anchor batches.  info (may be NULL): n_nonfinite
+ *                              over all evaluated batches, batches_skipped (COLLISION, GENERIC).  A node with no element: exactly 0.
+ *   admm_hip_gradient_query     context-free host evaluation, the device's bits; needs no GPU: the arguments of admm_hip_energy_query
+ *                              -> g [n][rows]; the same argument checks.
+ *   admm_hip_stress_query       likewise for the tet kinds: dx [n][9], params [n][ADMM_KIND_PARAMS], volume [n] (the rest volumes; the
+ *                              scale s follows from them as in admm_hip_read_energy_scale) -> stress7 [n][7].  ADMM_ERR_ARG: a kind that
+ *                              is not a tet kind, n < 0, a NULL array with n > 0.  n = 0: ADMM_OK, nothing is read.
+ * Sharded contexts: every call covers THIS rank's local elements (admm_hip_local_elements); the ranks' node vectors add up to the
+ * one-rank vector within 2^-52 sum |share| per component (they are not gathered into one).                                                                                    */
+typedef struct admm_hip_force_info {
+    int64_t n_nonfinite, batches_skipped;
+} admm_hip_force_info;
+int admm_hip_batch_gradient(admm_hip_ctx *ctx, int batch, double *g, double *corner_forces, int64_t *n_nonfinite);
+int admm_hip_batch_gradient_dx(admm_hip_ctx *ctx, int batch, const double *dx, double *g);
+int admm_hip_batch_stress(admm_hip_ctx *ctx, int batch, double *stress7, int64_t *n_nonfinite);
+int admm_hip_node_forces(admm_hip_ctx *ctx, double *f_elastic, double *f_anchor, admm_hip_force_info *info);
+int admm_hip_gradient_query(int kind, int64_t n, const double *dx, const double *params, const double *rest, const double *scale, double *g);
+int admm_hip_stress_query(int kind, int64_t n, const double *dx, const double *params, const double *volume, double *stress7);
+
 #ifdef __cplusplus
 }
 #endif
