@@ -74,6 +74,11 @@ class ForceInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AccelerationRecord(C.Structure):
+    _fields_ = [("rho", C.c_double)] + [(n, C.c_int32) for n in ("accepted", "m_used", "extrapolated", "solve_failed")] + \
+               [("theta", C.c_double * 8), ("gram", C.c_double * 64), ("rhs", C.c_double * 8)]
+
+
 class AdmmHipError(RuntimeError):
     pass
 
@@ -126,6 +131,10 @@ def lib():
         L.admm_hip_gradient_query.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _dp, _dp]
         L.admm_hip_stress_query.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _dp]
         L.admm_hip_enable_objective.argtypes = [C.c_void_p, C.c_int]
+        L.admm_hip_set_acceleration.argtypes = [C.c_void_p, C.c_int]
+        L.admm_hip_get_acceleration_log.argtypes = [C.c_void_p, C.POINTER(AccelerationRecord), C.c_int, C.POINTER(C.c_int)]
+        L.admm_hip_get_acceleration_default.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        L.admm_hip_acceleration_query.argtypes = [C.c_int, _dp, _dp, _dp]
         L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
         L.admm_hip_add_nodes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
@@ -508,6 +517,23 @@ def gradient_query(kind, dx, params, rest, scale):
     if rc:
         raise AdmmHipError("admm_hip_gradient_query error %d" % rc)
     return out
+
+
+def acceleration_query(gram, rhs):
+    """the small solve of Anderson acceleration on the host (admm_hip_acceleration_query; csrc/anderson.hpp, the device's bits; needs no
+    GPU): gram [m_k][m_k] = dF^T W^2 dF before regularisation (its lower triangle is read), rhs [m_k] -> theta [m_k], the solution of
+    (gram + 1e-12 tr(gram) / m_k I) theta = rhs; zeros where a Cholesky pivot is not positive.  1 <= m_k <= 8."""
+    A = np.ascontiguousarray(gram, dtype=np.float64)
+    b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
+    mk = b.size
+    if A.ndim != 2 or A.shape != (mk, mk) or not 1 <= mk <= 8:
+        rc = lib().admm_hip_acceleration_query(0, None, None, None)
+        raise AdmmHipError("admm_hip_acceleration_query error %d" % rc)
+    th = np.zeros(mk)
+    rc = lib().admm_hip_acceleration_query(mk, _d(A), _d(b), _d(th))
+    if rc:
+        raise AdmmHipError("admm_hip_acceleration_query error %d" % rc)
+    return th
 
 
 def stress_query(kind, dx, params, volume):
@@ -923,6 +949,32 @@ class System:
         self._chk(self.L.admm_hip_get_objective(self.h, _d(a), _d(e), capacity, C.byref(n)))
         k = min(n.value, capacity)
         return a[:k], e[:k], n.value
+
+    # ---- Anderson acceleration of the ADMM iteration (extension; include/admm_hip.h) ----
+    def set_acceleration(self, window):
+        """window m of the history, 0 .. 8; 0 (the default) switches acceleration off"""
+        self._chk(self.L.admm_hip_set_acceleration(self.h, int(window)))
+
+    def acceleration_log(self, capacity=512):
+        """-> one dict per ADMM iteration of the last step: rho, accepted, m_used, extrapolated, solve_failed, theta [m_used],
+        gram [m_used][m_used] and rhs [m_used] (the system the device solved, before regularisation; differences oldest first)"""
+        rec = (AccelerationRecord * max(capacity, 1))(); n = C.c_int(0)
+        self._chk(self.L.admm_hip_get_acceleration_log(self.h, rec, capacity, C.byref(n)))
+        out = []
+        for r in rec[:min(n.value, capacity)]:
+            mk = r.m_used
+            out.append(dict(rho=r.rho, accepted=bool(r.accepted), m_used=mk, extrapolated=bool(r.extrapolated), solve_failed=bool(r.solve_failed),
+                            theta=np.array(r.theta[:mk]), gram=np.array(r.gram[:]).reshape(8, 8)[:mk, :mk].copy(), rhs=np.array(r.rhs[:mk])))
+        return out
+
+    def acceleration_default(self, batch):
+        """-> dict(z, u) [n_local][rows]: the stored default s_def of one batch (the last accepted local-step output), in read_local's layout"""
+        kind, _ = self.batches[batch]
+        n = self.local_elements(batch).size
+        rows = KIND_ROWS[kind] if kind != KIND_GENERIC else 0
+        z = np.zeros((n, rows)); u = np.zeros((n, rows))
+        self._chk(self.L.admm_hip_get_acceleration_default(self.h, batch, _d(z), _d(u)))
+        return dict(z=z, u=u)
 
     def set_allreduce(self, pyfunc):
         """pyfunc(dev_ptr:int, count:int, stream:int) -> 0 on success."""

@@ -82,6 +82,10 @@ static int mark(admm_hip_ctx *ctx, bool on = true) {
 int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     TRY(require_factor(ctx));
     using namespace admm_dev;
+    // Anderson acceleration (admm_hip_set_acceleration): refused before anything is launched, so that the state stands as it was
+    const bool accel = ctx->aa_m > 0;
+    if (accel && ctx->n_gen_rows) return fail(ctx, ADMM_ERR_UNSUPPORTED, "acceleration is not available in a context with user-defined (generic) batches: their z, u live on the host");
+    if (accel && ctx->world > 1) return fail(ctx, ADMM_ERR_UNSUPPORTED, "acceleration is not available in a sharded context (world = %d): the Gram matrix would have to be all-reduced", ctx->world);
     HIPCHK(hipSetDevice(ctx->device_id));
     const int n3 = 3 * ctx->n_nodes;
     if (ctx->graphs_stale) { drop_iteration_graphs(ctx); ctx->graphs_stale = false; }      // the transport changed since the iteration was captured
@@ -113,12 +117,15 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     TRY(mark(ctx));
     const bool track = ctx->res_on || ctx->tol_r > 0.0;
     if (track) TRY(ensure_residual_buffers(ctx, admm_iters));
-    ctx->keep_z = ctx->keep_z_user || track;
+    // Anderson acceleration (admm_hip_set_acceleration; abi_anderson.inc): the eager loop, the tets' z stored, its buffers before the loop
+    if (accel) { TRY(ensure_anderson_buffers(ctx, admm_iters)); TRY(anderson_begin_frame(ctx)); }
+    ctx->keep_z = ctx->keep_z_user || track || accel;
     // the per-iteration objective (admm_hip_enable_objective): its buffers exist before the loop, which then runs eagerly like a tracked one
     const bool objective = ctx->obj_on;
     if (objective && ctx->world > 1) return fail(ctx, ADMM_ERR_UNSUPPORTED, "the per-iteration objective is not available in a sharded context (world = %d)", ctx->world);
     if (objective) TRY(ensure_energy_buffers(ctx, admm_iters));
     ctx->obj_n = 0;
+    if (!accel) ctx->aa_log_n = 0;      // (the log is the last step's)
     if (ctx->n_gen_rows) {      // user-defined forces: curr_z = D * m_x before the loop (System.cpp:43)
         TRY(generic_begin(ctx, ctx->d_x));
         HIPCHK(hipEventSynchronize(ctx->gen_ev));
@@ -127,7 +134,7 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     // world > 1: the iteration contains an all-reduce.  A host hook cannot be captured; ncclAllReduce can (RCCL collectives are
     // stream-ordered device work), so with the communicator inside the library the multi-GPU iteration is one graph launch too.
     const bool comm_capturable = ctx->world == 1 || (ctx->rccl_comm != nullptr && ctx->graph_comm);
-    const bool use_graph = ctx->graph_enabled && (ctx->graph_forced || ctx->n_nodes < 100000) && comm_capturable && !(ctx->timing && ctx->timing_stride <= 1) && !track && !objective && admm_iters > 0 && !ctx->n_gen_rows;
+    const bool use_graph = ctx->graph_enabled && (ctx->graph_forced || ctx->n_nodes < 100000) && comm_capturable && !(ctx->timing && ctx->timing_stride <= 1) && !track && !objective && !accel && admm_iters > 0 && !ctx->n_gen_rows;
     if (use_graph && !ctx->iter_exec) {   // capture one iteration; every kernel argument is a fixed device address
         // a stream that cannot be captured (caller-supplied, already capturing ...) is not an error: launch eagerly instead
         const hipError_t be = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
@@ -180,11 +187,17 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
         if (timed) ++ctx->ev_timed;
         TRY(mark(ctx, timed));
         if (track) TRY(residual_snapshot(ctx, it == 0));
+        if (accel) TRY(anderson_snapshot(ctx, it == 0));
         TRY(generic_begin(ctx, ctx->d_xcur));
         TRY(launch_local(ctx, -1, track));
         TRY(generic_finish(ctx));
+        if (accel) {      // (inside the local-step interval of the timing events; the residuals first: they are measured on what the local step left)
+            if (track) { TRY(launch_residuals(ctx, it)); ctx->res_n = it + 1; }
+            TRY(anderson_accelerate(ctx, it, it + 1 == admm_iters));
+            ctx->aa_log_n = it + 1;
+        }
         TRY(mark(ctx, timed));
-        if (track) { TRY(launch_residuals(ctx, it)); ctx->res_n = it + 1; }
+        if (track && !accel) { TRY(launch_residuals(ctx, it)); ctx->res_n = it + 1; }
         TRY(launch_rhs(ctx));
         TRY(mark(ctx, timed));
         if (ctx->world > 1 && ctx->levels_top.empty()) {     // contiguous sharding: the whole RHS is summed, the solve is replicated

@@ -25,6 +25,7 @@
 #include "kernels_mesh.hpp"
 #include "kernels_energy.hpp"
 #include "kernels_gradient.hpp"
+#include "kernels_anderson.hpp"
 
 extern "C" int omp_get_max_threads(void);
 
@@ -72,6 +73,7 @@ extern "C" {
 #include "abi_setup.inc"
 #include "abi_energy.inc"
 #include "abi_gradient.inc"
+#include "abi_anderson.inc"
 #include "abi_step.inc"
 #include "abi_parity.inc"
 

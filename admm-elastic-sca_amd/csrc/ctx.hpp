@@ -62,6 +62,7 @@ struct Batch {
     // admm_hip_batch_stress: the stress SoA [7][n_local] and the rest volumes
     double *d_gg = nullptr, *d_gstress = nullptr, *d_gvol = nullptr; int *d_gcnt = nullptr; long long gr_cf_off = 0;
     std::vector<double> G;                // [12][n_local] selector block per element, corners in device order
+    long long aa_off_z = 0, aa_off_u = 0; // Anderson acceleration (abi_anderson.inc): where the batch's z and u sit in every state-sized buffer
     // ---- ADMM_KIND_GENERIC (user-defined forces): selector rows as CSR over the batch's rows
     std::vector<int64_t> g_elem_row;      // [n_total + 1] first batch row of every element
     std::vector<int64_t> g_rowptr;        // [rows + 1]
@@ -275,6 +276,13 @@ struct admm_hip_ctx {
     // CSRs of gradient_gather_kernel (0: elastic batches, 1: anchor batches), built by the first admm_hip_node_forces
     bool gr_ready = false, gr_csr_ready = false; double *d_gr_cf = nullptr, *d_gr_out = nullptr;
     int *d_gr_ptr[2] = {nullptr, nullptr}, *d_gr_stride[2] = {nullptr, nullptr}; long long *d_gr_off[2] = {nullptr, nullptr};
+    // Anderson acceleration (abi_anderson.inc, kernels_anderson.hpp; window 0 = off, the default; every buffer created by the first step
+    // that needs it, again when the window grows).  aa_T: doubles per state-sized vector (all batches' z and u, each segment at an even
+    // offset), aa_nblk: blocks of the elementwise launches; d_aa_ring, allocated for the window aa_cap_m, used as [2][aa_m + 1][aa_T]: the history's g, then its f;
+    // d_aa_log [aa_log_cap]: one record per iteration of the last step
+    int aa_m = 0, aa_cap_m = 0, aa_nblk = 0, aa_log_cap = 0, aa_log_n = 0; long long aa_T = 0; bool aa_ran = false;
+    void *d_aa_seg = nullptr, *d_aa_state = nullptr; admm_hip_acceleration_record *d_aa_log = nullptr;
+    double *d_aa_sin = nullptr, *d_aa_ring = nullptr, *d_aa_part = nullptr;
 
     // user-defined forces: host round trip per ADMM iteration (see admm_hip_add_generic_batch)
     admm_hip_project_fn project_hook = nullptr; void *project_user = nullptr;

@@ -326,6 +326,10 @@ int upload_all(admm_hip_ctx *ctx) {
     HIPCHK(hipSetDevice(ctx->device_id));
     free_device(ctx);
     ctx->res_ready = false;
+    // (Anderson acceleration's buffers went with the rest: the next accelerated step creates them again)
+    ctx->d_aa_seg = nullptr; ctx->d_aa_state = nullptr; ctx->d_aa_log = nullptr; ctx->d_aa_sin = nullptr; ctx->d_aa_ring = nullptr; ctx->d_aa_part = nullptr;
+    ctx->aa_cap_m = 0; ctx->aa_log_cap = 0; ctx->aa_log_n = 0; ctx->aa_ran = false;
+    for (Batch &b : ctx->batches) b.d_G = nullptr;
     {
         std::vector<double> px = permute_nodes(ctx->x, F.perm, 3), pv = permute_nodes(ctx->v, F.perm, 3), pm = permute_nodes(ctx->m3, F.perm, 3);
         TRY(upload(ctx, &ctx->d_x, px)); TRY(upload(ctx, &ctx->d_v, pv)); TRY(upload(ctx, &ctx->d_m3, pm));

@@ -49,11 +49,12 @@ public:
                 else if (arg == "-dt") val >> timestep_s;
                 else if (arg == "-v") val >> verbose;
                 else if (arg == "-it") val >> admm_iters;
+                else if (arg == "-aa") val >> anderson_window;
             }
             if (argc > 0) { std::string arg(argv[argc - 1]); if (arg == "-help") help(); }
         }
         void help() {                               // System.cpp:200-208
-            printf("\n==========================================\nArgs:\n\t-dt: time step (s)\n\t-v: verbosity (higher -> show more)\n\t-it: # admm iters\n==========================================\n");
+            printf("\n==========================================\nArgs:\n\t-dt: time step (s)\n\t-v: verbosity (higher -> show more)\n\t-it: # admm iters\n\t-aa: Anderson acceleration window (0 = off)\n==========================================\n");
         }
         double timestep_s;
         int verbose;
@@ -66,7 +67,11 @@ public:
         // extension, no reference counterpart: every ADMM iteration of step() records inertia(x_k) and elastic(x_k) of the incremental
         // potential (System::objective(); admm_hip_enable_objective).  Not available on a sharded system.
         bool track_objective;
-        Settings() : timestep_s(0.04), verbose(1), admm_iters(10), residual_tol_primal(0.0), residual_tol_dual(0.0), residual_check_every(1), track_objective(false) {}
+        // extension, no reference counterpart: Anderson acceleration of the ADMM iteration with a history of that many iterations
+        // (0 .. 8; admm_hip_set_acceleration, System::acceleration_log()).  0 (default) = the reference's iteration.  Not available on
+        // a sharded system or with user-defined forces.
+        int anderson_window;
+        Settings() : timestep_s(0.04), verbose(1), admm_iters(10), residual_tol_primal(0.0), residual_tol_dual(0.0), residual_check_every(1), track_objective(false), anderson_window(0) {}
     } settings;
 
     double elapsed_s;
@@ -327,6 +332,7 @@ public:
         if (!check(admm_hip_upload_state(gpu, m_x.data(), m_v.data()))) return false;
         if (!check(admm_hip_set_tolerance(gpu, settings.residual_tol_primal, settings.residual_tol_dual, settings.residual_check_every < 1 ? 1 : settings.residual_check_every))) return false;
         if (!check(admm_hip_enable_objective(gpu, settings.track_objective ? 1 : 0))) return false;
+        if (!check(admm_hip_set_acceleration(gpu, settings.anderson_window))) return false;
         if (!check(admm_hip_step(gpu, settings.admm_iters))) return false;
         if (!check(admm_hip_download_state(gpu, m_x.data(), m_v.data()))) return false;
         // released MovingAnchors follow their node: point->pos = Dx (AnchorForce.cpp:80-83)
@@ -430,6 +436,17 @@ public:
         o.inertia.resize(n); o.elastic.resize(n);
         if (!check(admm_hip_get_objective(gpu, o.inertia.data(), o.elastic.data(), n, &n))) { o.inertia.clear(); o.elastic.clear(); }
         return o;
+    }
+
+    // the last step()'s Anderson acceleration records under settings.anderson_window > 0, one per ADMM iteration (include/admm_hip.h)
+    std::vector<admm_hip_acceleration_record> acceleration_log() {
+        std::vector<admm_hip_acceleration_record> log;
+        if (!initialized) return log;
+        int n = 0;
+        if (!check(admm_hip_get_acceleration_log(gpu, nullptr, 0, &n)) || n <= 0) return log;
+        log.resize(n);
+        if (!check(admm_hip_get_acceleration_log(gpu, log.data(), n, &n))) log.clear();
+        return log;
     }
 
     admm_hip_ctx *context() { return gpu; }

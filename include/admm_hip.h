@@ -828,6 +828,50 @@ int admm_hip_node_forces(admm_hip_ctx *ctx, double *f_elastic, double *f_anchor,
 int admm_hip_gradient_query(int kind, int64_t n, const double *dx, const double *params, const double *rest, const double *scale, double *g);
 int admm_hip_stress_query(int kind, int64_t n, const double *dx, const double *params, const double *volume, double *stress7);
 
+/* ---- Anderson acceleration of the ADMM iteration ---------------------------------------------------------------------------------------
+ * Extension, no reference counterpart (Zhang, Peng, Ouyang, Deng: Accelerating ADMM for Efficient Simulation and Optimization, 2019).
+ * One ADMM iteration maps the state s = (z, u) over all elements of all built-in batches to G(s): the right-hand side and the solve turn
+ * s into x, the local step turns (x, u) into the next (z, u).  With a window m >= 1 every iteration of admm_hip_step runs, between its
+ * local step and its right-hand side,
+ *     g = G(s_in) (what the local step left),  f = g - s_in (s_in: the z, u the iteration started from; at a frame's first iteration
+ *     z = D x),  rho = sum_e w_e^2 (|dz_e|^2 + |du_e|^2)   (its u part is the square of the primal residual of admm_hip_get_residuals).
+ *   Accept  -- the frame's first iteration, the first one after a reset, or rho < the rho of the last accepted iteration: s_def <- g;
+ *     (g, f) joins the history (the last m + 1 entries); with m_k = entries - 1 differences dF, dG of adjacent entries, theta solves
+ *     (dF^T W^2 dF + 1e-12 tr(dF^T W^2 dF) / m_k I) theta = dF^T W^2 f and s_out = g - sum_j theta_j dG_j (m_k = 0: s_out = g).
+ *   Reset   -- otherwise: s_out <- s_def, the history is emptied, the next iteration is accepted whatever its rho.
+ *   The LAST scheduled iteration of a step never extrapolates (s_out = g, or s_def on a reset): what ends a frame and what carries u into
+ *     the next frame or a checkpoint is an un-extrapolated output of G.  A tolerance exit (admm_hip_set_tolerance) is decided on the host
+ *     one iteration later and may end the frame on an extrapolated iterate.
+ * s_out goes to the batches' z and u (and the right-hand-side shares are rebuilt from it) before the iteration goes on.  The history
+ * lives within a frame: a checkpoint holds what it held.  The hyperelastic kinds' warm start is not part of s; the safeguard covers
+ * that.  The tracked residuals and the tolerance test keep their definitions, against the iterate that entered the iteration.
+ * Everything is decided on the device: no host synchronisation is added.  Sums use no atomics and an order that depends only on the
+ * element counts: results are bitwise reproducible.  One definition of the small solve, csrc/anderson.hpp, for host and device.
+ * Cost: the history is 2 (m + 1) copies of (z, u), allocated by the first step that needs it (1M-tet bar, m = 6: 2.0 GB); a
+ * step with m >= 1 runs the eager loop (no captured graph, like residual tracking) and stores the tets' z (admm_hip_keep_z is moot).
+ *   admm_hip_set_acceleration   window m, 0 <= m <= 8 (else ADMM_ERR_ARG); 0 = off, the default: admm_hip_step launches exactly what it
+ *                              did, and captured graphs stay valid.  Before or after finalize, on a host-only context too.  With
+ *                              m >= 1 admm_hip_step returns ADMM_ERR_UNSUPPORTED for a context with user-defined (generic) batches
+ *                              or a sharded one (world > 1: the Gram matrix would have to be all-reduced).
+ *   admm_hip_get_acceleration_log  one record per ADMM iteration of the last step, at most `capacity`; *n = the iterations it ran.
+ *                              gram, rhs: the m_used x m_used system the device solved before regularisation (row stride 8; differences
+ *                              oldest first); theta: its solution (zeros when solve_failed: a pivot was not positive; no extrapolation
+ *                              then); on a reset m_used = 0.  extrapolated: s_out differs from g by the theta combination.
+ *   admm_hip_get_acceleration_default  the stored s_def of one batch, z and u [n_local][rows] in the layout of admm_hip_read_local
+ *                              (either may be NULL).  ADMM_ERR_STATE before the first accelerated step.
+ *   admm_hip_acceleration_query  context-free host twin of the device's solve, the same bits; needs no GPU: gram [m_k][m_k] row-major
+ *                              (its lower triangle is read), rhs [m_k] -> theta [m_k] (zeros where a pivot is not positive).
+ *                              ADMM_ERR_ARG: m_k outside 1..8, a NULL array.                                                          */
+typedef struct admm_hip_acceleration_record {
+    double rho;
+    int32_t accepted, m_used, extrapolated, solve_failed;
+    double theta[8], gram[64], rhs[8];
+} admm_hip_acceleration_record;
+int admm_hip_set_acceleration(admm_hip_ctx *ctx, int window);
+int admm_hip_get_acceleration_log(admm_hip_ctx *ctx, admm_hip_acceleration_record *records, int capacity, int *n);
+int admm_hip_get_acceleration_default(admm_hip_ctx *ctx, int batch, double *z, double *u);
+int admm_hip_acceleration_query(int m_k, const double *gram, const double *rhs, double *theta);
+
 #ifdef __cplusplus
 }
 #endif
