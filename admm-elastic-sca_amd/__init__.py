@@ -74,6 +74,18 @@ class ForceInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ReactionInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("batches_collision", "batches_anchor", "batches_skipped", "n_contacts")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# admm_hip_contact: 64 bytes, the four bytes behind `node` are padding
+CONTACT_DTYPE = np.dtype(dict(names=["node", "f", "point", "depth"], formats=[np.int32, (np.float64, 3), (np.float64, 3), np.float64],
+                              offsets=[0, 8, 32, 56], itemsize=64))
+
+
 class AccelerationRecord(C.Structure):
     _fields_ = [("rho", C.c_double)] + [(n, C.c_int32) for n in ("accepted", "m_used", "extrapolated", "solve_failed")] + \
                [("theta", C.c_double * 8), ("gram", C.c_double * 64), ("rhs", C.c_double * 8)]
@@ -135,6 +147,11 @@ def lib():
         L.admm_hip_get_acceleration_log.argtypes = [C.c_void_p, C.POINTER(AccelerationRecord), C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_get_acceleration_default.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
         L.admm_hip_acceleration_query.argtypes = [C.c_int, _dp, _dp, _dp]
+        L.admm_hip_batch_reaction.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        L.admm_hip_node_reactions.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(ReactionInfo)]
+        L.admm_hip_get_contacts.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.admm_hip_contact_resultant.argtypes = [C.c_void_p, C.c_double, _dp, _dp, C.POINTER(C.c_int64)]
+        L.admm_hip_reaction_query.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _ip, _dp]
         L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
         L.admm_hip_add_nodes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
@@ -534,6 +551,24 @@ def acceleration_query(gram, rhs):
     if rc:
         raise AdmmHipError("admm_hip_acceleration_query error %d" % rc)
     return th
+
+
+def reaction_query(w2, u, z, x, depth_min=1e-10, pivot=(0.0, 0.0, 0.0)):
+    """the reactions of one-node constraints on the host (admm_hip_reaction_query; csrc/reaction.hpp, the device's bits; needs no GPU):
+    w2 [n] (or a scalar): weight^2, u, z, x [n][3] -> dict(f [n][3] = w2 ((z - u) - x), depth [n] = |u|, flag [n] = depth > depth_min,
+    force [3], torque [3]: the resultant of the flagged elements about `pivot`, summed in the order csrc/reaction.hpp states)"""
+    u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 3)
+    n = u.shape[0]
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, 3)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+    assert z.shape == u.shape and x.shape == u.shape
+    w = np.ascontiguousarray(np.broadcast_to(np.asarray(w2, dtype=np.float64), (n,)))
+    pv = np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
+    f = np.zeros((n, 3)); depth = np.zeros(n); flag = np.zeros(n, np.int32); r6 = np.zeros(6)
+    rc = lib().admm_hip_reaction_query(n, _d(w), _d(u), _d(z), _d(x), float(depth_min), _d(pv), _d(f), _d(depth), _i(flag), _d(r6))
+    if rc:
+        raise AdmmHipError("admm_hip_reaction_query error %d" % rc)
+    return dict(f=f, depth=depth, flag=flag.astype(bool), force=r6[:3].copy(), torque=r6[3:].copy())
 
 
 def stress_query(kind, dx, params, volume):
@@ -939,6 +974,39 @@ class System:
         d = info.as_dict()
         d.update(elastic=fe, anchor=fa)
         return d
+
+    # ---- contact and anchor reactions of the last frame (extension; include/admm_hip.h) ----
+    def batch_reaction(self, batch):
+        """-> (f [n_local][3], depth [n_local]) of one COLLISION or ANCHOR batch, in read_local's order: the force every element's
+        constraint exerted on its node in the last frame, f = w^2 ((z - u) - x), and |u|"""
+        n = self.local_elements(batch).size
+        f = np.zeros((n, 3)); depth = np.zeros(n)
+        self._chk(self.L.admm_hip_batch_reaction(self.h, batch, _d(f), _d(depth)))
+        return f, depth
+
+    def node_reactions(self):
+        """-> (f_contact [n_nodes][3], f_anchor [n_nodes][3], info) in the caller's node order; info: dict(batches_collision,
+        batches_anchor, batches_skipped, n_contacts: the nodes with depth > 0); a sharded context returns this rank's share"""
+        fc = np.zeros((self.n_nodes, 3)); fa = np.zeros((self.n_nodes, 3)); info = ReactionInfo()
+        self._chk(self.L.admm_hip_node_reactions(self.h, _d(fc), _d(fa), C.byref(info)))
+        return fc, fa, info.as_dict()
+
+    def contacts(self, depth_min=1e-10, capacity=None):
+        """-> the nodes in contact (depth > depth_min) as a structured array with the fields node, f, point, depth, ascending node index.
+        depth_min, a length: above the rounding residue a free node's u carries (a few ulp of |x|), below any penetration you care about.
+        capacity (default: all nodes) bounds the records returned; the true count of the last call stays in `last_contact_count`."""
+        cap = self.n_nodes if capacity is None else int(capacity)
+        rec = np.zeros(max(cap, 0), CONTACT_DTYPE); cnt = C.c_int64(0)
+        self._chk(self.L.admm_hip_get_contacts(self.h, float(depth_min), rec.ctypes.data_as(C.c_void_p) if cap > 0 else None, cap, C.byref(cnt)))
+        self.last_contact_count = cnt.value
+        return rec[:min(cnt.value, max(cap, 0))]
+
+    def contact_resultant(self, pivot=(0.0, 0.0, 0.0), depth_min=1e-10):
+        """-> (force [3], torque [3] about `pivot`, count) over the nodes in contact (depth > depth_min)"""
+        pv = np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
+        out = np.zeros(6); cnt = C.c_int64(0)
+        self._chk(self.L.admm_hip_contact_resultant(self.h, float(depth_min), _d(pv), _d(out), C.byref(cnt)))
+        return out[:3].copy(), out[3:].copy(), cnt.value
 
     def enable_objective(self, on=True):
         self._chk(self.L.admm_hip_enable_objective(self.h, 1 if on else 0))

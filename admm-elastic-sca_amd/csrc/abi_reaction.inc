@@ -1,0 +1,186 @@
+// abi_reaction.inc -- C ABI: the reactions of the one-node constraints (COLLISION, ANCHOR) in the last frame, per element and per node,
+// the compact list of the nodes in contact and their resultant (kernels_reaction.hpp, reaction.hpp)
+// (a part of the device translation unit admm_hip.hip: the kernels can live in one translation unit only)
+// Extension, no reference counterpart.  Nothing here writes x, v, u, z, the warm starts, the cost counters or the sides, and nothing
+// drops a captured graph: the kernels read the state and write buffers of their own.  Every launch and copy is asynchronous on the
+// context's stream, which the call then waits for once (DESIGN.md section 7, "Streams").
+
+static bool reaction_reported(const Batch &b) { return b.kind == ADMM_KIND_COLLISION || b.kind == ADMM_KIND_ANCHOR; }
+static int reaction_blocks(int n) { return (n + admm_dev::RX_BLOCK - 1) / admm_dev::RX_BLOCK; }
+
+// what every entry checks after its own arguments: a device context with a usable factor that has stepped at least once
+static int require_reactions(admm_hip_ctx *ctx, const char *who) {
+    TRY(require_factor(ctx));
+    if (ctx->frames == 0) return fail(ctx, ADMM_ERR_STATE, "%s: no frame has run yet: a reaction is that of the last admm_hip_step", who);
+    return ADMM_OK;
+}
+
+// every buffer the kernels write and the gather's two CSRs (0: the collision batches, 1: the anchor batches; batch order, then local
+// element order), created by the first call
+static int ensure_reaction_buffers(admm_hip_ctx *ctx) {
+    using namespace admm_dev;
+    HIPCHK(hipSetDevice(ctx->device_id));
+    if (ctx->rx_ready) return ADMM_OK;
+    const int n = ctx->n_nodes;
+    long long total = 0;      // (what a call that failed further down allocated is reused: the sizes depend on the scene alone)
+    for (Batch &b : ctx->batches) {
+        if (!reaction_reported(b)) continue;
+        b.rx_off = total;
+        total += (long long)RX_ROWS * std::max(b.n_local, 1);
+    }
+    if (!ctx->d_rx_el) TRY(dalloc(ctx, &ctx->d_rx_el, (size_t)std::max(total, 1ll)));
+    if (!ctx->d_rx_node) TRY(dalloc(ctx, &ctx->d_rx_node, 10 * (size_t)std::max(n, 1)));
+    if (!ctx->d_rx_blk) TRY(dalloc(ctx, &ctx->d_rx_blk, 2 * (size_t)std::max(reaction_blocks(n), 1)));
+    if (!ctx->d_rx_count) TRY(dalloc(ctx, &ctx->d_rx_count, 1));
+    if (!ctx->d_rx_rec) { ContactRecord *r = nullptr; TRY(dalloc(ctx, &r, (size_t)std::max(n, 1))); ctx->d_rx_rec = r; }
+    if (!ctx->d_rx_part) TRY(dalloc(ctx, &ctx->d_rx_part, 6 * (size_t)std::max(energy_blocks(n), 1) + 6));
+    for (int which = 0; which < 2; ++which) {
+        const int kind = which ? ADMM_KIND_ANCHOR : ADMM_KIND_COLLISION;
+        std::vector<int> ptr((size_t)n + 1, 0);
+        for (const Batch &b : ctx->batches) {
+            if (b.kind != kind) continue;
+            for (int el = 0; el < b.n_local; ++el) ptr[(size_t)b.idx[b.local[el]] + 1]++;
+        }
+        for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
+        std::vector<int> pos(ptr.begin(), ptr.end() - 1), stride((size_t)std::max(ptr[n], 1), 0);
+        std::vector<long long> off((size_t)std::max(ptr[n], 1), 0);
+        for (const Batch &b : ctx->batches) {
+            if (b.kind != kind) continue;
+            for (int el = 0; el < b.n_local; ++el) {
+                const int k = pos[b.idx[b.local[el]]]++;
+                off[k] = b.rx_off + el;
+                stride[k] = b.n_local;
+            }
+        }
+        if (!ctx->d_rx_ptr[which]) TRY(dalloc(ctx, &ctx->d_rx_ptr[which], ptr.size()));
+        if (!ctx->d_rx_off[which]) TRY(dalloc(ctx, &ctx->d_rx_off[which], off.size()));
+        if (!ctx->d_rx_stride[which]) TRY(dalloc(ctx, &ctx->d_rx_stride[which], stride.size()));
+        HIPCHK(hipMemcpyAsync(ctx->d_rx_ptr[which], ptr.data(), sizeof(int) * ptr.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->d_rx_off[which], off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->d_rx_stride[which], stride.data(), sizeof(int) * stride.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));      // (the vectors leave scope)
+    }
+    ctx->rx_ready = true;
+    return ADMM_OK;
+}
+
+// the per-element kernel of one batch: seven rows at rx_off of d_rx_el
+static int launch_batch_reaction(admm_hip_ctx *ctx, const Batch &b) {
+    using namespace admm_dev;
+    const int nblk = energy_blocks(b.n_local);
+    if (nblk) hipLaunchKernelGGL(reaction_elem_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, b.n_local, (const int *)b.d_idx, (const double *)b.d_w2, (const double *)b.d_u,
+                                 (const double *)b.d_z, (const double *)ctx->d_x, ctx->d_rx_el + b.rx_off);
+    HIPCHK(hipGetLastError());
+    return ADMM_OK;
+}
+
+// every reported batch's elements, then the nodes' sums, depths and points -> d_rx_node
+static int launch_node_reactions(admm_hip_ctx *ctx, admm_hip_reaction_info *info) {
+    using namespace admm_dev;
+    for (const Batch &b : ctx->batches) {
+        if (!reaction_reported(b)) { if (info) ++info->batches_skipped; continue; }
+        if (info) ++(b.kind == ADMM_KIND_ANCHOR ? info->batches_anchor : info->batches_collision);
+        TRY(launch_batch_reaction(ctx, b));
+    }
+    const int n = ctx->n_nodes, nblk = energy_blocks(n);
+    if (nblk) hipLaunchKernelGGL(reaction_gather_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, n, (const int *)ctx->d_rx_ptr[0], (const long long *)ctx->d_rx_off[0], (const int *)ctx->d_rx_stride[0],
+                                 (const int *)ctx->d_rx_ptr[1], (const long long *)ctx->d_rx_off[1], (const int *)ctx->d_rx_stride[1], (const double *)ctx->d_rx_el, ctx->d_rx_node);
+    HIPCHK(hipGetLastError());
+    return ADMM_OK;
+}
+
+// count, scan and -- with `records` -- scatter of the nodes with depth > depth_min into d_rx_rec; the count stays on the device, at d_rx_count
+static int launch_compaction(admm_hip_ctx *ctx, double depth_min, bool records) {
+    using namespace admm_dev;
+    const int n = ctx->n_nodes, nblk = reaction_blocks(n);
+    int *cnt = ctx->d_rx_blk, *off = ctx->d_rx_blk + std::max(nblk, 1);
+    const double *depth = ctx->d_rx_node + 6 * (size_t)n;
+    if (nblk) hipLaunchKernelGGL(contact_count_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, depth, depth_min, cnt);
+    hipLaunchKernelGGL(contact_scan_kernel, dim3(1), dim3(RX_SCAN), 0, ctx->stream, nblk, (const int *)cnt, off, ctx->d_rx_count);
+    if (records && nblk) hipLaunchKernelGGL(contact_scatter_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, (const double *)ctx->d_rx_node, depth_min, (const int *)off, (long long)n,
+                                            (ContactRecord *)ctx->d_rx_rec);
+    HIPCHK(hipGetLastError());
+    return ADMM_OK;
+}
+
+int admm_hip_batch_reaction(admm_hip_ctx *ctx, int batch, double *f, double *depth) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (batch < 0 || batch >= (int)ctx->batches.size()) return ADMM_ERR_ARG;
+    const Batch &b = ctx->batches[batch];
+    if (!reaction_reported(b)) return fail(ctx, ADMM_ERR_UNSUPPORTED, "batch_reaction: batch %d (kind %d) is neither a collision nor an anchor batch", batch, b.kind);
+    TRY(require_reactions(ctx, "batch_reaction"));
+    TRY(ensure_reaction_buffers(ctx));
+    TRY(launch_batch_reaction(ctx, b));
+    const int n = b.n_local;
+    std::vector<double> t(4 * (size_t)std::max(n, 1), 0.0);
+    if (n) HIPCHK(hipMemcpyAsync(t.data(), ctx->d_rx_el + b.rx_off, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int el = 0; el < n; ++el) {
+        if (f) for (int j = 0; j < 3; ++j) f[3 * (size_t)el + j] = t[(size_t)j * n + el];
+        if (depth) depth[el] = t[(size_t)3 * n + el];
+    }
+    return ADMM_OK;
+}
+
+int admm_hip_node_reactions(admm_hip_ctx *ctx, double *f_contact, double *f_anchor, admm_hip_reaction_info *info) {
+    if (!ctx) return ADMM_ERR_ARG;
+    TRY(require_reactions(ctx, "node_reactions"));
+    TRY(ensure_reaction_buffers(ctx));
+    admm_hip_reaction_info I{};
+    TRY(launch_node_reactions(ctx, &I));
+    TRY(launch_compaction(ctx, 0.0, false));
+    const size_t n = (size_t)ctx->n_nodes;
+    long long count = 0;
+    if (f_contact && n) HIPCHK(hipMemcpyAsync(f_contact, ctx->d_rx_node, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (f_anchor && n) HIPCHK(hipMemcpyAsync(f_anchor, ctx->d_rx_node + 3 * n, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&count, ctx->d_rx_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    I.n_contacts = count;
+    if (info) *info = I;
+    return ADMM_OK;
+}
+
+int admm_hip_get_contacts(admm_hip_ctx *ctx, double depth_min, admm_hip_contact *records, int64_t capacity, int64_t *count) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (!(depth_min >= 0.0) || capacity < 0 || (capacity && !records)) return fail(ctx, ADMM_ERR_ARG, "get_contacts: depth_min must be >= 0 (got %g), capacity >= 0 and records given with it", depth_min);
+    TRY(require_reactions(ctx, "get_contacts"));
+    TRY(ensure_reaction_buffers(ctx));
+    TRY(launch_node_reactions(ctx, nullptr));
+    TRY(launch_compaction(ctx, depth_min, true));
+    // (the count is not known before the synchronisation: the copy covers what the capacity could hold, the caller gets the filled part)
+    static_assert(sizeof(admm_hip_contact) == sizeof(admm_dev::ContactRecord), "admm_hip_contact is the device's record");
+    const size_t want = (size_t)std::min<int64_t>(capacity, ctx->n_nodes);
+    std::vector<admm_hip_contact> tmp(want);
+    long long c = 0;
+    if (want) HIPCHK(hipMemcpyAsync(tmp.data(), ctx->d_rx_rec, sizeof(admm_hip_contact) * want, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&c, ctx->d_rx_count, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const size_t k = (size_t)std::min<long long>(c, (long long)want);
+    if (k) std::memcpy(records, tmp.data(), sizeof(admm_hip_contact) * k);
+    if (count) *count = c;
+    return ADMM_OK;
+}
+
+int admm_hip_contact_resultant(admm_hip_ctx *ctx, double depth_min, const double pivot[3], double out6[6], int64_t *count) {
+    using namespace admm_dev;
+    if (!ctx) return ADMM_ERR_ARG;
+    if (!(depth_min >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "contact_resultant: depth_min must be >= 0, got %g", depth_min);
+    TRY(require_reactions(ctx, "contact_resultant"));
+    TRY(ensure_reaction_buffers(ctx));
+    TRY(launch_node_reactions(ctx, nullptr));
+    TRY(launch_compaction(ctx, depth_min, true));
+    const int nblk = energy_blocks(ctx->n_nodes);
+    double *part = ctx->d_rx_part, *tot = ctx->d_rx_part + 6 * (size_t)std::max(nblk, 1);
+    const double p0 = pivot ? pivot[0] : 0.0, p1 = pivot ? pivot[1] : 0.0, p2 = pivot ? pivot[2] : 0.0;
+    if (nblk) hipLaunchKernelGGL(contact_resultant_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, (const ContactRecord *)ctx->d_rx_rec, p0, p1, p2, nblk, part);
+    for (int q = 0; q < 6; ++q)
+        hipLaunchKernelGGL(energy_reduce_kernel, dim3(1), dim3(ENERGY_REDUCE), 0, ctx->stream, nblk, (const double *)(part + (size_t)q * nblk), (const int *)nullptr, tot + q, (long long *)nullptr);
+    HIPCHK(hipGetLastError());
+    double h[6]; long long c = 0;
+    HIPCHK(hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&c, ctx->d_rx_count, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (out6) for (int q = 0; q < 6; ++q) out6[q] = h[q];
+    if (count) *count = c;
+    return ADMM_OK;
+}

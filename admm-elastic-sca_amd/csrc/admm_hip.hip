@@ -26,6 +26,7 @@
 #include "kernels_energy.hpp"
 #include "kernels_gradient.hpp"
 #include "kernels_anderson.hpp"
+#include "kernels_reaction.hpp"
 
 extern "C" int omp_get_max_threads(void);
 
@@ -74,6 +75,7 @@ extern "C" {
 #include "abi_energy.inc"
 #include "abi_gradient.inc"
 #include "abi_anderson.inc"
+#include "abi_reaction.inc"
 #include "abi_step.inc"
 #include "abi_parity.inc"
 

@@ -62,6 +62,7 @@ struct Batch {
     // admm_hip_batch_stress: the stress SoA [7][n_local] and the rest volumes
     double *d_gg = nullptr, *d_gstress = nullptr, *d_gvol = nullptr; int *d_gcnt = nullptr; long long gr_cf_off = 0;
     std::vector<double> G;                // [12][n_local] selector block per element, corners in device order
+    long long rx_off = 0;                 // reactions (abi_reaction.inc): where a collision / anchor batch's rows sit in the context's d_rx_el
     long long aa_off_z = 0, aa_off_u = 0; // Anderson acceleration (abi_anderson.inc): where the batch's z and u sit in every state-sized buffer
     // ---- ADMM_KIND_GENERIC (user-defined forces): selector rows as CSR over the batch's rows
     std::vector<int64_t> g_elem_row;      // [n_total + 1] first batch row of every element
@@ -276,6 +277,13 @@ struct admm_hip_ctx {
     // CSRs of gradient_gather_kernel (0: elastic batches, 1: anchor batches), built by the first admm_hip_node_forces
     bool gr_ready = false, gr_csr_ready = false; double *d_gr_cf = nullptr, *d_gr_out = nullptr;
     int *d_gr_ptr[2] = {nullptr, nullptr}, *d_gr_stride[2] = {nullptr, nullptr}; long long *d_gr_off[2] = {nullptr, nullptr};
+    // reactions of the collision and anchor batches (abi_reaction.inc; every buffer created by the first call).  d_rx_el: every reported
+    // batch's elements, SoA [7][n_local] per batch at Batch::rx_off (f, depth, z); d_rx_node: f_contact [n][3], f_anchor [n][3], depth [n],
+    // point [n][3] in the caller's node order; the two CSRs of reaction_gather_kernel (0: collision batches, 1: anchor batches); d_rx_blk:
+    // the compaction's block counts, then their offsets; d_rx_count: the contacts' count; d_rx_rec [n_nodes] records; d_rx_part: the
+    // resultant's partials [6][blocks], then its six totals
+    bool rx_ready = false; double *d_rx_el = nullptr, *d_rx_node = nullptr, *d_rx_part = nullptr; int *d_rx_blk = nullptr; long long *d_rx_count = nullptr; void *d_rx_rec = nullptr;
+    int *d_rx_ptr[2] = {nullptr, nullptr}, *d_rx_stride[2] = {nullptr, nullptr}; long long *d_rx_off[2] = {nullptr, nullptr};
     // Anderson acceleration (abi_anderson.inc, kernels_anderson.hpp; window 0 = off, the default; every buffer created by the first step
     // that needs it, again when the window grows).  aa_T: doubles per state-sized vector (all batches' z and u, each segment at an even
     // offset), aa_nblk: blocks of the elementwise launches; d_aa_ring, allocated for the window aa_cap_m, used as [2][aa_m + 1][aa_T]: the history's g, then its f;

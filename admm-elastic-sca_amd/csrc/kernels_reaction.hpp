@@ -1,0 +1,153 @@
+// kernels_reaction.hpp -- the reactions of reaction.hpp evaluated on the device: per COLLISION / ANCHOR element the force its constraint
+// exerted on its node in the last frame and its depth, the nodes' sums in the caller's node order, the compact list of the nodes in
+// contact and their resultant.  Extension, no reference counterpart; no product path launches any of this unless the caller asks
+// (admm_hip_batch_reaction, admm_hip_node_reactions, admm_hip_get_contacts, admm_hip_contact_resultant).  Everything reads u, z, x and
+// writes buffers of its own; no atomics anywhere: two calls on the same state give the same bits.
+//
+// reaction_elem_kernel, one lane per element, ENERGY_BLOCK = 64-element blocks: reads w2[e], the element's u and z (SoA [3][n], coalesced)
+// and its node's x (gathered through idx) and writes seven rows of SoA [7][n]: f0 f1 f2, depth, z0 z1 z2 (the point: a copy, so that
+// the gather reads one buffer with one stride).  A lane beyond the batch returns before its first load.
+//
+// reaction_gather_kernel, one lane per node in the CALLER's node order: two CSRs built on the host at first use (0: the collision
+// batches, 1: the anchor batches), entries in batch order, then local element order.  Per CSR the lane adds its entries' forces
+// sequentially, s = 0.0; s = s + v.  Over the collision entries it also keeps the node's depth and point: depth = 0.0, point = 0; an entry
+// with d > depth replaces both (the largest depth; ties and d = 0 keep the earlier one; a NaN depth never wins).  Output, one buffer:
+// f_contact [n][3], f_anchor [n][3], depth [n], point [n][3].  A node with no element gets exactly 0.0 everywhere.
+//
+// Compaction of the nodes with depth > depth_min, in ascending node index, three launches and no spinning across workgroups:
+//   contact_count_kernel    RX_BLOCK = 128 nodes per block (two waves): a wave counts by __popcll(__ballot(flag)), the waves' counts meet in LDS,
+//                           one count per block
+//   contact_scan_kernel     ONE workgroup of RX_SCAN = 64 lanes (one wave): an exclusive scan of the block counts, chunk after chunk of
+//                           64 blocks in ascending order with a running carry (a wave shuffle scan inside a chunk: no LDS, no barrier);
+//                           block offsets and the total, which stays on the device
+//   contact_scatter_kernel  the count kernel's flags again; a node's place = its block's offset + the counts of the waves before its own
+//                           (LDS) + __popcll(ballot & lanes below); writes the 64-byte record when the place is below `capacity`
+// contact_resultant_kernel: one lane per record k < count (the count is read from the device), ENERGY_BLOCK-record blocks, every lane
+// stays (k >= count: +0.0): the six terms of reaction.hpp summed per block by track_block_sum; the blocks' partials go through
+// energy_reduce_kernel, one launch per component -- the fixed-order two-stage sum of kernels_energy.hpp, restated in reaction.hpp.
+//
+// Cost: not measured, no timing claimed.  Expected to be bound by memory: an element reads 84 B (idx, w2, u, z, its node's x) and writes
+// 56 B; a node's gather reads its CSR bounds, a 12 B entry and 56 B per incident element and writes 80 B; the count reads 8 B per node,
+// the scatter 64 B per node in contact and writes as much.
+#pragma once
+#include "kernels_energy.hpp"
+#include "reaction.hpp"
+
+namespace admm_dev {
+
+constexpr int RX_BLOCK = 128, RX_WAVES = RX_BLOCK / 64, RX_SCAN = 64;
+constexpr int RX_ROWS = 7;      // rows of the element buffer: f0 f1 f2, depth, z0 z1 z2
+static_assert(admm_reaction::RESULTANT_BLOCK == ENERGY_BLOCK && admm_reaction::RESULTANT_REDUCE == ENERGY_REDUCE, "reaction.hpp restates the sums of kernels_energy.hpp");
+static_assert(RX_SCAN == 64, "contact_scan_kernel is a one-wave shuffle scan");
+
+struct ContactRecord { int node; int pad_; double f[3], point[3], depth; };      // = admm_hip_contact
+static_assert(sizeof(ContactRecord) == 64, "the record is 64 bytes");
+
+__global__ __launch_bounds__(ENERGY_BLOCK) void reaction_elem_kernel(const int n, const int *__restrict__ idx, const double *__restrict__ w2, const double *__restrict__ u,
+                                                                     const double *__restrict__ z, const double *__restrict__ x, double *__restrict__ out) {
+    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x;
+    if (e >= n) return;
+    const int id = idx[e];
+    double U[3], Z[3], X[3], f[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { U[j] = u[(size_t)j * n + e]; Z[j] = z[(size_t)j * n + e]; X[j] = x[3 * (size_t)id + j]; }
+    admm_reaction::force(w2[e], U, Z, X, f);
+    const double d = admm_reaction::depth(U);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { out[(size_t)j * n + e] = f[j]; out[(size_t)(4 + j) * n + e] = Z[j]; }
+    out[(size_t)3 * n + e] = d;
+}
+
+// entry k of a CSR: row r of its element at el[off[k] + r stride[k]]
+__global__ __launch_bounds__(ENERGY_BLOCK) void reaction_gather_kernel(const int n_nodes, const int *__restrict__ ptr_c, const long long *__restrict__ off_c, const int *__restrict__ stride_c,
+                                                                       const int *__restrict__ ptr_a, const long long *__restrict__ off_a, const int *__restrict__ stride_a,
+                                                                       const double *__restrict__ el, double *__restrict__ out) {
+    const int i = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x;
+    if (i >= n_nodes) return;
+    const size_t n = (size_t)n_nodes;
+    double s[3] = {0.0, 0.0, 0.0}, depth = 0.0, pt[3] = {0.0, 0.0, 0.0};
+    for (int k = ptr_c[i], k1 = ptr_c[i + 1]; k < k1; ++k) {
+        const double *p = el + off_c[k];
+        const size_t st = (size_t)stride_c[k];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s[j] = s[j] + p[j * st];
+        const double d = p[3 * st];
+        if (d > depth) { depth = d; pt[0] = p[4 * st]; pt[1] = p[5 * st]; pt[2] = p[6 * st]; }
+    }
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int k = ptr_a[i], k1 = ptr_a[i + 1]; k < k1; ++k) {
+        const double *p = el + off_a[k];
+        const size_t st = (size_t)stride_a[k];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a[j] = a[j] + p[j * st];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { out[3 * (size_t)i + j] = s[j]; out[3 * n + 3 * (size_t)i + j] = a[j]; out[7 * n + 3 * (size_t)i + j] = pt[j]; }
+    out[6 * n + i] = depth;
+}
+
+// depth [n_nodes] -> one count per RX_BLOCK nodes
+__global__ __launch_bounds__(RX_BLOCK) void contact_count_kernel(const int n_nodes, const double *__restrict__ depth, const double depth_min, int *__restrict__ blk_count) {
+    __shared__ int wave_count[RX_WAVES];
+    const int i = (int)blockIdx.x * RX_BLOCK + threadIdx.x;
+    const bool c = i < n_nodes && admm_reaction::in_contact(depth[i], depth_min);
+    const unsigned long long m = __ballot(c);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < RX_WAVES; ++w) t += wave_count[w]; blk_count[blockIdx.x] = t; }
+}
+
+// exclusive scan of n_blocks counts -> blk_off, *total; one wave
+__global__ __launch_bounds__(RX_SCAN) void contact_scan_kernel(const int n_blocks, const int *__restrict__ blk_count, int *__restrict__ blk_off, long long *__restrict__ total) {
+    const int lane = threadIdx.x;
+    int carry = 0;
+    for (int base = 0; base < n_blocks; base += RX_SCAN) {      // (uniform: every lane runs every chunk)
+        const int i = base + lane;
+        const int v = i < n_blocks ? blk_count[i] : 0;
+        int incl = v;
+#pragma unroll
+        for (int d = 1; d < RX_SCAN; d <<= 1) { const int o = __shfl_up(incl, d, RX_SCAN); if (lane >= d) incl += o; }
+        if (i < n_blocks) blk_off[i] = carry + incl - v;
+        carry += __shfl(incl, RX_SCAN - 1, RX_SCAN);
+    }
+    if (lane == 0) *total = carry;
+}
+
+// the records of the nodes in contact, ascending node index, from the gather's output `nodes` (its layout); places >= capacity are dropped
+__global__ __launch_bounds__(RX_BLOCK) void contact_scatter_kernel(const int n_nodes, const double *__restrict__ nodes, const double depth_min, const int *__restrict__ blk_off,
+                                                                   const long long capacity, ContactRecord *__restrict__ rec) {
+    __shared__ int wave_count[RX_WAVES];
+    const int i = (int)blockIdx.x * RX_BLOCK + threadIdx.x;
+    const size_t n = (size_t)n_nodes;
+    const double d = i < n_nodes ? nodes[6 * n + i] : 0.0;
+    const bool c = i < n_nodes && admm_reaction::in_contact(d, depth_min);
+    const unsigned long long m = __ballot(c);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_count[wave] = __popcll(m);
+    __syncthreads();
+    if (!c) return;
+    long long place = blk_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) place += wave_count[w];
+    if (place >= capacity) return;
+    ContactRecord r;
+    r.node = i; r.pad_ = 0; r.depth = d;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { r.f[j] = nodes[3 * (size_t)i + j]; r.point[j] = nodes[7 * n + 3 * (size_t)i + j]; }
+    rec[place] = r;
+}
+
+// the contacts' six terms summed per ENERGY_BLOCK records: partial [6][n_blocks]; records beyond *count add +0.0
+__global__ __launch_bounds__(ENERGY_BLOCK) void contact_resultant_kernel(const long long *__restrict__ count, const ContactRecord *__restrict__ rec, const double p0, const double p1, const double p2,
+                                                                         const int n_blocks, double *__restrict__ partial) {
+    const long long k = (long long)blockIdx.x * ENERGY_BLOCK + threadIdx.x;
+    double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (k < *count) {
+        const double pivot[3] = {p0, p1, p2};
+        const ContactRecord r = rec[k];
+        admm_reaction::resultant_terms(r.f, r.point, pivot, t);
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) track_block_sum(t[q], &partial[(size_t)q * n_blocks + blockIdx.x]);
+}
+
+} // namespace admm_dev

@@ -415,6 +415,43 @@ public:
         f.n_nonfinite = (long)info.n_nonfinite; f.batches_skipped = (long)info.batches_skipped; f.ok = true;
         return f;
     }
+    // extension, no reference counterpart (admm_hip_node_reactions): the forces the collision and the anchor constraints exerted on their
+    // nodes in the last step(), f = w^2 ((z - u) - x), [n_nodes][3] in m_x's node order; n_contacts: the nodes with depth |u| > 0.
+    // ok = false: the call failed (not initialized, no GPU, no step() yet).
+    struct NodeReactions { std::vector<double> contact, anchor; long batches_collision, batches_anchor, batches_skipped, n_contacts; bool ok; };
+    NodeReactions node_reactions() {
+        NodeReactions r; r.batches_collision = r.batches_anchor = r.batches_skipped = r.n_contacts = 0; r.ok = false;
+        if (!initialized) return r;
+        r.contact.assign((size_t)m_x.size(), 0.0); r.anchor.assign((size_t)m_x.size(), 0.0);
+        admm_hip_reaction_info info;
+        if (!check(admm_hip_node_reactions(gpu, r.contact.data(), r.anchor.data(), &info))) { r.contact.clear(); r.anchor.clear(); return r; }
+        r.batches_collision = (long)info.batches_collision; r.batches_anchor = (long)info.batches_anchor;
+        r.batches_skipped = (long)info.batches_skipped; r.n_contacts = (long)info.n_contacts; r.ok = true;
+        return r;
+    }
+    // the nodes in contact (admm_hip_get_contacts): depth > depth_min (a length: above the rounding residue of a free node's u, a few ulp of
+    // |x|, below any penetration you care about), ascending node index in m_x's order; empty when none or when the call failed
+    std::vector<admm_hip_contact> contacts(double depth_min = 1e-10) {
+        std::vector<admm_hip_contact> c;
+        if (!initialized) return c;
+        c.resize((size_t)m_x.size() / 3);
+        int64_t n = 0;
+        if (!check(admm_hip_get_contacts(gpu, depth_min, c.data(), (int64_t)c.size(), &n))) n = 0;
+        c.resize((size_t)(n < (int64_t)c.size() ? n : (int64_t)c.size()));
+        return c;
+    }
+    // their resultant (admm_hip_contact_resultant): the force and its torque about `pivot`; count < 0: the call failed
+    struct ContactResultant { double force[3], torque[3]; long count; };
+    ContactResultant contact_resultant(double px = 0.0, double py = 0.0, double pz = 0.0, double depth_min = 1e-10) {
+        ContactResultant r = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, -1};
+        if (!initialized) return r;
+        const double pivot[3] = {px, py, pz};
+        double out[6]; int64_t n = 0;
+        if (!check(admm_hip_contact_resultant(gpu, depth_min, pivot, out, &n))) return r;
+        for (int j = 0; j < 3; ++j) { r.force[j] = out[j]; r.torque[j] = out[3 + j]; }
+        r.count = (long)n;
+        return r;
+    }
     // the Cauchy stress of the tets of device batch `batch` (admm_hip_batch_stress): seven doubles per tet, xx, yy, zz, xy, xz, yz, von
     // Mises, in the order of admm_hip_read_local; empty when the call failed (not a tet batch, not initialized, no GPU)
     std::vector<double> batch_stress(int batch) {

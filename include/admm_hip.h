@@ -872,6 +872,71 @@ int admm_hip_get_acceleration_log(admm_hip_ctx *ctx, admm_hip_acceleration_recor
 int admm_hip_get_acceleration_default(admm_hip_ctx *ctx, int batch, double *z, double *u);
 int admm_hip_acceleration_query(int m_k, const double *gram, const double *rhs, double *theta);
 
+/* ---- contact and anchor reactions: which nodes touch something, and how hard -----------------------------------------------------------
+ * Extension, no reference counterpart.  A frame's last global solve satisfies
+ *     M (x - x_bar) / dt^2 = sum_i D_i^T w_i^2 (z_i - u_i - D_i x)        (up to the linear solve's residual)
+ * with z_i, u_i what the last local step stored and x the final position.  For the two kinds with D_i = I on one node, COLLISION and
+ * ANCHOR, element i's term is the force the constraint exerted on its node in that frame:
+ *     f_i = w_i^2 ((z_i - u_i) - x_node)        depth_i = |u_i| = sqrt((u0 u0 + u1 u1) + u2 u2)        point_i = z_i
+ * and a node is IN CONTACT where depth > depth_min.  A free node is not at u = 0 exactly -- u + (dx - (dx + u)) leaves rounding residue of
+ * a few ulp of |x| -- so depth_min is the caller's, in length units, >= 0 (ADMM_ERR_ARG otherwise, NaN included): choose it above that
+ * residue and below any penetration you care about.  One definition, csrc/reaction.hpp, compiled without fused multiply-adds for the host
+ * and the device: both give the same bits.  w^2 is the weight^2 the batch holds (admm_hip_set_weights / admm_hip_recompute_weights).
+ * Every compute call reads the device state as it stands, runs on the context's stream and waits for it once; none writes x, v, u, z, the
+ * warm starts, the cost counters or the sides, and none drops a captured graph.  Their buffers are created by the first call; a context
+ * that never calls them uploads and launches exactly what it did.  No atomics, fixed orders (csrc/kernels_reaction.hpp): a node adds its
+ * elements sequentially in batch order, then local element order; its depth is the largest of its collision elements' and its point the
+ * z of that element (ties: the first); the contacts come in ascending node index; the resultant is summed in the order csrc/reaction.hpp
+ * states.  Two calls on the same state return the same bits.  Cost: not measured.
+ * Order of the checks: the call's own arguments (ADMM_ERR_ARG; a batch of another kind: ADMM_ERR_UNSUPPORTED), then a host-only context
+ * (device_id < 0: ADMM_ERR_HIP, like every compute call), then ADMM_ERR_STATE before finalize, with no usable factor, or before the first
+ * admm_hip_step: a reaction is that of the last frame.
+ * Valid until the state is next changed from outside: the entries combine the u and z of the last admm_hip_step with the x the device
+ * holds now, and the library does not notice admm_hip_set_x / admm_hip_upload_state, admm_hip_write_local, admm_hip_set_weights or a
+ * local_step_only / local_step_dx in between -- after any of them the values mean nothing until the next admm_hip_step.
+ *   admm_hip_batch_reaction     one COLLISION or ANCHOR batch: f [n_local][3] and depth [n_local] in the order of admm_hip_read_local.
+ *   admm_hip_node_reactions     f_contact, f_anchor [n_nodes][3] in the caller's node order: the collision batches' and the anchor batches'
+ *                              sums.  info: the batches reported (batches_collision, batches_anchor) and passed over (batches_skipped: every
+ *                              other kind), n_contacts = the nodes with depth > 0.  A node with no such element: exactly 0.
+ *   admm_hip_get_contacts       the nodes with depth > depth_min as records {node, f, point, depth}, ascending node index; f = the node's
+ *                              f_contact.  *count = how many there are; records [capacity] receives the first min(count, capacity).
+ *                              The price of the one synchronisation: the count is not known when the copy is queued, so the call
+ *                              moves min(capacity, n_nodes) records of 64 bytes from the device whatever the count is (only the filled
+ *                              ones reach `records`).  A caller with few contacts among many nodes passes a small capacity and calls
+ *                              again when *count exceeds it, or takes the count from admm_hip_contact_resultant first.
+ *   admm_hip_contact_resultant  out6 = {sum f, sum (point - pivot) x f} over those contacts (pivot NULL: the origin), *count likewise.
+ *   admm_hip_reaction_query     context-free host evaluation, the device's bits; needs no GPU: w2 [n], u, z, x [n][3] -> f [n][3],
+ *                              depth [n], flag [n] (depth > depth_min), resultant6 over the flagged elements in index order with
+ *                              point = z.  ADMM_ERR_ARG: n < 0, depth_min not >= 0, a NULL input with n > 0.
+ * Any output pointer may be NULL.
+ * What it holds under the solver's options:
+ *   every collision form (admm_hip_debug_collision_form 0-7): the report reads only u, z and x, which every form leaves by the same
+ *     epilogue.  Friction's tangential part is inside f; normal and tangential parts are not told apart.
+ *   admm_hip_keep_z(ctx, 0): only the tet kernels honour it; the collision and anchor kernels store z in every iteration.
+ *   an early exit by tolerance: the identity holds for the last iteration that ran.
+ *   Anderson acceleration: every iteration writes its s_out to the batches' z and u and rebuilds the right-hand-side shares from them
+ *     before the solve, so what the batches hold after a frame is what the last solve consumed, extrapolated or not, reset or not.
+ *   a released anchor (active = 0) goes through the same formula, no special case: its z is x_prev + u with x_prev the iterate the last
+ *     local step saw, so f = w^2 (x_prev - x) up to rounding residue -- the last iteration's increment, zero at convergence.  The same holds
+ *     for a collision element that touches nothing: its depth is residue (no contact), its f that increment.
+ * Not covered: which list entry a contact belongs to and per-obstacle resultants (the last mover is not stored), reactions on the triangles
+ * of a body or sheet surface (the push is one-sided), user-defined (GENERIC) batches, a per-iteration history.
+ * Sharded contexts: every call covers THIS rank's local elements; the ranks' node vectors add up to the one-rank vector (they are not
+ * gathered into one), and a node's contact is reported by the rank that owns its collision element.                                    */
+typedef struct admm_hip_reaction_info {
+    int64_t batches_collision, batches_anchor, batches_skipped, n_contacts;
+} admm_hip_reaction_info;
+typedef struct admm_hip_contact {
+    int32_t node;
+    double f[3], point[3], depth;
+} admm_hip_contact;
+int admm_hip_batch_reaction(admm_hip_ctx *ctx, int batch, double *f, double *depth);
+int admm_hip_node_reactions(admm_hip_ctx *ctx, double *f_contact, double *f_anchor, admm_hip_reaction_info *info);
+int admm_hip_get_contacts(admm_hip_ctx *ctx, double depth_min, admm_hip_contact *records, int64_t capacity, int64_t *count);
+int admm_hip_contact_resultant(admm_hip_ctx *ctx, double depth_min, const double pivot[3], double out6[6], int64_t *count);
+int admm_hip_reaction_query(int64_t n, const double *w2, const double *u, const double *z, const double *x, double depth_min, const double *pivot,
+                            double *f, double *depth, int32_t *flag, double *resultant6);
+
 #ifdef __cplusplus
 }
 #endif
