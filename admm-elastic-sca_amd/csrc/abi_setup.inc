@@ -65,6 +65,7 @@ int admm_hip_create(admm_hip_ctx **out, int device_id) {
     if (const char *g = getenv("ADMM_HIP_DIST_TOP")) ctx->dist_top_wanted = atoi(g) != 0 ? 1 : 0;
     if (const char *g = getenv("ADMM_HIP_DIST_TOP_MIN_NODES")) ctx->dist_top_min_nodes = atoi(g);
     if (const char *g = getenv("ADMM_HIP_SWEEP_FUSE")) ctx->sweep_fuse = atoi(g) != 0;
+    if (const char *g = getenv("ADMM_HIP_SWEEP_FUSE_BWD")) ctx->sweep_fuse_bwd = atoi(g) != 0;
     *out = ctx;
     return ADMM_OK;
 }

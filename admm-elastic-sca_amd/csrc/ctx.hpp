@@ -258,6 +258,11 @@ struct admm_hip_ctx {
     bool sweep_fuse = true;
     int fuse_cut = -1, n_fuse = 0, fuse_lds = 0;  // cut level (-1: nothing fused), subtrees, dynamic LDS bytes of the fused launches
     int *d_fuse_rec = nullptr; int64_t *d_fuse_off = nullptr;      // the subtrees' records (ints) and their offsets [n_fuse + 1]
+    // ... and the backward sweep's launch over those of them whose backward record fits the LDS cap as well (bwd_record.hpp;
+    // ADMM_HIP_SWEEP_FUSE_BWD=0: the backward sweep keeps its per-level launches, the forward one stays fused)
+    bool sweep_fuse_bwd = true;
+    int n_fuse_bwd = 0, fuse_bwd_lds = 0;
+    int *d_fuse_bwd_rec = nullptr; int64_t *d_fuse_bwd_off = nullptr;
     int64_t graph_launches = 0;               // hipGraphLaunch calls so far (admm_hip_debug_graph_state)
     bool graphs_stale = false;                // a captured iteration holds the communicator it was captured with: set when that changes (comm.cpp), honoured by the next admm_hip_step
     bool graph_comm = false;                  // ADMM_HIP_GRAPH_COMM=1: also capture the multi-GPU iteration (ncclAllReduce inside the graph)

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dev_types.hpp"
+#include "bwd_record.hpp"
 
 namespace admm_dev {
 
@@ -669,7 +670,9 @@ __global__ __launch_bounds__(64 * NW) void solve_fwd_big_kernel(const SweepItem 
 // (Tried and dropped: walking whole bottom subtrees inside one workgroup with
 // workgroup barriers between levels -- fewer launches but 5-20 % slower, the
 // per-level launches expose more parallelism to hide the dependent index ->
-// slot -> value loads.)
+// slot -> value loads.  That was a walker whose loads depended on values it had
+// just computed; solve_bwd_kernel_subtree below keeps the hand-off in LDS and is
+// the form that is faster than the per-level launches.)
 // Sum n per-lane values across the 64 lanes of a wave with a transposing butterfly: at every one of the six
 // steps a lane keeps one half of its values and receives its partner's copies of that half, so the count
 // halves while all lanes stay busy: 14 shuffles for 12 values (7 for 3) instead of 6 per value.  Fixed
@@ -785,6 +788,135 @@ __global__ __launch_bounds__(64 * NWB) void solve_bwd_kernel(const SweepItem *__
         if (j0 + c < k) X[3 * (size_t)(first + j0 + c) + m] = v[0];
     }
     ADMM_SWEEP_STAMP(2);
+}
+
+// Backward sweep over the bottom subtrees of the tree (upload.inc bwd_subtree_record; the record: bwd_record.hpp): one workgroup per
+// subtree walks its levels top-down, the mirror image of solve_fwd_subtree_kernel.  Per level the waves first stage [w_s; -x(R_s)] of
+// every member once (the rows of the level's stage table shared among all threads; w_s from global W, a row of a member higher up in
+// this subtree from the x area in LDS, a row above the subtree from global X, which earlier launches wrote), then the waves take
+// (member, four-column group) tasks.  A task is the CW = 4
+// body of solve_bwd_kernel for those four columns, bitwise: lane l sums the rows jc0 + l + 64 n in ascending order, jc0 the first column
+// of the block of B = 4 * bwd_small_nw columns the per-level launch would have put them in, panel entries above the diagonal counting
+// as 0.0, then wave_sum_transpose<12, 32>.  x goes to global X and, for a member with members below it, to the x area: a lower level never
+// reads this workgroup's own global writes, and the levels are separated by barriers that wait for LDS alone.  The panel loads depend
+// on no computed value: a wave's work at a level is one stream of (task, 64-row group) units, the first requested before the staging
+// barrier, every further one before the one in front of it is consumed, across tasks too, into two register buffers used in turns.
+// The loads are unconditional -- an entry that does not count re-reads the task's first one -- and the values are masked as bits when
+// they are consumed: straight-line code whose outstanding loads the compiler can count, so that the wait for one group leaves the next
+// in flight (profiles/r09/README.md: what the forms without this cost).
+__device__ __forceinline__ bool bwd_sub_counts(int f, int k, int j0, int i, int c) { return j0 + c < k && i < f && i >= j0 + c; }
+__device__ __forceinline__ void bwd_sub_request(const double *Pj, int f, int k, int j0, int i, long long (&p)[4]) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const unsigned off = bwd_sub_counts(f, k, j0, i, c) ? (unsigned)(i + f * c) << 3 : 0u;
+        p[c] = __double_as_longlong(*reinterpret_cast<const double *>(reinterpret_cast<const char *>(Pj) + off));
+    }
+}
+__global__ __launch_bounds__(64 * SUB_WAVES, 6) void solve_bwd_kernel_subtree(const int *__restrict__ recs, const int64_t *__restrict__ rec_off, const double *__restrict__ panels,
+                                                                           const double *__restrict__ W, double *X, int bmask) {
+    extern __shared__ double sub_lds[];
+    int *meta = reinterpret_cast<int *>(sub_lds);
+    const int wave = sub_uniform(threadIdx.x >> 6), lane = threadIdx.x & 63;      // (uniform: the task stream's state stays in scalar registers)
+    {
+        const int64_t o0 = rec_off[blockIdx.x], o1 = rec_off[blockIdx.x + 1];
+        const int4 *src = reinterpret_cast<const int4 *>(recs + o0);
+        int4 *dst = reinterpret_cast<int4 *>(meta);
+        const int n4 = (int)((o1 - o0) >> 2);
+        for (int q = threadIdx.x; q < n4; q += 64 * SUB_WAVES) dst[q] = src[q];
+    }
+    __syncthreads();
+    const int n_lv = meta[BS_LEVELS], mem0 = meta[BS_MEM0], task0 = meta[BS_TASK0];
+    double *xs = sub_lds + meta[BS_XBUF];
+    double *vs = sub_lds + meta[BS_VBUF];
+    const int *lvt = meta + BS_HDR + n_lv + 1, *lvs = meta + BS_HDR + 2 * (n_lv + 1);
+    const int *stage = meta + meta[BS_STAGE0];
+    // row e of the stage table -> its three values: -x from the x area, w from global W, or -x from global X.  Both loads are
+    // unconditional (the one that does not apply reads offset 0 / node 0 and is dropped) so that a thread's rows are all requested at once.
+    auto staged = [&](int e, double (&a)[3]) {
+        const bool lds = e >= 0;
+        const int n = -1 - e;
+        const bool w = (n & 1) != 0;
+        const double *gp = (w ? W : (const double *)X) + 3 * (size_t)(lds ? 0 : n >> 1);
+        const double *lp = xs + (lds ? e : 0);
+        const double g0 = gp[0], g1 = gp[1], g2 = gp[2], l0 = lp[0], l1 = lp[1], l2 = lp[2];
+        a[0] = lds ? -l0 : (w ? g0 : -g0); a[1] = lds ? -l1 : (w ? g1 : -g1); a[2] = lds ? -l2 : (w ? g2 : -g2);
+    };
+    // a task's geometry (wave-uniform): the member's shape, the first of its four columns, the first row of its lanes
+    struct Task { int k, f, first, j0, jc0, xoff, voff; const double *Pj; };
+    auto task = [&](int t) {
+        const int tv = sub_uniform(meta[task0 + t]);
+        const int *M = meta + mem0 + BS_MEM * (tv >> 4);
+        Task g;
+        g.k = sub_uniform(M[BS_K]); g.f = g.k + sub_uniform(M[BS_R]); g.first = sub_uniform(M[BS_FIRST]);
+        g.xoff = sub_uniform(M[BS_XOFF]); g.voff = sub_uniform(M[BS_VOFF]);
+        g.j0 = 4 * (tv & 15); g.jc0 = g.j0 & ~bmask;
+        g.Pj = panels + sub_join64(sub_uniform(M[BS_POFF]), sub_uniform(M[BS_POFF + 1])) + (size_t)g.f * g.j0;
+        return g;
+    };
+    for (int lv = 0; lv < n_lv; ++lv) {
+        const int te = lvt[lv + 1];
+        // the wave's work at this level as one stream of units -- (task, 64-row group), a task's groups in ascending order, then the
+        // wave's next task: the unit after the current one is always requested before the current one is consumed, across tasks too
+        int t = lvt[lv] + wave, ib = 0;      // the current unit: task and first row of its group
+        Task g{};
+        long long A[4], B[4];      // the current unit's panel entries and the next one's, in turns
+        if (t < te) { g = task(t); ib = g.jc0; bwd_sub_request(g.Pj, g.f, g.k, g.j0, ib + lane, A); }
+        {   // stage the level: row q of its part of the table to vs + 3 q, two rows per thread and pass
+            const int *st = stage + lvs[lv];
+            const int ns = lvs[lv + 1] - lvs[lv];
+            constexpr int NT = 64 * SUB_WAVES;
+            for (int q = threadIdx.x; q < ns; q += 2 * NT) {
+                const bool two = q + NT < ns;
+                const int q1 = two ? q + NT : q;
+                const int e0 = st[q], e1 = st[q1];
+                double a[3], b[3];
+                staged(e0, a); staged(e1, b);
+                vs[3 * q] = a[0]; vs[3 * q + 1] = a[1]; vs[3 * q + 2] = a[2];
+                if (two) { vs[3 * q1] = b[0]; vs[3 * q1 + 1] = b[1]; vs[3 * q1 + 2] = b[2]; }
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // this level's vectors are staged (LDS only: the panel rows stay in flight)
+        double acc[4][3];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { acc[c][0] = 0.0; acc[c][1] = 0.0; acc[c][2] = 0.0; }
+        // one unit: request the next one into `nxt` (past the wave's last unit: a group beyond the front, nothing counts), consume `cur`
+        auto step = [&](long long (&cur)[4], long long (&nxt)[4]) {
+            int tn = t, in = ib + 64;
+            Task gn = g;
+            if (in >= g.f) { tn = t + SUB_WAVES; if (tn < te) { gn = task(tn); in = gn.jc0; } }
+            bwd_sub_request(gn.Pj, gn.f, gn.k, gn.j0, in + lane, nxt);
+            const int i = ib + lane;
+            if (i < g.f) {
+                const double *vi = vs + g.voff + 3 * i;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const double p = __longlong_as_double(cur[c] & (bwd_sub_counts(g.f, g.k, g.j0, i, c) ? -1ll : 0ll));
+                    acc[c][0] += p * vi[0]; acc[c][1] += p * vi[1]; acc[c][2] += p * vi[2];
+                }
+            }
+            if (tn != t) {      // the task's last group: its four columns' sums across the wave
+                double s[12];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { s[3 * c] = acc[c][0]; s[3 * c + 1] = acc[c][1]; s[3 * c + 2] = acc[c][2]; acc[c][0] = 0.0; acc[c][1] = 0.0; acc[c][2] = 0.0; }
+                int base = 0, cnt = 12;
+                wave_sum_transpose<12, 32>(s, lane, base, cnt);
+                if (cnt >= 1) {
+                    const int c = base / 3, m = base - 3 * c;
+                    if (g.j0 + c < g.k) {
+                        X[3 * (size_t)(g.first + g.j0 + c) + m] = s[0];
+                        if (g.xoff >= 0) xs[g.xoff + 3 * (g.j0 + c) + m] = s[0];
+                    }
+                }
+            }
+            t = tn; ib = in; g = gn;
+        };
+        while (t < te) {
+            step(A, B);
+            if (t >= te) break;
+            step(B, A);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // this level's x is in LDS, its staged vectors are free
+    }
 }
 
 // Roots of the elimination tree: x_s = (L_ss L_ss^T)^-1 t_s, both sweeps in one product.  t_s = y_s - (children's contributions)

@@ -457,6 +457,9 @@ int launch_solve(admm_hip_ctx *ctx, hipEvent_t mid, hipEvent_t ex0 = nullptr, hi
         if (mid) HIPCHK(hipEventRecord(mid, ctx->stream));
         if (!ctx->levels_top.empty() && !ctx->dist_top) backward(ctx->levels_top, ctx->stream);
         backward(ctx->levels, ctx->stream);
+        if (ctx->n_fuse_bwd)      // the bottom subtrees last, one workgroup each (bwd_small_nw: the block width of the per-level launches they replace)
+            hipLaunchKernelGGL(solve_bwd_kernel_subtree, dim3(ctx->n_fuse_bwd), dim3(64 * SUB_WAVES), ctx->fuse_bwd_lds, ctx->stream, (const int *)ctx->d_fuse_bwd_rec,
+                               (const int64_t *)ctx->d_fuse_bwd_off, (const double *)ctx->d_panels, (const double *)ctx->d_w, ctx->d_xcur, 4 * ctx->bwd_small_nw - 1);
         HIPCHK(hipGetLastError());
         if (bad_pair) return fail(ctx, ADMM_ERR_STATE, "backward sweep: no kernel for a level's (columns per wave, waves per block) pair");
         return ADMM_OK;

@@ -23,15 +23,71 @@ unsigned long long *g_swp_base; size_t g_swp_wgs; std::vector<int> g_swp_meta;
 // (a root of the elimination tree at or below the cut) and trees whose front rows receive more than four contributions (no cg4) stay on
 // the per-level path.  fused[s] = 1 for the supernodes the fused launch sweeps.  ADMM_HIP_VERBOSE: one "plan fused" line per call, early returns
 // included (tests/test_sweep_subtree*.py assert the shapes they reach from it).
-int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std::vector<char> &fused) {
+// ... and of the backward sweep (solve_bwd_kernel_subtree; the record's layout: bwd_record.hpp).  The backward record of the subtree under
+// t, whose members bylv lists per level: the members top-down, per member its shape, where its staged vector [w_s; -x(R_s)] lies while
+// its level runs, where its x is kept for the members below it (none for a member without children), and for every front row beyond
+// its columns where x of that row is: in the x area (a column of a member higher up in this subtree) or in global X (above the subtree)
+// -- as one stage table per level, a row of it per row of the level's staged vectors, so that the workgroup's threads share them evenly.
+// One task per (member, four columns).  node_x: scratch, -1 for every node on entry and on return.  -> the workgroup's LDS bytes.
+int bwd_subtree_record(const admm_hip_ctx *ctx, const std::vector<std::vector<int> > &bylv, const std::vector<std::vector<int> > &children, std::vector<int> &node_x,
+                       std::vector<int> &v) {
+    using namespace admm_dev;
+    const Factor &F = ctx->F;
+    std::vector<int> lvm{0}, lvt{0}, lvs{0}, mem, tasks, stage;
+    int xd = 0, vmax = 0, nm = 0;
+    for (int l = (int)bylv.size() - 1; l >= 0; --l) {
+        if (bylv[l].empty()) continue;
+        int vd = 0;
+        for (int s : bylv[l]) {
+            const Supernode &S = F.sn[s];
+            int it[BS_MEM] = {};
+            it[BS_K] = S.ncols; it[BS_R] = S.nrows; it[BS_FIRST] = S.first; it[BS_XOFF] = -1; it[BS_VOFF] = vd; it[BS_ROW0] = (int)stage.size();
+            sub_split64(ctx->dev_panel_off[s], it + BS_POFF);
+            vd += 3 * (S.ncols + S.nrows);
+            for (int j = 0; j < S.ncols; ++j) stage.push_back(-1 - (2 * (S.first + j) + 1));
+            for (int q = 0; q < S.nrows; ++q) { const int node = F.rows[S.rows_off + q]; stage.push_back(node_x[node] >= 0 ? node_x[node] : -1 - 2 * node); }
+            if (!children[s].empty()) {
+                it[BS_XOFF] = xd;
+                for (int j = 0; j < S.ncols; ++j) node_x[S.first + j] = xd + 3 * j;
+                xd += 3 * S.ncols;
+            }
+            for (int g = 0; 4 * g < S.ncols; ++g) tasks.push_back(nm * 16 + g);
+            mem.insert(mem.end(), it, it + BS_MEM);
+            ++nm;
+        }
+        vmax = std::max(vmax, vd);
+        lvm.push_back(nm); lvt.push_back((int)tasks.size()); lvs.push_back((int)stage.size());
+    }
+    for (const std::vector<int> &lv : bylv) for (int s : lv) if (!children[s].empty()) for (int j = 0; j < F.sn[s].ncols; ++j) node_x[F.sn[s].first + j] = -1;
+    const int nl = (int)lvm.size() - 1;
+    const int mem0 = (BS_HDR + 3 * (nl + 1) + 3) & ~3, task0 = mem0 + BS_MEM * nm, stage0 = task0 + (int)tasks.size();
+    const int n_ints = (stage0 + (int)stage.size() + 3) & ~3;
+    v.assign(n_ints, 0);
+    const int xbuf = n_ints / 2, vbuf = xbuf + xd, end = vbuf + vmax;      // (doubles)
+    v[BS_LEVELS] = nl; v[BS_NMEM] = nm; v[BS_MEM0] = mem0; v[BS_NTASK] = (int)tasks.size(); v[BS_TASK0] = task0; v[BS_XBUF] = xbuf; v[BS_VBUF] = vbuf; v[BS_END] = end;
+    v[BS_NSTAGE] = (int)stage.size(); v[BS_STAGE0] = stage0;
+    for (int l = 0; l <= nl; ++l) { v[BS_HDR + l] = lvm[l]; v[BS_HDR + nl + 1 + l] = lvt[l]; v[BS_HDR + 2 * (nl + 1) + l] = lvs[l]; }
+    std::copy(mem.begin(), mem.end(), v.begin() + mem0);
+    std::copy(tasks.begin(), tasks.end(), v.begin() + task0);
+    std::copy(stage.begin(), stage.end(), v.begin() + stage0);
+    return 8 * end;
+}
+
+// fused_bwd[s] = 1 for the supernodes the fused backward launch sweeps: the members of those of the subtrees above whose backward record fits the
+// LDS cap too (a subset of fused: a subtree over the cap here keeps its per-level backward items only).  Every backward record passes
+// bwd_record_check before it is uploaded.  ADMM_HIP_VERBOSE: one "plan fused_bwd" line per call beside the "plan fused" one.
+int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std::vector<char> &fused, std::vector<char> &fused_bwd) {
     using namespace admm_dev;
     const Factor &F = ctx->F;
     const int ns = (int)F.sn.size();
-    fused.assign(ns, 0);
+    fused.assign(ns, 0); fused_bwd.assign(ns, 0);
     ctx->fuse_cut = -1; ctx->n_fuse = 0; ctx->fuse_lds = 0;
+    ctx->n_fuse_bwd = 0; ctx->fuse_bwd_lds = 0;
     const bool verbose = getenv("ADMM_HIP_VERBOSE") != nullptr;
+    const char *why_bwd_off = !ctx->sweep_fuse ? "ADMM_HIP_SWEEP_FUSE=0" : (!ctx->sweep_fuse_bwd ? "ADMM_HIP_SWEEP_FUSE_BWD=0" : (F.n > BS_MAX_NODES ? "too many nodes" : nullptr));
+    auto bwd_off = [&](const char *why) { if (verbose) fprintf(stderr, "admm_hip: plan fused_bwd off (%s)\n", why); };
     const char *why_off = !ctx->sweep_fuse ? "ADMM_HIP_SWEEP_FUSE=0" : (F.cg4.empty() ? "front rows with more than four contributions" : (F.levels.empty() ? "no cut level" : nullptr));
-    if (why_off) { if (verbose) fprintf(stderr, "admm_hip: plan fused off (%s)\n", why_off); return ADMM_OK; }
+    if (why_off) { if (verbose) fprintf(stderr, "admm_hip: plan fused off (%s)\n", why_off); bwd_off(why_bwd_off ? why_bwd_off : "no fused forward subtrees"); return ADMM_OK; }
     auto mine = [&](int s) { return !own || (*own)[s] == want; };
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, ctx->device_id));
@@ -50,19 +106,22 @@ int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std:
         }
         if (roots >= 2 * cus) cut = l;
     }
-    if (cut < 0) { if (verbose) fprintf(stderr, "admm_hip: plan fused off (no cut level)\n"); return ADMM_OK; }
+    if (cut < 0) { if (verbose) fprintf(stderr, "admm_hip: plan fused off (no cut level)\n"); bwd_off(why_bwd_off ? why_bwd_off : "no fused forward subtrees"); return ADMM_OK; }
     std::vector<std::vector<int> > children(ns);
     for (int s = 0; s < ns; ++s) if (F.sn[s].parent >= 0) children[F.sn[s].parent].push_back(s);
     std::vector<int> local_slot(F.n_slots, -1);      // member's contribution slot -> LDS offset (doubles, from the contribution area)
-    struct Rec { std::vector<int> v; double bytes; std::vector<int> members; };
+    struct Rec { std::vector<int> v; double bytes; std::vector<int> members; std::vector<int> bwd; };      // (bwd: empty = per-level backward items)
     std::vector<Rec> recs;
     int lds_max = 0, left = 0;      // (left: subtrees that stay on the per-level path)
+    std::vector<int> node_x(F.n, -1);      // (bwd_subtree_record's scratch)
+    int bwd_lds_max = 0, n_bwd = 0, candidates = 0;
     // the shapes the fused records reach (ADMM_HIP_VERBOSE only): levels per record, the most child contributions into one front row,
     // members whose parent lies two or more levels up, non-root members without contribution rows
     int lv_min = 0, lv_max = 0, maxin = 0, skip = 0, empty = 0;
     for (int t = 0; t < ns; ++t) {
         const int p = F.sn[t].parent;
         if (!mine(t) || F.sn[t].level > cut || p < 0 || F.sn[p].level <= cut) continue;
+        ++candidates;
         std::vector<int> mem, stack{t};      // the subtree, then per level
         while (!stack.empty()) { const int s = stack.back(); stack.pop_back(); mem.push_back(s); for (int c : children[s]) stack.push_back(c); }
         const int nlv = F.sn[t].level + 1;
@@ -129,11 +188,24 @@ int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std:
             for (size_t q = 0; q < maps.size(); q += 4) maxin = std::max(maxin, (maps[q] >= 0) + (maps[q + 1] >= 0) + (maps[q + 2] >= 0) + (maps[q + 3] >= 0));
             for (int s : mem) if (s != t) { skip += F.sn[F.sn[s].parent].level - F.sn[s].level >= 2; empty += F.sn[s].nrows == 0; }
         }
-        recs.push_back({std::move(v), bytes, std::move(mem)});
+        std::vector<int> bwd;
+        if (!why_bwd_off) {
+            const int bl = bwd_subtree_record(ctx, bylv, children, node_x, bwd);
+            if (bl > lds_cap) bwd.clear();
+            else {
+                char msg[256];
+                if (!bwd_record_check(bwd.data(), (int64_t)bwd.size(), F.n, ctx->dev_panels_size, msg, (int)sizeof msg)) return fail(ctx, ADMM_ERR_STATE, "%s", msg);
+                bwd_lds_max = std::max(bwd_lds_max, bl); ++n_bwd;
+            }
+        }
+        recs.push_back({std::move(v), bytes, std::move(mem), std::move(bwd)});
     }
     if (verbose)
         fprintf(stderr, "admm_hip: plan fused cut %d subtrees %d left %d lds %d cap %d levels %d..%d maxin %d skip %d empty %d\n", cut, (int)recs.size(), left, lds_max, lds_cap,
                 lv_min, lv_max, maxin, skip, empty);
+    if (why_bwd_off) bwd_off(why_bwd_off);
+    else if (!n_bwd) bwd_off(recs.empty() ? "no fused forward subtrees" : "every subtree over the LDS cap");
+    else if (verbose) fprintf(stderr, "admm_hip: plan fused_bwd cut %d subtrees %d left %d lds %d cap %d\n", cut, n_bwd, candidates - n_bwd, bwd_lds_max, lds_cap);
     if (recs.empty()) return ADMM_OK;
     // the largest subtrees start first
     std::stable_sort(recs.begin(), recs.end(), [](const Rec &a, const Rec &b) { return a.bytes > b.bytes; });
@@ -141,6 +213,12 @@ int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std:
     for (const Rec &r : recs) { all.insert(all.end(), r.v.begin(), r.v.end()); off.push_back((int64_t)all.size()); for (int s : r.members) fused[s] = 1; }
     TRY(upload(ctx, &ctx->d_fuse_rec, all)); TRY(upload(ctx, &ctx->d_fuse_off, off));
     ctx->fuse_cut = cut; ctx->n_fuse = (int)recs.size(); ctx->fuse_lds = lds_max;
+    if (n_bwd) {      // (in the forward launch's order: the largest subtrees start first)
+        std::vector<int> ball; std::vector<int64_t> boff{0};
+        for (const Rec &r : recs) if (!r.bwd.empty()) { ball.insert(ball.end(), r.bwd.begin(), r.bwd.end()); boff.push_back((int64_t)ball.size()); for (int s : r.members) fused_bwd[s] = 1; }
+        TRY(upload(ctx, &ctx->d_fuse_bwd_rec, ball)); TRY(upload(ctx, &ctx->d_fuse_bwd_off, boff));
+        ctx->n_fuse_bwd = n_bwd; ctx->fuse_bwd_lds = bwd_lds_max;
+    }
     return ADMM_OK;
 }
 
@@ -181,8 +259,8 @@ int upload_factor(admm_hip_ctx *ctx) {
     if (subtree) { passes.push_back({ctx->rank, &ctx->levels}); passes.push_back({-1, &ctx->levels_top}); }
     else passes.push_back({0, &ctx->levels});
     const std::vector<int> *own = subtree ? &ctx->sn_owner : nullptr;
-    std::vector<char> fused;      // supernodes of the fused bottom subtrees (this rank's own ones under subtree sharding): no per-level items
-    TRY(fuse_subtrees(ctx, own, subtree ? ctx->rank : 0, fused));
+    std::vector<char> fused, fused_bwd;      // supernodes of the fused bottom subtrees (this rank's own ones under subtree sharding): no per-level items in the forward / the backward sweep
+    TRY(fuse_subtrees(ctx, own, subtree ? ctx->rank : 0, fused, fused_bwd));
     // Subtree sharding: which top supernodes' x does a rank need?  The forward sweep over the top is complete on every rank (it sums
     // towards the root), but the backward sweep only has to reach the separators a rank touches: those that appear among the front rows
     // of its own subtrees, those its elements have a node in, and their ancestors.  Everybody evaluates the rule for EVERY rank (no
@@ -229,6 +307,7 @@ int upload_factor(admm_hip_ctx *ctx) {
                 if (!in_fused) for (int t = 0; t < tiles; ++t) { it.part = t; if (fwd_small) sm.push_back(it); else bg.push_back(it); }
                 const int chunks = (S.ncols + L.bwd_nw * L.bwd_cw - 1) / (L.bwd_nw * L.bwd_cw);
                 if (subtree && ps.want < 0 && !top_needed[s]) continue;      // replicated top: no backward work for a separator this rank never reads
+                if (ps.want >= 0 && fused_bwd[s]) continue;
                 for (int c = 0; c < chunks; ++c) { it.part = c; bw.push_back(it); }
             }
             if (ctx->xcd_min_supernodes > 0) { xcd_order(sm, admm_dev::FWD_SMALL_WAVES, ctx->xcd_min_supernodes); xcd_order(bg, 1, ctx->xcd_min_supernodes); xcd_order(bw, 1, ctx->xcd_min_supernodes); }
