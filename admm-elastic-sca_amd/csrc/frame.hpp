@@ -1,5 +1,5 @@
 // frame.hpp -- the rigid frame of a collision list entry and the analytic shapes' pushes, shared by the host (mesh.cpp:
-// admm_hip_shape_query, admm_hip_mesh_query_framed) and the device (kernels_local.hpp collide_analytic, project_collision_framed_kernel).
+// admm_hip_shape_query, admm_hip_mesh_query_framed) and the device (kernels_collision.hpp collide_analytic, project_collision_framed_kernel).
 // Both sides compile it with -ffp-contract=off and keep the operation order below, so they give the same bits.  Extension, no reference
 // counterpart beyond the three pushes themselves (CollisionFloor.hpp:51-58, CollisionSphere.hpp:50-66, CollisionCylinder.hpp:48-66).
 //

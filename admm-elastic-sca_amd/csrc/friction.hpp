@@ -1,5 +1,5 @@
 // friction.hpp -- Coulomb friction at a collision contact, shared by the host (mesh.cpp: admm_hip_friction_query) and the device
-// (kernels_local.hpp project_collision_friction_kernel).  Both sides compile it with -ffp-contract=off and keep the operation order
+// (kernels_collision.hpp project_collision_friction_kernel).  Both sides compile it with -ffp-contract=off and keep the operation order
 // below, so they give the same bits.  Extension, no reference counterpart (the reference's contacts are frictionless).
 //
 // In a collision element the candidate is p = Dx + u, and at a resting contact u is the contact impulse over the weight: the depth by

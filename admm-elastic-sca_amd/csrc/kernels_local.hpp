@@ -390,730 +390,10 @@ void project_tet_kernel(BatchDev b, const double *__restrict__ x, BatchDev tail,
 }
 
 // ---------------------------------------------------------------------------
-// CollisionForce, CollisionForce.cpp:38-70: one element per node, D = I;
-// the point Dx+u is pushed out of every analytic shape it penetrates, in list
-// order (CollisionFloor.hpp:51-58, CollisionSphere.hpp:50-66, CollisionCylinder.hpp:48-66)
+// CollisionForce, CollisionForce.cpp:38-70: the eight forms of its projection
+// and the latch of side memory
 // ---------------------------------------------------------------------------
-// one analytic shape of the list (floor, sphere, z-cylinder: frame.hpp collide_round, which names each of them) pushes p out; shared by
-// project_collision_block and project_collision_mesh_kernel.  A list with a box or a framed entry never comes here (launch.inc framed_on).
-__device__ __forceinline__ void collide_analytic(const ShapeTable *__restrict__ shapes, const int q, double p[3]) {
-    const double c0 = shapes->par[q][0], c1 = shapes->par[q][1], c2 = shapes->par[q][2], R = shapes->par[q][3];
-    admm_frame::collide_round(shapes->type[q], c0, c1, c2, R, p);
-}
-__device__ __forceinline__ void project_collision_block(const BatchDev &b, const double *__restrict__ x, const ShapeTable *__restrict__ shapes, const int lb) {
-    const int e = b.e0 + lb * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];      // (with the other loads: behind the u / z stores it would wait for them)
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) collide_analytic(shapes, q, p);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// ... with closed triangle meshes in the list (ADMM_SHAPE_MESH, mesh_query.hpp): one lane per node as above, the analytic shapes through
-// collide_analytic, a mesh instance through a BVH traversal whose stack is the lane's column of an LDS array (no private array indexed at
-// run time).  A point on or outside the instance's root box cannot be inside the mesh and skips the traversal.  tag (contexts with a mesh
-// owner only, else null): the body tag of every node in device order; a node skips every mesh its body owns (its own surface).
-__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_mesh_kernel(BatchDev b, const double *__restrict__ x, const ShapeTable *__restrict__ shapes,
-                                                                             const admm_mesh::MeshDev *__restrict__ meshes, const int *__restrict__ tag) {
-    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
-    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const int own = tag ? tag[id] : -1;
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        if (shapes->type[q] != ADMM_SHAPE_MESH) { collide_analytic(shapes, q, p); continue; }
-        const admm_mesh::MeshDev m = meshes[(int)shapes->par[q][3]];
-        if (own >= 0 && m.owner == own) continue;
-        const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
-        const double qq[3] = {p[0] - t[0], p[1] - t[1], p[2] - t[2]};
-        if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
-        admm_mesh::Hit h;
-        admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
-        if (admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0) { p[0] = t[0] + h.c[0]; p[1] = t[1] + h.c[1]; p[2] = t[2] + h.c[2]; }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// ... with Coulomb friction at the contacts (friction.hpp; a context with any coefficient > 0 launches this form for its collision batches,
-// MESH: it has meshes registered).  One lane per node as above, the same pushes through collide_analytic and the same BVH traversal;
-// after every shape that moved the point, admm_friction::apply clamps the tangential part of p' - x0 against mu * depth, and the next shape
-// starts from the result.  xs: the frame-start x in device order (ctx->d_x, which no kernel writes during the ADMM loop): one more 24-byte
-// gather per node, issued beside the other loads, ahead of the u / z stores (see dst above).
-template <bool MESH>
-__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_friction_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
-                                                                                 const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
-                                                                                 const int *__restrict__ tag) {
-    __shared__ int stack[MESH ? admm_mesh::MAX_DEPTH : 1][LOCAL_BLOCK];
-    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3], x0[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        x0[j] = xs[3 * (size_t)id + j];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const int own = (MESH && tag) ? tag[id] : -1;
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        const double before[3] = {p[0], p[1], p[2]};
-        if (!MESH || shapes->type[q] != ADMM_SHAPE_MESH) collide_analytic(shapes, q, p);
-        else {
-            const admm_mesh::MeshDev m = meshes[(int)shapes->par[q][3]];
-            if (own >= 0 && m.owner == own) continue;
-            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
-            const double qq[3] = {p[0] - t[0], p[1] - t[1], p[2] - t[2]};
-            if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
-            admm_mesh::Hit h;
-            admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
-            if (admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0) { p[0] = t[0] + h.c[0]; p[1] = t[1] + h.c[1]; p[2] = t[2] + h.c[2]; }
-        }
-        admm_friction::apply(before, p, x0, shapes->mu[q]);      // (a shape that did not move the point: depth 0, nothing happens)
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// ... against obstacles that move (a context where moving_friction_on holds, launch.inc, launches this form for its collision batches;
-// the two instantiations above stay as they are).  One lane per node, the same pushes, traversal and owner skip; after a shape moved the
-// point, w = the displacement of its surface over the frame at the contact p' (friction.hpp rigid_displacement from the entry's nine
-// doubles of shapes->motion, uniform across the wave; at a mesh hit whose mesh has vertex velocities plus dt times their interpolation
-// with the hit triangle's barycentric weights: three cid ints and three 24-byte gathers) goes into admm_friction::apply_moving.  A body
-// surface's entry takes the surface's coefficient (MeshMotion::mu) in place of the entry's, which is 0 for it.  Every load of an entry is
-// issued before the rule, and all of them ahead of the u / z stores (see dst above).  mm: null without meshes.
-template <bool MESH>
-__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_friction_moving_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
-                                                                                        const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
-                                                                                        const admm_mesh::MeshMotion *__restrict__ mm, const int *__restrict__ tag, const double dt) {
-    __shared__ int stack[MESH ? admm_mesh::MAX_DEPTH : 1][LOCAL_BLOCK];
-    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3], x0[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        x0[j] = xs[3 * (size_t)id + j];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const int own = (MESH && tag) ? tag[id] : -1;
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        const double before[3] = {p[0], p[1], p[2]};
-        double mu = shapes->mu[q];
-        double vi0 = 0.0, vi1 = 0.0, vi2 = 0.0;      // the mesh's vertex velocities at the hit
-        bool vhit = false;
-        if (!MESH || shapes->type[q] != ADMM_SHAPE_MESH) collide_analytic(shapes, q, p);
-        else {
-            const int mi = (int)shapes->par[q][3];
-            const admm_mesh::MeshDev m = meshes[mi];
-            if (own >= 0 && m.owner == own) continue;
-            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
-            const double qq[3] = {p[0] - t[0], p[1] - t[1], p[2] - t[2]};
-            if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
-            admm_mesh::Hit h;
-            admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
-            if (admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0) {
-                p[0] = t[0] + h.c[0]; p[1] = t[1] + h.c[1]; p[2] = t[2] + h.c[2];
-                const admm_mesh::MeshMotion mo = mm[mi];
-                if (mo.body) mu = mo.mu;
-                if (mo.vel && mu > 0.0) {
-                    const admm_mesh::Tri &tr = m.tris[h.slot];
-                    const int *c = mo.cid + 3 * (size_t)tr.orig;
-                    const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
-                    const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
-                    double bw[3];
-                    admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
-                    vi0 = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi1 = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi2 = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
-                    vhit = true;
-                }
-            }
-        }
-        if (!(mu > 0.0)) continue;
-        double w[3];
-        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
-        if (vhit) { w[0] = w[0] + dt * vi0; w[1] = w[1] + dt * vi1; w[2] = w[2] + dt * vi2; }
-        admm_friction::apply_moving(before, p, x0, w, mu);      // (a shape that did not move the point: depth 0, nothing happens)
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// ... with a rigid frame per entry and the oriented box (frame.hpp; a context where framed_on holds, launch.inc, launches this form for
-// its collision batches whatever else the list holds; every kernel above stays as it is).  One lane per node.  For an entry whose frame
-// is not the identity (shapes->framed, uniform across the wave) the candidate goes to local coordinates, the entry's unframed code runs
-// there -- collide_round or collide_box, or for a mesh the box test, closest and inside with the translation t -- and only a point that
-// code moved goes back to world coordinates; every other point keeps its bits.  Then, for mu > 0, the moving form of the friction rule on
-// the world-space before, p', x0 and w as in project_collision_friction_moving_kernel (a zero motion gives w = 0 and the bits of the rule
-// at rest); a framed mesh's interpolated vertex velocity is in the mesh's own coordinates and is rotated by R first.  mm: null without
-// meshes.
-template <bool MESH>
-__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_framed_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
-                                                                               const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
-                                                                               const admm_mesh::MeshMotion *__restrict__ mm, const int *__restrict__ tag, const double dt) {
-    __shared__ int stack[MESH ? admm_mesh::MAX_DEPTH : 1][LOCAL_BLOCK];
-    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3], x0[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        x0[j] = xs[3 * (size_t)id + j];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const int own = (MESH && tag) ? tag[id] : -1;
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        const double before[3] = {p[0], p[1], p[2]};
-        const double *f = shapes->frame[q];
-        const bool framed = shapes->framed[q] != 0;
-        const int ty = shapes->type[q];
-        double mu = shapes->mu[q];
-        double vi[3] = {0.0, 0.0, 0.0};      // the mesh's vertex velocities at the hit, world axes
-        bool vhit = false;
-        if (!MESH || ty != ADMM_SHAPE_MESH) {
-            if (!admm_frame::collide_entry(ty, shapes->par[q], f, framed, p)) continue;
-        } else {
-            const int mi = (int)shapes->par[q][3];
-            const admm_mesh::MeshDev m = meshes[mi];
-            if (own >= 0 && m.owner == own) continue;
-            double l[3] = {p[0], p[1], p[2]};
-            if (framed) admm_frame::to_local(f, p, l);
-            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
-            const double qq[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
-            if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
-            admm_mesh::Hit h;
-            admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
-            if (!(admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0)) continue;
-            l[0] = t[0] + h.c[0]; l[1] = t[1] + h.c[1]; l[2] = t[2] + h.c[2];
-            if (framed) admm_frame::to_world(f, l, p); else { p[0] = l[0]; p[1] = l[1]; p[2] = l[2]; }
-            const admm_mesh::MeshMotion mo = mm[mi];
-            if (mo.body) mu = mo.mu;
-            if (mo.vel && mu > 0.0) {
-                const admm_mesh::Tri &tr = m.tris[h.slot];
-                const int *c = mo.cid + 3 * (size_t)tr.orig;
-                const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
-                const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
-                double bw[3];
-                admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
-                vi[0] = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi[1] = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi[2] = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
-                if (framed) admm_frame::rotate(f, vi, vi);
-                vhit = true;
-            }
-        }
-        if (!(mu > 0.0)) continue;
-        double w[3];
-        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
-        if (vhit) { w[0] = w[0] + dt * vi[0]; w[1] = w[1] + dt * vi[1]; w[2] = w[2] + dt * vi[2]; }
-        admm_friction::apply_moving(before, p, x0, w, mu);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// ... with open meshes as thick shells (mesh_query.hpp; a context where shell_on holds, launch.inc, launches this form for its collision
-// batches whatever else the list holds; every kernel above stays as it is).  A sibling of project_collision_framed_kernel: one lane per
-// node, the same LDS stack column and owner skip, frames, the box, coefficients, motions and vertex velocities as there.  For an entry
-// whose mesh is open (thick[mesh] > 0, uniform across the wave) the mesh branch differs in three places: the box test is the inflated
-// one, the decision is d2 < r^2 on the hit of the search bounded by r^2, and the push target is at distance r from the closest point on
-// the side the point is on.  Everything after the push runs on the world-space points unchanged; closed meshes and analytic entries in
-// the same list run the framed kernel's code.  thick: the half thickness of every mesh, parallel to meshes (0: closed).
-__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_shell_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
-                                                                               const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
-                                                                               const admm_mesh::MeshMotion *__restrict__ mm, const double *__restrict__ thick, const int *__restrict__ tag,
-                                                                              const double dt) {
-    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
-    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3], x0[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        x0[j] = xs[3 * (size_t)id + j];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const int own = tag ? tag[id] : -1;
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        const double before[3] = {p[0], p[1], p[2]};
-        const double *f = shapes->frame[q];
-        const bool framed = shapes->framed[q] != 0;
-        const int ty = shapes->type[q];
-        double mu = shapes->mu[q];
-        double vi[3] = {0.0, 0.0, 0.0};      // the mesh's vertex velocities at the hit, world axes
-        bool vhit = false;
-        if (ty != ADMM_SHAPE_MESH) {
-            if (!admm_frame::collide_entry(ty, shapes->par[q], f, framed, p)) continue;
-        } else {
-            const int mi = (int)shapes->par[q][3];
-            const admm_mesh::MeshDev m = meshes[mi];
-            if (own >= 0 && m.owner == own) continue;
-            double l[3] = {p[0], p[1], p[2]};
-            if (framed) admm_frame::to_local(f, p, l);
-            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
-            const double qq[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
-            const double r = thick[mi];
-            admm_mesh::Hit h;
-            if (r > 0.0) {      // an open mesh: the shell rule (mesh_query.hpp), steps 1 to 4
-                if (!admm_mesh::in_shell_box(qq, m.nodes[0], r)) continue;
-                admm_mesh::closest_within(m.nodes, m.tris, qq, r * r, stk, h);
-                if (!admm_mesh::shell_collides(h, r)) continue;
-                double o[3];
-                admm_mesh::shell_push(qq, h, m.nrm, r, o);
-                l[0] = t[0] + o[0]; l[1] = t[1] + o[1]; l[2] = t[2] + o[2];
-            } else {
-                if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
-                admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
-                if (!(admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0)) continue;
-                l[0] = t[0] + h.c[0]; l[1] = t[1] + h.c[1]; l[2] = t[2] + h.c[2];
-            }
-            if (framed) admm_frame::to_world(f, l, p); else { p[0] = l[0]; p[1] = l[1]; p[2] = l[2]; }
-            const admm_mesh::MeshMotion mo = mm[mi];
-            if (mo.body) mu = mo.mu;
-            if (mo.vel && mu > 0.0) {
-                const admm_mesh::Tri &tr = m.tris[h.slot];
-                const int *c = mo.cid + 3 * (size_t)tr.orig;
-                const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
-                const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
-                double bw[3];
-                admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
-                vi[0] = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi[1] = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi[2] = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
-                if (framed) admm_frame::rotate(f, vi, vi);
-                vhit = true;
-            }
-        }
-        if (!(mu > 0.0)) continue;
-        double w[3];
-        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
-        if (vhit) { w[0] = w[0] + dt * vi[0]; w[1] = w[1] + dt * vi[1]; w[2] = w[2] + dt * vi[2]; }
-        admm_friction::apply_moving(before, p, x0, w, mu);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// ... with a sheet surface that collides with itself (admm_hip_set_sheet_self_collision; a context where self_on holds, launch.inc,
-// launches this form for its collision batches; every kernel above stays as it is).  A sibling of project_collision_shell_kernel: the
-// same lane per node, LDS stack column, owner skip, frames, box, coefficients, motions and vertex velocities.  For an entry whose mesh
-// the node's body owns: self[mesh] == 0 (uniform across the wave): skipped, as there; != 0: the shell branch with
-// closest_within_excluding and the node's vertex id vid[node], so that the triangles around the node are left out.  Any other entry runs
-// the shell kernel's code and gives its bits (skip = -1).  The surface is the frame-start one: a node meets where the rest of the cloth
-// was at the start of the frame.  self: the flag of every mesh, parallel to meshes; vid: one id per node in device order (-1: none).
-// tests/test_collision_form_ladder.py holds this kernel to the bits of every form below it, on lists that a far trigger entry moves here.
-__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_self_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
-                                                                               const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
-                                                                               const admm_mesh::MeshMotion *__restrict__ mm, const double *__restrict__ thick, const int *__restrict__ tag,
-                                                                              const int *__restrict__ self, const int *__restrict__ vid,
-                                                                              const double dt) {
-    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
-    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3], x0[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        x0[j] = xs[3 * (size_t)id + j];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const int own = tag ? tag[id] : -1;
-    const int vi_own = vid[id];      // the node's vertex id on the self-colliding sheet that owns it (-1: none)
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        const double before[3] = {p[0], p[1], p[2]};
-        const double *f = shapes->frame[q];
-        const bool framed = shapes->framed[q] != 0;
-        const int ty = shapes->type[q];
-        double mu = shapes->mu[q];
-        double vi[3] = {0.0, 0.0, 0.0};      // the mesh's vertex velocities at the hit, world axes
-        bool vhit = false;
-        if (ty != ADMM_SHAPE_MESH) {
-            if (!admm_frame::collide_entry(ty, shapes->par[q], f, framed, p)) continue;
-        } else {
-            const int mi = (int)shapes->par[q][3];
-            const admm_mesh::MeshDev m = meshes[mi];
-            const bool mine = own >= 0 && m.owner == own;
-            if (mine && !self[mi]) continue;
-            double l[3] = {p[0], p[1], p[2]};
-            if (framed) admm_frame::to_local(f, p, l);
-            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
-            const double qq[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
-            const double r = thick[mi];
-            admm_mesh::Hit h;
-            if (r > 0.0) {      // an open mesh: the shell rule (mesh_query.hpp), steps 1 to 4
-                if (!admm_mesh::in_shell_box(qq, m.nodes[0], r)) continue;
-                // the node's own sheet: without the triangles around its vertex (their corner ids: three loads per leaf triangle, per lane);
-                // any other entry: skip = -1, nothing is left out and cid is not read -- closest_within's operations
-                admm_mesh::closest_within_excluding(m.nodes, m.tris, mm[mi].cid, mine ? vi_own : -1, qq, r * r, stk, h);
-                if (!admm_mesh::shell_collides(h, r)) continue;
-                double o[3];
-                admm_mesh::shell_push(qq, h, m.nrm, r, o);
-                l[0] = t[0] + o[0]; l[1] = t[1] + o[1]; l[2] = t[2] + o[2];
-            } else {
-                if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
-                admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
-                if (!(admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0)) continue;
-                l[0] = t[0] + h.c[0]; l[1] = t[1] + h.c[1]; l[2] = t[2] + h.c[2];
-            }
-            if (framed) admm_frame::to_world(f, l, p); else { p[0] = l[0]; p[1] = l[1]; p[2] = l[2]; }
-            const admm_mesh::MeshMotion mo = mm[mi];
-            if (mo.body) mu = mo.mu;
-            if (mo.vel && mu > 0.0) {
-                const admm_mesh::Tri &tr = m.tris[h.slot];
-                const int *c = mo.cid + 3 * (size_t)tr.orig;
-                const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
-                const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
-                double bw[3];
-                admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
-                vi[0] = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi[1] = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi[2] = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
-                if (framed) admm_frame::rotate(f, vi, vi);
-                vhit = true;
-            }
-        }
-        if (!(mu > 0.0)) continue;
-        double w[3];
-        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
-        if (vhit) { w[0] = w[0] + dt * vi[0]; w[1] = w[1] + dt * vi[1]; w[2] = w[2] + dt * vi[2]; }
-        admm_friction::apply_moving(before, p, x0, w, mu);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// ... with an open mesh that has side memory (admm_hip_set_collision_mesh_side_memory, mesh_query.hpp; a context where sided_on holds,
-// launch.inc, launches this form for its collision batches; every kernel above stays as it is).  A sibling of
-// project_collision_self_kernel: the same lane per node, LDS stack column, owner skip, frames, box, coefficients, motions, vertex
-// velocities and self-collision branch.  For an entry whose mesh has a reach (reach[mesh] > 0, uniform across the wave) a lane reads its
-// node's side s = side[slot[mesh] * side_stride + node]: s == 0 runs the self kernel's shell branch (the same code, the same bits),
-// s != 0 runs sided_project with the mesh's boundary table -- the search bounded by R, the unsigned rule on the node's own side or at a
-// boundary hit, the mirror push for a node that has crossed.  A node of the body that owns the mesh holds s == 0 (the latch skips it).
-// Everything after the push is unchanged.  self, vid: null where no sheet self-collides.
-__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_sided_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
-                                                                               const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
-                                                                               const admm_mesh::MeshMotion *__restrict__ mm, const double *__restrict__ thick, const int *__restrict__ tag,
-                                                                               const int *__restrict__ self, const int *__restrict__ vid,
-                                                                               const double *__restrict__ reach, const int *__restrict__ side_slot, const int *const *__restrict__ bnd,
-                                                                               const int *__restrict__ side, const int side_stride, const double dt) {
-    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
-    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3], x0[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        x0[j] = xs[3 * (size_t)id + j];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const int own = tag ? tag[id] : -1;
-    const int vi_own = vid ? vid[id] : -1;      // the node's vertex id on the self-colliding sheet that owns it (-1: none)
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        const double before[3] = {p[0], p[1], p[2]};
-        const double *f = shapes->frame[q];
-        const bool framed = shapes->framed[q] != 0;
-        const int ty = shapes->type[q];
-        double mu = shapes->mu[q];
-        double vi[3] = {0.0, 0.0, 0.0};      // the mesh's vertex velocities at the hit, world axes
-        bool vhit = false;
-        if (ty != ADMM_SHAPE_MESH) {
-            if (!admm_frame::collide_entry(ty, shapes->par[q], f, framed, p)) continue;
-        } else {
-            const int mi = (int)shapes->par[q][3];
-            const admm_mesh::MeshDev m = meshes[mi];
-            const bool mine = own >= 0 && m.owner == own;
-            if (mine && !(self && self[mi])) continue;
-            double l[3] = {p[0], p[1], p[2]};
-            if (framed) admm_frame::to_local(f, p, l);
-            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
-            const double qq[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
-            const double r = thick[mi];
-            admm_mesh::Hit h;
-            if (r > 0.0) {
-                const double R = reach[mi];
-                const int sd = (R > 0.0 && !mine) ? side[(size_t)side_slot[mi] * (size_t)side_stride + id] : 0;      // (an owner's node: the unsigned rule)
-                double o[3];
-                if (sd != 0) {      // a remembered side: mesh_query.hpp, projection steps 1 to 4
-                    bool crossed;
-                    if (!admm_mesh::sided_project(m.nodes, m.tris, m.nrm, bnd[mi], qq, sd, r, R, stk, h, o, crossed)) continue;
-                } else {            // the self kernel's shell branch
-                    if (!admm_mesh::in_shell_box(qq, m.nodes[0], r)) continue;
-                    admm_mesh::closest_within_excluding(m.nodes, m.tris, mm[mi].cid, mine ? vi_own : -1, qq, r * r, stk, h);
-                    if (!admm_mesh::shell_collides(h, r)) continue;
-                    admm_mesh::shell_push(qq, h, m.nrm, r, o);
-                }
-                l[0] = t[0] + o[0]; l[1] = t[1] + o[1]; l[2] = t[2] + o[2];
-            } else {
-                if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
-                admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
-                if (!(admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0)) continue;
-                l[0] = t[0] + h.c[0]; l[1] = t[1] + h.c[1]; l[2] = t[2] + h.c[2];
-            }
-            if (framed) admm_frame::to_world(f, l, p); else { p[0] = l[0]; p[1] = l[1]; p[2] = l[2]; }
-            const admm_mesh::MeshMotion mo = mm[mi];
-            if (mo.body) mu = mo.mu;
-            if (mo.vel && mu > 0.0) {
-                const admm_mesh::Tri &tr = m.tris[h.slot];
-                const int *c = mo.cid + 3 * (size_t)tr.orig;
-                const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
-                const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
-                double bw[3];
-                admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
-                vi[0] = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi[1] = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi[2] = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
-                if (framed) admm_frame::rotate(f, vi, vi);
-                vhit = true;
-            }
-        }
-        if (!(mu > 0.0)) continue;
-        double w[3];
-        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
-        if (vhit) { w[0] = w[0] + dt * vi[0]; w[1] = w[1] + dt * vi[1]; w[2] = w[2] + dt * vi[2]; }
-        admm_friction::apply_moving(before, p, x0, w, mu);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// ... with a closed body surface that collides with itself (admm_hip_set_body_self_collision, mesh_query.hpp; a context where bodyself_on
-// holds, launch.inc, launches this form for its collision batches; every kernel above stays as it is).  A sibling of
-// project_collision_sided_kernel: the same lane per node, LDS stack column, owner skip, frames, box, coefficients, motions, vertex
-// velocities, self-collision and side-memory branches (reach, side_slot, bnd, side: null where no mesh has memory).  The one difference:
-// an entry that names a mesh the node's body owns and whose lengths bself[3 mi..] = {r, R, rho} have r > 0.  A surface node (vid >= 0)
-// runs body_self_project against the rest vertices rest[mi] -- the search bounded by R that passes over what is near the node in the
-// rest shape, the unsigned rule outside, the mirror push for a node that has crossed the skin --, an interior node skips the entry as
-// before.  Everything after the push is unchanged.
-// tests/test_collision_form_ladder.py holds this kernel to the bits of every form below it, on lists that a far trigger entry moves here.
-__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_bodyself_kernel(BatchDev b, const double *__restrict__ x, const double *__restrict__ xs,
-                                                                               const ShapeTable *__restrict__ shapes, const admm_mesh::MeshDev *__restrict__ meshes,
-                                                                               const admm_mesh::MeshMotion *__restrict__ mm, const double *__restrict__ thick, const int *__restrict__ tag,
-                                                                               const int *__restrict__ self, const int *__restrict__ vid,
-                                                                               const double *__restrict__ reach, const int *__restrict__ side_slot, const int *const *__restrict__ bnd,
-                                                                               const int *__restrict__ side, const int side_stride,
-                                                                               const double *__restrict__ bself, const double *const *__restrict__ rest, const double dt) {
-    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
-    const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    const int n = b.n;
-    if (e >= b.e1) return;
-    const int id = b.idx[e];
-    const int ds = b.dst[e];
-    const double s = b.w2h2[e];
-    double dx[3], u[3], p[3], x0[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        dx[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) dx[j] = b.dx_override[(size_t)j * n + e];
-        x0[j] = xs[3 * (size_t)id + j];
-        u[j] = b.u[(size_t)j * n + e];
-        p[j] = dx[j] + u[j];
-    }
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const int own = tag ? tag[id] : -1;
-    const int vi_own = vid ? vid[id] : -1;      // the node's vertex id on the self-colliding surface that owns it (-1: none)
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        const double before[3] = {p[0], p[1], p[2]};
-        const double *f = shapes->frame[q];
-        const bool framed = shapes->framed[q] != 0;
-        const int ty = shapes->type[q];
-        double mu = shapes->mu[q];
-        double vi[3] = {0.0, 0.0, 0.0};      // the mesh's vertex velocities at the hit, world axes
-        bool vhit = false;
-        if (ty != ADMM_SHAPE_MESH) {
-            if (!admm_frame::collide_entry(ty, shapes->par[q], f, framed, p)) continue;
-        } else {
-            const int mi = (int)shapes->par[q][3];
-            const admm_mesh::MeshDev m = meshes[mi];
-            const bool mine = own >= 0 && m.owner == own;
-            const bool bs = mine && bself[3 * mi] > 0.0;      // the node's body owns the mesh and its surface collides with itself (uniform per entry and body)
-            if (mine && !bs && !(self && self[mi])) continue;
-            if (bs && vi_own < 0) continue;                    // an interior node
-            double l[3] = {p[0], p[1], p[2]};
-            if (framed) admm_frame::to_local(f, p, l);
-            const double t[3] = {shapes->par[q][0], shapes->par[q][1], shapes->par[q][2]};
-            const double qq[3] = {l[0] - t[0], l[1] - t[1], l[2] - t[2]};
-            const double r = thick[mi];
-            admm_mesh::Hit h;
-            if (bs) {           // mesh_query.hpp, self-collision of a closed body surface (no translation, no frame: refused on a body surface)
-                double o[3]; bool crossed;
-                if (!admm_mesh::body_self_project(m.nodes, m.tris, m.nrm, mm[mi].cid, rest[mi], vi_own, qq, bself[3 * mi], bself[3 * mi + 1], bself[3 * mi + 2], stk, h, o,
-                                                  crossed)) continue;
-                l[0] = o[0]; l[1] = o[1]; l[2] = o[2];
-            } else if (r > 0.0) {
-                const double R = reach ? reach[mi] : 0.0;
-                const int sd = (R > 0.0 && !mine) ? side[(size_t)side_slot[mi] * (size_t)side_stride + id] : 0;      // (an owner's node: the unsigned rule)
-                double o[3];
-                if (sd != 0) {      // a remembered side: mesh_query.hpp, projection steps 1 to 4
-                    bool crossed;
-                    if (!admm_mesh::sided_project(m.nodes, m.tris, m.nrm, bnd[mi], qq, sd, r, R, stk, h, o, crossed)) continue;
-                } else {            // the self kernel's shell branch
-                    if (!admm_mesh::in_shell_box(qq, m.nodes[0], r)) continue;
-                    admm_mesh::closest_within_excluding(m.nodes, m.tris, mm[mi].cid, mine ? vi_own : -1, qq, r * r, stk, h);
-                    if (!admm_mesh::shell_collides(h, r)) continue;
-                    admm_mesh::shell_push(qq, h, m.nrm, r, o);
-                }
-                l[0] = t[0] + o[0]; l[1] = t[1] + o[1]; l[2] = t[2] + o[2];
-            } else {
-                if (!admm_mesh::in_box(qq, m.nodes[0])) continue;
-                admm_mesh::closest(m.nodes, m.tris, qq, stk, h);
-                if (!(admm_mesh::inside(m.nodes[0], m.nrm, qq, h) && h.d2 > 0.0)) continue;
-                l[0] = t[0] + h.c[0]; l[1] = t[1] + h.c[1]; l[2] = t[2] + h.c[2];
-            }
-            if (framed) admm_frame::to_world(f, l, p); else { p[0] = l[0]; p[1] = l[1]; p[2] = l[2]; }
-            const admm_mesh::MeshMotion mo = mm[mi];
-            if (mo.body) mu = mo.mu;
-            if (mo.vel && mu > 0.0) {
-                const admm_mesh::Tri &tr = m.tris[h.slot];
-                const int *c = mo.cid + 3 * (size_t)tr.orig;
-                const double *va = mo.vel + 3 * (size_t)c[0], *vb = mo.vel + 3 * (size_t)c[1], *vc = mo.vel + 3 * (size_t)c[2];
-                const double a0 = va[0], a1 = va[1], a2 = va[2], b0 = vb[0], b1 = vb[1], b2 = vb[2], c0 = vc[0], c1 = vc[1], c2 = vc[2];
-                double bw[3];
-                admm_mesh::tri_weights(qq, tr.v, h.reg, bw);
-                vi[0] = bw[0] * a0 + (bw[1] * b0 + bw[2] * c0); vi[1] = bw[0] * a1 + (bw[1] * b1 + bw[2] * c1); vi[2] = bw[0] * a2 + (bw[1] * b2 + bw[2] * c2);
-                if (framed) admm_frame::rotate(f, vi, vi);
-                vhit = true;
-            }
-        }
-        if (!(mu > 0.0)) continue;
-        double w[3];
-        admm_friction::rigid_displacement(shapes->motion[q], dt, p, w);
-        if (vhit) { w[0] = w[0] + dt * vi[0]; w[1] = w[1] + dt * vi[1]; w[2] = w[2] + dt * vi[2]; }
-        admm_friction::apply_moving(before, p, x0, w, mu);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double un = u[j] + (dx[j] - p[j]);
-        b.u[(size_t)j * n + e] = un; b.z[(size_t)j * n + e] = p[j];
-        b.fslot[3 * (size_t)ds + j] = s * (p[j] - un);
-    }
-}
-
-// the latch of side memory (mesh_query.hpp side_latch), once per frame from the frame-start x, eager at the start of admm_hip_step
-// (launch.inc: latch_sides): one lane per node in device order, the traversal stack in the lane's LDS column.  For every entry of the
-// current list that names a mesh with memory (slot >= 0; a list names such a mesh once): a node whose body owns the mesh is skipped,
-// any other node's side is replaced by the latch of its position in the entry's coordinates.  tag: null without owners.
-__global__ __launch_bounds__(LOCAL_BLOCK) void collision_side_kernel(const int n_nodes, const double *__restrict__ x, const ShapeTable *__restrict__ shapes,
-                                                                      const admm_mesh::MeshDev *__restrict__ meshes, const double *__restrict__ thick, const int *__restrict__ tag,
-                                                                      const double *__restrict__ reach, const int *__restrict__ side_slot, const int *const *__restrict__ bnd,
-                                                                      int *__restrict__ side) {
-    __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
-    const int id = (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
-    if (id >= n_nodes) return;
-    struct LdsStack { int *col; __device__ int &operator[](int i) { return col[i * LOCAL_BLOCK]; } } stk{&stack[0][threadIdx.x]};
-    const double p[3] = {x[3 * (size_t)id], x[3 * (size_t)id + 1], x[3 * (size_t)id + 2]};
-    const int own = tag ? tag[id] : -1;
-    const int ns = shapes->n;
-    for (int q = 0; q < ns; ++q) {
-        if (shapes->type[q] != ADMM_SHAPE_MESH) continue;
-        const int mi = (int)shapes->par[q][3];
-        const int sl = side_slot[mi];
-        if (sl < 0) continue;
-        const admm_mesh::MeshDev m = meshes[mi];
-        if (own >= 0 && m.owner == own) continue;
-        const double *f = shapes->frame[q];
-        double l[3] = {p[0], p[1], p[2]};
-        if (shapes->framed[q] != 0) admm_frame::to_local(f, p, l);
-        const double qq[3] = {l[0] - shapes->par[q][0], l[1] - shapes->par[q][1], l[2] - shapes->par[q][2]};
-        int *sp = side + (size_t)sl * (size_t)n_nodes + id;
-        *sp = admm_mesh::side_latch(m.nodes, m.tris, m.nrm, bnd[mi], qq, *sp, thick[mi], reach[mi], stk);
-    }
-}
+#include "kernels_collision.hpp"
 
 // ---------------------------------------------------------------------------
 // Spring, Force.cpp:52-71   (rows: x_a - x_b)

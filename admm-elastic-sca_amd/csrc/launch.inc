@@ -207,70 +207,53 @@ int update_bodies(admm_hip_ctx *ctx) {
     return ADMM_OK;
 }
 
-// the latch of side memory (kernels_local.hpp collision_side_kernel): every node's side on every mesh with memory that the current list
-// names, from the frame-start x; eager on ctx->stream right after update_bodies (outside the iteration and frame graphs).  Every address
-// was fixed at finalize.  Every rank holds the full frame-start x, so every rank latches every node from the same bits.
+// the device tables of the collision kernels (kernels_collision.hpp CollisionTables).  Every address was fixed at finalize; a table that
+// the context does not have is null: the mesh tables without meshes, d_body_tag without an owner, d_mesh_self / d_self_vid without a
+// self-colliding sheet (d_self_vid: or body), the side tables without a mesh with memory, d_mesh_bself / d_mesh_rest without a
+// self-colliding body.  xs = the frame-start x: d_x is written by the epilogue only.
+admm_dev::CollisionTables collision_tables(const admm_hip_ctx *ctx) {
+    admm_dev::CollisionTables T{};
+    T.xs = ctx->d_x; T.shapes = ctx->d_shapes; T.meshes = ctx->d_meshes; T.mm = ctx->d_mesh_motion; T.thick = ctx->d_mesh_thick; T.tag = ctx->d_body_tag;
+    T.self = ctx->d_mesh_self; T.vid = ctx->d_self_vid;
+    T.reach = ctx->d_mesh_reach; T.side_slot = ctx->d_mesh_side_slot; T.bnd = ctx->d_mesh_bnd; T.side = ctx->d_side; T.side_stride = ctx->n_nodes;
+    T.bself = ctx->d_mesh_bself; T.rest = ctx->d_mesh_rest;
+    T.dt = ctx->dt;
+    return T;
+}
+
+// the latch of side memory (kernels_collision.hpp collision_side_kernel): every node's side on every mesh with memory that the current
+// list names, from the frame-start x; eager on ctx->stream right after update_bodies (outside the iteration and frame graphs).  Every
+// rank holds the full frame-start x, so every rank latches every node from the same bits.
 int latch_sides(admm_hip_ctx *ctx) {
     using namespace admm_dev;
     if (!ctx->d_side || !sided_on(ctx)) return ADMM_OK;
     const int n = ctx->n_nodes;
-    hipLaunchKernelGGL(collision_side_kernel, dim3((unsigned)((n + LOCAL_BLOCK - 1) / LOCAL_BLOCK)), dim3(LOCAL_BLOCK), 0, ctx->stream, n, (const double *)ctx->d_x,
-                       (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag,
-                       (const double *)ctx->d_mesh_reach, (const int *)ctx->d_mesh_side_slot, (const int *const *)ctx->d_mesh_bnd, ctx->d_side);
+    hipLaunchKernelGGL(collision_side_kernel, dim3((unsigned)((n + LOCAL_BLOCK - 1) / LOCAL_BLOCK)), dim3(LOCAL_BLOCK), 0, ctx->stream, collision_tables(ctx));
     HIPCHK(hipGetLastError());
     return ADMM_OK;
 }
 
-// a collision batch of a context with mesh obstacles, friction, framed entries or boxes
+// a collision batch of a context with mesh obstacles, friction, framed entries or boxes: the kernel of the list's form.  (Forms 4 and up
+// imply meshes; a body surface with a coefficient implies meshes and an entry's motion implies friction_on, so form 2 is reached.)
 void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
-    if (bodyself_on(ctx)) {      // (d_mesh_bself, d_mesh_rest and d_self_vid were uploaded at finalize: the lengths are set before it; the side and sheet tables: null where there is none)
-        hipLaunchKernelGGL(project_collision_bodyself_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
-                           (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, (const int *)ctx->d_mesh_self, (const int *)ctx->d_self_vid,
-                           (const double *)ctx->d_mesh_reach, (const int *)ctx->d_mesh_side_slot, (const int *const *)ctx->d_mesh_bnd, (const int *)ctx->d_side,
-                           ctx->n_nodes, (const double *)ctx->d_mesh_bself, (const double *const *)ctx->d_mesh_rest, ctx->dt);
-    } else if (sided_on(ctx)) {      // (implies shell_on; the side tables were uploaded at finalize: the reach is set before it.  d_mesh_self, d_self_vid: null without a self-colliding sheet)
-        hipLaunchKernelGGL(project_collision_sided_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
-                           (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, (const int *)ctx->d_mesh_self, (const int *)ctx->d_self_vid,
-                           (const double *)ctx->d_mesh_reach, (const int *)ctx->d_mesh_side_slot, (const int *const *)ctx->d_mesh_bnd, (const int *)ctx->d_side,
-                           ctx->n_nodes, ctx->dt);
-    } else if (self_on(ctx)) {      // (implies shell_on; d_mesh_self and d_self_vid were uploaded at finalize: the flag is set before it)
-        hipLaunchKernelGGL(project_collision_self_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
-                           (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, (const int *)ctx->d_mesh_self, (const int *)ctx->d_self_vid, ctx->dt);
-    } else if (shell_on(ctx)) {      // (implies meshes)
-        hipLaunchKernelGGL(project_collision_shell_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
-                           (const double *)ctx->d_mesh_thick, (const int *)ctx->d_body_tag, ctx->dt);
-    } else if (framed_on(ctx)) {
-        if (!ctx->meshes.empty())
-            hipLaunchKernelGGL(project_collision_framed_kernel<true>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                               (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
-                               (const int *)ctx->d_body_tag, ctx->dt);
-        else
-            hipLaunchKernelGGL(project_collision_framed_kernel<false>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                               (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)nullptr, (const admm_mesh::MeshMotion *)nullptr, (const int *)nullptr, ctx->dt);
-    } else if (moving_friction_on(ctx)) {      // (a body surface with a coefficient implies meshes, an entry's motion implies friction_on: this launch is reached)
-        if (!ctx->meshes.empty())
-            hipLaunchKernelGGL(project_collision_friction_moving_kernel<true>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                               (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const admm_mesh::MeshMotion *)ctx->d_mesh_motion,
-                               (const int *)ctx->d_body_tag, ctx->dt);
-        else
-            hipLaunchKernelGGL(project_collision_friction_moving_kernel<false>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                               (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)nullptr, (const admm_mesh::MeshMotion *)nullptr, (const int *)nullptr, ctx->dt);
-    } else if (!friction_on(ctx))
-        hipLaunchKernelGGL(project_collision_mesh_kernel, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur,
-                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const int *)ctx->d_body_tag);
-    else if (!ctx->meshes.empty())      // x0 = the frame-start x: d_x is written by the epilogue only
-        hipLaunchKernelGGL(project_collision_friction_kernel<true>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes, (const int *)ctx->d_body_tag);
-    else
-        hipLaunchKernelGGL(project_collision_friction_kernel<false>, grid, block, 0, ctx->stream, d, (const double *)ctx->d_xcur, (const double *)ctx->d_x,
-                           (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)nullptr, (const int *)nullptr);
+    const double *x = ctx->d_xcur;
+    const CollisionTables T = collision_tables(ctx);
+    const bool mesh = !ctx->meshes.empty();
+#define ADMM_COLLIDE(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, 0, ctx->stream, d, x, T)
+    switch (collision_form(ctx)) {
+    case 7: ADMM_COLLIDE(project_collision_bodyself_kernel); break;
+    case 6: ADMM_COLLIDE(project_collision_sided_kernel); break;
+    case 5: ADMM_COLLIDE(project_collision_self_kernel); break;
+    case 4: ADMM_COLLIDE(project_collision_shell_kernel); break;
+    case 3: if (mesh) ADMM_COLLIDE(project_collision_framed_kernel<true>); else ADMM_COLLIDE(project_collision_framed_kernel<false>); break;
+    case 2: if (mesh) ADMM_COLLIDE(project_collision_friction_moving_kernel<true>); else ADMM_COLLIDE(project_collision_friction_moving_kernel<false>); break;
+    case 1: if (mesh) ADMM_COLLIDE(project_collision_friction_kernel<true>); else ADMM_COLLIDE(project_collision_friction_kernel<false>); break;
+    default: ADMM_COLLIDE(project_collision_mesh_kernel); break;      // (form 0 in a launch of its own: collision_own_launch, so the context has meshes)
+    }
+#undef ADMM_COLLIDE
 }
 
 int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {

@@ -1,5 +1,5 @@
 // mesh_query.hpp -- triangle-mesh obstacles (ADMM_SHAPE_MESH: closed meshes, and open surfaces as thick shells): the point query shared by the host (mesh.cpp:
-// admm_hip_mesh_query, the class mirror's CollisionMesh) and the device (kernels_local.hpp project_collision_mesh_kernel).
+// admm_hip_mesh_query, the class mirror's CollisionMesh) and the device (kernels_collision.hpp project_collision_mesh_kernel).
 // Both sides compile it with -ffp-contract=off and run the same traversal in the same order, so they give the same bits.
 //
 // Query of a point q (already relative to the instance's translation):

@@ -1,4 +1,4 @@
-"""The eight collision kernel forms held to each other's bits (csrc/launch.inc collision_form, csrc/kernels_local.hpp project_collision_*):
+"""The eight collision kernel forms held to each other's bits (csrc/launch.inc collision_form, csrc/kernels_collision.hpp project_collision_*):
 one context that set_collision_shapes walks through every form, a ladder of lists L0 .. L7 that each add what their form introduces, and
 for every list Lk the same list with a trigger entry Tj appended that nothing reaches, which moves every collision element onto the kernel
 of form j > k.
@@ -6,7 +6,7 @@ of form j > k.
 CPU: every list composed on the host from the host twins alone (shape_query, Mesh.query / query_excluding / query_sided / query_self,
 mesh_velocity_query and its excluding / self forms, friction_query_moving), with the counts that keep the GPU tests from passing vacuously.
 GPU: the base rungs (form k on Lk) bitwise the host composition; the 28 ladder pairs (form j on Lk + Tj bitwise form k on Lk); a context
-without meshes against the big one on an analytic list; three frames of step(10) on L3 + Tj for j = 3 .. 7 bitwise equal.
+without meshes against the big one on the analytic entries of L0 .. L3; three frames of step(10) on L3 + Tj for j = 3 .. 7 bitwise equal.
 
 The scene (registered in this order, so that mesh ids never change): 0 a closed icosphere, 1 a closed cube, 2 the surface of a 2 x 2 x 2
 tet body, 3 an open grid (a thick shell), 4 the folded strip of test_sheet_self_collision at half size (a self-colliding sheet), 5 an open
@@ -176,6 +176,11 @@ def _scene(pkg):
 
 def _entries(C, k, j):
     return C["lists"][k] + ([C["trig"][j]] if j > k else [])
+
+
+def _analytic(C, k):
+    """the entries of Lk that are not meshes: floor, sphere, cylinder, from L3 on the box"""
+    return [e for e in C["lists"][k] if e["ty"] != MESH]
 
 
 def _system(pkg, C, device_id, gravity=False):
@@ -441,7 +446,9 @@ def test_form_j_gives_form_k_bits(pkg, k, j):
 @pytest.mark.gpu
 def test_analytic_only_context_gives_the_same_bits(pkg):
     """a context without meshes (project_collision_kernel) against the big one (project_collision_mesh_kernel) on floor, sphere,
-    cylinder: the same nodes, elements, candidates and u"""
+    cylinder: the same nodes, elements, candidates and u.  Then the analytic entries of L1, L2 and L3 with their coefficients, motions
+    and frames (L3: the box too): form k on both contexts, the MESH = false instantiation of the friction, moving-friction and framed
+    kernels against the MESH = true one"""
     C = _scene(pkg)
     _rung(pkg, 0, 0)
     big = _GPU["s"]
@@ -452,19 +459,25 @@ def test_analytic_only_context_gives_the_same_bits(pkg):
     b = a.add_forces(KIND["COLLISION"], C["elems"], [W])
     a.set_collision_shapes([e["ty"] for e in E], [e["par"] for e in E])
     a.initialize()
-    out = []
-    for s, bt in ((a, b), (big, big.batch)):
-        s.set_collision_shapes([], np.zeros((0, 4)))
-        s.set_collision_shapes([e["ty"] for e in E], [e["par"] for e in E])
-        assert s.collision_form() == 0
-        s.m_x = C["x0"].ravel()
-        s.write_local(bt, u=C["u"])
-        s.local_step_dx(bt, C["dx"])
-        r = s.read_local(bt)
-        out.append((r["z"].copy(), r["u"].copy()))
-    moved = (out[0][0] != C["dx"] + C["u"]).any(1).sum()
-    assert moved >= 100, moved
-    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
+    for k in range(4):
+        E = _analytic(C, k)
+        out = []
+        for s, bt in ((a, b), (big, big.batch)):
+            s.set_collision_shapes([], np.zeros((0, 4)))
+            s.set_collision_shapes([e["ty"] for e in E], [e["par"] for e in E])
+            if k >= 1:
+                s.set_collision_friction([e["mu"] for e in E])
+                s.set_collision_motion([e["motion"] for e in E])
+                s.set_collision_frames([e["frame"] for e in E])
+            assert s.collision_form() == k, (k, s.collision_form())
+            s.m_x = C["x0"].ravel()
+            s.write_local(bt, u=C["u"])
+            s.local_step_dx(bt, C["dx"])
+            r = s.read_local(bt)
+            out.append((r["z"].copy(), r["u"].copy()))
+        moved = (out[0][0] != C["dx"] + C["u"]).any(1).sum()
+        assert moved >= 100, (k, moved)
+        assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1]), k
 
 
 @pytest.mark.gpu

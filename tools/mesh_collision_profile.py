@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """The mesh-collision launch on the headline bar (32x32x163 cubes, 178 596 nodes): a collision batch over all nodes whose shape list is
 ONE level-6 icosphere (81 920 triangles) of radius 0.6 centred on the bar's axis halfway along it (`mesh`), or an analytic sphere of the
-same radius and centre (`sphere`).  Run under  rocprofv3 --kernel-trace --stats -- python tools/mesh_collision_profile.py mesh|sphere
-usage: mesh_collision_profile.py mesh|sphere [frames=3] [iters=10] [nx ny nz]"""
+same radius and centre (`sphere`), or the icosphere turned about its centre with a friction coefficient (`framed`: every element on
+project_collision_framed_kernel<true>, the lowest instantiation of the body that forms 3 to 7 share).
+Run under  rocprofv3 --kernel-trace --stats -- python tools/mesh_collision_profile.py mesh|sphere|framed
+usage: mesh_collision_profile.py mesh|sphere|framed [frames=3] [iters=10] [nx ny nz]"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from __graft_entry__ import load_package
+from test_collision_frames import _frame, _rot
 from test_collision_mesh import icosphere
 
 pkg = load_package()
@@ -21,10 +24,14 @@ s = pkg.make_bar_system(nx, ny, nz, device_id=0, h=h)
 n = (nx + 1) * (ny + 1) * (nz + 1)
 s.add_forces(pkg.KIND["COLLISION"], np.arange(n, dtype=np.int32), [32.0])
 c = np.array([nx * h / 2, ny * h / 2, nz * h / 2])
-if mode == "mesh":
+if mode in ("mesh", "framed"):
     V, F = icosphere(6, R)
     mid = s.add_collision_mesh(V, F)
     s.set_collision_shapes([pkg.SHAPE["MESH"]], [[*c, mid]])
+    if mode == "framed":
+        s.set_collision_friction([0.3])
+        s.set_collision_frames([_frame(_rot([0.2, 1.0, -0.4], 0.8), c)])
+        assert s.collision_form() == 3, s.collision_form()
 else:
     s.set_collision_shapes([pkg.SHAPE["SPHERE"]], [[*c, R]])
 s.keep_z(False)
