@@ -86,6 +86,17 @@ CONTACT_DTYPE = np.dtype(dict(names=["node", "f", "point", "depth"], formats=[np
                               offsets=[0, 8, 32, 56], itemsize=64))
 
 
+class GroupMoments(C.Structure):
+    """admm_hip_group_moments: a damping group's mass, centre of mass, momentum, angular momentum and inertia about it, angular velocity"""
+    _fields_ = [("mass", C.c_double), ("com", C.c_double * 3), ("p", C.c_double * 3), ("l", C.c_double * 3), ("inertia", C.c_double * 6), ("omega", C.c_double * 3),
+                ("t_total", C.c_double), ("t_rigid", C.c_double), ("n_nodes", C.c_int64), ("degenerate", C.c_int32), ("pad_", C.c_int32)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n in ("mass", "t_total", "t_rigid", "n_nodes", "degenerate")}
+        d.update({n: np.array(getattr(self, n)[:]) for n in ("com", "p", "l", "inertia", "omega")})
+        return d
+
+
 class AccelerationRecord(C.Structure):
     _fields_ = [("rho", C.c_double)] + [(n, C.c_int32) for n in ("accepted", "m_used", "extrapolated", "solve_failed")] + \
                [("theta", C.c_double * 8), ("gram", C.c_double * 64), ("rhs", C.c_double * 8)]
@@ -152,6 +163,10 @@ def lib():
         L.admm_hip_get_contacts.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.admm_hip_contact_resultant.argtypes = [C.c_void_p, C.c_double, _dp, _dp, C.POINTER(C.c_int64)]
         L.admm_hip_reaction_query.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _ip, _dp]
+        L.admm_hip_add_damping_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int)]
+        L.admm_hip_set_damping.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+        L.admm_hip_get_group_moments.argtypes = [C.c_void_p, C.c_int, C.POINTER(GroupMoments)]
+        L.admm_hip_damping_query.argtypes = [C.c_int64, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, C.POINTER(GroupMoments)]
         L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
         L.admm_hip_add_nodes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
@@ -569,6 +584,22 @@ def reaction_query(w2, u, z, x, depth_min=1e-10, pivot=(0.0, 0.0, 0.0)):
     if rc:
         raise AdmmHipError("admm_hip_reaction_query error %d" % rc)
     return dict(f=f, depth=depth, flag=flag.astype(bool), force=r6[:3].copy(), torque=r6[3:].copy())
+
+
+def damping_query(m, x, v, dt, drag, internal):
+    """the velocity filter of one damping group on the host (admm_hip_damping_query; csrc/damping.hpp, the device's bits; needs no GPU):
+    m [n] (or a scalar): the nodes' masses, x, v [n][3], dt, the rates drag and internal in 1/s -> (v_out [n][3], moments: the dict of
+    System.group_moments for the input state)"""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+    n = x.shape[0]
+    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3)
+    assert v.shape == x.shape
+    mm = np.ascontiguousarray(np.broadcast_to(np.asarray(m, dtype=np.float64), (n,)))
+    out = np.zeros((n, 3)); rec = GroupMoments()
+    rc = lib().admm_hip_damping_query(n, _d(mm), _d(x), _d(v), float(dt), float(drag), float(internal), _d(out), C.byref(rec))
+    if rc:
+        raise AdmmHipError("admm_hip_damping_query error %d" % rc)
+    return out, rec.as_dict()
 
 
 def stress_query(kind, dx, params, volume):
@@ -1007,6 +1038,26 @@ class System:
         out = np.zeros(6); cnt = C.c_int64(0)
         self._chk(self.L.admm_hip_contact_resultant(self.h, float(depth_min), _d(pv), _d(out), C.byref(cnt)))
         return out[:3].copy(), out[3:].copy(), cnt.value
+
+    # ---- velocity damping per node group, applied after every frame (extension; include/admm_hip.h) ----
+    def add_damping_group(self, node_first=0, node_count=None, drag=0.0, internal=0.0):
+        """-> group id.  Nodes [node_first, node_first + node_count) in the caller's order (None: through the last node), rates in 1/s:
+        drag (ether drag), internal (removes what is not the group's rigid-body motion).  Before initialize() only."""
+        cnt = self.n_nodes - int(node_first) if node_count is None else int(node_count)
+        g = C.c_int()
+        self._chk(self.L.admm_hip_add_damping_group(self.h, int(node_first), cnt, float(drag), float(internal), C.byref(g)))
+        return g.value
+
+    def set_damping(self, group, drag, internal):
+        """new rates of one group, in effect from the next step() on"""
+        self._chk(self.L.admm_hip_set_damping(self.h, int(group), float(drag), float(internal)))
+
+    def group_moments(self, group):
+        """-> dict(mass, com [3], p [3], l [3] about com, inertia [6] = xx yy zz xy xz yz about com, omega [3], t_total, t_rigid, n_nodes,
+        degenerate) of one damping group from the device's current x, v"""
+        rec = GroupMoments()
+        self._chk(self.L.admm_hip_get_group_moments(self.h, int(group), C.byref(rec)))
+        return rec.as_dict()
 
     def enable_objective(self, on=True):
         self._chk(self.L.admm_hip_enable_objective(self.h, 1 if on else 0))

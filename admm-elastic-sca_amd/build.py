@@ -9,6 +9,7 @@
                                            stress (gradient.hpp), g++ -O3 -ffp-contract=off likewise
   anderson_host.cpp                      : the host twin of Anderson acceleration's small solve (anderson.hpp), likewise
   reaction_host.cpp                      : the host twin of the contact and anchor reactions and their resultant (reaction.hpp), likewise
+  damping_host.cpp                       : the host twin of the velocity damping per node group and its moments (damping.hpp), likewise
   admm_hip.hip                           : the device translation unit: kernels (kernels_*.hpp, factor_dev.hpp), device factorization,
                                            upload, launches, step loop, C ABI; hipcc --offload-arch=gfx950, -ffp-contract=off
                                            (operation order = reference's)
@@ -83,6 +84,7 @@ def _jobs(extra_hip_flags, tag):
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "gradient_host.cpp", "gradient_host.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "anderson_host.cpp", "anderson_host.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "reaction_host.cpp", "reaction_host.o"),
+        (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "damping_host.cpp", "damping_host.o"),
         ([hipcc] + HIP_FLAGS + list(extra_hip_flags), "admm_hip.hip", "admm_hip%s.o" % tag),
     ]
 

@@ -27,6 +27,7 @@
 #include "kernels_gradient.hpp"
 #include "kernels_anderson.hpp"
 #include "kernels_reaction.hpp"
+#include "kernels_damping.hpp"
 
 extern "C" int omp_get_max_threads(void);
 
@@ -76,6 +77,7 @@ extern "C" {
 #include "abi_gradient.inc"
 #include "abi_anderson.inc"
 #include "abi_reaction.inc"
+#include "abi_damping.inc"
 #include "abi_step.inc"
 #include "abi_parity.inc"
 

@@ -289,6 +289,14 @@ struct admm_hip_ctx {
     // resultant's partials [6][blocks], then its six totals
     bool rx_ready = false; double *d_rx_el = nullptr, *d_rx_node = nullptr, *d_rx_part = nullptr; int *d_rx_blk = nullptr; long long *d_rx_count = nullptr; void *d_rx_rec = nullptr;
     int *d_rx_ptr[2] = {nullptr, nullptr}, *d_rx_stride[2] = {nullptr, nullptr}; long long *d_rx_off[2] = {nullptr, nullptr};
+    // velocity damping per node group (abi_damping.inc, kernels_damping.hpp, damping.hpp; no group = off, the default).  damp_groups: the
+    // caller's groups in the order they were added; rate_dirty: the device's rate entry is older than drag / internal.  Device side, created
+    // by upload_all when there is a group: the block -> (group, first node) table, the groups' ranges, their rates (written by
+    // damping_set_rate_kernel from kernel arguments, at the start of the first filter that runs after a change), the moments records,
+    // v_c [groups][3] and the stages' partials [9][damp_blocks]
+    struct DampGroupHost { int node_first = 0, node_count = 0; double drag = 0.0, internal = 0.0; bool rate_dirty = true; };
+    std::vector<DampGroupHost> damp_groups;
+    int damp_blocks = 0; void *d_damp_blk = nullptr, *d_damp_grp = nullptr, *d_damp_rate = nullptr, *d_damp_mom = nullptr; double *d_damp_vc = nullptr, *d_damp_part = nullptr;
     // Anderson acceleration (abi_anderson.inc, kernels_anderson.hpp; window 0 = off, the default; every buffer created by the first step
     // that needs it, again when the window grows).  aa_T: doubles per state-sized vector (all batches' z and u, each segment at an even
     // offset), aa_nblk: blocks of the elementwise launches; d_aa_ring, allocated for the window aa_cap_m, used as [2][aa_m + 1][aa_T]: the history's g, then its f;

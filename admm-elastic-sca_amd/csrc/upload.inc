@@ -774,6 +774,27 @@ int upload_all(admm_hip_ctx *ctx) {
             TRY(upload(ctx, &E.d_idx, sorted)); TRY(upload(ctx, &E.d_level_ptr, lptr));
         } else if (!pidx.empty()) TRY(upload(ctx, &E.d_idx, pidx));
     }
+    // damping groups (kernels_damping.hpp): one block per 64 consecutive nodes of a group, counted from its first node; a context with
+    // no group uploads nothing
+    ctx->damp_blocks = 0; ctx->d_damp_blk = ctx->d_damp_grp = ctx->d_damp_rate = ctx->d_damp_mom = nullptr; ctx->d_damp_vc = ctx->d_damp_part = nullptr;
+    if (!ctx->damp_groups.empty()) {
+        using namespace admm_dev;
+        const size_t ng = ctx->damp_groups.size();
+        std::vector<DampGroup> grp(ng); std::vector<DampBlock> blk;
+        for (size_t g = 0; g < ng; ++g) {
+            admm_hip_ctx::DampGroupHost &H = ctx->damp_groups[g];
+            const int nb = (H.node_count + DAMP_BLOCK - 1) / DAMP_BLOCK;
+            grp[g] = DampGroup{H.node_first, H.node_count, (int)blk.size(), nb};
+            for (int b = 0; b < nb; ++b) blk.push_back(DampBlock{(int)g, H.node_first + b * DAMP_BLOCK});
+            H.rate_dirty = true;
+        }
+        ctx->damp_blocks = (int)blk.size();
+        DampBlock *db = nullptr; DampGroup *dg = nullptr; DampRate *dr = nullptr; admm_damping::Moments *dm = nullptr;
+        TRY(upload(ctx, &db, blk)); TRY(upload(ctx, &dg, grp)); TRY(dalloc(ctx, &dr, ng)); TRY(dalloc(ctx, &dm, ng));
+        TRY(dalloc(ctx, &ctx->d_damp_vc, 3 * ng)); TRY(dalloc(ctx, &ctx->d_damp_part, (size_t)admm_damping::N_SUMS_2 * blk.size()));
+        HIPCHK(hipMemset(dr, 0, sizeof(DampRate) * ng)); HIPCHK(hipMemset(dm, 0, sizeof(admm_damping::Moments) * ng)); HIPCHK(hipMemset(ctx->d_damp_vc, 0, sizeof(double) * 3 * ng));
+        ctx->d_damp_blk = db; ctx->d_damp_grp = dg; ctx->d_damp_rate = dr; ctx->d_damp_mom = dm;
+    }
     HIPCHK(hipDeviceSynchronize());
     ctx->info.t_upload_s = now_s() - t0;
     return ADMM_OK;

@@ -279,6 +279,10 @@ public:
             std::vector<int32_t> il32(il.begin(), il.end());
             if (!check(admm_hip_add_explicit(gpu, type, d, cnt, il32.empty() ? nullptr : il32.data(), &explicit_slot[i]))) return false;
         }
+        for (size_t g = 0; g < damping_groups.size(); ++g) {      // (a bad range, an overlap or a bad rate fails here, with the library's message)
+            const DampingGroup &d = damping_groups[g];
+            if (!check(admm_hip_add_damping_group(gpu, d.node_first, d.node_count < 0 ? dof / 3 - d.node_first : d.node_count, d.drag, d.internal, nullptr))) return false;
+        }
         if (!check(admm_hip_finalize(gpu))) return false;
         // write back what Force::initialize / get_selector compute in the reference
         user_local.clear();
@@ -486,6 +490,35 @@ public:
         return log;
     }
 
+    // extension, no reference counterpart (admm_hip_add_damping_group): velocity damping of the nodes [node_first, node_first + node_count)
+    // of m_x's node order (node_count < 0: through the last node), applied on the device after every step(): `drag` (1/s) is ether drag,
+    // `internal` (1/s) removes the velocity that is not the group's rigid-body motion, so a flying, spinning body keeps both while its
+    // jiggle dies.  Groups are disjoint.  Before initialize() only, which hands them to the library and fails on a bad one; returns the
+    // group's id (-1: refused because the system is initialized already).
+    struct DampingGroup { int node_first, node_count; double drag, internal; };
+    int add_damping_group(int node_first = 0, int node_count = -1, double drag = 0.0, double internal = 0.0) {
+        if (initialized) { std::cerr << "\n**Solver Error: add_damping_group after initialize()" << std::endl; return -1; }
+        const DampingGroup d = {node_first, node_count, drag, internal};
+        damping_groups.push_back(d);
+        return (int)damping_groups.size() - 1;
+    }
+    // new rates of one group (admm_hip_set_damping), in effect from the next step() on; before or after initialize()
+    bool set_damping(int group, double drag, double internal) {
+        if (group < 0 || group >= (int)damping_groups.size()) { std::cerr << "\n**Solver Error: set_damping: group " << group << " does not exist" << std::endl; return false; }
+        if (initialized && !check(admm_hip_set_damping(gpu, group, drag, internal))) return false;
+        damping_groups[group].drag = drag; damping_groups[group].internal = internal;
+        return true;
+    }
+    // a group's mass, centre of mass, momentum, angular momentum and inertia about it, angular velocity and kinetic energies from the
+    // device state as the last step() left it (admm_hip_get_group_moments); ok = false: the call failed (not initialized, no such group)
+    struct GroupMoments { admm_hip_group_moments m; bool ok; };
+    GroupMoments group_moments(int group) {
+        GroupMoments r; std::memset(&r.m, 0, sizeof r.m); r.ok = false;
+        if (!initialized) return r;
+        r.ok = check(admm_hip_get_group_moments(gpu, group, &r.m));
+        return r;
+    }
+
     admm_hip_ctx *context() { return gpu; }
 
 protected:
@@ -510,6 +543,7 @@ protected:
     VectorXd user_Dx, user_u, user_z;
     void *pinned_x, *pinned_v, *seen_x, *seen_v; size_t pinned_bytes;
     std::vector<double> anchor_tgt, anchor_loc; std::vector<int32_t> anchor_act, anchor_ids;     // step(): this frame's control points
+    std::vector<DampingGroup> damping_groups;      // add_damping_group's records, handed to the library by initialize()
     int init_count;                        // initialize() calls so far (every rank counts alike: part of the rendezvous file's name)
 
     // world > 1: hand rank / world / mode to the library and install the all-reduce -- a caller's hook, or (default) an RCCL

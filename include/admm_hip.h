@@ -937,6 +937,48 @@ int admm_hip_contact_resultant(admm_hip_ctx *ctx, double depth_min, const double
 int admm_hip_reaction_query(int64_t n, const double *w2, const double *u, const double *z, const double *x, double depth_min, const double *pivot,
                             double *f, double *depth, int32_t *flag, double *resultant6);
 
+/* ---- velocity damping per node group, applied after every frame ---------------------------------------------------------------------------
+ * Extension, no reference counterpart.  A damping group is a range [node_first, node_first + node_count) of nodes in the caller's node
+ * order with two rates in 1/s: drag >= 0 (ether drag) and internal >= 0 (the momentum-preserving damping of Mueller et al., Position
+ * Based Dynamics, section 3.5: it removes the velocity that is not the group's rigid-body motion, so a thrown or spinning body keeps
+ * flying and spinning while its jiggle dies).  Groups are disjoint.  admm_hip_step applies the filter to the v its epilogue left, with x
+ * the new positions and m the nodes' scalar masses:
+ *     M = sum m,  c = sum m x / M,  v_c = sum m v / M,  r = x - c
+ *     L = sum m r x (v - v_c),  I = sum m (|r|^2 1 - r r^T),  omega = I^-1 L
+ *     v <- v + beta ((v_c + omega x r) - v),  beta = internal dt / (1 + internal dt);    then v <- s v,  s = 1 / (1 + drag dt)
+ * A group with internal == 0 takes v <- s v alone; a group with both rates zero is not touched.  A group of fewer than three nodes, or
+ * with det I <= 1e-10 (tr I / 3)^3 (DAMPING_DEGENERATE: all nodes on a line), is degenerate: omega = 0, so its rotation is damped too.
+ * One definition, csrc/damping.hpp, compiled without fused multiply-adds for the host and the device, with the sums' order written
+ * out (64-node blocks from the group's first node, then the energies' two-stage reduction; no atomics): both give the same bits, which
+ * depend neither on the elimination order nor on sharding.  Every rank of a sharded context filters its own whole copy of v.
+ * Launches (csrc/kernels_damping.hpp), on the context's stream, eager, outside the captured graphs, inside the epilogue interval of the
+ * timing events: five per frame when any group has internal > 0, one when only drag is set, none when every rate is zero or there is
+ * no group -- such a context launches what it launched before and produces bitwise the same frames.
+ *   admm_hip_add_damping_group   extension, no reference counterpart.  Before finalize only (ADMM_ERR_STATE after).  ADMM_ERR_ARG, with
+ *                                admm_hip_last_error naming the value: a range outside the nodes added so far, node_count < 1, an overlap
+ *                                with an earlier group (both are named), a negative or non-finite rate.  *group_id: 0, 1, ... in call order.
+ *   admm_hip_set_damping         extension, no reference counterpart.  Before or after finalize: new rates for one group, in effect from the
+ *                                next admm_hip_step on; no synchronisation, legal between steps on a caller's stream.
+ *   admm_hip_get_group_moments   extension, no reference counterpart.  The sums above from the context's current x, v, computed on demand
+ *                                (four launches, one synchronisation), also for a group with zero rates.  Needs a device and a finalized
+ *                                context (ADMM_ERR_STATE otherwise).  t_total = sum 1/2 m |v|^2, t_rigid = 1/2 M |v_c|^2 + 1/2 omega . L;
+ *                                inertia = xx yy zz xy xz yz about com; l about com.
+ *   admm_hip_damping_query       extension, no reference counterpart.  Context-free host evaluation of one group of n nodes, the device's
+ *                                bits; needs no GPU: m [n], x, v [n][3] -> v_out [n][3], *moments (of the input state).  Either output may
+ *                                be NULL.  ADMM_ERR_ARG: n < 1, a NULL input, dt not > 0, a negative or non-finite rate.
+ * Not covered: stiffness-proportional (Rayleigh) damping, per-element strain-rate damping, drag towards a wind field, groups that are
+ * not ranges.                                                                                                                            */
+typedef struct admm_hip_group_moments {
+    double mass, com[3], p[3], l[3], inertia[6], omega[3], t_total, t_rigid;
+    int64_t n_nodes;
+    int32_t degenerate, pad_;
+} admm_hip_group_moments;
+int admm_hip_add_damping_group(admm_hip_ctx *ctx, int node_first, int node_count, double drag, double internal, int *group_id);
+int admm_hip_set_damping(admm_hip_ctx *ctx, int group, double drag, double internal);
+int admm_hip_get_group_moments(admm_hip_ctx *ctx, int group, admm_hip_group_moments *out);
+int admm_hip_damping_query(int64_t n, const double *m, const double *x, const double *v, double dt, double drag, double internal,
+                           double *v_out, admm_hip_group_moments *moments);
+
 #ifdef __cplusplus
 }
 #endif
