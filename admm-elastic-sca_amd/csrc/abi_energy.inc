@@ -30,27 +30,38 @@ static int ensure_energy_buffers(admm_hip_ctx *ctx, int iters) {
     return ADMM_OK;
 }
 
-// the per-element kernel of one batch on the positions x (device order), then -- total != null -- the batch's sum and count
+// the per-element kernel of one batch's kind for the output o (EnergyOut: `what` = "energy", GradOut: "gradient") on the positions x
+// (device order); an empty batch launches nothing.  (extern "C++": this file is included inside extern "C", where no template may stand)
+extern "C++" {
+template <class Out> static int launch_element_kernel(admm_hip_ctx *ctx, const Batch &b, const double *x, const Out &o, const char *what) {
+    using namespace admm_dev;
+    const int nblk = energy_blocks(b.n_local);
+    if (!nblk) return ADMM_OK;
+    ElementKernel<Out> k = nullptr;
+    switch (b.kind) {
+    case ADMM_KIND_TET_NH: k = tet_kernel<ADMM_KIND_TET_NH>(o); break;
+    case ADMM_KIND_TET_STVK: k = tet_kernel<ADMM_KIND_TET_STVK>(o); break;
+    case ADMM_KIND_TET_LINEAR: k = tet_kernel<ADMM_KIND_TET_LINEAR>(o); break;
+    case ADMM_KIND_TET_VOLUME: k = tet_kernel<ADMM_KIND_TET_VOLUME>(o); break;
+    case ADMM_KIND_TRI_STRAIN: k = tri_kernel<ADMM_KIND_TRI_STRAIN>(o); break;
+    case ADMM_KIND_TRI_AREA: k = tri_kernel<ADMM_KIND_TRI_AREA>(o); break;
+    case ADMM_KIND_TRI_FUNG: k = tri_kernel<ADMM_KIND_TRI_FUNG>(o); break;
+    case ADMM_KIND_BEND: k = bend_kernel(o); break;
+    case ADMM_KIND_SPRING: k = spring_kernel(o); break;
+    case ADMM_KIND_ANCHOR: k = anchor_kernel(o); break;
+    default: return fail(ctx, ADMM_ERR_UNSUPPORTED, "no %s is evaluated for kind %d", what, b.kind);
+    }
+    hipLaunchKernelGGL(k, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, batch_dev(ctx, b), x, o);
+    HIPCHK(hipGetLastError());
+    return ADMM_OK;
+}
+} // extern "C++"
+
+// the energy kernel of one batch on the positions x (device order), then -- total != null -- the batch's sum and count
 static int launch_batch_energy(admm_hip_ctx *ctx, const Batch &b, const double *x, double *total, long long *count) {
     using namespace admm_dev;
-    const BatchDev d = batch_dev(ctx, b);
-    const EnergyOut o{b.d_escale, b.d_eE, b.d_epart, b.d_ecnt};
-    const int nblk = energy_blocks(b.n_local);
-    const dim3 grid(nblk), block(ENERGY_BLOCK);
-    if (nblk) switch (b.kind) {
-    case ADMM_KIND_TET_NH: hipLaunchKernelGGL(energy_tet_kernel<ADMM_KIND_TET_NH>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TET_STVK: hipLaunchKernelGGL(energy_tet_kernel<ADMM_KIND_TET_STVK>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TET_LINEAR: hipLaunchKernelGGL(energy_tet_kernel<ADMM_KIND_TET_LINEAR>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TET_VOLUME: hipLaunchKernelGGL(energy_tet_kernel<ADMM_KIND_TET_VOLUME>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TRI_STRAIN: hipLaunchKernelGGL(energy_tri_kernel<ADMM_KIND_TRI_STRAIN>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TRI_AREA: hipLaunchKernelGGL(energy_tri_kernel<ADMM_KIND_TRI_AREA>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TRI_FUNG: hipLaunchKernelGGL(energy_tri_kernel<ADMM_KIND_TRI_FUNG>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_BEND: hipLaunchKernelGGL(energy_bend_kernel, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_SPRING: hipLaunchKernelGGL(energy_spring_kernel, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_ANCHOR: hipLaunchKernelGGL(energy_anchor_kernel, grid, block, 0, ctx->stream, d, x, o); break;
-    default: return fail(ctx, ADMM_ERR_UNSUPPORTED, "no energy is evaluated for kind %d", b.kind);
-    }
-    if (total) hipLaunchKernelGGL(energy_reduce_kernel, dim3(1), dim3(ENERGY_REDUCE), 0, ctx->stream, nblk, (const double *)b.d_epart, (const int *)b.d_ecnt, total, count);
+    TRY(launch_element_kernel(ctx, b, x, EnergyOut{b.d_escale, b.d_eE, b.d_epart, b.d_ecnt}, "energy"));
+    if (total) hipLaunchKernelGGL(energy_reduce_kernel, dim3(1), dim3(ENERGY_REDUCE), 0, ctx->stream, energy_blocks(b.n_local), (const double *)b.d_epart, (const int *)b.d_ecnt, total, count);
     HIPCHK(hipGetLastError());
     return ADMM_OK;
 }
@@ -125,13 +136,6 @@ int admm_hip_energy(admm_hip_ctx *ctx, admm_hip_energy_totals *out) {
     return ADMM_OK;
 }
 
-// per-element values of a batch after its kernel ran: device [n_local] -> host
-static int read_batch_energy(admm_hip_ctx *ctx, const Batch &b, double *per_elem) {
-    if (per_elem && b.n_local) HIPCHK(hipMemcpyAsync(per_elem, b.d_eE, sizeof(double) * (size_t)b.n_local, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return ADMM_OK;
-}
-
 int admm_hip_batch_energy(admm_hip_ctx *ctx, int batch, double *total, double *per_elem, int64_t *n_infinite) {
     TRY(require_device(ctx));
     if (batch < 0 || batch >= (int)ctx->batches.size()) return ADMM_ERR_ARG;
@@ -147,7 +151,8 @@ int admm_hip_batch_energy(admm_hip_ctx *ctx, int batch, double *total, double *p
     double t = 0.0; long long c = 0;
     HIPCHK(hipMemcpyAsync(&t, ctx->d_en_out + 3 + batch, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(&c, ctx->d_en_cnt + batch, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    TRY(read_batch_energy(ctx, b, per_elem));
+    if (per_elem && b.n_local) HIPCHK(hipMemcpyAsync(per_elem, b.d_eE, sizeof(double) * (size_t)b.n_local, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     if (total) *total = t;
     if (n_infinite) *n_infinite = c;
     return ADMM_OK;
@@ -160,17 +165,13 @@ int admm_hip_batch_energy_dx(admm_hip_ctx *ctx, int batch, const double *dx, dou
     Batch &b = ctx->batches[batch];
     if (!energy_evaluated(b)) return fail(ctx, ADMM_ERR_UNSUPPORTED, "batch_energy_dx: no energy is evaluated for batch %d (kind %d)", batch, b.kind);
     TRY(ensure_energy_buffers(ctx, 0));
-    const int rows = ADMM_KIND_ROWS[b.kind], n = b.n_local;
-    if (n == 0) return ADMM_OK;
-    std::vector<double> tmp((size_t)rows * n);
-    for (int e = 0; e < n; ++e) for (int r = 0; r < rows; ++r) tmp[(size_t)r * n + e] = dx[(size_t)e * rows + r];
-    if (!b.d_dx_buf) TRY(dalloc(ctx, &b.d_dx_buf, tmp.size()));
-    HIPCHK(hipMemcpyAsync(b.d_dx_buf, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    b.d_dx_override = b.d_dx_buf;
-    int rc = launch_batch_energy(ctx, b, ctx->d_x, nullptr, nullptr);
-    b.d_dx_override = nullptr;             // production launches never see the override
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    return read_batch_energy(ctx, b, per_elem);
+    if (b.n_local == 0) return ADMM_OK;
+    SuppliedRows rows(ctx, b);
+    TRY(rows.stage(dx));
+    TRY(launch_batch_energy(ctx, b, ctx->d_x, nullptr, nullptr));
+    if (per_elem) HIPCHK(hipMemcpyAsync(per_elem, b.d_eE, sizeof(double) * (size_t)b.n_local, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(rows.wait());
+    return ADMM_OK;
 }
 
 // this rank's elements' scale s, in the order of admm_hip_read_local

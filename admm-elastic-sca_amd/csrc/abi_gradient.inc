@@ -44,65 +44,40 @@ static int stored_corner(const Batch &b, int e, int c) {
     return c;
 }
 
+// a gather kernel's CSR (node_csr.hpp) to the device, on the context's stream: the three arrays are created at first use (a call that
+// failed further down left what it had allocated: reused, the sizes depend on the scene alone), and the call waits, since h is the caller's
+static int upload_node_csr(admm_hip_ctx *ctx, const NodeCsrHost &h, NodeCsr &d) {
+    if (!d.ptr) TRY(dalloc(ctx, &d.ptr, h.ptr.size()));
+    if (!d.off) TRY(dalloc(ctx, &d.off, h.off.size()));
+    if (!d.stride) TRY(dalloc(ctx, &d.stride, h.stride.size()));
+    HIPCHK(hipMemcpyAsync(d.ptr, h.ptr.data(), sizeof(int) * h.ptr.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d.off, h.off.data(), sizeof(long long) * h.off.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d.stride, h.stride.data(), sizeof(int) * h.stride.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ADMM_OK;
+}
+
 // the two CSRs of gradient_gather_kernel (0: elastic batches, 1: anchor batches) over the caller's nodes: batch order, then local element
 // order, then the element's corners as the caller listed them; built by the first admm_hip_node_forces
 static int ensure_gather_csr(admm_hip_ctx *ctx) {
     if (ctx->gr_csr_ready) return ADMM_OK;
-    const int n = ctx->n_nodes;
     for (int which = 0; which < 2; ++which) {
-        std::vector<int> ptr((size_t)n + 1, 0);
+        std::vector<NodeCsrEntry> entries;
         for (const Batch &b : ctx->batches) {
             if (!energy_evaluated(b) || (b.kind == ADMM_KIND_ANCHOR) != (which == 1)) continue;
             const int nn = ADMM_KIND_NODES[b.kind];
-            for (int el = 0; el < b.n_local; ++el) for (int c = 0; c < nn; ++c) ptr[(size_t)b.idx[(size_t)b.local[el] * nn + c] + 1]++;
+            for (int el = 0; el < b.n_local; ++el) for (int c = 0; c < nn; ++c)
+                entries.push_back({b.idx[(size_t)b.local[el] * nn + c], b.gr_cf_off + 3ll * stored_corner(b, b.local[el], c) * b.n_local + el, b.n_local});
         }
-        for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
-        std::vector<int> pos(ptr.begin(), ptr.end() - 1), stride((size_t)std::max(ptr[n], 1), 0);
-        std::vector<long long> off((size_t)std::max(ptr[n], 1), 0);
-        for (const Batch &b : ctx->batches) {
-            if (!energy_evaluated(b) || (b.kind == ADMM_KIND_ANCHOR) != (which == 1)) continue;
-            const int nn = ADMM_KIND_NODES[b.kind];
-            for (int el = 0; el < b.n_local; ++el) for (int c = 0; c < nn; ++c) {
-                const int e = b.local[el], k = pos[b.idx[(size_t)e * nn + c]]++;
-                off[k] = b.gr_cf_off + 3ll * stored_corner(b, e, c) * b.n_local + el;
-                stride[k] = b.n_local;
-            }
-        }
-        // (a call that failed further down left what it had allocated: reused, the sizes depend on the scene alone)
-        if (!ctx->d_gr_ptr[which]) TRY(dalloc(ctx, &ctx->d_gr_ptr[which], ptr.size()));
-        if (!ctx->d_gr_off[which]) TRY(dalloc(ctx, &ctx->d_gr_off[which], off.size()));
-        if (!ctx->d_gr_stride[which]) TRY(dalloc(ctx, &ctx->d_gr_stride[which], stride.size()));
-        HIPCHK(hipMemcpyAsync(ctx->d_gr_ptr[which], ptr.data(), sizeof(int) * ptr.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->d_gr_off[which], off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->d_gr_stride[which], stride.data(), sizeof(int) * stride.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));      // (the vectors leave scope)
+        TRY(upload_node_csr(ctx, build_node_csr(ctx->n_nodes, entries), ctx->gr_csr[which]));
     }
     ctx->gr_csr_ready = true;
     return ADMM_OK;
 }
 
-// the per-element kernel of one batch on the positions x (device order); stress: also the tets' seven stress values
+// the gradient kernel of one batch on the positions x (device order); stress: also the tets' seven stress values
 static int launch_batch_gradient(admm_hip_ctx *ctx, const Batch &b, const double *x, bool stress) {
-    using namespace admm_dev;
-    const BatchDev d = batch_dev(ctx, b);
-    const GradOut o{b.d_escale, b.d_gg, ctx->d_gr_cf + b.gr_cf_off, b.d_gcnt, stress ? b.d_gstress : nullptr, stress ? b.d_gvol : nullptr};
-    const int nblk = energy_blocks(b.n_local);
-    const dim3 grid(nblk), block(ENERGY_BLOCK);
-    if (nblk) switch (b.kind) {
-    case ADMM_KIND_TET_NH: hipLaunchKernelGGL(gradient_tet_kernel<ADMM_KIND_TET_NH>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TET_STVK: hipLaunchKernelGGL(gradient_tet_kernel<ADMM_KIND_TET_STVK>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TET_LINEAR: hipLaunchKernelGGL(gradient_tet_kernel<ADMM_KIND_TET_LINEAR>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TET_VOLUME: hipLaunchKernelGGL(gradient_tet_kernel<ADMM_KIND_TET_VOLUME>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TRI_STRAIN: hipLaunchKernelGGL(gradient_tri_kernel<ADMM_KIND_TRI_STRAIN>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TRI_AREA: hipLaunchKernelGGL(gradient_tri_kernel<ADMM_KIND_TRI_AREA>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_TRI_FUNG: hipLaunchKernelGGL(gradient_tri_kernel<ADMM_KIND_TRI_FUNG>, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_BEND: hipLaunchKernelGGL(gradient_bend_kernel, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_SPRING: hipLaunchKernelGGL(gradient_spring_kernel, grid, block, 0, ctx->stream, d, x, o); break;
-    case ADMM_KIND_ANCHOR: hipLaunchKernelGGL(gradient_anchor_kernel, grid, block, 0, ctx->stream, d, x, o); break;
-    default: return fail(ctx, ADMM_ERR_UNSUPPORTED, "no gradient is evaluated for kind %d", b.kind);
-    }
-    HIPCHK(hipGetLastError());
-    return ADMM_OK;
+    return launch_element_kernel(ctx, b, x, admm_dev::GradOut{b.d_escale, b.d_gg, ctx->d_gr_cf + b.gr_cf_off, b.d_gcnt, stress ? b.d_gstress : nullptr, stress ? b.d_gvol : nullptr}, "gradient");
 }
 
 // device SoA [rows][n] -> host element-major [n][rows], after the stream has run; the block counts' sum
@@ -135,7 +110,7 @@ int admm_hip_batch_gradient(admm_hip_ctx *ctx, int batch, double *g, double *cor
     std::vector<double> tg, tc; std::vector<int> cnt;
     TRY(read_gradient_soa(ctx, b.d_gg, rows, n, tg)); TRY(read_gradient_soa(ctx, ctx->d_gr_cf + b.gr_cf_off, 3 * nn, n, tc)); TRY(read_gradient_count(ctx, b, cnt));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (g) for (int el = 0; el < n; ++el) for (int r = 0; r < rows; ++r) g[(size_t)el * rows + r] = tg[(size_t)r * n + el];
+    to_element_major(tg, rows, n, g);
     if (corner_forces) for (int el = 0; el < n; ++el) for (int c = 0; c < nn; ++c) {      // the corners as the caller listed them
         const int sc = stored_corner(b, b.local[el], c);
         for (int j = 0; j < 3; ++j) corner_forces[((size_t)el * nn + c) * 3 + j] = tc[(size_t)(3 * sc + j) * n + el];
@@ -153,17 +128,13 @@ int admm_hip_batch_gradient_dx(admm_hip_ctx *ctx, int batch, const double *dx, d
     TRY(ensure_gradient_buffers(ctx));
     const int rows = ADMM_KIND_ROWS[b.kind], n = b.n_local;
     if (n == 0) return ADMM_OK;
-    std::vector<double> tmp((size_t)rows * n), tg;
-    for (int e = 0; e < n; ++e) for (int r = 0; r < rows; ++r) tmp[(size_t)r * n + e] = dx[(size_t)e * rows + r];
-    if (!b.d_dx_buf) TRY(dalloc(ctx, &b.d_dx_buf, tmp.size()));
-    HIPCHK(hipMemcpyAsync(b.d_dx_buf, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    b.d_dx_override = b.d_dx_buf;
-    int rc = launch_batch_gradient(ctx, b, ctx->d_x, false);
-    b.d_dx_override = nullptr;             // production launches never see the override
-    if (!rc && g) rc = read_gradient_soa(ctx, b.d_gg, rows, n, tg);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (g) for (int el = 0; el < n; ++el) for (int r = 0; r < rows; ++r) g[(size_t)el * rows + r] = tg[(size_t)r * n + el];
+    std::vector<double> tg;      // (before `supplied`: it is a target of the stream's copies until supplied has waited)
+    SuppliedRows supplied(ctx, b);
+    TRY(supplied.stage(dx));
+    TRY(launch_batch_gradient(ctx, b, ctx->d_x, false));
+    if (g) TRY(read_gradient_soa(ctx, b.d_gg, rows, n, tg));
+    HIPCHK(supplied.wait());
+    to_element_major(tg, rows, n, g);
     return ADMM_OK;
 }
 
@@ -179,11 +150,9 @@ int admm_hip_batch_stress(admm_hip_ctx *ctx, int batch, double *stress7, int64_t
     std::vector<double> ts;
     TRY(read_gradient_soa(ctx, b.d_gstress, 7, n, ts));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    to_element_major(ts, 7, n, stress7);
     int64_t bad = 0;
-    for (int el = 0; el < n; ++el) {
-        if (!admm_energy::finite(ts[(size_t)6 * n + el])) ++bad;      // (all seven or none: gradient.hpp)
-        if (stress7) for (int r = 0; r < 7; ++r) stress7[(size_t)el * 7 + r] = ts[(size_t)r * n + el];
-    }
+    for (int el = 0; el < n; ++el) if (!admm_energy::finite(ts[(size_t)6 * n + el])) ++bad;      // (all seven or none: gradient.hpp)
     if (n_nonfinite) *n_nonfinite = bad;
     return ADMM_OK;
 }
@@ -205,8 +174,8 @@ int admm_hip_node_forces(admm_hip_ctx *ctx, double *f_elastic, double *f_anchor,
     for (int which = 0; which < 2; ++which) {
         double *host = which ? f_anchor : f_elastic, *dev = ctx->d_gr_out + (size_t)which * 3 * n;
         if (!host || !nblk) continue;
-        hipLaunchKernelGGL(gradient_gather_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, n, (const int *)ctx->d_gr_ptr[which], (const long long *)ctx->d_gr_off[which],
-                           (const int *)ctx->d_gr_stride[which], (const double *)ctx->d_gr_cf, dev);
+        const NodeCsr &csr = ctx->gr_csr[which];
+        hipLaunchKernelGGL(gradient_gather_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, n, (const int *)csr.ptr, (const long long *)csr.off, (const int *)csr.stride, (const double *)ctx->d_gr_cf, dev);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(host, dev, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     }

@@ -6,7 +6,7 @@ static int read_soa(admm_hip_ctx *ctx, const double *d, int rows, int n, double 
     if (!out || n == 0) return ADMM_OK;
     std::vector<double> tmp((size_t)rows * n);
     HIPCHK(hipMemcpy(tmp.data(), d, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int e = 0; e < n; ++e) for (int r = 0; r < rows; ++r) out[(size_t)e * rows + r] = tmp[(size_t)r * n + e];
+    to_element_major(tmp, rows, n, out);
     return ADMM_OK;
 }
 
@@ -110,17 +110,12 @@ int admm_hip_local_step_dx(admm_hip_ctx *ctx, int batch, const double *dx) {
     HIPCHK(hipSetDevice(ctx->device_id));
     Batch &b = ctx->batches[batch];
     if (b.kind == ADMM_KIND_GENERIC) return fail(ctx, ADMM_ERR_UNSUPPORTED, "local_step_dx: a generic batch's project() is the caller's own code");
-    const int rows = ADMM_KIND_ROWS[b.kind], n = b.n_local;
-    if (n == 0) return ADMM_OK;
-    std::vector<double> tmp((size_t)rows * n);
-    for (int e = 0; e < n; ++e) for (int r = 0; r < rows; ++r) tmp[(size_t)r * n + e] = dx[(size_t)e * rows + r];
-    if (!b.d_dx_buf) TRY(dalloc(ctx, &b.d_dx_buf, tmp.size()));
-    HIPCHK(hipMemcpy(b.d_dx_buf, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
-    b.d_dx_override = b.d_dx_buf;
+    if (b.n_local == 0) return ADMM_OK;
+    SuppliedRows rows(ctx, b);
+    TRY(rows.stage(dx));
     KeepZ kz(ctx);
     int rc = launch_local(ctx, batch);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    b.d_dx_override = nullptr;             // production launches never see the override
+    hipError_t e = rows.wait();
     if (rc) return rc;
     if (e != hipSuccess) return fail(ctx, ADMM_ERR_HIP, "local_step_dx: %s", hipGetErrorString(e));
     return ADMM_OK;

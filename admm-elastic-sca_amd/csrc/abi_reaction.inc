@@ -36,29 +36,10 @@ static int ensure_reaction_buffers(admm_hip_ctx *ctx) {
     if (!ctx->d_rx_part) TRY(dalloc(ctx, &ctx->d_rx_part, 6 * (size_t)std::max(energy_blocks(n), 1) + 6));
     for (int which = 0; which < 2; ++which) {
         const int kind = which ? ADMM_KIND_ANCHOR : ADMM_KIND_COLLISION;
-        std::vector<int> ptr((size_t)n + 1, 0);
-        for (const Batch &b : ctx->batches) {
-            if (b.kind != kind) continue;
-            for (int el = 0; el < b.n_local; ++el) ptr[(size_t)b.idx[b.local[el]] + 1]++;
-        }
-        for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
-        std::vector<int> pos(ptr.begin(), ptr.end() - 1), stride((size_t)std::max(ptr[n], 1), 0);
-        std::vector<long long> off((size_t)std::max(ptr[n], 1), 0);
-        for (const Batch &b : ctx->batches) {
-            if (b.kind != kind) continue;
-            for (int el = 0; el < b.n_local; ++el) {
-                const int k = pos[b.idx[b.local[el]]]++;
-                off[k] = b.rx_off + el;
-                stride[k] = b.n_local;
-            }
-        }
-        if (!ctx->d_rx_ptr[which]) TRY(dalloc(ctx, &ctx->d_rx_ptr[which], ptr.size()));
-        if (!ctx->d_rx_off[which]) TRY(dalloc(ctx, &ctx->d_rx_off[which], off.size()));
-        if (!ctx->d_rx_stride[which]) TRY(dalloc(ctx, &ctx->d_rx_stride[which], stride.size()));
-        HIPCHK(hipMemcpyAsync(ctx->d_rx_ptr[which], ptr.data(), sizeof(int) * ptr.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->d_rx_off[which], off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->d_rx_stride[which], stride.data(), sizeof(int) * stride.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));      // (the vectors leave scope)
+        std::vector<NodeCsrEntry> entries;
+        for (const Batch &b : ctx->batches) if (b.kind == kind)
+            for (int el = 0; el < b.n_local; ++el) entries.push_back({b.idx[b.local[el]], b.rx_off + el, b.n_local});
+        TRY(upload_node_csr(ctx, build_node_csr(n, entries), ctx->rx_csr[which]));
     }
     ctx->rx_ready = true;
     return ADMM_OK;
@@ -83,8 +64,9 @@ static int launch_node_reactions(admm_hip_ctx *ctx, admm_hip_reaction_info *info
         TRY(launch_batch_reaction(ctx, b));
     }
     const int n = ctx->n_nodes, nblk = energy_blocks(n);
-    if (nblk) hipLaunchKernelGGL(reaction_gather_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, n, (const int *)ctx->d_rx_ptr[0], (const long long *)ctx->d_rx_off[0], (const int *)ctx->d_rx_stride[0],
-                                 (const int *)ctx->d_rx_ptr[1], (const long long *)ctx->d_rx_off[1], (const int *)ctx->d_rx_stride[1], (const double *)ctx->d_rx_el, ctx->d_rx_node);
+    const NodeCsr &cc = ctx->rx_csr[0], &ca = ctx->rx_csr[1];
+    if (nblk) hipLaunchKernelGGL(reaction_gather_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, n, (const int *)cc.ptr, (const long long *)cc.off, (const int *)cc.stride,
+                                 (const int *)ca.ptr, (const long long *)ca.off, (const int *)ca.stride, (const double *)ctx->d_rx_el, ctx->d_rx_node);
     HIPCHK(hipGetLastError());
     return ADMM_OK;
 }

@@ -21,6 +21,7 @@
 #include "factor.hpp"
 #include "dev_types.hpp"
 #include "mesh_host.hpp"
+#include "node_csr.hpp"
 
 namespace admm_lib {
 
@@ -280,15 +281,13 @@ struct admm_hip_ctx {
     // gradients and nodal forces (abi_gradient.inc; every buffer created on first use).  d_gr_cf: every evaluated batch's corner forces,
     // SoA [3 nodes][n_local] per batch; d_gr_out [2][3 n_nodes]: the elastic and the anchor forces in the caller's node order; the two
     // CSRs of gradient_gather_kernel (0: elastic batches, 1: anchor batches), built by the first admm_hip_node_forces
-    bool gr_ready = false, gr_csr_ready = false; double *d_gr_cf = nullptr, *d_gr_out = nullptr;
-    int *d_gr_ptr[2] = {nullptr, nullptr}, *d_gr_stride[2] = {nullptr, nullptr}; long long *d_gr_off[2] = {nullptr, nullptr};
+    bool gr_ready = false, gr_csr_ready = false; double *d_gr_cf = nullptr, *d_gr_out = nullptr; admm_lib::NodeCsr gr_csr[2];
     // reactions of the collision and anchor batches (abi_reaction.inc; every buffer created by the first call).  d_rx_el: every reported
     // batch's elements, SoA [7][n_local] per batch at Batch::rx_off (f, depth, z); d_rx_node: f_contact [n][3], f_anchor [n][3], depth [n],
     // point [n][3] in the caller's node order; the two CSRs of reaction_gather_kernel (0: collision batches, 1: anchor batches); d_rx_blk:
     // the compaction's block counts, then their offsets; d_rx_count: the contacts' count; d_rx_rec [n_nodes] records; d_rx_part: the
     // resultant's partials [6][blocks], then its six totals
-    bool rx_ready = false; double *d_rx_el = nullptr, *d_rx_node = nullptr, *d_rx_part = nullptr; int *d_rx_blk = nullptr; long long *d_rx_count = nullptr; void *d_rx_rec = nullptr;
-    int *d_rx_ptr[2] = {nullptr, nullptr}, *d_rx_stride[2] = {nullptr, nullptr}; long long *d_rx_off[2] = {nullptr, nullptr};
+    bool rx_ready = false; double *d_rx_el = nullptr, *d_rx_node = nullptr, *d_rx_part = nullptr; int *d_rx_blk = nullptr; long long *d_rx_count = nullptr; void *d_rx_rec = nullptr; admm_lib::NodeCsr rx_csr[2];
     // velocity damping per node group (abi_damping.inc, kernels_damping.hpp, damping.hpp; no group = off, the default).  damp_groups: the
     // caller's groups in the order they were added; rate_dirty: the device's rate entry is older than drag / internal.  Device side, created
     // by upload_all when there is a group: the block -> (group, first node) table, the groups' ranges, their rates (written by

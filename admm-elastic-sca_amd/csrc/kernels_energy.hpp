@@ -3,8 +3,8 @@
 //
 // Per-element kernels, one per family (tets, triangles, hinges, springs, anchors): one lane per element, 64-element blocks of their
 // own -- independent of the local step's block size, launch mode, cost order and pre-reduction.  The loads are the local step's (SoA,
-// coalesced; the nodes' x gathered through idx), D_i x is formed by the local step's arithmetic (tets: tet_load_dx itself) and
-// dx_override replaces it as it does there.  A lane beyond the batch returns before its first load.  Every lane writes E[e]; the
+// coalesced; the nodes' x gathered through idx), D_i x is formed by the local step's arithmetic (tets: tet_load_dx itself; the others:
+// tri_load_dx, bend_load_dx, spring_load_dx, anchor_load_dx below, shared with the gradient kernels) and dx_override replaces it as it does there.  A lane beyond the batch returns before its first load.  Every lane writes E[e]; the
 // block writes one partial, its lanes' values summed by the fixed butterfly of track_block_sum, where an element whose energy is not
 // finite adds 0 to the partial and 1 to the block's count.
 //
@@ -66,13 +66,11 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void energy_tet_kernel(BatchDev b, co
     energy_store(o, e, val);
 }
 
-// KIND: ADMM_KIND_TRI_STRAIN / _AREA / _FUNG   (project_tri_block's loads and D_i x)
-template <int KIND>
-__global__ __launch_bounds__(ENERGY_BLOCK) void energy_tri_kernel(BatchDev b, const double *__restrict__ x, EnergyOut o) {
-    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
-    if (e >= n) return;
+// The other families' inputs, as tet_load_dx gives the tets': the rest data that the energy and the gradient (kernels_gradient.hpp) both
+// need and d = D_i x by the local step's arithmetic (project_tri_block, project_bend_block, project_spring_block, project_anchor_elem:
+// their loads, their operation order), which dx_override then replaces.
+__device__ __forceinline__ void tri_load_dx(const BatchDev &b, const double *__restrict__ x, int e, int n, double (&B)[6], double (&d)[6]) {
     const int4 id = reinterpret_cast<const int4 *>(b.idx)[e];
-    double B[6], d[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) B[i] = b.rest[(size_t)i * n + e];
 #pragma unroll
@@ -84,22 +82,12 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void energy_tri_kernel(BatchDev b, co
             if (b.dx_override) d[3 * r + j] = b.dx_override[(size_t)(3 * r + j) * n + e];
         }
     }
-    const double s = o.scale[e];
-    double val;
-    if (KIND == ADMM_KIND_TRI_FUNG) val = admm_energy::tri_fung(d, b.par[e], s);
-    else if (KIND == ADMM_KIND_TRI_AREA) val = admm_energy::tri_area(d, (int)b.par[(size_t)1 * n + e], b.par[(size_t)2 * n + e], b.par[(size_t)3 * n + e], s);
-    else val = admm_energy::tri_strain(d, s);
-    energy_store(o, e, val);
 }
-
-// hinges (project_bend_block's loads and D_i x)
-__global__ __launch_bounds__(ENERGY_BLOCK) void energy_bend_kernel(BatchDev b, const double *__restrict__ x, EnergyOut o) {
-    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
-    if (e >= n) return;
+// hinges: the rows x0 - x2, x3 - x2, x1 - x2
+__device__ __forceinline__ void bend_load_dx(const BatchDev &b, const double *__restrict__ x, int e, int n, double &a0, double &a1, double &a3, double (&d)[9]) {
     const int4 id = reinterpret_cast<const int4 *>(b.idx)[e];
-    const double a0 = b.rest[(size_t)0 * n + e], a1 = b.rest[(size_t)1 * n + e], a3 = b.rest[(size_t)3 * n + e];
+    a0 = b.rest[(size_t)0 * n + e]; a1 = b.rest[(size_t)1 * n + e]; a3 = b.rest[(size_t)3 * n + e];
     const int plus[3] = {id.x, id.w, id.y};
-    double d[9];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const double x2 = x[3 * (size_t)id.z + j];
@@ -110,40 +98,78 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void energy_bend_kernel(BatchDev b, c
             if (b.dx_override) d[3 * r + j] = b.dx_override[(size_t)(3 * r + j) * n + e];
         }
     }
-    energy_store(o, e, admm_energy::bend(d, a0, a1, a3, o.scale[e]));
 }
-
-// springs (project_spring_block's loads and D_i x)
-__global__ __launch_bounds__(ENERGY_BLOCK) void energy_spring_kernel(BatchDev b, const double *__restrict__ x, EnergyOut o) {
-    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
-    if (e >= n) return;
+// springs: the row x0 - x1
+__device__ __forceinline__ void spring_load_dx(const BatchDev &b, const double *__restrict__ x, int e, int n, double &rest_length, double (&d)[3]) {
     const int ia = b.idx[2 * (size_t)e], ib = b.idx[2 * (size_t)e + 1];
-    const double rest_length = b.rest[e];
-    double d[3];
+    rest_length = b.rest[e];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const double xa = x[3 * (size_t)ia + j], xb = x[3 * (size_t)ib + j];
         d[j] = (ia < ib) ? ((0.0 + 1.0 * xa) + -1.0 * xb) : ((0.0 + -1.0 * xb) + 1.0 * xa);
         if (b.dx_override) d[j] = b.dx_override[(size_t)j * n + e];
     }
-    energy_store(o, e, admm_energy::spring(d, rest_length, o.scale[e]));
 }
-
-// anchors (project_anchor_elem's loads): an active anchor's distance from its target, weighted; a released one: 0
-__global__ __launch_bounds__(ENERGY_BLOCK) void energy_anchor_kernel(BatchDev b, const double *__restrict__ x, EnergyOut o) {
-    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
-    if (e >= n) return;
+// anchors: the node itself, its target (a released anchor: 0) and whether it is active
+__device__ __forceinline__ void anchor_load_dx(const BatchDev &b, const double *__restrict__ x, int e, int n, double (&t)[3], bool &act, double (&d)[3]) {
     const int id = b.idx[e];
-    const bool act = b.active[e] != 0;
-    double d[3], t[3];
+    act = b.active[e] != 0;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         d[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
         if (b.dx_override) d[j] = b.dx_override[(size_t)j * n + e];
         t[j] = act ? b.targets[3 * (size_t)e + j] : 0.0;
     }
+}
+
+// KIND: ADMM_KIND_TRI_STRAIN / _AREA / _FUNG
+template <int KIND>
+__global__ __launch_bounds__(ENERGY_BLOCK) void energy_tri_kernel(BatchDev b, const double *__restrict__ x, EnergyOut o) {
+    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
+    if (e >= n) return;
+    double B[6], d[6];
+    tri_load_dx(b, x, e, n, B, d);
+    const double s = o.scale[e];
+    double val;
+    if (KIND == ADMM_KIND_TRI_FUNG) val = admm_energy::tri_fung(d, b.par[e], s);
+    else if (KIND == ADMM_KIND_TRI_AREA) val = admm_energy::tri_area(d, (int)b.par[(size_t)1 * n + e], b.par[(size_t)2 * n + e], b.par[(size_t)3 * n + e], s);
+    else val = admm_energy::tri_strain(d, s);
+    energy_store(o, e, val);
+}
+
+__global__ __launch_bounds__(ENERGY_BLOCK) void energy_bend_kernel(BatchDev b, const double *__restrict__ x, EnergyOut o) {
+    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
+    if (e >= n) return;
+    double a0, a1, a3, d[9];
+    bend_load_dx(b, x, e, n, a0, a1, a3, d);
+    energy_store(o, e, admm_energy::bend(d, a0, a1, a3, o.scale[e]));
+}
+
+__global__ __launch_bounds__(ENERGY_BLOCK) void energy_spring_kernel(BatchDev b, const double *__restrict__ x, EnergyOut o) {
+    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
+    if (e >= n) return;
+    double rest_length, d[3];
+    spring_load_dx(b, x, e, n, rest_length, d);
+    energy_store(o, e, admm_energy::spring(d, rest_length, o.scale[e]));
+}
+
+// an active anchor's distance from its target, weighted; a released one: 0
+__global__ __launch_bounds__(ENERGY_BLOCK) void energy_anchor_kernel(BatchDev b, const double *__restrict__ x, EnergyOut o) {
+    const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
+    if (e >= n) return;
+    double d[3], t[3]; bool act;
+    anchor_load_dx(b, x, e, n, t, act, d);
     energy_store(o, e, admm_energy::anchor(d, t, b.w2[e], act));      // (the live weight^2: admm_hip_recompute_weights refreshes it)
 }
+
+// An element kernel of either output (EnergyOut here, GradOut in kernels_gradient.hpp) and each family's kernel, picked by the output's
+// type: the one switch over the kinds (launch_element_kernel, abi_energy.inc) names the family and gets that output's kernel.
+template <class Out> using ElementKernel = void (*)(BatchDev, const double *, Out);
+template <int KIND> inline ElementKernel<EnergyOut> tet_kernel(const EnergyOut &) { return energy_tet_kernel<KIND>; }
+template <int KIND> inline ElementKernel<EnergyOut> tri_kernel(const EnergyOut &) { return energy_tri_kernel<KIND>; }
+inline ElementKernel<EnergyOut> bend_kernel(const EnergyOut &) { return energy_bend_kernel; }
+inline ElementKernel<EnergyOut> spring_kernel(const EnergyOut &) { return energy_spring_kernel; }
+inline ElementKernel<EnergyOut> anchor_kernel(const EnergyOut &) { return energy_anchor_kernel; }
 
 // n partials (and, cnt != null, n counts) -> *total (and *count), in the fixed order described at the top.  One workgroup.
 __global__ __launch_bounds__(ENERGY_REDUCE) void energy_reduce_kernel(const int n, const double *__restrict__ partial, const int *__restrict__ cnt,

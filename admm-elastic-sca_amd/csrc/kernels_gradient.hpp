@@ -4,8 +4,8 @@
 //
 // Per-element kernels, one per family as in kernels_energy.hpp: one lane per element, ENERGY_BLOCK = 64-element blocks of their own --
 // independent of the local step's block size, launch mode, cost order and pre-reduction.  The loads are the energy kernels' (the local
-// step's: SoA, coalesced; the nodes' x gathered through idx), D_i x is formed by the local step's arithmetic (tets: tet_load_dx itself)
-// and dx_override replaces it as it does there.  A lane beyond the batch returns before its first load.  Every lane writes
+// step's: SoA, coalesced; the nodes' x gathered through idx), D_i x is formed by the local step's arithmetic (tet_load_dx and the energy
+// kernels' tri_load_dx, bend_load_dx, spring_load_dx, anchor_load_dx themselves) and dx_override replaces it as it does there.  A lane beyond the batch returns before its first load.  Every lane writes
 //     g   SoA [rows][n]
 //     cf  SoA [3 nodes][n], cf[3 c + j] = component j of the force on stored corner c (the corner order of idx on the device):
 //           tets       -((g[j] B(c, 0) + g[3 + j] B(c, 1)) + g[6 + j] B(c, 2))      B(c, r) = rest[c + 4 r]
@@ -79,24 +79,13 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_tet_kernel(BatchDev b, 
     gradient_count(o, !ok);
 }
 
-// KIND: ADMM_KIND_TRI_STRAIN / _AREA / _FUNG   (energy_tri_kernel's loads and D_i x)
+// KIND: ADMM_KIND_TRI_STRAIN / _AREA / _FUNG
 template <int KIND>
 __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_tri_kernel(BatchDev b, const double *__restrict__ x, GradOut o) {
     const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
     if (e >= n) return;
-    const int4 id = reinterpret_cast<const int4 *>(b.idx)[e];
     double B[6], d[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) B[i] = b.rest[(size_t)i * n + e];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double xa = x[3 * (size_t)id.x + j], xb = x[3 * (size_t)id.y + j], xc = x[3 * (size_t)id.z + j];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            d[3 * r + j] = ((0.0 + B[0 + 3 * r] * xa) + B[1 + 3 * r] * xb) + B[2 + 3 * r] * xc;
-            if (b.dx_override) d[3 * r + j] = b.dx_override[(size_t)(3 * r + j) * n + e];
-        }
-    }
+    tri_load_dx(b, x, e, n, B, d);
     const double s = o.scale[e];
     double g[6];
     if (KIND == ADMM_KIND_TRI_FUNG) admm_gradient::tri_fung(d, b.par[e], s, g);
@@ -112,24 +101,11 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_tri_kernel(BatchDev b, 
     gradient_count(o, !ok);
 }
 
-// hinges (energy_bend_kernel's loads and D_i x)
 __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_bend_kernel(BatchDev b, const double *__restrict__ x, GradOut o) {
     const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
     if (e >= n) return;
-    const int4 id = reinterpret_cast<const int4 *>(b.idx)[e];
-    const double a0 = b.rest[(size_t)0 * n + e], a1 = b.rest[(size_t)1 * n + e], a3 = b.rest[(size_t)3 * n + e];
-    const int plus[3] = {id.x, id.w, id.y};
-    double d[9], g[9];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double x2 = x[3 * (size_t)id.z + j];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const double xp = x[3 * (size_t)plus[r] + j];
-            d[3 * r + j] = (plus[r] < id.z) ? ((0.0 + 1.0 * xp) + -1.0 * x2) : ((0.0 + -1.0 * x2) + 1.0 * xp);
-            if (b.dx_override) d[3 * r + j] = b.dx_override[(size_t)(3 * r + j) * n + e];
-        }
-    }
+    double a0, a1, a3, d[9], g[9];
+    bend_load_dx(b, x, e, n, a0, a1, a3, d);
     admm_gradient::bend(d, a0, a1, a3, o.scale[e], g);
     const bool ok = admm_gradient::all_finite<9>(g);
 #pragma unroll
@@ -144,19 +120,11 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_bend_kernel(BatchDev b,
     gradient_count(o, !ok);
 }
 
-// springs (energy_spring_kernel's loads and D_i x)
 __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_spring_kernel(BatchDev b, const double *__restrict__ x, GradOut o) {
     const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
     if (e >= n) return;
-    const int ia = b.idx[2 * (size_t)e], ib = b.idx[2 * (size_t)e + 1];
-    const double rest_length = b.rest[e];
-    double d[3], g[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double xa = x[3 * (size_t)ia + j], xb = x[3 * (size_t)ib + j];
-        d[j] = (ia < ib) ? ((0.0 + 1.0 * xa) + -1.0 * xb) : ((0.0 + -1.0 * xb) + 1.0 * xa);
-        if (b.dx_override) d[j] = b.dx_override[(size_t)j * n + e];
-    }
+    double rest_length, d[3], g[3];
+    spring_load_dx(b, x, e, n, rest_length, d);
     admm_gradient::spring(d, rest_length, o.scale[e], g);
     const bool ok = admm_gradient::all_finite<3>(g);
 #pragma unroll
@@ -168,19 +136,11 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_spring_kernel(BatchDev 
     gradient_count(o, !ok);
 }
 
-// anchors (energy_anchor_kernel's loads)
 __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_anchor_kernel(BatchDev b, const double *__restrict__ x, GradOut o) {
     const int e = (int)blockIdx.x * ENERGY_BLOCK + threadIdx.x, n = b.n;
     if (e >= n) return;
-    const int id = b.idx[e];
-    const bool act = b.active[e] != 0;
-    double d[3], t[3], g[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        d[j] = 0.0 + 1.0 * x[3 * (size_t)id + j];
-        if (b.dx_override) d[j] = b.dx_override[(size_t)j * n + e];
-        t[j] = act ? b.targets[3 * (size_t)e + j] : 0.0;
-    }
+    double d[3], t[3], g[3]; bool act;
+    anchor_load_dx(b, x, e, n, t, act, d);
     admm_gradient::anchor(d, t, b.w2[e], act, g);      // (the live weight^2, as the energy kernel)
     const bool ok = admm_gradient::all_finite<3>(g);
 #pragma unroll
@@ -190,6 +150,13 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_anchor_kernel(BatchDev 
     }
     gradient_count(o, !ok);
 }
+
+// the families' kernels of this output (kernels_energy.hpp: ElementKernel)
+template <int KIND> inline ElementKernel<GradOut> tet_kernel(const GradOut &) { return gradient_tet_kernel<KIND>; }
+template <int KIND> inline ElementKernel<GradOut> tri_kernel(const GradOut &) { return gradient_tri_kernel<KIND>; }
+inline ElementKernel<GradOut> bend_kernel(const GradOut &) { return gradient_bend_kernel; }
+inline ElementKernel<GradOut> spring_kernel(const GradOut &) { return gradient_spring_kernel; }
+inline ElementKernel<GradOut> anchor_kernel(const GradOut &) { return gradient_anchor_kernel; }
 
 // out[3 i + j] (caller's node i) = the compensated sum (above) of the node's incident corner forces in CSR order; entry k: component j at cf[off[k] + j stride[k]]
 __global__ __launch_bounds__(ENERGY_BLOCK) void gradient_gather_kernel(const int n_nodes, const int *__restrict__ ptr, const long long *__restrict__ off, const int *__restrict__ stride,

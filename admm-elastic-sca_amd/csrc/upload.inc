@@ -813,6 +813,33 @@ BatchDev batch_dev(const admm_hip_ctx *ctx, const Batch &b) {
     return d;
 }
 
+// Parity entries (admm_hip_local_step_dx, admm_hip_batch_energy_dx, admm_hip_batch_gradient_dx): the caller's D_i x rows, element-major
+// [n_local][rows], in place of the batch's gather for the launches made while this object lives.  stage() transposes them to SoA,
+// creates the batch's d_dx_buf at first use, queues the copy on the context's stream and sets the override; the staging vector is
+// the object's until the stream has been waited for (wait(), or the destructor where no one has), and the destructor clears the
+// override on every path: production launches never see it.
+struct SuppliedRows {
+    admm_hip_ctx *ctx; Batch &b; std::vector<double> soa; bool pending = false;
+    SuppliedRows(admm_hip_ctx *c, Batch &b_) : ctx(c), b(b_) {}
+    ~SuppliedRows() { if (pending) (void)hipStreamSynchronize(ctx->stream); b.d_dx_override = nullptr; }
+    int stage(const double *dx) {
+        const int rows = ADMM_KIND_ROWS[b.kind], n = b.n_local;
+        soa.resize((size_t)rows * n);
+        for (int e = 0; e < n; ++e) for (int r = 0; r < rows; ++r) soa[(size_t)r * n + e] = dx[(size_t)e * rows + r];
+        if (!b.d_dx_buf) TRY(dalloc(ctx, &b.d_dx_buf, soa.size()));
+        pending = true;
+        HIPCHK(hipMemcpyAsync(b.d_dx_buf, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        b.d_dx_override = b.d_dx_buf;
+        return ADMM_OK;
+    }
+    hipError_t wait() { pending = false; return hipStreamSynchronize(ctx->stream); }
+};
+
+// host SoA [rows][n] -> the caller's element-major [n][rows] (out == null: nothing)
+void to_element_major(const std::vector<double> &soa, int rows, int n, double *out) {
+    if (out) for (int e = 0; e < n; ++e) for (int r = 0; r < rows; ++r) out[(size_t)e * rows + r] = soa[(size_t)r * n + e];
+}
+
 FactorDev factor_dev(const admm_hip_ctx *ctx) {
     FactorDev f{};
     f.panels = ctx->d_panels; f.sn_first = ctx->d_sn_first; f.sn_ncols = ctx->d_sn_ncols; f.sn_nrows = ctx->d_sn_nrows;

@@ -558,6 +558,7 @@ def test_two_shards_add_up_to_one_rank(pkg, monkeypatch):
     assert np.abs(fc1).max() > 10 * tol_c and np.abs(fa1).max() > 10 * tol_a      # the forces are well above the bounds: zeros would not pass
     assert sum(o[2]["n_contacts"] for o in out) == info1["n_contacts"] >= 1
     assert sorted(np.concatenate([s.local_elements(one.coll) for s in shards]).tolist()) == list(range(one.N))
+    assert min(s.local_elements(one.anch).size for s in shards) == 0      # one rank holds no anchor: an empty batch went through its gather
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
