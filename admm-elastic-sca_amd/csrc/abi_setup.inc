@@ -210,62 +210,62 @@ int admm_hip_set_gravity(admm_hip_ctx *ctx, int which, double gx, double gy, dou
     if (ctx->explicit_simple) { double *g = ctx->grav.g[which]; g[0] = gx; g[1] = gy; g[2] = gz; }
     return ADMM_OK;
 }
-// a body surface sits where its nodes are: an entry that names one with a translation is refused (here when the surface is already
-// registered, at finalize otherwise)
-static int check_body_translations(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
-    for (int j = 0; j < n_shapes; ++j) {
-        if (types[j] != ADMM_SHAPE_MESH) continue;
-        const double *p = params + 4 * (size_t)j;
-        const int id = (int)p[3];
-        if (id >= 0 && id < (int)ctx->mesh_role.size() && !ctx->mesh_role[id].body_nodes.empty() && (p[0] != 0.0 || p[1] != 0.0 || p[2] != 0.0))
-            return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which follows its nodes: its translation must be 0 (have %g, %g, %g)",
-                        j, id, p[0], p[1], p[2]);
+// What a list may not ask of a body surface, which sits where its nodes are and moves with them -- checked wherever the list or one of
+// its per-entry arguments changes (for a surface already registered) and at finalize, rule after rule in this order, each over all
+// entries; a rule whose argument is null (translations: false) is not checked:
+//   translations   an entry that names one carries no translation
+//   mu             ... and no friction coefficient: the body's own is admm_hip_set_body_surface_friction
+//   motion         ... and no rigid motion [n_shapes][9]: the surface's motion is its nodes'
+//   frames         ... and no frame [n_shapes][12] (the identity rotation passes whatever its pivot)
+static int check_body_entries(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params, bool translations, const double *mu, const double *motion,
+                              const double *frames) {
+    int body[ADMM_MAX_SHAPES], nb = 0;      // the entries that name a body surface, and its id
+    for (int j = 0; j < n_shapes; ++j) { const admm_hip_ctx::CollisionMesh *m = entry_mesh(ctx, types, params, j); if (m && m->body()) body[nb++] = j; }
+    auto id = [&](int j) { return (int)params[4 * (size_t)j + 3]; };
+    if (translations) for (int q = 0; q < nb; ++q) {
+        const int j = body[q]; const double *p = params + 4 * (size_t)j;
+        if (p[0] != 0.0 || p[1] != 0.0 || p[2] != 0.0)
+            return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which follows its nodes: its translation must be 0 (have %g, %g, %g)", j, id(j), p[0], p[1], p[2]);
     }
-    return ADMM_OK;
-}
-// friction against a body surface would need the surface's velocity: an entry that names one takes no coefficient (checked wherever the
-// list or the coefficients change, and at finalize)
-static int check_body_friction(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params, const double *mu) {
-    for (int j = 0; j < n_shapes; ++j) {
-        if (types[j] != ADMM_SHAPE_MESH || mu[j] == 0.0) continue;
-        const int id = (int)params[4 * (size_t)j + 3];
-        if (id >= 0 && id < (int)ctx->mesh_role.size() && !ctx->mesh_role[id].body_nodes.empty())
-            return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which moves with its nodes: its friction coefficient must be 0 (have %g)", j, id, mu[j]);
+    if (mu) for (int q = 0; q < nb; ++q) {
+        const int j = body[q];
+        if (mu[j] != 0.0) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which moves with its nodes: its friction coefficient must be 0 (have %g)", j, id(j), mu[j]);
     }
-    return ADMM_OK;
-}
-// ... and no rigid motion: the surface's motion is its nodes' (admm_hip_set_body_surface_friction)
-static int check_body_motion(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params, const double *motion) {
-    for (int j = 0; j < n_shapes; ++j) {
-        if (types[j] != ADMM_SHAPE_MESH) continue;
-        const int id = (int)params[4 * (size_t)j + 3];
-        if (!(id >= 0 && id < (int)ctx->mesh_role.size() && !ctx->mesh_role[id].body_nodes.empty())) continue;
+    if (motion) for (int q = 0; q < nb; ++q) {
+        const int j = body[q];
         for (int k = 0; k < 9; ++k)
             if (motion[9 * (size_t)j + k] != 0.0)
-                return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which moves with its nodes: its rigid motion must be 0 (component %d is %g)", j, id, k, motion[9 * (size_t)j + k]);
+                return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which moves with its nodes: its rigid motion must be 0 (component %d is %g)", j, id(j), k, motion[9 * (size_t)j + k]);
     }
-    return ADMM_OK;
-}
-// ... and no frame: it sits where its nodes are (frames: [n_shapes][12]; the identity rotation passes whatever its pivot)
-static int check_body_frames(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params, const double *frames) {
-    for (int j = 0; j < n_shapes; ++j) {
-        if (types[j] != ADMM_SHAPE_MESH || admm_frame::identity(frames + 12 * (size_t)j)) continue;
-        const int id = (int)params[4 * (size_t)j + 3];
-        if (id >= 0 && id < (int)ctx->mesh_role.size() && !ctx->mesh_role[id].body_nodes.empty())
-            return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which follows its nodes: its frame must be the identity", j, id);
+    if (frames) for (int q = 0; q < nb; ++q) {
+        const int j = body[q];
+        if (!admm_frame::identity(frames + 12 * (size_t)j))
+            return fail(ctx, ADMM_ERR_ARG, "collision shape %d: mesh %d is a body surface, which follows its nodes: its frame must be the identity", j, id(j));
     }
     return ADMM_OK;
 }
 // side memory: a node has one side per mesh, so a list names a mesh with memory in one entry at most
 static int check_side_entries(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
     for (int j = 0; j < n_shapes; ++j) {
-        if (types[j] != ADMM_SHAPE_MESH) continue;
-        const int id = (int)params[4 * (size_t)j + 3];
-        if (!(id >= 0 && id < (int)ctx->mesh_role.size() && ctx->mesh_role[id].side_reach > 0.0)) continue;
+        const admm_hip_ctx::CollisionMesh *m = entry_mesh(ctx, types, params, j);
+        if (!m || !(m->side_reach > 0.0)) continue;
         for (int k = 0; k < j; ++k)
-            if (types[k] == ADMM_SHAPE_MESH && (int)params[4 * (size_t)k + 3] == id)
-                return fail(ctx, ADMM_ERR_ARG, "collision shapes %d and %d both name mesh %d, which has side memory: a node has one side per mesh", k, j, id);
+            if (entry_mesh(ctx, types, params, k) == m)
+                return fail(ctx, ADMM_ERR_ARG, "collision shapes %d and %d both name mesh %d, which has side memory: a node has one side per mesh", k, j, (int)params[4 * (size_t)j + 3]);
     }
+    return ADMM_OK;
+}
+// a setter changed the shape table: once finalized it goes to the device again (between frames; the values change under a captured graph
+// like shape parameters) -- with_motion: and the mesh motion table with it -- and a change of the collision batches' kernels (form_before:
+// collision_form before the change) drops the captured graphs
+static int push_shapes(admm_hip_ctx *ctx, int form_before, bool with_motion = false) {
+    if (!ctx->finalized || ctx->device_id < 0) return ADMM_OK;
+    HIPCHK(hipSetDevice(ctx->device_id));
+    HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
+    const std::vector<admm_mesh::MeshMotion> mo = with_motion ? mesh_motion_table(ctx) : std::vector<admm_mesh::MeshMotion>();
+    if (!mo.empty()) HIPCHK(hipMemcpyAsync(ctx->d_mesh_motion, mo.data(), sizeof(admm_mesh::MeshMotion) * mo.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (form_before != collision_form(ctx).form) drop_iteration_graphs(ctx);
     return ADMM_OK;
 }
 int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t *types, const double *params) {
@@ -284,14 +284,13 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
                 if (!(h > 0.0 && std::isfinite(h))) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: the box's half extent %d is %g: it must be positive and finite", j, k, h);
             }
     }
-    TRY(check_body_translations(ctx, n_shapes, types, params));
+    TRY(check_body_entries(ctx, n_shapes, types, params, true, nullptr, nullptr, nullptr));
     TRY(check_side_entries(ctx, n_shapes, types, params));
-    // (a list of the same length keeps its coefficients: one that now names a body surface where a coefficient is set is refused here
-    //  once finalized, by finalize before)
-    if (ctx->finalized && n_shapes == ctx->shapes.n) TRY(check_body_friction(ctx, n_shapes, types, params, ctx->shapes.mu));
-    if (n_shapes == ctx->shapes.n) TRY(check_body_motion(ctx, n_shapes, types, params, &ctx->shapes.motion[0][0]));      // (kept motions likewise)
-    if (n_shapes == ctx->shapes.n) TRY(check_body_frames(ctx, n_shapes, types, params, &ctx->shapes.frame[0][0]));       // (and kept frames)
-    const int form = collision_form(ctx);
+    // (a list of the same length keeps its coefficients, motions and frames: one that now names a body surface where one of them is set is
+    //  refused here -- a coefficient once finalized, by finalize before)
+    if (n_shapes == ctx->shapes.n)
+        TRY(check_body_entries(ctx, n_shapes, types, params, false, ctx->finalized ? ctx->shapes.mu : nullptr, &ctx->shapes.motion[0][0], &ctx->shapes.frame[0][0]));
+    const int form = collision_form(ctx).form;
     if (n_shapes != ctx->shapes.n) {      // a list of another length: its coefficients and motions start at 0, its frames at the identity (the same length keeps them)
         for (double &m : ctx->shapes.mu) m = 0.0;
         for (auto &m : ctx->shapes.motion) for (double &c : m) c = 0.0;
@@ -302,13 +301,7 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
         ctx->shapes.type[j] = types[j];
         for (int q = 0; q < 4; ++q) ctx->shapes.par[j][q] = params[4 * (size_t)j + q];
     }
-    if (ctx->finalized && ctx->device_id >= 0) {
-        HIPCHK(hipSetDevice(ctx->device_id));
-        HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (form != collision_form(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
-    }
-    return ADMM_OK;
+    return push_shapes(ctx, form);
 }
 
 // extension, no reference counterpart (include/admm_hip.h): one Coulomb coefficient per entry of the current shape list.  The values live in
@@ -320,16 +313,10 @@ int admm_hip_set_collision_friction(admm_hip_ctx *ctx, int n_shapes, const doubl
     if (n_shapes && !mu) return fail(ctx, ADMM_ERR_ARG, "collision friction: no coefficients");
     for (int j = 0; j < n_shapes; ++j)
         if (!(mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, mu[j]);
-    TRY(check_body_friction(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], mu));
-    const int form = collision_form(ctx);
+    TRY(check_body_entries(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], false, mu, nullptr, nullptr));
+    const int form = collision_form(ctx).form;
     for (int j = 0; j < n_shapes; ++j) ctx->shapes.mu[j] = mu[j];
-    if (ctx->finalized && ctx->device_id >= 0) {
-        HIPCHK(hipSetDevice(ctx->device_id));
-        HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (form != collision_form(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
-    }
-    return ADMM_OK;
+    return push_shapes(ctx, form);
 }
 
 // extension, no reference counterpart (include/admm_hip.h): the rigid frame of every entry of the current list (NULL: the identity)
@@ -344,39 +331,15 @@ int admm_hip_set_collision_frames(admm_hip_ctx *ctx, int n_shapes, const double 
             if (bad == 2 && which < 9) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: its frame's R is not a rotation: element (%d, %d) of R^T R - I is %g, beyond 1e-12", j, which / 3, which % 3, by);
             if (bad == 2) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: its frame's R is not a rotation: det R - 1 is %g, beyond 1e-12", j, by);
         }
-        TRY(check_body_frames(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], frames));
+        TRY(check_body_entries(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], false, nullptr, nullptr, frames));
     }
-    const int form = collision_form(ctx);
+    const int form = collision_form(ctx).form;
     if (!frames) reset_frames(ctx);
     else for (int j = 0; j < n_shapes; ++j) {
         for (int k = 0; k < 12; ++k) ctx->shapes.frame[j][k] = frames[12 * (size_t)j + k];
         ctx->shapes.framed[j] = admm_frame::identity(ctx->shapes.frame[j]) ? 0 : 1;
     }
-    if (ctx->finalized && ctx->device_id >= 0) {
-        HIPCHK(hipSetDevice(ctx->device_id));
-        HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (form != collision_form(ctx)) drop_iteration_graphs(ctx);      // the collision batches change kernels
-    }
-    return ADMM_OK;
-}
-
-// a call that changed what moves: the shape table and the mesh table go to the device again (between frames; the values change under a
-// captured graph like shape parameters), and a change of the collision batches' kernels drops the captured graphs
-static int push_motion(admm_hip_ctx *ctx, int form_before) {
-    if (!ctx->finalized || ctx->device_id < 0) return ADMM_OK;
-    HIPCHK(hipSetDevice(ctx->device_id));
-    HIPCHK(hipMemcpyAsync(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice, ctx->stream));
-    std::vector<admm_mesh::MeshMotion> mo(ctx->meshes.size());
-    for (size_t mi = 0; mi < mo.size(); ++mi) {
-        const admm_hip_ctx::MeshMove &mv = ctx->mesh_move[mi];
-        const bool body = !ctx->mesh_role[mi].body_nodes.empty();
-        mo[mi] = admm_mesh::MeshMotion{ctx->mesh_upd[mi].cid, (body || mv.has_vel) ? mv.d_vel : nullptr, body ? mv.body_mu : 0.0, body ? 1 : 0, 0};
-    }
-    if (!mo.empty()) HIPCHK(hipMemcpyAsync(ctx->d_mesh_motion, mo.data(), sizeof(admm_mesh::MeshMotion) * mo.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (form_before != collision_form(ctx)) drop_iteration_graphs(ctx);
-    return ADMM_OK;
+    return push_shapes(ctx, form);
 }
 
 // extension, no reference counterpart (include/admm_hip.h): the rigid motion of every entry of the current list
@@ -387,55 +350,59 @@ int admm_hip_set_collision_motion(admm_hip_ctx *ctx, int n_shapes, const double 
     for (int j = 0; j < n_shapes; ++j)
         for (int k = 0; k < 9; ++k)
             if (!std::isfinite(motion[9 * (size_t)j + k])) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: motion component %d is not finite (%g)", j, k, motion[9 * (size_t)j + k]);
-    TRY(check_body_motion(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], motion));
-    const int form = collision_form(ctx);
+    TRY(check_body_entries(ctx, n_shapes, ctx->shapes.type, &ctx->shapes.par[0][0], false, nullptr, motion, nullptr));
+    const int form = collision_form(ctx).form;
     for (int j = 0; j < n_shapes; ++j) for (int k = 0; k < 9; ++k) ctx->shapes.motion[j][k] = motion[9 * (size_t)j + k];
-    return push_motion(ctx, form);
+    return push_shapes(ctx, form, true);
 }
 
 // ... the velocity of every vertex of a registered obstacle mesh (vel NULL: none again)
 int admm_hip_set_collision_mesh_velocity(admm_hip_ctx *ctx, int mesh_id, int nv, const double *vel) {
     if (!ctx) return ADMM_ERR_ARG;
     if (!ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision mesh velocities are set after finalize");
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    if (!ctx->mesh_role[mesh_id].body_nodes.empty())
+    admm_hip_ctx::CollisionMesh *mv = mesh_by_id(ctx, mesh_id);
+    if (!mv) return ADMM_ERR_ARG;
+    if (mv->body())
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a body surface, which moves with its nodes: it takes no velocities from the caller", mesh_id);
-    const admm_hip_mesh &M = ctx->meshes[mesh_id];
+    const admm_hip_mesh &M = mv->mesh;
     if (vel && nv != M.nv) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: %d vertex velocities given, the mesh has %d vertices", mesh_id, nv, M.nv);
     if (vel) for (int v = 0; v < nv; ++v)
         if (!admm_mesh::finite3(vel + 3 * (size_t)v)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: the velocity of vertex %d is not finite", mesh_id, v);
-    const int form = collision_form(ctx);
-    admm_hip_ctx::MeshMove &mv = ctx->mesh_move[mesh_id];
+    const int form = collision_form(ctx).form;
     if (vel && ctx->device_id >= 0) {
         HIPCHK(hipSetDevice(ctx->device_id));
-        if (!mv.d_vel) { TRY(dalloc(ctx, &mv.d_vel, 3 * (size_t)nv)); drop_iteration_graphs(ctx); }      // (allocated here, never by admm_hip_step)
-        HIPCHK(hipMemcpyAsync(mv.d_vel, vel, sizeof(double) * 3 * (size_t)nv, hipMemcpyHostToDevice, ctx->stream));
+        if (!mv->d_vel) { TRY(dalloc(ctx, &mv->d_vel, 3 * (size_t)nv)); drop_iteration_graphs(ctx); }      // (allocated here, never by admm_hip_step)
+        HIPCHK(hipMemcpyAsync(mv->d_vel, vel, sizeof(double) * 3 * (size_t)nv, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (vel) mv.vel.assign(vel, vel + 3 * (size_t)nv); else mv.vel.clear();
-    mv.has_vel = vel != nullptr;
-    return push_motion(ctx, form);
+    if (vel) mv->vel.assign(vel, vel + 3 * (size_t)nv); else mv->vel.clear();
+    mv->has_vel = vel != nullptr;
+    return push_shapes(ctx, form, true);
 }
 
 // ... the coefficient of a body surface: of the body, for every entry that names the surface
 int admm_hip_set_body_surface_friction(admm_hip_ctx *ctx, int mesh_id, double mu) {
     if (!ctx) return ADMM_ERR_ARG;
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size() || ctx->mesh_role[mesh_id].body_nodes.empty())
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size() || !ctx->meshes[mesh_id].body())
         return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a body surface", mesh_id);
     if (!(mu >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "body surface %d: friction coefficient %g is negative or not a number", mesh_id, mu);
-    const int form = collision_form(ctx);
-    ctx->mesh_move[mesh_id].body_mu = mu;
-    return push_motion(ctx, form);
+    const int form = collision_form(ctx).form;
+    ctx->meshes[mesh_id].body_mu = mu;
+    return push_shapes(ctx, form, true);
+}
+
+// a mesh becomes a registered one: the context's record of it, everything but the mesh itself at its default (an obstacle without an owner)
+static admm_hip_ctx::CollisionMesh &register_mesh(admm_hip_ctx *ctx, const admm_hip_mesh &mesh, int *mesh_id) {
+    ctx->meshes.emplace_back();
+    ctx->meshes.back().mesh = mesh;
+    if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
+    return ctx->meshes.back();
 }
 
 // extension, no reference counterpart (include/admm_hip.h): the context keeps its own copy, uploaded at finalize
 int admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, int *mesh_id) {
     if (!ctx || !mesh || mesh->nodes.empty()) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision meshes must be registered before finalize");
-    ctx->meshes.push_back(*mesh);
-    ctx->mesh_role.emplace_back();
-    ctx->mesh_move.emplace_back();
-    if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
+    register_mesh(ctx, *mesh, mesh_id);
     return ADMM_OK;
 }
 
@@ -443,8 +410,8 @@ int admm_hip_add_collision_mesh(admm_hip_ctx *ctx, const admm_hip_mesh *mesh, in
 static int check_owner_range(admm_hip_ctx *ctx, int mesh_id, int first, int count) {
     if (first < 0 || count < 1 || first > ctx->n_nodes - count)
         return fail(ctx, ADMM_ERR_ARG, "node range [%d, %d) is not inside the %d nodes added so far", first, first + count, ctx->n_nodes);
-    for (size_t i = 0; i < ctx->mesh_role.size(); ++i) {
-        const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+    for (size_t i = 0; i < ctx->meshes.size(); ++i) {
+        const admm_hip_ctx::CollisionMesh &R = ctx->meshes[i];
         if ((int)i == mesh_id || !R.own_count || (R.own_first == first && R.own_count == count)) continue;
         if (first < R.own_first + R.own_count && R.own_first < first + count)
             return fail(ctx, ADMM_ERR_ARG, "node range [%d, %d) overlaps the owner range [%d, %d) of mesh %d without being equal to it", first, first + count,
@@ -479,14 +446,10 @@ static int add_node_surface(admm_hip_ctx *ctx, int node_first, int node_count, i
     const int rc = half_thickness > 0.0 ? admm_hip_mesh_create_open(&M, (int)nodes.size(), verts.data(), n_tris, lt.data(), half_thickness, msg, (int)sizeof msg)
                                         : admm_hip_mesh_create(&M, (int)nodes.size(), verts.data(), n_tris, lt.data(), msg, (int)sizeof msg);
     if (rc) return fail(ctx, rc, "body surface: %s", msg);
-    ctx->meshes.push_back(*M);
+    admm_hip_ctx::CollisionMesh &R = register_mesh(ctx, *M, mesh_id);
     admm_hip_mesh_destroy(M);
-    admm_hip_ctx::MeshRole R;
     R.own_first = node_first; R.own_count = node_count; R.body_nodes = std::move(nodes);
-    if (!(half_thickness > 0.0)) R.rest = verts;      // a closed body surface keeps its rest shape (admm_hip_set_body_self_collision)
-    ctx->mesh_role.push_back(std::move(R));
-    ctx->mesh_move.emplace_back();
-    if (mesh_id) *mesh_id = (int)ctx->meshes.size() - 1;
+    if (!R.open()) R.rest = verts;      // a closed body surface keeps its rest shape (admm_hip_set_body_self_collision)
     return ADMM_OK;
 }
 
@@ -505,13 +468,13 @@ int admm_hip_add_sheet_surface(admm_hip_ctx *ctx, int node_first, int node_count
 int admm_hip_set_sheet_self_collision(admm_hip_ctx *ctx, int mesh_id, int on) {
     if (!ctx) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "sheet self-collision must be set before finalize");
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    if (ctx->mesh_role[mesh_id].body_nodes.empty())
+    admm_hip_ctx::CollisionMesh *R = mesh_by_id(ctx, mesh_id);
+    if (!R) return ADMM_ERR_ARG;
+    if (!R->body())
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is an obstacle mesh, not a sheet surface: it has no nodes to collide with itself", mesh_id);
-    if (!(ctx->meshes[mesh_id].thickness > 0.0))
+    if (!R->open())
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed body surface, not a sheet surface: self-collision of a closed surface is not supported", mesh_id);
-    ctx->mesh_role[mesh_id].self_collision = on != 0;
+    R->self_collision = on != 0;
     return ADMM_OK;
 }
 
@@ -520,12 +483,12 @@ int admm_hip_set_sheet_self_collision(admm_hip_ctx *ctx, int mesh_id, int on) {
 int admm_hip_set_body_self_collision(admm_hip_ctx *ctx, int mesh_id, double r, double reach, double rest_radius) {
     if (!ctx) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "body self-collision must be set before finalize");
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    admm_hip_ctx::MeshRole &R = ctx->mesh_role[mesh_id];
-    if (R.body_nodes.empty())
+    admm_hip_ctx::CollisionMesh *Rp = mesh_by_id(ctx, mesh_id);
+    if (!Rp) return ADMM_ERR_ARG;
+    admm_hip_ctx::CollisionMesh &R = *Rp;
+    if (!R.body())
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is an obstacle mesh, not a body surface: it has no nodes to collide with itself", mesh_id);
-    if (ctx->meshes[mesh_id].thickness > 0.0)
+    if (R.open())
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a sheet surface, not a closed body surface: use admm_hip_set_sheet_self_collision", mesh_id);
     if (!std::isfinite(r) || !std::isfinite(reach) || !std::isfinite(rest_radius))
         return fail(ctx, ADMM_ERR_ARG, "body surface %d: self-collision lengths r %g, reach %g, rest radius %g: a value is not finite", mesh_id, r, reach, rest_radius);
@@ -541,16 +504,16 @@ int admm_hip_set_body_self_collision(admm_hip_ctx *ctx, int mesh_id, double r, d
 // its nodes would be pushed from the first frame; and a node takes its vertex id from one self-colliding surface only, sheet or body
 static int check_body_self_collision(admm_hip_ctx *ctx) {
     for (size_t i = 0; i < ctx->meshes.size(); ++i) {
-        const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+        const admm_hip_ctx::CollisionMesh &R = ctx->meshes[i];
         if (!(R.body_self[0] > 0.0)) continue;
         for (size_t k = 0; k < ctx->meshes.size(); ++k) {      // (owner ranges overlap only when they are equal)
-            const admm_hip_ctx::MeshRole &Q = ctx->mesh_role[k];
+            const admm_hip_ctx::CollisionMesh &Q = ctx->meshes[k];
             if (k == i || Q.own_first != R.own_first || Q.own_count != R.own_count) continue;
             if (Q.self_collision || (k < i && Q.body_self[0] > 0.0))
                 return fail(ctx, ADMM_ERR_ARG, "surfaces %d and %d both collide with themselves and share the node range [%d, %d): a node takes its vertex id from one such surface",
                             (int)std::min(i, k), (int)std::max(i, k), R.own_first, R.own_first + R.own_count);
         }
-        admm_hip_mesh cur = ctx->meshes[i];
+        admm_hip_mesh cur = R.mesh;
         std::vector<double> verts(3 * R.body_nodes.size());
         for (size_t k = 0; k < R.body_nodes.size(); ++k) for (int j = 0; j < 3; ++j) verts[3 * k + j] = ctx->x[3 * (size_t)R.body_nodes[k] + j];
         char msg[512];
@@ -571,17 +534,17 @@ static int check_body_self_collision(admm_hip_ctx *ctx) {
 // vertex id from one such sheet only
 static int check_sheet_self_collision(admm_hip_ctx *ctx) {
     for (size_t i = 0; i < ctx->meshes.size(); ++i) {
-        const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
+        const admm_hip_ctx::CollisionMesh &R = ctx->meshes[i];
         if (!R.self_collision) continue;
         for (size_t k = 0; k < i; ++k)      // (owner ranges overlap only when they are equal)
-            if (ctx->mesh_role[k].self_collision && ctx->mesh_role[k].own_first == R.own_first && ctx->mesh_role[k].own_count == R.own_count)
+            if (ctx->meshes[k].self_collision && ctx->meshes[k].own_first == R.own_first && ctx->meshes[k].own_count == R.own_count)
                 return fail(ctx, ADMM_ERR_ARG, "sheet surfaces %d and %d both collide with themselves and share the node range [%d, %d): a node takes its vertex id from one such sheet",
                             (int)k, (int)i, R.own_first, R.own_first + R.own_count);
         int v = -1, t = -1; double d = 0.0;
-        if (admm_mesh::sheet_rest_violation(ctx->meshes[i], &v, &t, &d)) {
-            const int *c = ctx->meshes[i].cid.data() + 3 * (size_t)t;
+        if (admm_mesh::sheet_rest_violation(R.mesh, &v, &t, &d)) {
+            const int *c = R.mesh.cid.data() + 3 * (size_t)t;
             return fail(ctx, ADMM_ERR_ARG, "sheet surface %d: vertex %d (node %d) lies at distance %g from triangle %d (%d, %d, %d), which it is not a corner of: nearer than the half "
-                        "thickness %g, the sheet would collide with itself at rest", (int)i, v, R.body_nodes[v], d, t, c[0], c[1], c[2], ctx->meshes[i].thickness);
+                        "thickness %g, the sheet would collide with itself at rest", (int)i, v, R.body_nodes[v], d, t, c[0], c[1], c[2], R.mesh.thickness);
         }
     }
     return ADMM_OK;
@@ -591,17 +554,17 @@ static int check_sheet_self_collision(admm_hip_ctx *ctx) {
 // (no kernel changes, captured graphs stay)
 int admm_hip_set_collision_mesh_thickness(admm_hip_ctx *ctx, int mesh_id, double half_thickness) {
     if (!ctx) return ADMM_ERR_ARG;
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    if (!(ctx->meshes[mesh_id].thickness > 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed mesh: it has no thickness", mesh_id);
+    admm_hip_ctx::CollisionMesh *m = mesh_by_id(ctx, mesh_id);
+    if (!m) return ADMM_ERR_ARG;
+    if (!m->open()) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed mesh: it has no thickness", mesh_id);
     if (!(half_thickness > 0.0 && std::isfinite(half_thickness)))
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: half thickness %g: it must be positive and finite", mesh_id, half_thickness);
-    if (ctx->mesh_role[mesh_id].side_reach > 0.0 && half_thickness > ctx->mesh_role[mesh_id].side_reach)
-        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: half thickness %g exceeds the reach %g of its side memory", mesh_id, half_thickness, ctx->mesh_role[mesh_id].side_reach);
-    ctx->meshes[mesh_id].thickness = half_thickness;
+    if (m->side_reach > 0.0 && half_thickness > m->side_reach)
+        return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: half thickness %g exceeds the reach %g of its side memory", mesh_id, half_thickness, m->side_reach);
+    m->mesh.thickness = half_thickness;
     if (ctx->finalized && ctx->device_id >= 0) {
         HIPCHK(hipSetDevice(ctx->device_id));
-        HIPCHK(hipMemcpyAsync(ctx->d_mesh_thick + mesh_id, &ctx->meshes[mesh_id].thickness, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->d_mesh_thick + mesh_id, &m->mesh.thickness, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     return ADMM_OK;
@@ -612,28 +575,28 @@ int admm_hip_set_collision_mesh_thickness(admm_hip_ctx *ctx, int mesh_id, double
 int admm_hip_set_collision_mesh_side_memory(admm_hip_ctx *ctx, int mesh_id, double reach) {
     if (!ctx) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "side memory must be set before finalize");
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    const double r = ctx->meshes[mesh_id].thickness;
+    admm_hip_ctx::CollisionMesh *m = mesh_by_id(ctx, mesh_id);
+    if (!m) return ADMM_ERR_ARG;
+    const double r = m->mesh.thickness;
     if (!(r > 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a closed mesh: it has an inside and needs no side memory", mesh_id);
     if (!std::isfinite(reach)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: reach %g is not finite", mesh_id, reach);
     if (reach != 0.0 && !(reach >= r)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: reach %g is below its half thickness %g", mesh_id, reach, r);
     if (reach != 0.0) {      // (the current list may already name it twice)
-        const double before = ctx->mesh_role[mesh_id].side_reach;
-        ctx->mesh_role[mesh_id].side_reach = reach;
+        const double before = m->side_reach;
+        m->side_reach = reach;
         const int rc = check_side_entries(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]);
-        if (rc) { ctx->mesh_role[mesh_id].side_reach = before; return rc; }
+        if (rc) { m->side_reach = before; return rc; }
     }
-    ctx->mesh_role[mesh_id].side_reach = reach;
+    m->side_reach = reach;
     return ADMM_OK;
 }
 
 int admm_hip_set_collision_mesh_owner(admm_hip_ctx *ctx, int mesh_id, int node_first, int node_count) {
     if (!ctx) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "mesh owners must be set before finalize");
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    admm_hip_ctx::MeshRole &R = ctx->mesh_role[mesh_id];
+    admm_hip_ctx::CollisionMesh *Rp = mesh_by_id(ctx, mesh_id);
+    if (!Rp) return ADMM_ERR_ARG;
+    admm_hip_ctx::CollisionMesh &R = *Rp;
     if (node_count == 0) { R.own_first = R.own_count = 0; return ADMM_OK; }
     TRY(check_owner_range(ctx, mesh_id, node_first, node_count));
     R.own_first = node_first; R.own_count = node_count;
@@ -643,12 +606,12 @@ int admm_hip_set_collision_mesh_owner(admm_hip_ctx *ctx, int mesh_id, int node_f
 int admm_hip_get_body_surface_status(admm_hip_ctx *ctx, int mesh_id, int64_t *updated, int64_t *refused, int *last_bad_tri) {
     if (!ctx) return ADMM_ERR_ARG;
     if (!ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "body surface status before finalize");
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size() || ctx->mesh_role[mesh_id].body_nodes.empty())
+    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size() || !ctx->meshes[mesh_id].body())
         return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a body surface", mesh_id);
     admm_mesh::BodyStatus st{0, 0, -1, 0};
     if (ctx->device_id >= 0) {
         HIPCHK(hipSetDevice(ctx->device_id));
-        HIPCHK(hipMemcpyAsync(&st, ctx->mesh_upd[mesh_id].status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(&st, ctx->meshes[mesh_id].upd.status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     if (updated) *updated = st.updated;
@@ -661,9 +624,9 @@ int admm_hip_get_body_surface_status(admm_hip_ctx *ctx, int mesh_id, int64_t *up
 int admm_hip_collision_mesh_copy(admm_hip_ctx *ctx, int mesh_id, admm_hip_mesh **out) {
     if (!ctx || !out) return ADMM_ERR_ARG;
     *out = nullptr;
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    *out = new (std::nothrow) admm_hip_mesh(ctx->meshes[mesh_id]);
+    const admm_hip_ctx::CollisionMesh *m = mesh_by_id(ctx, mesh_id);
+    if (!m) return ADMM_ERR_ARG;
+    *out = new (std::nothrow) admm_hip_mesh(m->mesh);
     return *out ? ADMM_OK : fail(ctx, ADMM_ERR_ARG, "out of memory");
 }
 
@@ -671,11 +634,11 @@ int admm_hip_collision_mesh_copy(admm_hip_ctx *ctx, int mesh_id, admm_hip_mesh *
 // rewritten in place (launch.inc: update_mesh_device)
 int admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, const double *verts) {
     if (!ctx) return ADMM_ERR_ARG;
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    if (!ctx->mesh_role[mesh_id].body_nodes.empty())
+    admm_hip_ctx::CollisionMesh *m = mesh_by_id(ctx, mesh_id);
+    if (!m) return ADMM_ERR_ARG;
+    if (m->body())
         return fail(ctx, ADMM_ERR_ARG, "collision mesh %d is a body surface, which follows its nodes: it takes no vertices from the caller", mesh_id);
-    admm_hip_mesh &M = ctx->meshes[mesh_id];
+    admm_hip_mesh &M = m->mesh;
     if (!ctx->finalized || ctx->device_id < 0) {
         char msg[512];
         const int rc = admm_mesh::mesh_set_vertices(M, nv, verts, msg, (int)sizeof msg);
@@ -783,18 +746,12 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     for (const Explicit &E : ctx->explicits) for (int32_t v : E.idx) if (v >= ctx->n_nodes) return fail(ctx, ADMM_ERR_ARG, "explicit force references node %d (have %d)", v, ctx->n_nodes);
     if (const char *e = getenv("ADMM_HIP_SHARD")) ctx->shard_mode = (std::string(e) == "subtree") ? ADMM_SHARD_SUBTREE : ADMM_SHARD_CONTIGUOUS;
     if (const char *g = getenv("ADMM_HIP_FACTOR_LOCAL")) ctx->factor_local = atoi(g) != 0;      // (overrides admm_hip_set_factor_local; host_factor picks the tree by it)
-    TRY(check_body_translations(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
-    TRY(check_body_friction(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], ctx->shapes.mu));
-    TRY(check_body_motion(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], &ctx->shapes.motion[0][0]));
-    TRY(check_body_frames(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], &ctx->shapes.frame[0][0]));
+    TRY(check_body_entries(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0], true, ctx->shapes.mu, &ctx->shapes.motion[0][0], &ctx->shapes.frame[0][0]));
     for (int j = 0; j < ctx->shapes.n; ++j)
         if (!(ctx->shapes.mu[j] >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision shape %d: friction coefficient %g is negative or not a number", j, ctx->shapes.mu[j]);
     TRY(check_sheet_self_collision(ctx));
     TRY(check_body_self_collision(ctx));
     TRY(check_side_entries(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
-    ctx->side_slot.assign(ctx->meshes.size(), -1); ctx->n_side_slots = 0;      // side memory: one row of sides per mesh with a reach
-    for (size_t i = 0; i < ctx->meshes.size(); ++i) if (ctx->mesh_role[i].side_reach > 0.0) ctx->side_slot[i] = ctx->n_side_slots++;
-    if (ctx->device_id < 0) ctx->h_side.assign((size_t)ctx->n_side_slots * (size_t)ctx->n_nodes, 0);
     TRY(host_assemble(ctx, false));
     TRY(host_factor(ctx, false));
     ctx->info.rank = ctx->rank; ctx->info.world = ctx->world;
@@ -808,7 +765,11 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     // all-reduce the whole right-hand side and solve the whole system on every rank, subtree shards (either top) rebuild the full x by
     // the masked all-reduce before the velocity update (shard_sync_x), and a dense solve is not sharded.  Every rank registers the same
     // surfaces and updates them from the same bits, so nothing of them goes over the collectives.
-    if (ctx->device_id >= 0) TRY(upload_all(ctx));
+    const admm_lib::MeshTables plan = plan_context_meshes(ctx);      // (collision_plan.hpp; in device order, so behind host_factor)
+    ctx->n_side_slots = plan.n_side_rows;                           // side memory: one row of sides per mesh with a reach
+    for (size_t i = 0; i < ctx->meshes.size(); ++i) ctx->meshes[i].side_row = plan.side_row[i];
+    if (ctx->device_id < 0) ctx->h_side.assign((size_t)ctx->n_side_slots * (size_t)ctx->n_nodes, 0);
+    if (ctx->device_id >= 0) TRY(upload_all(ctx, plan));
     ctx->finalized = true;
     return ADMM_OK;
 }

@@ -249,18 +249,18 @@ int admm_hip_debug_graph_state(admm_hip_ctx *ctx, int *iter_graph, int *frame_gr
 // which kernels the collision batches launch for the current list (launch.inc: collision_form)
 int admm_hip_debug_collision_form(admm_hip_ctx *ctx, int *form) {
     if (!ctx || !form) return ADMM_ERR_ARG;
-    *form = collision_form(ctx);
+    *form = collision_form(ctx).form;
     return ADMM_OK;
 }
 
 // side memory (include/admm_hip.h): the sides of one mesh with memory, n_nodes values in the caller's node order (the device holds them in
 // factor order; a host-only context keeps them on the host)
 static int side_row(admm_hip_ctx *ctx, int mesh_id, int *row) {
-    if (mesh_id < 0 || mesh_id >= (int)ctx->meshes.size())
-        return fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
-    if (!(ctx->mesh_role[mesh_id].side_reach > 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d has no side memory", mesh_id);
+    const admm_hip_ctx::CollisionMesh *m = mesh_by_id(ctx, mesh_id);
+    if (!m) return ADMM_ERR_ARG;
+    if (!(m->side_reach > 0.0)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d has no side memory", mesh_id);
     if (!ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "collision sides exist from finalize on");
-    *row = ctx->side_slot[mesh_id];
+    *row = m->side_row;
     return ADMM_OK;
 }
 int admm_hip_get_collision_sides(admm_hip_ctx *ctx, int mesh_id, int32_t *side) {

@@ -22,6 +22,7 @@
 #include "dev_types.hpp"
 #include "mesh_host.hpp"
 #include "node_csr.hpp"
+#include "collision_plan.hpp"
 
 namespace admm_lib {
 
@@ -131,11 +132,13 @@ struct admm_hip_ctx {
     admm_dev::Gravity grav{};             // fast path: only constant all-node forces
     std::vector<Explicit> explicits; bool explicit_simple = true;
     admm_dev::ShapeTable shapes{}; admm_dev::ShapeTable *d_shapes = nullptr;
-    // closed triangle meshes named by ADMM_SHAPE_MESH entries (admm_hip_add_collision_mesh, before finalize): with at least one, the collision
-    // batches run project_collision_mesh_kernel instead of a segment of project_multi_kernel; their arrays are uploaded at finalize
-    std::vector<admm_hip_mesh> meshes; admm_mesh::MeshDev *d_meshes = nullptr;
-    // admm_hip_update_collision_mesh after finalize (kernels_mesh.hpp) rewrites a mesh's device arrays in place; the host copy above
-    // then keeps only the topology.  Every buffer the update needs is allocated at finalize, one set per mesh:
+    // triangle meshes named by ADMM_SHAPE_MESH entries, registered before finalize (admm_hip_add_collision_mesh: an obstacle;
+    // admm_hip_add_body_surface / admm_hip_add_sheet_surface: a surface of simulated nodes): with at least one, the collision batches run
+    // project_collision_mesh_kernel instead of a segment of project_multi_kernel.  One record per mesh, indexed by mesh id (mesh_by_id):
+    // everything the host knows about it; its arrays are uploaded at finalize, the device tables parallel to d_meshes are built from the
+    // records (collision_plan.hpp: plan_mesh_tables; upload.inc)
+    // admm_hip_update_collision_mesh after finalize (kernels_mesh.hpp) rewrites a mesh's device arrays in place; the host copy then
+    // keeps only the topology.  Every buffer the update needs is allocated at finalize, one set per mesh:
     struct MeshUpdate {
         admm_mesh::Node *nodes; admm_mesh::Tri *tris; admm_mesh::Nrm *nrm;       // the live arrays (d_meshes points at them)
         double *verts, *fn, *vn, *part;                                          // staged vertices, face / vertex normals, volume partials
@@ -143,23 +146,29 @@ struct admm_hip_ctx {
         // body surfaces only (else null): the device node id of every vertex, the surface's own check and its BodyStatus
         int *dnode; admm_mesh::UpdateCheck *chk; admm_mesh::BodyStatus *status;
     };
-    std::vector<MeshUpdate> mesh_upd; admm_mesh::UpdateCheck *d_mesh_chk = nullptr;
-    // what a mesh is to the scene, parallel to `meshes`: its owner, the node range [own_first, own_first + own_count) whose collision
-    // elements skip it (own_count 0: none; admm_hip_set_collision_mesh_owner), and for a body surface (admm_hip_add_body_surface) the
-    // node behind every vertex, ascending -- the device rebuilds it from them at every step (launch.inc: update_bodies)
-    // self_collision (a sheet surface only, admm_hip_set_sheet_self_collision): its own nodes meet it outside their 1-ring instead of skipping it
-    // side_reach (an open mesh only, admm_hip_set_collision_mesh_side_memory): > 0: the mesh has side memory with this reach, 0: none
-    // body_self (a closed body surface only, admm_hip_set_body_self_collision): {r, R, rho}, r > 0: its surface nodes meet it outside what is
-    // near them in the rest shape; rest: the vertices [nv][3] as admm_hip_add_body_surface registered them
-    struct MeshRole { int own_first = 0, own_count = 0; std::vector<int> body_nodes; bool self_collision = false; double side_reach = 0.0;
-                      double body_self[3] = {0.0, 0.0, 0.0}; std::vector<double> rest; };
-    std::vector<MeshRole> mesh_role;
-    // obstacles that move (admm_hip_set_collision_motion: shapes.motion; admm_hip_set_collision_mesh_velocity, admm_hip_set_body_surface_friction):
-    // per mesh, parallel to `meshes`, the host's record and the device table the moving friction kernel reads.  d_vel: an obstacle's
-    // vertex velocities, allocated by the call that first sets them (has_vel: in effect); a body surface's are allocated at finalize and
-    // gathered from the frame-start v at every step (launch.inc: update_bodies).  body_mu: a body surface's coefficient.
-    struct MeshMove { double *d_vel = nullptr; bool has_vel = false; double body_mu = 0.0; std::vector<double> vel; };
-    std::vector<MeshMove> mesh_move; admm_mesh::MeshMotion *d_mesh_motion = nullptr;
+    struct CollisionMesh {
+        admm_hip_mesh mesh;
+        // what the mesh is to the scene: its owner, the node range [own_first, own_first + own_count) whose collision elements skip it
+        // (own_count 0: none; admm_hip_set_collision_mesh_owner), and for a body surface the node behind every vertex, ascending -- the
+        // device rebuilds it from them at every step (launch.inc: update_bodies)
+        // self_collision (a sheet surface only, admm_hip_set_sheet_self_collision): its own nodes meet it outside their 1-ring instead of skipping it
+        // side_reach (an open mesh only, admm_hip_set_collision_mesh_side_memory): > 0: the mesh has side memory with this reach, 0: none
+        // body_self (a closed body surface only, admm_hip_set_body_self_collision): {r, R, rho}, r > 0: its surface nodes meet it outside what
+        // is near them in the rest shape; rest: the vertices [nv][3] as admm_hip_add_body_surface registered them
+        int own_first = 0, own_count = 0; std::vector<int> body_nodes; bool self_collision = false; double side_reach = 0.0;
+        double body_self[3] = {0.0, 0.0, 0.0}; std::vector<double> rest;
+        // how it moves (admm_hip_set_collision_mesh_velocity, admm_hip_set_body_surface_friction; an entry's rigid motion is
+        // shapes.motion).  d_vel: an obstacle's vertex velocities, allocated by the call that first sets them (has_vel: in effect); a
+        // body surface's are allocated at finalize and gathered from the frame-start v at every step (launch.inc: update_bodies).
+        // body_mu: a body surface's coefficient.
+        double *d_vel = nullptr; bool has_vel = false; double body_mu = 0.0; std::vector<double> vel;
+        MeshUpdate upd{};             // the device buffers (finalize; all null in a host-only context)
+        int side_row = -1;            // its row of d_side / h_side (finalize; -1: no side memory)
+        bool body() const { return !body_nodes.empty(); }         // a surface of simulated nodes, not an obstacle
+        bool open() const { return mesh.thickness > 0.0; }        // a thick shell, not a closed mesh
+    };
+    std::vector<CollisionMesh> meshes; admm_mesh::MeshDev *d_meshes = nullptr; admm_mesh::UpdateCheck *d_mesh_chk = nullptr;
+    admm_mesh::MeshMotion *d_mesh_motion = nullptr;      // per mesh, parallel to d_meshes: what the moving friction kernel reads (upload.inc: mesh_motion_table)
     // open meshes (thick shells, admm_hip_mesh::thickness > 0): the half thickness of every mesh, parallel to d_meshes (0: a closed mesh), a
     // table of its own that project_collision_shell_kernel alone reads; admm_hip_set_collision_mesh_thickness writes one entry
     double *d_mesh_thick = nullptr;
@@ -170,10 +179,10 @@ struct admm_hip_ctx {
     // contexts where some open mesh has side memory (mesh_query.hpp; else all null / empty): per mesh, parallel to d_meshes, its reach (0:
     // none), its row in d_side (-1: none) and its boundary table (null: none); d_side [n_side_slots][n_nodes] in device node order, one
     // int32 side per node and mesh with memory.  collision_side_kernel writes d_side at the start of every step,
-    // project_collision_sided_kernel reads all four.  side_slot: the host's copy of the rows; h_side: the sides of a host-only context
-    // (caller's node order).
+    // project_collision_sided_kernel reads all four.  CollisionMesh::side_row: the host's copy of the rows; h_side: the sides of a
+    // host-only context (caller's node order).
     double *d_mesh_reach = nullptr; int *d_mesh_side_slot = nullptr; const int **d_mesh_bnd = nullptr; int32_t *d_side = nullptr;
-    int n_side_slots = 0; std::vector<int> side_slot; std::vector<int32_t> h_side;
+    int n_side_slots = 0; std::vector<int32_t> h_side;
     // contexts where some body surface collides with itself (mesh_query.hpp; else both null): per mesh, parallel to d_meshes, the three
     // lengths {r, R, rho} (zeros: off) and the rest vertices [nv][3] (null: none); project_collision_bodyself_kernel alone reads them, with
     // d_self_vid for the nodes' vertex ids
@@ -329,6 +338,19 @@ int fail(admm_hip_ctx *c, int code, const char *fmt, ...);      // (comm.cpp)
 // (a failed call also leaves HIP's sticky last-error set: cleared here, so that an unrelated hipGetLastError() check later -- in this context or
 //  another one of the process -- does not report this failure a second time as its own)
 #define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (void)hipGetLastError(); return fail(ctx, ADMM_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
+
+// the record of a registered mesh; null, with the refusal every entry point gives an unknown id, where there is none
+inline admm_hip_ctx::CollisionMesh *mesh_by_id(admm_hip_ctx *ctx, int mesh_id) {
+    if (mesh_id >= 0 && mesh_id < (int)ctx->meshes.size()) return &ctx->meshes[mesh_id];
+    fail(ctx, ADMM_ERR_ARG, "mesh_id %d is not a registered mesh (have %d)", mesh_id, (int)ctx->meshes.size());
+    return nullptr;
+}
+// the record that entry j of a shape list (types [n], params [n][4]) names; null: not a mesh entry, or no such mesh
+inline const admm_hip_ctx::CollisionMesh *entry_mesh(const admm_hip_ctx *ctx, const int32_t *types, const double *params, int j) {
+    if (types[j] != ADMM_SHAPE_MESH) return nullptr;
+    const int id = (int)params[4 * (size_t)j + 3];
+    return id >= 0 && id < (int)ctx->meshes.size() ? &ctx->meshes[id] : nullptr;
+}
 
 template <class T> int dalloc(admm_hip_ctx *ctx, T **p, size_t n) {
     *p = nullptr;

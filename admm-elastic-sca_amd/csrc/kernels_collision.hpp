@@ -19,35 +19,35 @@
 //      tangential part of p' - x0 against mu * depth (an entry that did not move the point: depth 0, nothing happens), and the next entry
 //      starts from the result.  xs: the frame-start x in device order (ctx->d_x, which no kernel writes during the ADMM loop): one more
 //      24-byte gather per node.
-//   2  project_collision_friction_moving_kernel<MESH>: obstacles that move (launch.inc moving_friction_on).  After an entry moved the
+//   2  project_collision_friction_moving_kernel<MESH>: obstacles that move (collision_plan.hpp: trigger 2).  After an entry moved the
 //      point and for mu > 0, w = the displacement of its surface over the frame at the contact p' (friction.hpp rigid_displacement from
 //      the entry's nine doubles of shapes->motion, uniform across the wave; at a mesh hit whose mesh has vertex velocities plus dt times
 //      their interpolation with the hit triangle's barycentric weights: three cid ints and three 24-byte gathers) goes into
 //      admm_friction::apply_moving; a zero motion gives w = 0 and the bits of the rule at rest.  A body surface's entry takes the
 //      surface's coefficient (MeshMotion::mu) in place of the entry's, which is 0 for it.  mm: null without meshes.
-//   3  project_collision_framed_kernel<MESH>: a rigid frame per entry and the oriented box (frame.hpp; launch.inc framed_on).  For an
+//   3  project_collision_framed_kernel<MESH>: a rigid frame per entry and the oriented box (frame.hpp; collision_plan.hpp: trigger 3).  For an
 //      entry whose frame is not the identity (shapes->framed, uniform across the wave) the candidate goes to local coordinates, the
 //      entry's unframed code runs there -- collide_round or collide_box, or for a mesh the box test, closest and inside with the
 //      translation t -- and only a point that code moved goes back to world coordinates; every other point keeps its bits.  Friction
 //      runs on the world-space before, p', x0 and w as in form 2; a framed mesh's interpolated vertex velocity is in the mesh's own
 //      coordinates and is rotated by R first.
-//   4  project_collision_shell_kernel: open meshes as thick shells (mesh_query.hpp; launch.inc shell_on, which implies meshes).  For an
+//   4  project_collision_shell_kernel: open meshes as thick shells (mesh_query.hpp; collision_plan.hpp: trigger 4, which implies meshes).  For an
 //      entry whose mesh is open (thick[mesh] > 0, uniform across the wave) the mesh branch differs in three places: the box test is the
 //      inflated one, the decision is d2 < r^2 on the hit of the search bounded by r^2, and the push target is at distance r from the
 //      closest point on the side the point is on.  thick: the half thickness of every mesh, parallel to meshes (0: closed).
-//   5  project_collision_self_kernel: a sheet surface that collides with itself (admm_hip_set_sheet_self_collision; launch.inc self_on).
+//   5  project_collision_self_kernel: a sheet surface that collides with itself (admm_hip_set_sheet_self_collision; collision_plan.hpp: trigger 5).
 //      For an entry whose mesh the node's body owns: self[mesh] == 0 (uniform across the wave): skipped, as below; != 0: the shell branch
 //      without the triangles around the node's vertex vid[node] (their corner ids: three loads per leaf triangle, per lane).  The surface
 //      is the frame-start one: a node meets where the rest of the cloth was at the start of the frame.  self: the flag of every mesh,
 //      parallel to meshes; vid: one id per node in device order (-1: none); both uploaded at finalize, not null in this form.
-//   6  project_collision_sided_kernel: an open mesh with side memory (admm_hip_set_collision_mesh_side_memory; launch.inc sided_on).
+//   6  project_collision_sided_kernel: an open mesh with side memory (admm_hip_set_collision_mesh_side_memory; collision_plan.hpp sided).
 //      For an entry whose mesh has a reach (reach[mesh] > 0, uniform across the wave) a lane reads its node's side
 //      s = side[side_slot[mesh] * side_stride + node]: s == 0 runs the shell branch, s != 0 runs sided_project with the mesh's boundary
 //      table bnd[mesh] -- the search bounded by R, the unsigned rule on the node's own side or at a boundary hit, the mirror push for a
 //      node that has crossed.  A node of the body that owns the mesh holds s == 0 (the latch skips it).  self, vid: null where no sheet
 //      self-collides; reach, side_slot, bnd, side: uploaded at finalize, not null in this form.
-//   7  project_collision_bodyself_kernel: a closed body surface that collides with itself (admm_hip_set_body_self_collision; launch.inc
-//      bodyself_on).  An entry that names a mesh the node's body owns and whose lengths bself[3 mesh ..] = {r, R, rho} have r > 0
+//   7  project_collision_bodyself_kernel: a closed body surface that collides with itself (admm_hip_set_body_self_collision;
+//      collision_plan.hpp: trigger 7).  An entry that names a mesh the node's body owns and whose lengths bself[3 mesh ..] = {r, R, rho} have r > 0
 //      (uniform per entry and body): a surface node (vid >= 0) runs body_self_project against the rest vertices rest[mesh] -- the search
 //      bounded by R that passes over what is near the node in the rest shape, the unsigned rule outside, the mirror push for a node that
 //      has crossed the skin (no translation, no frame: refused on a body surface) --, an interior node skips the entry.  reach,
@@ -104,7 +104,7 @@ __device__ __forceinline__ void collision_store(const BatchDev &b, const int e, 
     }
 }
 
-// one analytic shape of the list pushes p out.  A list with a box or a framed entry never comes here (launch.inc framed_on).
+// one analytic shape of the list pushes p out.  A list with a box or a framed entry never comes here (collision_plan.hpp: trigger 3).
 __device__ __forceinline__ void collide_analytic(const ShapeTable *__restrict__ shapes, const int q, double p[3]) {
     const double c0 = shapes->par[q][0], c1 = shapes->par[q][1], c2 = shapes->par[q][2], R = shapes->par[q][3];
     admm_frame::collide_round(shapes->type[q], c0, c1, c2, R, p);

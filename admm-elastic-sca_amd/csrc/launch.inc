@@ -13,89 +13,22 @@ void tet_trace_next(hipStream_t st) {
     hipMemcpyToSymbolAsync(HIP_SYMBOL(admm_dev::g_tet_trace), &p, sizeof(p), 0, hipMemcpyHostToDevice, st);
 }
 #endif
+// which kernels the collision batches launch for the current list, and whether in a launch of their own (collision_plan.hpp: the forms 0
+// to 7, their triggers, own_launch and sided): one pass over the list, from the current coefficients, motions, frames and mesh records.
+// Evaluated at every launch or capture, never kept: a setter changes it between frames, and the one that does drops the captured graphs
+// (abi_setup.inc: push_shapes).  A form's kernel is an instantiation beside the others, not a flag inside them: a list that sets off no
+// higher trigger launches exactly the kernels it launched before that form existed.
+admm_lib::CollisionForm collision_form(const admm_hip_ctx *ctx) {
+    return admm_lib::collision_form_of(ctx->shapes, (int)ctx->meshes.size(), [ctx](int id) {
+        const admm_hip_ctx::CollisionMesh &m = ctx->meshes[id];
+        return admm_lib::MeshFacts{m.body(), m.mesh.thickness, m.self_collision, m.side_reach, m.body_self[0], m.body_mu, m.has_vel};
+    });
+}
+
 // The scene's batches as segments of ONE project_multi_kernel launch (false: launch batch after batch -- a kind without a segment
-// body, more than MULTI_MAX batches, or a tet batch with its anchors right behind it, which already is one launch).
-// does any entry of the shape list carry a friction coefficient?  Then the collision batches run project_collision_friction_kernel in a
-// launch of their own; with all of them zero every launch is the frictionless one.  Decided from the current coefficients at every launch
-// or capture: a call that flips it drops the captured graphs (abi_setup.inc).
-bool friction_on(const admm_hip_ctx *ctx) {
-    for (int q = 0; q < ctx->shapes.n; ++q) if (ctx->shapes.mu[q] > 0.0) return true;
-    return false;
-}
-
-// ... and does a contact's obstacle move?  An entry with a coefficient whose rigid motion is not all zero or whose mesh has vertex
-// velocities set, or a body surface with a coefficient named in the list: the collision batches then run the moving form of the
-// friction kernel.  Evaluated at every launch or capture like friction_on; a call that changes collision_form drops the captured graphs.
-bool moving_friction_on(const admm_hip_ctx *ctx) {
-    for (int q = 0; q < ctx->shapes.n; ++q) {
-        const int id = ctx->shapes.type[q] == ADMM_SHAPE_MESH ? (int)ctx->shapes.par[q][3] : -1;
-        const admm_hip_ctx::MeshMove *mv = id >= 0 && id < (int)ctx->mesh_move.size() ? &ctx->mesh_move[id] : nullptr;
-        if (mv && !ctx->mesh_role[id].body_nodes.empty() && mv->body_mu > 0.0) return true;
-        if (!(ctx->shapes.mu[q] > 0.0)) continue;
-        if (mv && mv->has_vel) return true;
-        for (int k = 0; k < 9; ++k) if (ctx->shapes.motion[q][k] != 0.0) return true;
-    }
-    return false;
-}
-// ... and does the list hold an entry whose frame is not the identity (admm_hip_set_collision_frames) or a box?  Then the collision
-// batches run project_collision_framed_kernel, the one kernel that knows frames and boxes, in a launch of their own, in both launch modes
-// (the fused launch leaves them out like it does with meshes or friction; the per-batch path goes through launch_collision_mesh too).  A
-// framed instantiation beside the kernels, not a flag inside them: every other list launches exactly the kernels it launched before.
-bool framed_on(const admm_hip_ctx *ctx) {
-    for (int q = 0; q < ctx->shapes.n; ++q) if (ctx->shapes.framed[q] || ctx->shapes.type[q] == ADMM_SHAPE_BOX) return true;
-    return false;
-}
-// ... and does an entry of the current list name an open mesh (a thick shell, admm_hip_mesh_create_open / admm_hip_add_sheet_surface)?
-// Then the collision batches run project_collision_shell_kernel, the one kernel that knows the shell rule (and everything the framed
-// kernel knows), in a launch of their own in both launch modes.  A list that names none launches exactly what it launched before.
-bool shell_on(const admm_hip_ctx *ctx) {
-    for (int q = 0; q < ctx->shapes.n; ++q) {
-        if (ctx->shapes.type[q] != ADMM_SHAPE_MESH) continue;
-        const int id = (int)ctx->shapes.par[q][3];
-        if (id >= 0 && id < (int)ctx->meshes.size() && ctx->meshes[id].thickness > 0.0) return true;
-    }
-    return false;
-}
-// ... and does an entry of the current list name a sheet surface that collides with itself (admm_hip_set_sheet_self_collision)?  Then the
-// collision batches run project_collision_self_kernel, the shell form plus the search that leaves out a node's own 1-ring, in a launch of
-// their own in both launch modes.  A context where no sheet self-collides launches exactly what it launched before.
-bool self_on(const admm_hip_ctx *ctx) {
-    for (int q = 0; q < ctx->shapes.n; ++q) {
-        if (ctx->shapes.type[q] != ADMM_SHAPE_MESH) continue;
-        const int id = (int)ctx->shapes.par[q][3];
-        if (id >= 0 && id < (int)ctx->mesh_role.size() && ctx->mesh_role[id].self_collision) return true;
-    }
-    return false;
-}
-// ... and does an entry of the current list name an open mesh with side memory (admm_hip_set_collision_mesh_side_memory: reach > 0)?  Then
-// the collision batches run project_collision_sided_kernel, the self-collision form plus the remembered side, in a launch of their own in
-// both launch modes, and every step begins with the latch (latch_sides).  A context without such a mesh launches exactly what it did.
-bool sided_on(const admm_hip_ctx *ctx) {
-    for (int q = 0; q < ctx->shapes.n; ++q) {
-        if (ctx->shapes.type[q] != ADMM_SHAPE_MESH) continue;
-        const int id = (int)ctx->shapes.par[q][3];
-        if (id >= 0 && id < (int)ctx->mesh_role.size() && ctx->mesh_role[id].side_reach > 0.0) return true;
-    }
-    return false;
-}
-// ... and does an entry of the current list name a closed body surface that collides with itself (admm_hip_set_body_self_collision: r > 0)?
-// Then the collision batches run project_collision_bodyself_kernel, the side-memory form plus the rest-excluding search for the body's own
-// surface nodes, in a launch of their own in both launch modes.  A context where no body self-collides launches exactly what it did.
-bool bodyself_on(const admm_hip_ctx *ctx) {
-    for (int q = 0; q < ctx->shapes.n; ++q) {
-        if (ctx->shapes.type[q] != ADMM_SHAPE_MESH) continue;
-        const int id = (int)ctx->shapes.par[q][3];
-        if (id >= 0 && id < (int)ctx->mesh_role.size() && ctx->mesh_role[id].body_self[0] > 0.0) return true;
-    }
-    return false;
-}
-// which kernels the collision batches launch: 0 the frictionless ones, 1 the friction form, 2 its moving form, 3 the framed form, 4 the
-// shell form, 5 the self-collision form, 6 the side-memory form, 7 the body self-collision form
-int collision_form(const admm_hip_ctx *ctx) { return bodyself_on(ctx) ? 7 : sided_on(ctx) ? 6 : self_on(ctx) ? 5 : shell_on(ctx) ? 4 : framed_on(ctx) ? 3 : moving_friction_on(ctx) ? 2 : friction_on(ctx) ? 1 : 0; }
-// ... in a launch of their own (launch_collision_mesh) instead of a segment of project_multi_kernel or project_collision_kernel
-bool collision_own_launch(const admm_hip_ctx *ctx) { return !ctx->meshes.empty() || friction_on(ctx) || framed_on(ctx); }
-
-bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
+// body, more than MULTI_MAX batches, or a tet batch with its anchors right behind it, which already is one launch).  own_launch: the
+// collision batches stay out of the segments (collision_form)
+bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks, bool own_launch) {
     using namespace admm_dev;
     mb = MultiBatch{}; blocks = 0;
     // segments in the order of what a block costs, dearest first (the L-BFGS kinds, then the closed-form ones) whatever order the scene listed
@@ -124,7 +57,7 @@ bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
         case ADMM_KIND_TRI_STRAIN: code = MK_TRI_STRAIN; break;
         case ADMM_KIND_TRI_AREA: code = MK_TRI_AREA; break;
         case ADMM_KIND_TRI_FUNG: code = MK_TRI_FUNG; break;
-        case ADMM_KIND_COLLISION: if (collision_own_launch(ctx)) continue; code = MK_COLLISION; break;      // (meshes, friction, frames, boxes: own launch, launch_local)
+        case ADMM_KIND_COLLISION: if (own_launch) continue; code = MK_COLLISION; break;      // (meshes, friction, frames, boxes: own launch, launch_local)
         default: break;
         }
         if (code < 0 || mb.n == MULTI_MAX) return false;
@@ -141,34 +74,48 @@ bool build_multi(admm_hip_ctx *ctx, admm_dev::MultiBatch &mb, int &blocks) {
     return true;
 }
 
+dim3 mesh_grid(int n) { return dim3((unsigned)((std::max(n, 1) + admm_dev::MESH_BLOCK - 1) / admm_dev::MESH_BLOCK)); }
+
+// the commit of a mesh update (kernels_mesh.hpp), after the caller's check and volume stages: vertex normals, leaf slots, then the BVH
+// refitted level by level from the deepest up.  gate: a body surface's verdict, read on the device (null: an obstacle, whose caller
+// read the verdict back and comes here only to commit)
+void launch_mesh_commit(const admm_hip_ctx::CollisionMesh &m, const int *gate, hipStream_t st) {
+    using namespace admm_dev;
+    using namespace admm_mesh;
+    const admm_hip_mesh &M = m.mesh;
+    const admm_hip_ctx::MeshUpdate &u = m.upd;
+    const int nt = (int)M.tris.size(), nv = M.nv;
+    hipLaunchKernelGGL(mesh_vertex_normal_kernel, mesh_grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const double *)u.verts, (const int *)u.cid, (const double *)u.fn,
+                       (const int *)u.inc_ptr, (const int *)u.inc, u.vn, gate);
+    hipLaunchKernelGGL(mesh_slot_kernel, mesh_grid(nt), dim3(MESH_BLOCK), 0, st, nt, (const double *)u.verts, (const int *)u.cid, (const int *)u.adj,
+                       (const double *)u.fn, (const double *)u.vn, u.tris, u.nrm, gate);
+    for (int d = M.depth; d >= 0; --d) {
+        const int n = M.lvl_ptr[d + 1] - M.lvl_ptr[d];
+        hipLaunchKernelGGL(mesh_refit_kernel, mesh_grid(n), dim3(MESH_BLOCK), 0, st, (const int *)(u.lvl_nodes + M.lvl_ptr[d]), n, u.nodes, (const Tri *)u.tris, gate);
+    }
+}
+
 // admm_hip_update_collision_mesh after finalize (kernels_mesh.hpp): check, refuse without touching the live arrays, or commit;
 // synchronous on ctx->stream
 int update_mesh_device(admm_hip_ctx *ctx, int id, const double *verts) {
     using namespace admm_dev;
     using namespace admm_mesh;
-    const admm_hip_mesh &M = ctx->meshes[id];
-    const admm_hip_ctx::MeshUpdate &u = ctx->mesh_upd[id];
+    const admm_hip_ctx::CollisionMesh &m = ctx->meshes[id];
+    const admm_hip_mesh &M = m.mesh;
+    const admm_hip_ctx::MeshUpdate &u = m.upd;
     const int nt = (int)M.tris.size(), nv = M.nv, nchunk = (nt + VOL_CHUNK - 1) / VOL_CHUNK;
     const hipStream_t st = ctx->stream;
-    auto grid = [](int n) { return dim3((unsigned)((std::max(n, 1) + MESH_BLOCK - 1) / MESH_BLOCK)); };
     HIPCHK(hipMemcpyAsync(u.verts, verts, sizeof(double) * 3 * (size_t)nv, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ctx->d_mesh_chk, NO_TRI, 2, st));      // bad_tri = bad_vtx = none
-    hipLaunchKernelGGL(mesh_check_kernel, grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, ctx->d_mesh_chk);
-    hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, ctx->d_mesh_chk, (BodyStatus *)nullptr, M.thickness > 0.0 ? 1 : 0);
+    hipLaunchKernelGGL(mesh_check_kernel, mesh_grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, ctx->d_mesh_chk);
+    hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, ctx->d_mesh_chk, (BodyStatus *)nullptr, m.open() ? 1 : 0);
     UpdateCheck chk;
     HIPCHK(hipMemcpyAsync(&chk, ctx->d_mesh_chk, sizeof chk, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     char msg[512];
     if (mesh_refusal(M, verts, chk, msg, (int)sizeof msg)) return fail(ctx, ADMM_ERR_ARG, "collision mesh %d: %s", id, msg);
-    hipLaunchKernelGGL(mesh_vertex_normal_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const double *)u.verts, (const int *)u.cid, (const double *)u.fn,
-                       (const int *)u.inc_ptr, (const int *)u.inc, u.vn, (const int *)nullptr);
-    hipLaunchKernelGGL(mesh_slot_kernel, grid(nt), dim3(MESH_BLOCK), 0, st, nt, (const double *)u.verts, (const int *)u.cid, (const int *)u.adj,
-                       (const double *)u.fn, (const double *)u.vn, u.tris, u.nrm, (const int *)nullptr);
-    for (int d = M.depth; d >= 0; --d) {
-        const int n = M.lvl_ptr[d + 1] - M.lvl_ptr[d];
-        hipLaunchKernelGGL(mesh_refit_kernel, grid(n), dim3(MESH_BLOCK), 0, st, (const int *)(u.lvl_nodes + M.lvl_ptr[d]), n, u.nodes, (const Tri *)u.tris, (const int *)nullptr);
-    }
+    launch_mesh_commit(m, nullptr, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     return ADMM_OK;
@@ -181,27 +128,18 @@ int update_bodies(admm_hip_ctx *ctx) {
     using namespace admm_dev;
     using namespace admm_mesh;
     const hipStream_t st = ctx->stream;
-    auto grid = [](int n) { return dim3((unsigned)((std::max(n, 1) + MESH_BLOCK - 1) / MESH_BLOCK)); };
-    for (size_t id = 0; id < ctx->meshes.size(); ++id) {
-        const admm_hip_ctx::MeshUpdate &u = ctx->mesh_upd[id];
+    for (const admm_hip_ctx::CollisionMesh &m : ctx->meshes) {
+        const admm_hip_ctx::MeshUpdate &u = m.upd;
         if (!u.dnode) continue;
-        const admm_hip_mesh &M = ctx->meshes[id];
-        const int nt = (int)M.tris.size(), nv = M.nv, nchunk = (nt + VOL_CHUNK - 1) / VOL_CHUNK;
+        const int nt = (int)m.mesh.tris.size(), nv = m.mesh.nv, nchunk = (nt + VOL_CHUNK - 1) / VOL_CHUNK;
         const int *gate = &u.status->gate;
-        hipLaunchKernelGGL(mesh_gather_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_x, u.verts);
-        hipLaunchKernelGGL(mesh_check_kernel, grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, u.chk);
-        hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, u.chk, u.status, M.thickness > 0.0 ? 1 : 0);
+        hipLaunchKernelGGL(mesh_gather_kernel, mesh_grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_x, u.verts);
+        hipLaunchKernelGGL(mesh_check_kernel, mesh_grid(std::max(nt, nv)), dim3(MESH_BLOCK), 0, st, nt, nv, (const double *)u.verts, (const int *)u.cid, u.fn, u.part, u.chk);
+        hipLaunchKernelGGL(mesh_volume_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, nchunk, (const double *)u.part, u.chk, u.status, m.open() ? 1 : 0);
         // the vertices' frame-start velocities beside them, through the same map (d_v before the explicit forces); gated like the commit
         // kernels: a refused frame keeps the velocities that went with the last good surface
-        hipLaunchKernelGGL(mesh_gather_vel_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_v, ctx->mesh_move[id].d_vel, gate);
-        hipLaunchKernelGGL(mesh_vertex_normal_kernel, grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const double *)u.verts, (const int *)u.cid, (const double *)u.fn,
-                           (const int *)u.inc_ptr, (const int *)u.inc, u.vn, gate);
-        hipLaunchKernelGGL(mesh_slot_kernel, grid(nt), dim3(MESH_BLOCK), 0, st, nt, (const double *)u.verts, (const int *)u.cid, (const int *)u.adj,
-                           (const double *)u.fn, (const double *)u.vn, u.tris, u.nrm, gate);
-        for (int d = M.depth; d >= 0; --d) {
-            const int n = M.lvl_ptr[d + 1] - M.lvl_ptr[d];
-            hipLaunchKernelGGL(mesh_refit_kernel, grid(n), dim3(MESH_BLOCK), 0, st, (const int *)(u.lvl_nodes + M.lvl_ptr[d]), n, u.nodes, (const Tri *)u.tris, gate);
-        }
+        hipLaunchKernelGGL(mesh_gather_vel_kernel, mesh_grid(nv), dim3(MESH_BLOCK), 0, st, nv, (const int *)u.dnode, (const double *)ctx->d_v, m.d_vel, gate);
+        launch_mesh_commit(m, gate, st);
     }
     HIPCHK(hipGetLastError());
     return ADMM_OK;
@@ -226,7 +164,7 @@ admm_dev::CollisionTables collision_tables(const admm_hip_ctx *ctx) {
 // rank holds the full frame-start x, so every rank latches every node from the same bits.
 int latch_sides(admm_hip_ctx *ctx) {
     using namespace admm_dev;
-    if (!ctx->d_side || !sided_on(ctx)) return ADMM_OK;
+    if (!ctx->d_side || !collision_form(ctx).sided) return ADMM_OK;      // (sided, not form >= 6: a self-colliding body named beside a mesh whose memory no entry names is form 7 without a latch)
     const int n = ctx->n_nodes;
     hipLaunchKernelGGL(collision_side_kernel, dim3((unsigned)((n + LOCAL_BLOCK - 1) / LOCAL_BLOCK)), dim3(LOCAL_BLOCK), 0, ctx->stream, collision_tables(ctx));
     HIPCHK(hipGetLastError());
@@ -234,8 +172,8 @@ int latch_sides(admm_hip_ctx *ctx) {
 }
 
 // a collision batch of a context with mesh obstacles, friction, framed entries or boxes: the kernel of the list's form.  (Forms 4 and up
-// imply meshes; a body surface with a coefficient implies meshes and an entry's motion implies friction_on, so form 2 is reached.)
-void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
+// imply meshes; a body surface with a coefficient implies meshes and an entry's motion counts only beside its coefficient, so form 2 is reached.)
+void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b, int form) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
@@ -243,7 +181,7 @@ void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     const CollisionTables T = collision_tables(ctx);
     const bool mesh = !ctx->meshes.empty();
 #define ADMM_COLLIDE(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, 0, ctx->stream, d, x, T)
-    switch (collision_form(ctx)) {
+    switch (form) {
     case 7: ADMM_COLLIDE(project_collision_bodyself_kernel); break;
     case 6: ADMM_COLLIDE(project_collision_sided_kernel); break;
     case 5: ADMM_COLLIDE(project_collision_self_kernel); break;
@@ -251,7 +189,7 @@ void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
     case 3: if (mesh) ADMM_COLLIDE(project_collision_framed_kernel<true>); else ADMM_COLLIDE(project_collision_framed_kernel<false>); break;
     case 2: if (mesh) ADMM_COLLIDE(project_collision_friction_moving_kernel<true>); else ADMM_COLLIDE(project_collision_friction_moving_kernel<false>); break;
     case 1: if (mesh) ADMM_COLLIDE(project_collision_friction_kernel<true>); else ADMM_COLLIDE(project_collision_friction_kernel<false>); break;
-    default: ADMM_COLLIDE(project_collision_mesh_kernel); break;      // (form 0 in a launch of its own: collision_own_launch, so the context has meshes)
+    default: ADMM_COLLIDE(project_collision_mesh_kernel); break;      // (form 0 in a launch of its own: own_launch, so the context has meshes)
     }
 #undef ADMM_COLLIDE
 }
@@ -259,13 +197,14 @@ void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b) {
 int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
     using namespace admm_dev;
     hipStream_t const st = ctx->stream;
+    const admm_lib::CollisionForm cf = collision_form(ctx);      // the current list, read once for every batch of this call
     // the whole local step in one launch: every batch a segment of project_multi_kernel's grid
     if (only_batch < 0 && !track && ctx->local_multi) {
         MultiBatch mb{}; int blocks = 0;
-        if (build_multi(ctx, mb, blocks)) {
+        if (build_multi(ctx, mb, blocks, cf.own_launch)) {
             hipLaunchKernelGGL(project_multi_kernel, dim3(blocks), dim3(LOCAL_BLOCK), 0, st, mb, (const double *)ctx->d_xcur, (const ShapeTable *)ctx->d_shapes);
-            if (collision_own_launch(ctx))      // the collision batches were left out of the segments: their own launches
-                for (const Batch &b : ctx->batches) if (b.kind == ADMM_KIND_COLLISION && b.n_local > 0) launch_collision_mesh(ctx, b);
+            if (cf.own_launch)      // the collision batches were left out of the segments: their own launches
+                for (const Batch &b : ctx->batches) if (b.kind == ADMM_KIND_COLLISION && b.n_local > 0) launch_collision_mesh(ctx, b, cf.form);
             HIPCHK(hipGetLastError());
             return ADMM_OK;
         }
@@ -312,7 +251,7 @@ int launch_local(admm_hip_ctx *ctx, int only_batch = -1, bool track = false) {
         case ADMM_KIND_TRI_AREA: hipLaunchKernelGGL(project_tri_kernel<1>, grid, block, 0, st, d, x); break;
         case ADMM_KIND_TRI_FUNG: hipLaunchKernelGGL(project_tri_kernel<2>, grid, block, 0, st, d, x); break;
         case ADMM_KIND_COLLISION:
-            if (collision_own_launch(ctx)) launch_collision_mesh(ctx, b);
+            if (cf.own_launch) launch_collision_mesh(ctx, b, cf.form);
             else hipLaunchKernelGGL(project_collision_kernel, grid, block, 0, st, d, x, (const ShapeTable *)ctx->d_shapes);
             break;
         default: return fail(ctx, ADMM_ERR_UNSUPPORTED, "no kernel for kind %d", b.kind);
@@ -511,7 +450,6 @@ int residual_snapshot(admm_hip_ctx *ctx, bool first_iteration) {
     for (Batch &b : ctx->batches) {
         if (!b.n_local || b.kind == ADMM_KIND_GENERIC) continue;
         const int rows = ADMM_KIND_ROWS[b.kind];
-        const size_t bytes = sizeof(double) * (size_t)rows * b.n_local;
         if (b.res_fused) {     // z_prev is the kernel's own previous output; only the frame's warm start has to be put there
             if (first_iteration)
                 hipLaunchKernelGGL(admm_dev::residual_dx_kernel, dim3((b.n_local + admm_dev::RES_BLOCK - 1) / admm_dev::RES_BLOCK), dim3(admm_dev::RES_BLOCK), 0, ctx->stream,
@@ -524,7 +462,6 @@ int residual_snapshot(admm_hip_ctx *ctx, bool first_iteration) {
         if (first_iteration)   // the reference warm-starts curr_z = D * m_x before the loop (System.cpp:43)
             hipLaunchKernelGGL(admm_dev::residual_dx_kernel, dim3((b.n_local + admm_dev::RES_BLOCK - 1) / admm_dev::RES_BLOCK), dim3(admm_dev::RES_BLOCK), 0, ctx->stream,
                                b.n_local, ADMM_KIND_NODES[b.kind], rows / 3, idx_stride(b.kind), b.d_idx, b.d_G, ctx->d_x, b.d_z_prev);
-        (void)bytes;
     }
     return ADMM_OK;
 }

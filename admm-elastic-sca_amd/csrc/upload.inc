@@ -398,7 +398,105 @@ double energy_scale(const Batch &b, int e) {
     return 0.0;
 }
 
-int upload_all(admm_hip_ctx *ctx) {
+// the moving friction kernel's table (kernels_collision.hpp), one entry per mesh: its corner ids, its vertex velocities (null: none in
+// effect), a body surface's coefficient and flag.  Written at finalize and again by every call that changes what moves (abi_setup.inc:
+// push_shapes).  At finalize an obstacle has d_vel == nullptr and has_vel == false and a body surface's buffer has just been allocated,
+// so the one formula gives what finalize needs too.
+std::vector<admm_mesh::MeshMotion> mesh_motion_table(const admm_hip_ctx *ctx) {
+    std::vector<admm_mesh::MeshMotion> mo(ctx->meshes.size());
+    for (size_t mi = 0; mi < mo.size(); ++mi) {
+        const admm_hip_ctx::CollisionMesh &m = ctx->meshes[mi];
+        const bool body = m.body();
+        mo[mi] = admm_mesh::MeshMotion{m.upd.cid, (body || m.has_vel) ? m.d_vel : nullptr, body ? m.body_mu : 0.0, body ? 1 : 0, 0};
+    }
+    return mo;
+}
+
+// the records' part in the device tables, planned on the host (collision_plan.hpp); finalize, once F.iperm stands
+admm_lib::MeshTables plan_context_meshes(const admm_hip_ctx *ctx) {
+    std::vector<admm_lib::MeshPlanInput> in;
+    for (const admm_hip_ctx::CollisionMesh &m : ctx->meshes)
+        in.push_back(admm_lib::MeshPlanInput{m.own_first, m.own_count, m.body_nodes.data(), (int)m.body_nodes.size(), m.self_collision,
+                                             {m.body_self[0], m.body_self[1], m.body_self[2]}, m.side_reach});
+    return admm_lib::plan_mesh_tables(ctx->n_nodes, ctx->F.iperm.data(), in);
+}
+
+// mesh obstacles and surfaces: every mesh's BVH nodes, triangles and pseudo-normals, the table of them the kernels read (d_meshes) and
+// the per-feature tables parallel to it.  A table of the plan that is empty is not uploaded and its pointer stays null, so that a
+// context without the feature holds and launches what it did (launch.inc: collision_tables).
+int upload_meshes(admm_hip_ctx *ctx, const admm_lib::MeshTables &plan) {
+    const int n = ctx->n_nodes;
+    const size_t nm = ctx->meshes.size();
+    ctx->d_body_tag = nullptr; ctx->d_mesh_self = nullptr; ctx->d_self_vid = nullptr; ctx->d_mesh_bself = nullptr; ctx->d_mesh_rest = nullptr;
+    ctx->d_mesh_reach = nullptr; ctx->d_mesh_side_slot = nullptr; ctx->d_mesh_bnd = nullptr; ctx->d_side = nullptr;
+    if (!plan.tag.empty()) TRY(upload(ctx, &ctx->d_body_tag, plan.tag));
+    if (plan.any_sheet_self) TRY(upload(ctx, &ctx->d_mesh_self, plan.self_flag));
+    if (plan.any_sheet_self || plan.any_body_self) TRY(upload(ctx, &ctx->d_self_vid, plan.vid));
+    if (plan.any_body_self) {      // ... with the rest vertices of the body surfaces that collide with themselves
+        std::vector<const double *> rest(nm, nullptr);
+        for (size_t mi = 0; mi < nm; ++mi) {
+            if (!(ctx->meshes[mi].body_self[0] > 0.0)) continue;
+            double *rv = nullptr;
+            TRY(upload(ctx, &rv, ctx->meshes[mi].rest));
+            rest[mi] = rv;
+        }
+        TRY(upload(ctx, &ctx->d_mesh_bself, plan.body_self)); TRY(upload(ctx, &ctx->d_mesh_rest, rest));
+    }
+    std::vector<admm_mesh::MeshDev> md;
+    std::vector<double> thick(nm);
+    for (size_t mi = 0; mi < nm; ++mi) {
+        admm_hip_ctx::CollisionMesh &m = ctx->meshes[mi];
+        const admm_hip_mesh &M = m.mesh;
+        admm_mesh::MeshDev d{};
+        d.owner = plan.owner[mi];
+        admm_mesh::Node *nd; admm_mesh::Tri *tr; admm_mesh::Nrm *nr;
+        TRY(upload(ctx, &nd, M.nodes)); TRY(upload(ctx, &tr, M.tris)); TRY(upload(ctx, &nr, M.nrm));
+        d.nodes = nd; d.tris = tr; d.nrm = nr; d.n_nodes = (int)M.nodes.size(); d.n_tris = (int)M.tris.size();
+        md.push_back(d);
+        thick[mi] = M.thickness;
+        // what admm_hip_update_collision_mesh needs (kernels_mesh.hpp): neither it nor step allocates
+        admm_hip_ctx::MeshUpdate u{};
+        u.nodes = nd; u.tris = tr; u.nrm = nr;
+        const size_t nt = M.tris.size();
+        TRY(dalloc(ctx, &u.verts, 3 * (size_t)M.nv)); TRY(dalloc(ctx, &u.fn, 3 * nt)); TRY(dalloc(ctx, &u.vn, 3 * (size_t)M.nv));
+        TRY(dalloc(ctx, &u.part, (nt + admm_mesh::VOL_CHUNK - 1) / admm_mesh::VOL_CHUNK));
+        TRY(upload(ctx, &u.cid, M.cid)); TRY(upload(ctx, &u.adj, M.adj)); TRY(upload(ctx, &u.inc_ptr, M.inc_ptr)); TRY(upload(ctx, &u.inc, M.inc));
+        TRY(upload(ctx, &u.lvl_nodes, M.lvl_nodes));
+        // the moving friction kernel's velocities: an obstacle's buffer is allocated by admm_hip_set_collision_mesh_velocity
+        m.d_vel = nullptr; m.has_vel = false;
+        if (m.body()) {      // a body surface: its vertices' device node ids, its own check (re-armed by the device) and status, and its velocity buffer, which lives from here on (zero: v at finalize)
+            std::vector<int> dn(m.body_nodes.size());
+            for (size_t k = 0; k < dn.size(); ++k) dn[k] = ctx->F.iperm[m.body_nodes[k]];
+            TRY(upload(ctx, &u.dnode, dn));
+            TRY(upload(ctx, &u.chk, std::vector<admm_mesh::UpdateCheck>(1, admm_mesh::UpdateCheck{admm_mesh::NO_TRI, admm_mesh::NO_TRI, 0.0})));
+            TRY(upload(ctx, &u.status, std::vector<admm_mesh::BodyStatus>(1, admm_mesh::BodyStatus{0, 0, -1, 0})));
+            TRY(dalloc(ctx, &m.d_vel, 3 * (size_t)M.nv));
+            HIPCHK(hipMemset(m.d_vel, 0, sizeof(double) * 3 * (size_t)M.nv));
+        }
+        m.upd = u;
+    }
+    TRY(upload(ctx, &ctx->d_mesh_motion, mesh_motion_table(ctx)));
+    TRY(upload(ctx, &ctx->d_mesh_thick, thick));
+    TRY(upload(ctx, &ctx->d_meshes, md));
+    TRY(dalloc(ctx, &ctx->d_mesh_chk, 1));
+    if (plan.n_side_rows > 0) {      // side memory: the reach, the row of sides and the boundary table of every mesh, and the sides themselves (zero)
+        std::vector<double> reach(nm, 0.0);
+        std::vector<const int *> bnd(nm, nullptr);
+        for (size_t mi = 0; mi < nm; ++mi) {
+            if (plan.side_row[mi] < 0) continue;
+            reach[mi] = ctx->meshes[mi].side_reach;
+            int *b = nullptr;
+            TRY(upload(ctx, &b, ctx->meshes[mi].mesh.bnd));
+            bnd[mi] = b;
+        }
+        TRY(upload(ctx, &ctx->d_mesh_reach, reach)); TRY(upload(ctx, &ctx->d_mesh_side_slot, plan.side_row)); TRY(upload(ctx, &ctx->d_mesh_bnd, bnd));
+        TRY(dalloc(ctx, &ctx->d_side, (size_t)plan.n_side_rows * (size_t)n));
+        HIPCHK(hipMemset(ctx->d_side, 0, sizeof(int32_t) * (size_t)plan.n_side_rows * (size_t)n));
+    }
+    return ADMM_OK;
+}
+
+int upload_all(admm_hip_ctx *ctx, const admm_lib::MeshTables &plan) {
     const double t0 = now_s();
     const int n = ctx->n_nodes;
     const Factor &F = ctx->F;
@@ -636,122 +734,7 @@ int upload_all(admm_hip_ctx *ctx) {
     // collision shapes and the general explicit forces (index lists in factor order)
     TRY(dalloc(ctx, &ctx->d_shapes, 1));
     HIPCHK(hipMemcpy(ctx->d_shapes, &ctx->shapes, sizeof(admm_dev::ShapeTable), hipMemcpyHostToDevice));
-    if (!ctx->meshes.empty()) {      // mesh obstacles: BVH nodes, triangles, pseudo-normals, and the table of them the kernel reads
-        std::vector<admm_mesh::MeshDev> md;
-        ctx->mesh_upd.clear();
-        // owners: one group per distinct node range (ranges overlap only when equal: admm_hip_set_collision_mesh_owner), the group of
-        // every node in device order -- uploaded only when some mesh has an owner, so that other contexts launch as before
-        std::vector<std::pair<int, int> > groups;
-        std::vector<int> owner(ctx->meshes.size(), -1);
-        for (size_t i = 0; i < ctx->meshes.size(); ++i) {
-            const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
-            if (!R.own_count) continue;
-            size_t g = 0;
-            while (g < groups.size() && groups[g] != std::make_pair(R.own_first, R.own_count)) ++g;
-            if (g == groups.size()) groups.push_back(std::make_pair(R.own_first, R.own_count));
-            owner[i] = (int)g;
-        }
-        ctx->d_body_tag = nullptr;
-        if (!groups.empty()) {
-            std::vector<int> tag((size_t)n, -1);
-            for (size_t g = 0; g < groups.size(); ++g)
-                for (int k = groups[g].first; k < groups[g].first + groups[g].second; ++k) tag[F.iperm[k]] = (int)g;
-            TRY(upload(ctx, &ctx->d_body_tag, tag));
-        }
-        // sheets that collide with themselves: the per-mesh flag and every node's vertex id on its sheet, in this rank's device order --
-        // uploaded only when there is one, so that other contexts hold and launch what they did
-        ctx->d_mesh_self = nullptr; ctx->d_self_vid = nullptr;
-        {
-            std::vector<int> flag(ctx->meshes.size(), 0), vid((size_t)n, -1);
-            bool any = false, any_body = false;
-            for (size_t i = 0; i < ctx->meshes.size(); ++i) {
-                const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
-                const bool bs = R.body_self[0] > 0.0;      // a body surface that collides with itself: the same vertex ids (finalize: one such surface per node range)
-                if (!R.self_collision && !bs) continue;
-                if (R.self_collision) { any = true; flag[i] = 1; } else any_body = true;
-                for (size_t k = 0; k < R.body_nodes.size(); ++k) vid[F.iperm[R.body_nodes[k]]] = (int)k;
-            }
-            if (any) TRY(upload(ctx, &ctx->d_mesh_self, flag));
-            if (any || any_body) TRY(upload(ctx, &ctx->d_self_vid, vid));
-            // ... and the lengths and rest vertices of the body surfaces among them, only where there is one
-            ctx->d_mesh_bself = nullptr; ctx->d_mesh_rest = nullptr;
-            if (any_body) {
-                std::vector<double> len(3 * ctx->meshes.size(), 0.0);
-                std::vector<const double *> rest(ctx->meshes.size(), nullptr);
-                for (size_t i = 0; i < ctx->meshes.size(); ++i) {
-                    const admm_hip_ctx::MeshRole &R = ctx->mesh_role[i];
-                    if (!(R.body_self[0] > 0.0)) continue;
-                    for (int j = 0; j < 3; ++j) len[3 * i + j] = R.body_self[j];
-                    double *rv = nullptr;
-                    TRY(upload(ctx, &rv, R.rest));
-                    rest[i] = rv;
-                }
-                TRY(upload(ctx, &ctx->d_mesh_bself, len)); TRY(upload(ctx, &ctx->d_mesh_rest, rest));
-            }
-        }
-        for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) {
-            const admm_hip_mesh &M = ctx->meshes[mi];
-            admm_mesh::MeshDev d{};
-            d.owner = owner[mi];
-            admm_mesh::Node *nd; admm_mesh::Tri *tr; admm_mesh::Nrm *nr;
-            TRY(upload(ctx, &nd, M.nodes)); TRY(upload(ctx, &tr, M.tris)); TRY(upload(ctx, &nr, M.nrm));
-            d.nodes = nd; d.tris = tr; d.nrm = nr; d.n_nodes = (int)M.nodes.size(); d.n_tris = (int)M.tris.size();
-            md.push_back(d);
-            // what admm_hip_update_collision_mesh needs (kernels_mesh.hpp): neither it nor step allocates
-            admm_hip_ctx::MeshUpdate u{};
-            u.nodes = nd; u.tris = tr; u.nrm = nr;
-            const size_t nt = M.tris.size();
-            TRY(dalloc(ctx, &u.verts, 3 * (size_t)M.nv)); TRY(dalloc(ctx, &u.fn, 3 * nt)); TRY(dalloc(ctx, &u.vn, 3 * (size_t)M.nv));
-            TRY(dalloc(ctx, &u.part, (nt + admm_mesh::VOL_CHUNK - 1) / admm_mesh::VOL_CHUNK));
-            TRY(upload(ctx, &u.cid, M.cid)); TRY(upload(ctx, &u.adj, M.adj)); TRY(upload(ctx, &u.inc_ptr, M.inc_ptr)); TRY(upload(ctx, &u.inc, M.inc));
-            TRY(upload(ctx, &u.lvl_nodes, M.lvl_nodes));
-            const std::vector<int> &bn = ctx->mesh_role[mi].body_nodes;
-            if (!bn.empty()) {      // a body surface: its vertices' device node ids, its own check (re-armed by the device) and status
-                std::vector<int> dn(bn.size());
-                for (size_t k = 0; k < bn.size(); ++k) dn[k] = F.iperm[bn[k]];
-                TRY(upload(ctx, &u.dnode, dn));
-                TRY(upload(ctx, &u.chk, std::vector<admm_mesh::UpdateCheck>(1, admm_mesh::UpdateCheck{admm_mesh::NO_TRI, admm_mesh::NO_TRI, 0.0})));
-                TRY(upload(ctx, &u.status, std::vector<admm_mesh::BodyStatus>(1, admm_mesh::BodyStatus{0, 0, -1, 0})));
-            }
-            ctx->mesh_upd.push_back(u);
-        }
-        // the moving friction kernel's table: a body surface's velocity buffer lives from here on (zero: v at finalize); an obstacle's is
-        // allocated by admm_hip_set_collision_mesh_velocity
-        std::vector<admm_mesh::MeshMotion> mo(ctx->meshes.size());
-        for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) {
-            admm_hip_ctx::MeshMove &mv = ctx->mesh_move[mi];
-            const bool body = !ctx->mesh_role[mi].body_nodes.empty();
-            mv.d_vel = nullptr; mv.has_vel = false;
-            if (body) {
-                TRY(dalloc(ctx, &mv.d_vel, 3 * (size_t)ctx->meshes[mi].nv));
-                HIPCHK(hipMemset(mv.d_vel, 0, sizeof(double) * 3 * (size_t)ctx->meshes[mi].nv));
-            }
-            mo[mi] = admm_mesh::MeshMotion{ctx->mesh_upd[mi].cid, mv.d_vel, body ? mv.body_mu : 0.0, body ? 1 : 0, 0};
-        }
-        TRY(upload(ctx, &ctx->d_mesh_motion, mo));
-        std::vector<double> thick(ctx->meshes.size());
-        for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) thick[mi] = ctx->meshes[mi].thickness;
-        TRY(upload(ctx, &ctx->d_mesh_thick, thick));
-        TRY(upload(ctx, &ctx->d_meshes, md));
-        TRY(dalloc(ctx, &ctx->d_mesh_chk, 1));
-        // side memory: the reach, the row of sides and the boundary table of every mesh, and the sides themselves (zero) -- allocated only
-        // when a mesh has memory (side_slot and n_side_slots were set by finalize), so that other contexts hold and launch what they did
-        ctx->d_mesh_reach = nullptr; ctx->d_mesh_side_slot = nullptr; ctx->d_mesh_bnd = nullptr; ctx->d_side = nullptr;
-        if (ctx->n_side_slots > 0) {
-            std::vector<double> reach(ctx->meshes.size(), 0.0);
-            std::vector<const int *> bnd(ctx->meshes.size(), nullptr);
-            for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) {
-                if (ctx->side_slot[mi] < 0) continue;
-                reach[mi] = ctx->mesh_role[mi].side_reach;
-                int *b = nullptr;
-                TRY(upload(ctx, &b, ctx->meshes[mi].bnd));
-                bnd[mi] = b;
-            }
-            TRY(upload(ctx, &ctx->d_mesh_reach, reach)); TRY(upload(ctx, &ctx->d_mesh_side_slot, ctx->side_slot)); TRY(upload(ctx, &ctx->d_mesh_bnd, bnd));
-            TRY(dalloc(ctx, &ctx->d_side, (size_t)ctx->n_side_slots * (size_t)n));
-            HIPCHK(hipMemset(ctx->d_side, 0, sizeof(int32_t) * (size_t)ctx->n_side_slots * (size_t)n));
-        }
-    }
+    if (!ctx->meshes.empty()) TRY(upload_meshes(ctx, plan));
     for (Explicit &E : ctx->explicits) {
         std::vector<int> pidx(E.idx.size());
         for (size_t i = 0; i < E.idx.size(); ++i) pidx[i] = F.iperm[E.idx[i]];
