@@ -12,27 +12,11 @@ import subprocess
 import numpy as np
 import pytest
 
-from checkers import KIND, KIND_NODES, KIND_ROWS, Oracle
+from anderson_cases import (DT, LD, U, _frame_start_z, _pkg, _same_bits, build_system, check_log_invariants, check_rule_restated, checkpoint,
+                            flat_state, flat_weights, full_state, lattice_scene, needs_ld, restore)
+from checkers import KIND
 
 gpu = pytest.mark.gpu
-LD = np.longdouble
-U = 2.0 ** -53
-needs_ld = pytest.mark.skipif(np.finfo(LD).eps > 2.0 ** -63, reason="np.longdouble has no extended precision on this host")
-DT = 0.04
-
-
-def _pkg():
-    from __graft_entry__ import load_package
-    return load_package()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same_bits(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -137,18 +121,6 @@ def test_cpp_mirror_compiles(pkg):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # scenes
 # ---------------------------------------------------------------------------------------------------------------------------------
-def build_system(X, M3, forces, shapes=None, device_id=0):
-    s = _pkg().System(device_id=device_id)
-    s.set_timestep(DT)
-    s.add_nodes(np.asarray(X).ravel(), M3)
-    for kind, idx, par in forces:
-        s.add_forces(KIND[kind], idx, par)
-    if shapes is not None:
-        s.set_collision_shapes(*shapes)
-    s.add_gravity([0.0, -9.8, 0.0])
-    return s
-
-
 def mixed_scene():
     """a 2 x 2 x 4-cell TET_LINEAR bar along z, anchored at its k = 0 face, a few springs across it, and a floor some nodes are below:
     every prox is exact (no truncated minimiser).  -> X (started bent down through the floor), M3, forces, shapes"""
@@ -178,91 +150,12 @@ def mixed_system():
     return s, forces
 
 
-def lattice_scene(stiffness=1e4):
-    """the issue's spring lattice: 3 x 3 x 10 nodes, axis and diagonal springs, the bottom layer anchored, started bent"""
-    nx, ny, nl, h = 3, 3, 10, 0.1
-    idx = lambda i, j, l: (l * ny + j) * nx + i      # noqa: E731
-    X = np.array([[i * h, l * h, j * h] for l in range(nl) for j in range(ny) for i in range(nx)], dtype=np.float64)
-    springs = []
-    for l in range(nl):
-        for j in range(ny):
-            for i in range(nx):
-                for di, dj, dl in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, -1, 0), (1, 0, -1), (0, 1, -1)):
-                    i2, j2, l2 = i + di, j + dj, l + dl
-                    if 0 <= i2 < nx and 0 <= j2 < ny and 0 <= l2 < nl:
-                        springs.append((idx(i, j, l), idx(i2, j2, l2)))
-    anchors = np.array([idx(i, j, 0) for j in range(ny) for i in range(nx)], np.int32)
-    Xb = X.copy()
-    Xb[:, 0] += 0.3 * (X[:, 1] / X[:, 1].max()) ** 2
-    forces = [("SPRING", np.array(springs, np.int32), [stiffness]), ("ANCHOR", anchors, [-1.0, 1.0])]
-    return X, Xb, np.full(3 * X.shape[0], 0.1), forces
-
-
 def lattice_system(stiffness=1e4):
     X, Xb, M3, forces = lattice_scene(stiffness)
     s = build_system(X, M3, forces)
     s.initialize()
     s.m_x = Xb.ravel()
     return s, forces
-
-
-def checkpoint(s, forces):
-    """x, v, every batch's u and warm start: what DESIGN lists (the scenes here have no sides)"""
-    return dict(x=s.m_x, v=s.m_v, local=[s.read_local(b) for b in range(len(forces))])
-
-
-def restore(s, forces, cp):
-    s.m_x = cp["x"]; s.m_v = cp["v"]
-    for b, (kind, _, _) in enumerate(forces):
-        loc = cp["local"][b]
-        s.write_local(b, u=loc["u"], state=loc["state"] if loc["state"].shape[1] == 4 else None)
-
-
-def full_state(s, forces):
-    out = [s.m_x, s.m_v]
-    for b in range(len(forces)):
-        loc = s.read_local(b)
-        out += [loc["u"], loc["z"]]
-    return out
-
-
-def flat_state(s, forces, default=False):
-    """(z, u) of all batches as one vector"""
-    parts = []
-    for b in range(len(forces)):
-        loc = s.acceleration_default(b) if default else s.read_local(b)
-        parts += [loc["z"].ravel(), loc["u"].ravel()]
-    return np.concatenate(parts)
-
-
-def flat_weights(s, forces):
-    parts = []
-    for b, (kind, _, _) in enumerate(forces):
-        w = s.read_rest(b)["weight"]
-        w2 = np.repeat(w * w, KIND_ROWS[KIND[kind]])
-        parts += [w2, w2]
-    return np.concatenate(parts)
-
-
-def check_log_invariants(log, window):
-    """what holds in every log: rho of accepted iterations falls strictly between resets, the decisions follow from the logged rhos
-    exactly, m_used restarts at 0 after a reset and grows by one per accepted iteration up to the window.  -> number of resets"""
-    resets, armed, rho_acc, entries = 0, False, None, 0
-    for k, r in enumerate(log):
-        accept = (not armed) or r["rho"] < rho_acc
-        assert r["accepted"] == accept, (k, r["rho"], rho_acc)
-        if accept:
-            if armed:
-                assert r["rho"] < rho_acc
-            entries += 1
-            assert r["m_used"] == min(entries - 1, window), (k, r["m_used"], entries)
-            assert r["extrapolated"] == (r["m_used"] >= 1 and k + 1 < len(log) and not r["solve_failed"]) or k + 1 == len(log), k
-            armed, rho_acc = True, r["rho"]
-        else:
-            resets += 1
-            assert r["m_used"] == 0 and not r["extrapolated"]
-            armed, entries = False, 0
-    return resets
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -328,27 +221,6 @@ def test_three_iterations_extrapolate_once(pkg):
     assert np.isfinite(acc.m_x).all() and np.abs(acc.m_x - plain.m_x).max() < 0.05
 
 
-def _frame_start_z(forces, X, M3, x):
-    """D x of the frame-start x in the flat layout's z parts, in long double rounded to double (the CPU oracle's selector rows)"""
-    o = Oracle(); o.settings(DT, 1)
-    o.add_nodes(np.asarray(X).ravel(), M3)
-    for kind, idx, par in forces:
-        o.add_forces(KIND[kind], idx, par)
-    o.add_gravity([0, -9.8, 0])
-    assert o.initialize()
-    rr, cc, vv = o.D_triplets()
-    Dx = np.zeros(o.rows, dtype=LD)
-    np.add.at(Dx, rr, vv.astype(LD) * x.astype(LD)[cc])
-    gi = o.global_idx()
-    out, f0 = [], 0
-    for kind, idx, _ in forces:
-        n = np.asarray(idx).reshape(-1, KIND_NODES[KIND[kind]]).shape[0]
-        rows = KIND_ROWS[KIND[kind]]
-        out.append(np.concatenate([np.asarray(Dx[gi[f0 + e]:gi[f0 + e] + rows], dtype=np.float64) for e in range(n)]))
-        f0 += n
-    return out
-
-
 @gpu
 @needs_ld
 def test_the_rule_restated(pkg):
@@ -360,87 +232,7 @@ def test_the_rule_restated(pkg):
     s, _ = mixed_system()
     s.step(4); s.step(4)      # a state with u, v and contacts
     cp = checkpoint(s, forces)
-    s.set_acceleration(M)
-    w2 = flat_weights(s, forces)
-    logs, live, deflt = {}, {}, {}
-    for k in range(1, K + 1):
-        restore(s, forces, cp)
-        s.step(k)
-        logs[k] = s.acceleration_log(); live[k] = flat_state(s, forces); deflt[k] = flat_state(s, forces, default=True)
-        assert len(logs[k]) == k
-    # every run is a bitwise prefix of the next (the last iteration solves too; only its `extrapolated` differs)
-    for k in range(1, K):
-        for a, b in zip(logs[k], logs[k + 1][:k]):
-            for key in ("rho", "theta", "gram", "rhs"):
-                assert _same_bits(a[key], b[key]), (k, key)
-            assert (a["accepted"], a["m_used"], a["solve_failed"]) == (b["accepted"], b["m_used"], b["solve_failed"])
-        assert not logs[k][-1]["extrapolated"]
-    log = logs[K]
-    # s_out_k of the iterations that are not the last: a tolerance that everything meets, tested after iteration k only
-    sout = {K: live[K]}
-    for k in range(1, K):
-        restore(s, forces, cp)
-        s.set_tolerance(1e300, 1e300, k)
-        s.step(K)
-        lg = s.acceleration_log()
-        assert len(lg) == k
-        for a, b in zip(lg, log[:k]):      # tracking changes nothing the rule sees
-            assert _same_bits(a["rho"], b["rho"]) and _same_bits(a["theta"], b["theta"]) and a["extrapolated"] == b["extrapolated"]
-        sout[k] = flat_state(s, forces)
-        s.set_tolerance(0.0, 0.0, 1)
-    check_log_invariants(log, M)
-    # s_in of iteration 1: z = D x, u as restored
-    z0 = _frame_start_z(forces, X, M3, cp["x"])
-    s_in = np.concatenate([p for b in range(len(forces)) for p in (z0[b], cp["local"][b]["u"].ravel())])
-    hist = []      # (g, f) of the accepted iterations since the last reset, at most M + 1
-    n_ex = 0
-    for k in range(1, K + 1):
-        r = log[k - 1]
-        if not r["accepted"]:
-            assert _same_bits(sout[k], deflt[k]) and _same_bits(live[k], deflt[k])      # s_out = s_def, bitwise
-            hist = []
-            s_in = sout[k]
-            continue
-        g = deflt[k]      # iteration k was the last of run k and accepted: s_def = g_k
-        assert _same_bits(live[k], g)      # ... and the last iteration left it in z, u
-        f = g - s_in      # (the device forms f in double too: one rounding, the same one)
-        terms = w2.astype(LD) * (f.astype(LD) * f.astype(LD))
-        rho = float(np.sum(terms)); bound = terms.size * U * float(np.sum(np.abs(terms)))
-        print("iteration %d: rho %.17g logged %.17g |diff| %.3e bound %.3e" % (k, rho, r["rho"], abs(rho - r["rho"]), bound))
-        assert abs(rho - r["rho"]) <= bound, (k, rho, r["rho"], bound)
-        hist.append((g, f)); hist = hist[-(M + 1):]
-        mk = len(hist) - 1
-        assert r["m_used"] == mk
-        if mk == 0:
-            assert _same_bits(sout[k], g)
-            s_in = sout[k]
-            continue
-        dF = [hist[j + 1][1] - hist[j][1] for j in range(mk)]      # double differences, as on the device
-        dG = [hist[j + 1][0] - hist[j][0] for j in range(mk)]
-        for a in range(mk):
-            t = w2.astype(LD) * (dF[a].astype(LD) * f.astype(LD))
-            ref, bnd = float(np.sum(t)), t.size * U * float(np.sum(np.abs(t)))
-            assert abs(ref - r["rhs"][a]) <= bnd, (k, a, ref, r["rhs"][a], bnd)
-            for b in range(mk):
-                t = w2.astype(LD) * (dF[a].astype(LD) * dF[b].astype(LD))
-                ref, bnd = float(np.sum(t)), t.size * U * float(np.sum(np.abs(t)))
-                assert abs(ref - r["gram"][a, b]) <= bnd, (k, a, b, ref, r["gram"][a, b], bnd)
-                assert _same_bits(r["gram"][a, b], r["gram"][b, a])
-        assert not r["solve_failed"]
-        assert _same_bits(r["theta"], pkg.acceleration_query(r["gram"], r["rhs"])), k      # the host twin, bitwise
-        if k == K:
-            assert not r["extrapolated"]
-            continue
-        assert r["extrapolated"]
-        n_ex += 1
-        th = r["theta"]
-        ref = g.astype(LD) - sum(LD(th[j]) * dG[j].astype(LD) for j in range(mk))
-        bnd = (mk + 2) * U * (np.abs(g) + sum(abs(th[j]) * np.abs(dG[j]) for j in range(mk)))
-        err = np.abs(np.asarray(sout[k], dtype=LD) - ref).astype(np.float64)
-        print("iteration %d: m_k %d theta %s  max |s_out - ref| / bound %.3f" % (k, mk, th, float(np.max(err / np.maximum(bnd, 1e-300)))))
-        assert (err <= bnd).all(), (k, float(err.max()))
-        s_in = sout[k]
-    assert n_ex >= 3 and max(r["m_used"] for r in log) == M      # the window filled
+    check_rule_restated(s, X, M3, forces, cp, K, M)
 
 
 _LATTICE = {}
