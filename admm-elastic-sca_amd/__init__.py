@@ -21,6 +21,9 @@ LIB_PATH = os.path.join(HERE, "libadmm_hip.so")
 
 KIND = dict(ANCHOR=0, SPRING=1, TET_LINEAR=2, TET_VOLUME=3, TET_NH=4, TET_STVK=5, TRI_STRAIN=6, BEND=7, COLLISION=8, TRI_AREA=9, TRI_FUNG=10)
 SHARD = dict(contiguous=0, subtree=1)
+# System.debug_math: op -> doubles per record (in, out); the ops' names
+DEBUG_MATH_SHAPES = {0: (1, 1), 1: (1, 1), 2: (1, 1), 3: (1, 1), 4: (1, 1), 5: (2, 1), 6: (9, 21), 7: (9, 21), 8: (6, 12), 9: (12, 9)}
+DEBUG_MATH_OP = dict(log=0, exp=1, sqrt_in_1_4=2, sqrt_ge_1=3, rcp_in_1_2=4, eig_hypot=5, svd3=6, oriented_svd=7, svd32=8, mt_cstep=9)
 KIND_NODES = [1, 2, 4, 4, 4, 4, 3, 4, 1, 3, 3]
 KIND_ROWS = [3, 3, 9, 9, 9, 9, 6, 9, 3, 6, 6]
 KIND_PARAMS = [2, 1, 1, 3, 3, 3, 4, 1, 1, 4, 3]
@@ -1247,10 +1250,14 @@ class System:
         return y
 
     def debug_math(self, op, x):
-        """the device's log (op 0) / exp (op 1) on an array (parity tests)"""
+        """one function of csrc/local_math.hpp as the device executes it, one lane per record (parity tests; include/admm_hip.h
+        admm_hip_debug_math lists the ops): x (n, IN) -> (n, OUT); record i runs on lane i % 64 of wave i / 64"""
+        n_in, n_out = DEBUG_MATH_SHAPES[int(op)]
         x = np.ascontiguousarray(x, dtype=np.float64)
-        y = np.empty_like(x)
-        self._chk(self.L.admm_hip_debug_math(self.h, int(op), x.size, _d(x), _d(y)))
+        if x.ndim != 2 or x.shape[1] != n_in:
+            raise ValueError("debug_math op %d takes an (n, %d) array, got %s" % (op, n_in, x.shape))
+        y = np.empty((x.shape[0], n_out))
+        self._chk(self.L.admm_hip_debug_math(self.h, int(op), x.shape[0], _d(x), _d(y)))
         return y
 
     def debug_gemm(self, A, B, Cm, m, n, k, flags=0, alpha=1.0, beta=0.0):

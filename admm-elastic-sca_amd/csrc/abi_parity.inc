@@ -153,10 +153,59 @@ int admm_hip_debug_panel_solve_host(admm_hip_ctx *ctx, const double *b, double *
     return ADMM_OK;
 }
 
+// Parity-test hook: ONE function of local_math.hpp per launch, as the device build of the header executes it, one lane per record.
+// What the tests rely on (tests/test_device_math.py composes its waves from it): workgroups of 256 threads in one dimension, so record i
+// runs on lane i % 64 of wave i / 64; a lane beyond n returns before any of the function's code (it is not in a __ballot inside it); op is
+// a kernel argument, hence wave-uniform -- the switch below is a scalar branch and a launch runs one function.
+// Records are element-major: in [n][ADMM_DEBUG_MATH_IN[op]], out [n][ADMM_DEBUG_MATH_OUT[op]]; matrices in column-major order
+// (m00 m10 m20 m01 ...), the mt_cstep records as tests/host_math_shim.cpp hm_cstep_forms lays them out.
+static const int ADMM_DEBUG_MATH_OPS = 10;
+static const int ADMM_DEBUG_MATH_IN[ADMM_DEBUG_MATH_OPS] = {1, 1, 1, 1, 1, 2, 9, 9, 6, 12};
+static const int ADMM_DEBUG_MATH_OUT[ADMM_DEBUG_MATH_OPS] = {1, 1, 1, 1, 1, 1, 21, 21, 12, 9};
 namespace admm_dev {
-__global__ void debug_math_kernel(int op, int64_t n, const double *__restrict__ in, double *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = op == 0 ? admm_log(in[i]) : admm_exp(in[i]);
+__device__ __forceinline__ Mat3 debug_load3(const double *f) { Mat3 m; m.m00 = f[0]; m.m10 = f[1]; m.m20 = f[2]; m.m01 = f[3]; m.m11 = f[4]; m.m21 = f[5]; m.m02 = f[6]; m.m12 = f[7]; m.m22 = f[8]; return m; }
+__device__ __forceinline__ void debug_store3(const Mat3 &m, double *f) { f[0] = m.m00; f[1] = m.m10; f[2] = m.m20; f[3] = m.m01; f[4] = m.m11; f[5] = m.m21; f[6] = m.m02; f[7] = m.m12; f[8] = m.m22; }
+__global__ void __launch_bounds__(256) debug_math_kernel(int op, int64_t n, const double *__restrict__ in, double *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    switch (op) {
+    case 0: out[i] = admm_log(in[i]); break;
+    case 1: out[i] = admm_exp(in[i]); break;
+    case 2: out[i] = sqrt_in_1_4(in[i]); break;
+    case 3: out[i] = sqrt_ge_1(in[i]); break;
+    case 4: out[i] = rcp_in_1_2(in[i]); break;
+    case 5: out[i] = eig_hypot(in[2 * i], in[2 * i + 1]); break;
+    case 6: case 7: {
+        Mat3 U, V; double s0, s1, s2;
+        if (op == 6) svd3(debug_load3(in + 9 * i), U, s0, s1, s2, V);
+        else oriented_svd(debug_load3(in + 9 * i), s0, s1, s2, U, V);
+        double *o = out + 21 * i;
+        debug_store3(U, o); o[9] = s0; o[10] = s1; o[11] = s2; debug_store3(V, o + 12);
+        break;
+    }
+    case 8: {
+        double F[6], U2[6], V[4], s0, s1;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) F[k] = in[6 * i + k];
+        svd32(F, U2, s0, s1, V);
+        double *o = out + 12 * i;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o[k] = U2[k];
+        o[6] = s0; o[7] = s1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[8 + k] = V[k];
+        break;
+    }
+    default: {      // 9: in [stx fx dx sty fy dy stp fp dp stpmin stpmax brackt], out [stx fx dx sty fy dy stp brackt info]
+        const double *a = in + 12 * i;
+        double stx = a[0], fx = a[1], dx = a[2], sty = a[3], fy = a[4], dy = a[5], stp = a[6];
+        bool brackt = a[11] != 0.0; int info = 0;
+        mt_cstep(stx, fx, dx, sty, fy, dy, stp, a[7], a[8], brackt, a[9], a[10], info);
+        double *o = out + 9 * i;
+        o[0] = stx; o[1] = fx; o[2] = dx; o[3] = sty; o[4] = fy; o[5] = dy; o[6] = stp; o[7] = brackt; o[8] = info;
+        break;
+    }
+    }
 }
 } // namespace admm_dev
 int admm_hip_debug_gemm(admm_hip_ctx *ctx, int m, int n, int k, int lda, int ldb, int ldc, int flags, double alpha, double beta,
@@ -192,17 +241,18 @@ int admm_hip_debug_potrf_inv(admm_hip_ctx *ctx, int w, int ld, double *blk, doub
 }
 int admm_hip_debug_math(admm_hip_ctx *ctx, int op, int64_t n, const double *in, double *out) {
     TRY(require_device(ctx));
-    if (!in || !out || n < 0 || op < 0 || op > 1) return ADMM_ERR_ARG;
+    if (!in || !out || n < 0 || n > (int64_t)1 << 30 || op < 0 || op >= ADMM_DEBUG_MATH_OPS) return ADMM_ERR_ARG;
     if (n == 0) return ADMM_OK;
     HIPCHK(hipSetDevice(ctx->device_id));
+    const size_t sz_in = sizeof(double) * (size_t)n * ADMM_DEBUG_MATH_IN[op], sz_out = sizeof(double) * (size_t)n * ADMM_DEBUG_MATH_OUT[op];
     double *d_in = nullptr, *d_out = nullptr;
-    HIPCHK(hipMalloc(&d_in, sizeof(double) * n)); 
-    if (hipMalloc(&d_out, sizeof(double) * n) != hipSuccess) { (void)hipFree(d_in); return fail(ctx, ADMM_ERR_HIP, "hipMalloc failed"); }
+    HIPCHK(hipMalloc(&d_in, sz_in));
+    if (hipMalloc(&d_out, sz_out) != hipSuccess) { (void)hipFree(d_in); return fail(ctx, ADMM_ERR_HIP, "hipMalloc failed"); }
     int rc = ADMM_OK;
-    if (hipMemcpy(d_in, in, sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) rc = ADMM_ERR_HIP;
+    if (hipMemcpy(d_in, in, sz_in, hipMemcpyHostToDevice) != hipSuccess) rc = ADMM_ERR_HIP;
     if (!rc) {
         hipLaunchKernelGGL(admm_dev::debug_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, n, (const double *)d_in, d_out);
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess) rc = ADMM_ERR_HIP;
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(out, d_out, sz_out, hipMemcpyDeviceToHost) != hipSuccess) rc = ADMM_ERR_HIP;
     }
     (void)hipFree(d_in); (void)hipFree(d_out);
     return rc ? fail(ctx, rc, "debug_math failed") : ADMM_OK;

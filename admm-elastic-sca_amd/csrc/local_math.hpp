@@ -154,6 +154,10 @@ template <int P, int Q> ADMM_HD void rot_cols(Mat3 &m, double c, double s) {
 // (EIG/Jacobi/Jacobi.h:80-110, EIG/Core/MathFunctions.h:284-302) drop 25 of their ~295 instructions per rotation -- the tet kernels
 // sit on the VALU issue roof (profiles/r04/valu_roof.txt), so instructions are time.  A NaN argument comes out as NaN either way.
 // Host builds (tests/host_math_shim.cpp) keep libm's sqrt and the plain division: both are correctly rounded, i.e. the same bits.
+// Pinned on the device by tests/test_device_math.py (through admm_hip_debug_math): every bit against an integer-exact reference on
+// arguments whose result lies next to a rounding midpoint (tests/math_cases.py: 8558 for the square root, within 1.4e-12 ulp; 4456
+// for the reciprocal, within 2^-27 resp. 2^-14 ulp) and against the host on 2M more per helper.  One refinement less (the square
+// root's last correction, the reciprocal's second Newton step) is still right on all of the 2M and wrong on 8 resp. 6 of the directed ones.
 ADMM_HD double sqrt_core(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const double y = __builtin_amdgcn_rsq(x);
@@ -513,12 +517,16 @@ template <int TYPE> struct Prox {
 // other: 24 divisions + 4 square roots per call), so the operands are selected first and the tree is evaluated ONCE
 // (7 divisions + 1 square root).  Every lane still performs exactly its own case's operations on its own case's operands
 // in the reference's order, so the results are bitwise those of the branching form (tests/test_host_math.py runs this
-// code on the host against the reference's cstep through the projection fixtures).
+// code on the host against the reference's cstep through the projection fixtures;
+// tests/test_device_math.py runs it on the device, record by record against the host, in mixed waves).
 //
 // When ALL the lanes of a wavefront that reach the selection sit in the same case (31-43 % of the wave-level calls,
 // profiles/r04/tet_phase_profile.txt) the selects buy nothing: mt_cstep_case<C> below is that one case written out -- the
 // same operations on the same operands in the same order, minus the selects (and, in case 4 with no bracket anywhere in
 // the wave, minus the whole cubic) -- and mt_cstep takes it through a wave-uniform branch.
+// The host can only emulate that branch (tests/test_host_math.py: both forms, the same bits); tests/test_device_math.py takes it
+// on the device with waves composed lane by lane: one case per wave, case-4 waves with no, some and all lanes bracketed, and waves
+// some of whose lanes left at the guard above the ballot.
 #ifndef ADMM_CSTEP_UNIFORM
 #define ADMM_CSTEP_UNIFORM 1
 #endif

@@ -638,8 +638,17 @@ int admm_hip_apply_A(admm_hip_ctx *ctx, const double *x, double *y);
  * CPU test-suite only; no product path calls it.                               */
 int admm_hip_debug_panel_solve_host(admm_hip_ctx *ctx, const double *b, double *x);
 
-/* the device's log() / exp() (glibc's algorithms restated, local_math.hpp admm_log / admm_exp) applied to n doubles:
- * op 0 = log, 1 = exp.  Parity tests compare them bit for bit with the host's libm.                                */
+/* One function of the per-lane math (csrc/local_math.hpp) as the DEVICE build of the header executes it, on n records
+ * (parity tests: tests/test_gpu_parity.py, tests/test_device_math.py compare every bit).  in / out hold n records,
+ * element-major; doubles per record, in -> out:
+ *   op 0 admm_log 1 -> 1      op 1 admm_exp 1 -> 1       (glibc's algorithms restated; against the host's libm)
+ *   op 2 sqrt_in_1_4 1 -> 1   op 3 sqrt_ge_1 1 -> 1      op 4 rcp_in_1_2 1 -> 1      op 5 eig_hypot 2 -> 1
+ *   op 6 svd3 9 -> 21         op 7 oriented_svd 9 -> 21  (U, s0 s1 s2, V; matrices column-major: m00 m10 m20 m01 ...)
+ *   op 8 svd32 6 -> 12        (U's first two columns, s0 s1, V 2x2; all column-major)
+ *   op 9 mt_cstep 12 -> 9     ([stx fx dx sty fy dy stp fp dp stpmin stpmax brackt] -> [stx fx dx sty fy dy stp brackt info])
+ * The hook guarantees: one lane per record; workgroups of 256 threads, so record i runs on lane i % 64 of wave i / 64;
+ * lanes beyond n return before any of the function's code; op is a kernel argument (wave-uniform), a launch runs one
+ * function.  A caller can therefore compose the waves that mt_cstep's wave-uniform branches see.  n <= 2^30.          */
 int admm_hip_debug_math(admm_hip_ctx *ctx, int op, int64_t n, const double *in, double *out);
 /* Unit-test hooks for the kernels of the device factorization (csrc/factor_dev.hpp), host arrays in and out, column-major:
  *  gemm:      C (m x n, ldc) = beta C + alpha opA(A) opB(B) through gemm_f64_kernel; flags: 1 A transposed (stored k x m), 2 B transposed

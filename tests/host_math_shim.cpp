@@ -52,6 +52,18 @@ void hm_cstep_forms(int n, const double *in, int others_bracket, double *out_sel
     }
 }
 void hm_svd32(const double *F, double *U2, double *S, double *V) { svd32(F, U2, S[0], S[1], V); }
+// batched, in the record layouts of admm_hip_debug_math (include/admm_hip.h): what tests/test_device_math.py holds the device build against
+void hm_sqrt_in_1_4_n(long n, const double *x, double *y) { for (long i = 0; i < n; ++i) y[i] = sqrt_in_1_4(x[i]); }   // (the host branch: libm)
+void hm_sqrt_ge_1_n(long n, const double *x, double *y) { for (long i = 0; i < n; ++i) y[i] = sqrt_ge_1(x[i]); }
+void hm_rcp_in_1_2_n(long n, const double *x, double *y) { for (long i = 0; i < n; ++i) y[i] = rcp_in_1_2(x[i]); }
+void hm_hypot_n(long n, const double *in, double *out) { for (long i = 0; i < n; ++i) out[i] = eig_hypot(in[2 * i], in[2 * i + 1]); }
+void hm_svd3_n(long n, const double *in, double *out) {
+    for (long i = 0; i < n; ++i) { Mat3 u, v; double *o = out + 21 * i; svd3(ld(in + 9 * i), u, o[9], o[10], o[11], v); st(u, o); st(v, o + 12); }
+}
+void hm_oriented_svd_n(long n, const double *in, double *out) {
+    for (long i = 0; i < n; ++i) { Mat3 u, v; double *o = out + 21 * i; oriented_svd(ld(in + 9 * i), o[9], o[10], o[11], u, v); st(u, o); st(v, o + 12); }
+}
+void hm_svd32_n(long n, const double *in, double *out) { for (long i = 0; i < n; ++i) { double *o = out + 12 * i; svd32(in + 6 * i, o, o[6], o[7], o + 8); } }
 void hm_project_triarea_p(const double *d, int iters, double lmin, double lmax, double *p) { project_triarea_p(d, iters, lmin, lmax, p); }
 int hm_project_fung(const double *d, double mu, double *hess, double *z) { int it = 0; project_fung(d, mu, *hess, it, z); return it; }
 }

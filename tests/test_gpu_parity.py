@@ -1137,7 +1137,7 @@ def test_device_log_exp_bitwise(pkg, hm):
         x = np.ascontiguousarray(x)
         ref = np.zeros_like(x)
         ref_fn(C.c_int(x.size), x.ctypes.data_as(C.POINTER(C.c_double)), ref.ctypes.data_as(C.POINTER(C.c_double)))
-        got = s.debug_math(op, x)
+        got = s.debug_math(op, x.reshape(-1, 1)).ravel()
         ok = ~np.isnan(ref)
         bad = np.nonzero(got.view(np.int64)[ok] != ref.view(np.int64)[ok])[0]
         assert bad.size == 0, (op, bad.size, x[ok][bad[:5]], got[ok][bad[:5]], ref[ok][bad[:5]])

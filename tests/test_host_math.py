@@ -2,12 +2,14 @@
 for the host by tests/host_math_shim.cpp, against the oracle: bit-exact --
 the very same header is what the HIP kernels execute per lane."""
 import ctypes as C
+import math
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import math_cases
 from checkers import KIND, Oracle, dp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -27,6 +29,9 @@ def hm():
     lib.hm_project_tet_p.argtypes = [C.c_int, dp, C.c_double, C.c_double, dp]
     lib.hm_project_triarea_p.argtypes = [dp, C.c_int, C.c_double, C.c_double, dp]
     lib.hm_project_fung.argtypes = [dp, C.c_double, dp, dp]
+    for name in ("sqrt_in_1_4", "sqrt_ge_1", "rcp_in_1_2", "hypot", "svd3", "oriented_svd", "svd32"):
+        getattr(lib, "hm_%s_n" % name).argtypes = [C.c_long, dp, dp]
+    lib.hm_cstep_forms.argtypes = [C.c_int, dp, C.c_int, dp, dp]
     return lib
 
 
@@ -152,28 +157,8 @@ def test_cstep_one_case_form_is_bitwise_the_select_form(hm):
     """A wave whose lanes all sit in one More-Thuente case runs that case written out (mt_cstep_case<C>) instead of the
     select form: both must give the same bits for every input, including the degenerate ones (equal points, zero
     slopes, infinities) where the cubic produces NaN."""
-    rng = np.random.default_rng(77)
-    n = 200000
-    a = np.zeros((n, 12))
-    stx = rng.uniform(0, 2, n) * rng.choice([0, 1, 1, 1], n)
-    stp = stx + rng.choice([-1, 1, 1, 1], n) * 10 ** rng.uniform(-6, 1, n)
-    sty = np.where(rng.uniform(size=n) < 0.5, stx, stx + rng.choice([-1, 1], n) * 10 ** rng.uniform(-6, 1, n))
-    fx = rng.normal(size=n) * 10 ** rng.uniform(-2, 4, n)
-    a[:, 0] = stx; a[:, 1] = fx
-    a[:, 2] = -np.sign(stp - stx) * 10 ** rng.uniform(-8, 4, n)                 # a descent direction seen from stx
-    a[:, 3] = sty; a[:, 4] = fx + rng.normal(size=n) * 10 ** rng.uniform(-6, 2, n); a[:, 5] = rng.normal(size=n) * 10 ** rng.uniform(-8, 4, n)
-    a[:, 6] = stp
-    a[:, 7] = fx + rng.normal(size=n) * 10 ** rng.uniform(-8, 2, n)
-    a[:, 8] = rng.normal(size=n) * 10 ** rng.uniform(-8, 4, n)
-    br = rng.uniform(size=n) < 0.5
-    a[:, 11] = br
-    a[:, 9] = np.where(br, np.minimum(stx, sty) - 1e-3, stx); a[:, 10] = np.where(br, np.maximum(stx, sty) + 10, stp + 4 * (stp - stx))
-    k = np.arange(n)
-    a[k % 97 == 0, 8] = 0.0; a[k % 89 == 0, 2] *= 0; a[k % 83 == 0, 7] = a[k % 83 == 0, 1]      # zero slopes, equal values
-    a[k % 79 == 0, 8] = a[k % 79 == 0, 2]; a[k % 73 == 0, 8] = -a[k % 73 == 0, 2]
-    a[k % 71 == 0, 7] = np.inf; a[k % 67 == 0, 8] = np.inf; a[k % 61 == 0, 7] = np.nan
-    a[k % 59 == 0, 3] = a[k % 59 == 0, 6]                                                        # sty == stp: 0 / 0 in case 4
-    a = np.ascontiguousarray(a)
+    a = math_cases.cstep_records()
+    n = a.shape[0]
     seen = set()
     for others in (0, 1):
         o0 = np.zeros((n, 9)); o1 = np.zeros((n, 9))
@@ -238,3 +223,165 @@ def test_project_triarea_and_fung(hm):
             assert np.array_equal(z, b["z"][c], equal_nan=True), t
             u = u + (dx - z)
         assert hess[0] == b["state"][3] or (np.isnan(hess[0]) and np.isnan(b["state"][3]))
+
+
+# ---- the argument sets of tests/math_cases.py: what they are, and the host build on them ------------------------------------
+def run_hm(hm, name, x, n_out):
+    """hm_<name>_n on an (n, IN) array -> (n, n_out)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.zeros((x.shape[0], n_out))
+    getattr(hm, "hm_%s_n" % name)(x.shape[0], _p(x), _p(y))
+    return y
+
+
+def mismatches(got, want):
+    """indices of the records in which got and want differ in a bit -- a NaN counts as equal to any NaN (the payload is not part of
+    the contract), and as different from every number"""
+    got = np.asarray(got).reshape(len(got), -1); want = np.asarray(want).reshape(len(want), -1)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    same = (got.view(np.uint64) == want.view(np.uint64)) | (np.isnan(got) & np.isnan(want))
+    return np.nonzero(~same.all(axis=1))[0]
+
+
+def test_sqrt_hard_set_sits_next_to_midpoints():
+    """math_cases.sqrt_hard(): at least 4000 doubles in [1, 4), each with its exact root within 2^-36 ulp of a rounding midpoint --
+    shown with integers.  x = X 2^(K-106), in half-ulps of the root sqrt(x) = sqrt(N) with N = X 2^K, and a midpoint is an odd n:
+    |sqrt(N) - n| = |N - n^2| / (sqrt(N) + n) < |N - n^2| / n half-ulps, so |N - n^2| 2^35 < n puts the root within 2^-36 ulp."""
+    tr = math_cases.sqrt_hard_triples()
+    xs = set()
+    for X, K, n in tr:
+        assert (1 << 52) <= X < (1 << 53) and K in (54, 55) and n & 1 and (1 << 53) <= n < (1 << 54)
+        N = X << K
+        assert N != n * n and abs(N - n * n) << 35 < n
+        x = math.ldexp(X, K - 106)
+        assert 1.0 < x < 4.0 and x.hex() == math.ldexp(X, K - 106).hex() and int(x * 2.0 ** (106 - K)) == X
+        xs.add(x)
+    assert len(xs) >= 4000
+    h = math_cases.sqrt_hard()
+    assert set(h.tolist()) == xs and h.min() == np.nextafter(1.0, 2.0) and h.max() == np.nextafter(4.0, 0.0)
+    assert (h < 2.0).sum() > 1000 and (h >= 2.0).sum() > 1000                        # both binades, i.e. both parities of the exponent
+    assert np.array_equal(math_cases.sqrt_in_1_4_args()[: h.size], h)                 # ... and they lead the full set
+
+
+def test_rcp_hard_sets_sit_next_to_midpoints():
+    """1 / b for b = B 2^-52 in (1, 2) in half-ulps is 2^106 / B; it lies |B n - 2^106| / B half-ulps from the odd n, i.e.
+    |B n - 2^106| / (2 B) ulp.  (a) b = 2 - k 2^-52: within 2^-27 ulp; (b) the committed search in [1, sqrt 2], the range the Jacobi
+    rotation reaches: at least 256 arguments within 2^-14 ulp."""
+    a, b = math_cases.rcp_hard_a_pairs(), math_cases.rcp_hard_b_pairs()
+    assert len(a) == 4096 and len({B for B, n in b}) >= 256
+    for pairs, shift in ((a, 27), (b, 14)):
+        for B, n in pairs:
+            assert n & 1 and (1 << 52) < B < (1 << 53) and B * n != 1 << 106
+            assert abs(B * n - (1 << 106)) << shift < 2 * B
+    assert all(B * B <= 1 << 105 for B, n in b)                                       # b <= sqrt 2
+    assert all(B >= (1 << 53) - (1 << 13) for B, n in a)
+    h = math_cases.rcp_hard()
+    assert [int(v * 2.0 ** 52) for v in h] == [B for B, n in a + b] and np.all((h > 1.0) & (h < 2.0))
+    assert np.array_equal(math_cases.rcp_in_1_2_args()[: h.size], h)
+
+
+def test_integer_references_agree_with_numpy_on_the_hard_sets():
+    """The correctly rounded square root and reciprocal written with Python integers (math_cases.exact_sqrt / exact_rcp) against
+    np.sqrt and 1.0 / b where rounding is hardest: this host's sqrt and divide are correct there, which is what lets the device
+    tests use numpy as the reference for the millions of ordinary arguments."""
+    h = math_cases.sqrt_hard()
+    assert np.array_equal(np.array([math_cases.exact_sqrt(x) for x in h]), np.sqrt(h))
+    r = math_cases.rcp_hard()
+    assert np.array_equal(np.array([math_cases.exact_rcp(b) for b in r]), 1.0 / r)
+    # the integer references themselves, away from the hard sets: exact cases
+    for x, want in ((1.0, 1.0), (4.0, 2.0), (2.25, 1.5), (2.0 ** -1074, 2.0 ** -537), (2.0 ** 1022, 2.0 ** 511), (3.0, None), (float(3 ** 33), None)):
+        assert math_cases.exact_sqrt(x) == (math.sqrt(x) if want is None else want)
+    assert math_cases.exact_rcp(1.0) == 1.0 and math_cases.exact_rcp(1.5) == float.fromhex("0x1.5555555555555p-1") and math_cases.exact_rcp(2.0 ** -1000) == 2.0 ** 1000
+    # ... and every exponent
+    xs = np.exp(np.random.default_rng(8).uniform(-700, 700, 20000))
+    assert np.array_equal(np.array([math_cases.exact_sqrt(x) for x in xs]), np.sqrt(xs))
+    assert np.array_equal(np.array([math_cases.exact_rcp(x) for x in xs]), 1.0 / xs)
+
+
+def test_argument_sets_stay_inside_the_stated_ranges():
+    """no argument outside a helper's stated range (the range is its contract), and the corners the sets promise are there"""
+    s14, sge, rc = math_cases.sqrt_in_1_4_args(), math_cases.sqrt_ge_1_args(), math_cases.rcp_in_1_2_args()
+    assert np.all(np.isnan(s14) | ((s14 >= 1.0) & (s14 < 4.0))) and np.isnan(s14).sum() == math_cases.nans().size
+    assert np.all(np.isnan(sge) | (sge >= 1.0)) and np.isinf(sge).sum() > 1000 and np.finfo(np.float64).max in sge
+    assert np.all(np.isnan(rc) | ((rc >= 1.0) & (rc < 2.0))) and np.isnan(rc).sum() >= math_cases.nans().size
+    for v in (1.0, np.nextafter(1.0, 2.0), 2.0, np.nextafter(2.0, 0.0), np.nextafter(4.0, 0.0), 1.0 + 2.0 ** -52):
+        assert v in s14
+    with np.errstate(invalid="ignore"):
+        assert (np.sqrt(s14) ** 2 == s14).sum() > 90_000                                # exact squares (their neighbours sit beside them)
+    assert all(2.0 ** k in sge for k in range(1024)) and (sge > 1e300).sum() > 100
+    assert 1.0 in rc and np.nextafter(2.0, 0.0) in rc and math.sqrt(2.0) in rc
+    assert min(s14.size, sge.size, rc.size) > 1_900_000
+    for f in (math_cases.svd3_matrices, math_cases.svd32_matrices, math_cases.hypot_pairs):
+        assert f().shape[0] == 1_000_000
+
+
+def test_scalar_helpers_host_branch(hm):
+    """sqrt_in_1_4 / sqrt_ge_1 / rcp_in_1_2 as the host build has them (libm's sqrt, the plain division) on the full sets: the bits of
+    np.sqrt / 1.0 / b, NaN for NaN, +inf for +inf"""
+    with np.errstate(invalid="ignore"):
+        for name, x, ref in (("sqrt_in_1_4", math_cases.sqrt_in_1_4_args(), np.sqrt), ("sqrt_ge_1", math_cases.sqrt_ge_1_args(), np.sqrt),
+                             ("rcp_in_1_2", math_cases.rcp_in_1_2_args(), lambda b: 1.0 / b)):
+            got = run_hm(hm, name, x.reshape(-1, 1), 1)
+            bad = mismatches(got, ref(x))
+            assert bad.size == 0, (name, bad.size, [(x[i].hex(), got[i, 0].hex()) for i in bad[:5]])
+            assert np.array_equal(np.isnan(got[:, 0]), np.isnan(x))
+
+
+def hypot_numpy(x, y):
+    """numext::hypot as local_math.hpp eig_hypot restates it, in numpy: same operations, same order, std::max / std::min's choice of
+    the FIRST argument when a comparison with a NaN fails"""
+    ax, ay = np.abs(x), np.abs(y)
+    p = np.where(ax < ay, ay, ax)
+    q = np.where(ay < ax, ay, ax)
+    with np.errstate(all="ignore"):
+        qp = q / p
+        r = p * np.sqrt(1.0 + qp * qp)
+    return np.where(p == 0.0, 0.0, r)
+
+
+def test_hypot_n(hm):
+    xy = math_cases.hypot_pairs()
+    got = run_hm(hm, "hypot", xy, 1)
+    bad = mismatches(got, hypot_numpy(xy[:, 0], xy[:, 1]))
+    assert bad.size == 0, (bad.size, xy[bad[:5]], got[bad[:5]])
+    assert np.isnan(got).sum() > 10 and np.isinf(got).sum() > 10 and (got == 0).sum() > 1000 and ((got > 0) & (got < 2.3e-308)).sum() > 100
+
+
+def test_batched_svd_against_the_oracle(hm):
+    """hm_svd3_n / hm_svd32_n (the host build of the header in the device hook's record layout) against Oracle.svd3 / Oracle.svd32, bit
+    for bit, on every structured matrix and 20000 of the random ones (one oracle call per matrix, hence not the whole million)"""
+    for name, S, A, cut, n_out in (("svd3", math_cases.svd3_structured(), math_cases.svd3_matrices(), 9, 21),
+                                   ("svd32", math_cases.svd32_structured(), math_cases.svd32_matrices(), 6, 12)):
+        F = np.ascontiguousarray(A[: S.shape[0] + 20000])
+        assert np.array_equal(F[: S.shape[0]], S, equal_nan=True)
+        got = run_hm(hm, name, F, n_out)
+        want = np.empty_like(got)
+        orc = Oracle.svd3 if name == "svd3" else Oracle.svd32
+        for i in range(F.shape[0]):
+            U, s, V = orc(F[i])
+            want[i] = np.concatenate([U[:cut], s, V])
+        bad = mismatches(got, want)
+        assert bad.size == 0, (name, bad.size, F[bad[:3]], got[bad[:3]], want[bad[:3]])
+
+
+def det3_numpy(M):
+    """Matrix3d::determinant() in local_math.hpp det3's operation order on (n, 9) column-major matrices"""
+    m00, m10, m20, m01, m11, m21, m02, m12, m22 = M.T
+    with np.errstate(all="ignore"):
+        return m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20)
+
+
+def test_oriented_svd_is_svd3_plus_the_determinant_rule(hm):
+    """helper::oriented_svd (CORE/TetForce.cpp:80-102): the SVD, then a negative det(U) flips U's last column and s2, a negative
+    det(V^T) flips V's last column (V^T's last row) and s2 -- restated in numpy on top of hm_svd3_n, all 1M matrices"""
+    F = math_cases.svd3_matrices()
+    want = run_hm(hm, "svd3", F, 21)
+    got = run_hm(hm, "oriented_svd", F, 21)
+    flip_u = det3_numpy(want[:, 0:9]) < 0.0
+    flip_v = det3_numpy(want[:, 12:21][:, [0, 3, 6, 1, 4, 7, 2, 5, 8]]) < 0.0
+    with np.errstate(invalid="ignore"):
+        want[flip_u, 6:9] *= -1.0; want[flip_u, 11] *= -1.0
+        want[flip_v, 18:21] *= -1.0; want[flip_v, 11] *= -1.0
+    bad = mismatches(got, want)
+    assert bad.size == 0, (bad.size, F[bad[:3]])
+    assert (flip_u & flip_v).sum() > 1000 and (flip_u & ~flip_v).sum() > 1000 and (~flip_u & flip_v).sum() > 1000 and (~flip_u & ~flip_v).sum() > 1000
