@@ -35,37 +35,37 @@ int admm_hip_create(admm_hip_ctx **out, int device_id) {
     ctx->graph_enabled = false;      // diagnostic builds: eager launches only (their per-launch symbol updates are not capturable)
 #endif
     if (const char *g = getenv("ADMM_HIP_GRAPH_COMM")) ctx->graph_comm = atoi(g) != 0;
-    if (const char *g = getenv("ADMM_HIP_BWD_NW")) { const int v = atoi(g); if (v == 4 || v == 8 || v == 16) ctx->bwd_nw = v; }
-    if (const char *g = getenv("ADMM_HIP_FWD_SMALL_K")) ctx->fwd_small_k = atoi(g);
-    if (const char *g = getenv("ADMM_HIP_BWD_SMALL_K")) ctx->bwd_small_k = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_BWD_NW")) { const int v = atoi(g); if (v == 4 || v == 8 || v == 16) ctx->knobs.bwd_nw = v; }
+    if (const char *g = getenv("ADMM_HIP_FWD_SMALL_K")) ctx->knobs.fwd_small_k = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_BWD_SMALL_K")) ctx->knobs.bwd_small_k = atoi(g);
     if (const char *g = getenv("ADMM_HIP_TREE_SEARCH")) ctx->tree_search = atoi(g) != 0;
     if (const char *g = getenv("ADMM_HIP_STATE_DIRECT")) ctx->state_direct_max_nodes = atoi(g);      // systems up to that many nodes: upload_state / download_state without DMA (0: never)
     if (const char *g = getenv("ADMM_HIP_LOCAL_MULTI")) ctx->local_multi = atoi(g) != 0;
     if (const char *g = getenv("ADMM_HIP_TOP_BWD_ALL")) ctx->top_bwd_needed_only = atoi(g) == 0;
     if (const char *g = getenv("ADMM_HIP_ROOT_FUSE_K")) ctx->root_fuse_k = std::min(atoi(g), (int)admm_dev::ROOT_KCHUNK);
     if (const char *g = getenv("ADMM_HIP_FRAME_GRAPH")) ctx->frame_graph_on = atoi(g) != 0;      // 0: one graph launch per ADMM iteration instead of one per frame
-    if (const char *g = getenv("ADMM_HIP_BWD_SMALL_NW")) { const int v = atoi(g); if (v == 2 || v == 4 || v == 8 || v == 16) ctx->bwd_small_nw = v; }
-    if (const char *g = getenv("ADMM_HIP_XCD")) ctx->xcd_min_supernodes = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_BWD_SMALL_NW")) { const int v = atoi(g); if (v == 2 || v == 4 || v == 8 || v == 16) ctx->knobs.bwd_small_nw = v; }
+    if (const char *g = getenv("ADMM_HIP_XCD")) ctx->knobs.xcd_min_supernodes = atoi(g);
     if (const char *g = getenv("ADMM_HIP_TET_ORDER")) ctx->tet_order = atoi(g) != 0;
     if (const char *g = getenv("ADMM_HIP_TET_ORDER_MIN")) ctx->tet_order_min_blocks = atoi(g);
     if (const char *g = getenv("ADMM_HIP_FUSE_ANCHORS")) ctx->fuse_anchor_tail = atoi(g) != 0;
     if (const char *g = getenv("ADMM_HIP_FACTOR")) ctx->device_factor = std::string(g) != "host";
-    if (const char *g = getenv("ADMM_HIP_BWD_CW2_MIN")) ctx->bwd_cw2_min_cols = atoi(g);
-    if (const char *g = getenv("ADMM_HIP_BWD_CW2_MAX")) ctx->bwd_cw2_max_cols = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_BWD_CW2_MIN")) ctx->knobs.bwd_cw2_min_cols = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_BWD_CW2_MAX")) ctx->knobs.bwd_cw2_max_cols = atoi(g);
     if (const char *g = getenv("ADMM_HIP_PRERED")) ctx->tet_prered = atoi(g) != 0;
     if (const char *g = getenv("ADMM_HIP_STATE_ZEROCOPY")) ctx->state_zero_copy = atoi(g) != 0;
     if (const char *g = getenv("ADMM_HIP_TPB")) { const int v = atoi(g); if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) ctx->tet_tpb = v; }
     if (const char *g = getenv("ADMM_HIP_KEEP_Z")) ctx->keep_z_user = atoi(g) != 0;
-    if (const char *g = getenv("ADMM_HIP_BWD_NW_MIN_COLS")) ctx->bwd_nw_min_cols = atoi(g);
-    if (const char *g = getenv("ADMM_HIP_FWD_NW16_TILES")) ctx->fwd_nw16_max_tiles = atoi(g);
-    if (const char *g = getenv("ADMM_HIP_FWD_NW4")) ctx->fwd_nw4_kmax = atoi(g);
-    if (const char *g = getenv("ADMM_HIP_FWD_NW8")) ctx->fwd_nw8_kmax = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_BWD_NW_MIN_COLS")) ctx->knobs.bwd_nw_min_cols = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_FWD_NW16_TILES")) ctx->knobs.fwd_nw16_max_tiles = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_FWD_NW4")) ctx->knobs.fwd_nw4_kmax = atoi(g);
+    if (const char *g = getenv("ADMM_HIP_FWD_NW8")) ctx->knobs.fwd_nw8_kmax = atoi(g);
     if (const char *g = getenv("ADMM_HIP_DENSE_MAX")) ctx->dense_max = atoi(g);
-    if (const char *g = getenv("ADMM_HIP_ROOT_INVERSE")) ctx->root_inverse = atoi(g) != 0;
+    if (const char *g = getenv("ADMM_HIP_ROOT_INVERSE")) ctx->knobs.root_inverse = atoi(g) != 0;
     if (const char *g = getenv("ADMM_HIP_DIST_TOP")) ctx->dist_top_wanted = atoi(g) != 0 ? 1 : 0;
     if (const char *g = getenv("ADMM_HIP_DIST_TOP_MIN_NODES")) ctx->dist_top_min_nodes = atoi(g);
-    if (const char *g = getenv("ADMM_HIP_SWEEP_FUSE")) ctx->sweep_fuse = atoi(g) != 0;
-    if (const char *g = getenv("ADMM_HIP_SWEEP_FUSE_BWD")) ctx->sweep_fuse_bwd = atoi(g) != 0;
+    if (const char *g = getenv("ADMM_HIP_SWEEP_FUSE")) ctx->knobs.sweep_fuse = atoi(g) != 0;
+    if (const char *g = getenv("ADMM_HIP_SWEEP_FUSE_BWD")) ctx->knobs.sweep_fuse_bwd = atoi(g) != 0;
     *out = ctx;
     return ADMM_OK;
 }

@@ -1,5 +1,6 @@
 // bwd_record.hpp -- the record of one fused subtree of the backward sweep (solve_bwd_kernel_subtree, kernels_global.hpp; built by
-// upload.inc bwd_subtree_record) and its host check.  Plain C++: the device translation unit and tests/bwd_record_shim.cpp both read it.
+// sweep_plan.hpp bwd_subtree_record) and its host check.  Plain C++: the device translation unit, the host's plan, tests/bwd_record_shim.cpp
+// and tests/cpp/sweep_plan.cpp all read it.  The forward sweep's twin: fwd_record.hpp.
 //
 // The record (ints), copied to LDS once by the subtree's workgroup:
 //   header of BS_HDR ints: the fields BS_LEVELS.. below -- the x area, the staged vectors and the end of the workgroup's LDS in doubles
@@ -17,6 +18,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <vector>
+#include "fwd_record.hpp"      // (sub_split64 / sub_join64: the panel offset's two ints)
 
 namespace admm_dev {
 
@@ -50,7 +52,7 @@ inline bool bwd_record_check(const int *rec, int64_t n_ints, int64_t n_nodes, in
     for (int64_t q = 0; q < nm; ++q) {
         const int *M = rec + m0 + BS_MEM * q;
         const int64_t k = M[BS_K], r = M[BS_R], first = M[BS_FIRST], xo = M[BS_XOFF], vo = M[BS_VOFF], r0 = M[BS_ROW0];
-        const int64_t poff = (int64_t)(((uint64_t)(uint32_t)M[BS_POFF + 1] << 32) | (uint32_t)M[BS_POFF]);
+        const int64_t poff = sub_join64(M[BS_POFF], M[BS_POFF + 1]);
         if (k < 1 || k > BS_KMAX || r < 0) return bad("member shape", q, k);
         if (first < 0 || first + k > n_nodes) return bad("member columns outside the system", q, first);
         if (poff < 0 || poff + (k + r) * k > panels_size) return bad("panel offset", q, poff);

@@ -1,7 +1,7 @@
 // ctx.hpp -- the library's context (admm_hip_ctx) and the host-side records it is made of, shared by the library's translation units:
 //   admm_hip.hip     device code (kernels_*.hpp, factor_dev.hpp) + device factorization, upload, launches, step loop, C ABI
 //   host_setup.cpp   Force::initialize / get_selector data, assembly of A_s, ordering + symbolic / host numeric factorization
-//   partition.cpp    subtree sharding: owners of supernodes and elements, XCD-aware item order
+//   partition.cpp    subtree sharding: owners of supernodes and elements
 //   comm.cpp         RCCL (bound at run time) and the all-reduce hooks + their C ABI entry points
 // See include/admm_hip.h for the contract and DESIGN.md for the design.
 #pragma once
@@ -23,6 +23,7 @@
 #include "mesh_host.hpp"
 #include "node_csr.hpp"
 #include "collision_plan.hpp"
+#include "sweep_plan.hpp"
 
 namespace admm_lib {
 
@@ -93,11 +94,11 @@ struct Explicit {
     int *d_level_ptr = nullptr; int n_levels = 0;
 };
 
-constexpr int BWD_BIG_CW = 1;         // backward kernel: columns per wave on levels with supernodes wider than bwd_small_k
+// one level of one pass of the sweeps on the device: the item lists and choices of its LevelPlan (sweep_plan.hpp), uploaded
 struct LevelDev {
     int n_small = 0; admm_dev::SweepItem *d_small = nullptr;   // forward: wave items (levels of supernodes with k <= fwd_small_k)
     int n_big = 0, big_nw = 16; admm_dev::SweepItem *d_big = nullptr;   // forward: block items; waves per tile (4 / 8 / 16 by the level's widest supernode)
-    struct Root { int k, first; int64_t foff, inv_off; };
+    using Root = SweepRoot;
     std::vector<Root> roots;                                   // roots solved with their explicit inverse: gather + one row-wise product (no backward items)
     int n_bwd = 0, bwd_cw = 1, bwd_nw = 4; admm_dev::SweepItem *d_bwd = nullptr;   // backward: columns per wave, waves per block
     int level = 0; double mbytes = 0.0;                        // diagnostics: position in the tree, panel bytes of this level's supernodes
@@ -233,7 +234,6 @@ struct admm_hip_ctx {
     int *d_comm_top = nullptr, *d_comm_slots = nullptr; unsigned char *d_comm_mine = nullptr, *d_base_mask = nullptr, *d_keep_mask = nullptr;
     double *d_comm_buf = nullptr;
     // small systems: explicit inverse of the scalar system (factor order), one kernel per solve
-    bool root_inverse = true;                 // roots of the elimination tree: forward + backward as one product with (L L^T)^-1 (ADMM_HIP_ROOT_INVERSE=0: two sweeps)
     int dense_max = 2048; bool dense = false; std::vector<double> Ainv; double *d_ainv = nullptr;
     // one ADMM iteration (local kernels, RHS, all sweep launches) captured as a HIP graph: one launch per iteration
     // instead of 30-40; matters for the small shipped scenes, which are launch-bound.  Not used around timed iterations, with
@@ -254,23 +254,11 @@ struct admm_hip_ctx {
     bool tree_search = true;                       // pick the elimination tree of mid-size systems by the sweeps' cost model (ADMM_HIP_TREE_SEARCH=0: the rule-based tree)
     bool top_bwd_needed_only = true;              // subtree sharding: the backward sweep over the replicated top skips the separators this rank never reads (ADMM_HIP_TOP_BWD_ALL=1: all of them)
     int root_fuse_k = 2048;                       // roots of at most that many columns: t is gathered inside the product kernel (ADMM_HIP_ROOT_FUSE_K; 0 = never)
-    int fwd_small_k = 64, bwd_small_k = 64;       // levels whose widest supernode has at most this many columns: wave-per-tile forward kernel / 4 columns per wave backward
-    // backward sweep, wide levels with more columns than the chip holds waves (8 x 4 x 256) but at most twice as many: two columns per wave
-    // instead of a second round of workgroups for the few that did not fit (1M-tet bar: levels 3, 4, 6, 7 with 8.6-13.7 k columns:
-    // backward 0.212 -> 0.203 ms; including the top levels with 4.5-5.5 k columns: 0.229).  ADMM_HIP_BWD_CW2_MIN / _MAX, MIN 0 = off
-    int bwd_cw2_min_cols = 8192, bwd_cw2_max_cols = 16384;
-    int bwd_nw = 8, bwd_small_nw = 4;                               // backward sweep, levels of wide supernodes: waves (= columns) per block sharing one staging (ADMM_HIP_BWD_NW = 4 / 8 / 16)
-    int xcd_min_supernodes = 16;                  // levels with at least this many supernodes get the XCD-aware item order (0 = off; ADMM_HIP_XCD)
-    int bwd_nw_min_cols = 4096, fwd_nw16_max_tiles = 512;
-    int fwd_nw4_kmax = 200, fwd_nw8_kmax = 400;   // forward sweep: levels whose widest supernode has at most this many columns run 4 / 8 waves per tile (ADMM_HIP_FWD_NW4 / _NW8)
-    // the bottom subtrees of the elimination tree (every supernode up to the cut level) swept by ONE launch per sweep, one workgroup per
-    // subtree, the hand-off between its levels in LDS (upload.inc fuse_subtrees; ADMM_HIP_SWEEP_FUSE=0: per-level launches only)
-    bool sweep_fuse = true;
+    admm_lib::SweepKnobs knobs;                   // what the plan of the sweeps reads (sweep_plan.hpp): kernel shapes per level, the fused bottom subtrees
+    // the fused launches over the bottom subtrees, one workgroup per subtree (sweep_plan.hpp plan_fused_subtrees):
     int fuse_cut = -1, n_fuse = 0, fuse_lds = 0;  // cut level (-1: nothing fused), subtrees, dynamic LDS bytes of the fused launches
     int *d_fuse_rec = nullptr; int64_t *d_fuse_off = nullptr;      // the subtrees' records (ints) and their offsets [n_fuse + 1]
-    // ... and the backward sweep's launch over those of them whose backward record fits the LDS cap as well (bwd_record.hpp;
-    // ADMM_HIP_SWEEP_FUSE_BWD=0: the backward sweep keeps its per-level launches, the forward one stays fused)
-    bool sweep_fuse_bwd = true;
+    // ... and the backward sweep's, over those of them whose backward record fits the LDS cap as well (bwd_record.hpp)
     int n_fuse_bwd = 0, fuse_bwd_lds = 0;
     int *d_fuse_bwd_rec = nullptr; int64_t *d_fuse_bwd_off = nullptr;
     int64_t graph_launches = 0;               // hipGraphLaunch calls so far (admm_hip_debug_graph_state)
@@ -388,6 +376,5 @@ void top_needs(const admm_hip_ctx *ctx, std::vector<std::vector<char> > &need, s
 void shard_accounting(admm_hip_ctx *ctx);
 void plan_device_panels(admm_hip_ctx *ctx);
 void subtree_owners(const admm_host::Factor &F, int parts, std::vector<int> &owner, std::vector<double> &load, int &n_top, size_t &n_sub);
-void xcd_order(std::vector<admm_dev::SweepItem> &items, int group, int min_supernodes);
 
 } // namespace admm_lib

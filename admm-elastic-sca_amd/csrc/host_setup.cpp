@@ -154,7 +154,7 @@ int host_factor(admm_hip_ctx *ctx, bool reuse_symbolic) {
         // large systems: only the top region merges (root = top separator + its two half-separators, solved as one dense product
         // with its explicit inverse): the two top levels of both sweeps -- ~20 us of latency each at 1M tets -- become one
         // HBM-rate product of k^2 doubles (3335^2 x 8 B = 89 MB at the 1M-tet bar)
-        bool merge_root = merge_above == 0 && ctx->root_inverse;
+        bool merge_root = merge_above == 0 && ctx->knobs.root_inverse;
         if (const char *e = getenv("ADMM_HIP_MERGE_ROOT")) merge_root = atoi(e) != 0;
         // Subtree sharding: a rank's own subtrees are mid-size systems (22k nodes each at 8 ranks of the 178.6k-node bar) whose levels are
         // latency-bound, the replicated top is not: regions of up to 4/3 of a rank's share become four-way nodes, the top keeps its tree.
@@ -182,7 +182,7 @@ int host_factor(admm_hip_ctx *ctx, bool reuse_symbolic) {
         // replicated top's bytes grow with the rank count (4M-tet bar: 0.85 GB at 4 ranks, 1.66 GB of a rank's 2.4 GB at 8), the split root's shrink.
         auto build_tree = [&]() {
         ctx->dist_top = false;
-        if (own_subtrees && (ctx->dist_top_wanted == 1 || (ctx->dist_top_wanted < 0 && ctx->n_nodes >= ctx->dist_top_min_nodes)) && ctx->factor_local && ctx->root_inverse && ((ctx->device_id >= 0 && (ctx->rccl_comm || ctx->allreduce)) || getenv("ADMM_HIP_PLAN_AS_IF_DEVICE")) &&
+        if (own_subtrees && (ctx->dist_top_wanted == 1 || (ctx->dist_top_wanted < 0 && ctx->n_nodes >= ctx->dist_top_min_nodes)) && ctx->factor_local && ctx->knobs.root_inverse && ((ctx->device_id >= 0 && (ctx->rccl_comm || ctx->allreduce)) || getenv("ADMM_HIP_PLAN_AS_IF_DEVICE")) &&
             (ctx->world & (ctx->world - 1)) == 0 && ctx->world <= 16 && ctx->n_nodes > ctx->dense_max && !getenv("ADMM_HIP_ROOT_DEPTH") && !getenv("ADMM_HIP_MERGE_ROOT")) {
             int d = 0; while ((1 << d) < ctx->world) ++d;
             d = std::max(d, 2);      // (2 ranks: four subtrees, two per rank -- the merged-root tree of rounds 2-5; one level less inside a rank's subtrees than a two-way root)
@@ -230,7 +230,7 @@ int host_factor(admm_hip_ctx *ctx, bool reuse_symbolic) {
                     double mb = 0.0, inv_mb = 0.0; bool plain = false;
                     for (int sn : L) {
                         const Supernode &S = T.sn[sn];
-                        if (S.parent < 0 && S.ncols > ROOT_INV_MIN_COLS && ctx->root_inverse) inv_mb += 8e-6 * (double)S.ncols * root_inv_ld(S.ncols);
+                        if (S.parent < 0 && S.ncols > ROOT_INV_MIN_COLS && ctx->knobs.root_inverse) inv_mb += 8e-6 * (double)S.ncols * root_inv_ld(S.ncols);
                         else { plain = true; mb += 8e-6 * ((double)S.ncols * (S.ncols + 1) / 2 + (double)S.nrows * S.ncols); }
                     }
                     us += (plain ? 11.9 : 0.0) + 0.48 * mb + 0.176 * inv_mb;
@@ -247,7 +247,7 @@ int host_factor(admm_hip_ctx *ctx, bool reuse_symbolic) {
                 if (big && (lf == 128 || dp == 3)) continue;                     // (each analysis costs 30-60 ms there; eight-way nodes never paid above 50k nodes)
                 cands.push_back({lf, 100, dp, rd, false});
             }
-            if (big) cands.push_back({64, 0, 2, 0, ctx->root_inverse});          // the binary tree with the merged root (what the largest systems use): irregular meshes fill in faster under four-way nodes
+            if (big) cands.push_back({64, 0, 2, 0, ctx->knobs.root_inverse});          // the binary tree with the merged root (what the largest systems use): irregular meshes fill in faster under four-way nodes
             for (const Cand &cd : cands) {
                 if (cd.leaf == leaf && cd.depth == merge_depth && cd.root_depth == root_depth && cd.merge == merge_above && cd.merge_root == merge_root) continue;      // the rule-based tree itself
                 Factor T;

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dev_types.hpp"
+#include "fwd_record.hpp"
 #include "bwd_record.hpp"
 
 namespace admm_dev {
@@ -350,8 +351,7 @@ __device__ __forceinline__ void child_sum(const FactorDev &F, int64_t fr, const 
     }
 }
 
-constexpr int FWD_SMALL_KMAX = 64;
-constexpr int FWD_SMALL_WAVES = 4;    // wave items per block in the narrow-supernode forward kernel
+// (FWD_SMALL_KMAX, FWD_SMALL_WAVES: fwd_record.hpp, the host's plan reads them too)
 constexpr int FWD_SMALL_DEPTH = 8;    // panel columns per load group in the wave-per-tile forward kernels
 
 // ---- the tile body of the wave-per-tile forward kernels (solve_fwd_small_kernel, solve_fwd_subtree_kernel): one wave = one
@@ -469,21 +469,12 @@ __global__ __launch_bounds__(64 * FWD_SMALL_WAVES) void solve_fwd_small_kernel(i
     ADMM_SWEEP_STAMP(2);
 }
 
-// Forward sweep over the bottom subtrees of the tree (upload.inc fuse_subtrees): one workgroup per subtree walks its levels bottom-up;
+// Forward sweep over the bottom subtrees of the tree (sweep_plan.hpp plan_fused_subtrees): one workgroup per subtree walks its levels bottom-up;
 // a wave takes one (supernode, 64-row tile) at a time through the same tile body as solve_fwd_small_kernel<true> (quad_sums,
 // panel_first, panel_dot) -- bitwise the same w and root contributions.  The subtree's record (items, front maps) is copied to LDS
 // once; the members' contributions stay in LDS, so past that copy the only global loads are y and the panels, neither of which depends
 // on a value computed here, and the levels are separated by barriers that wait for LDS alone.  Only the root's contribution goes to C.
-// The record (ints): a header of SUB_HDR ints -- the fields SUB_LEVELS.. below, the contribution area and the staged vectors in doubles
-// from the start of LDS -- then from SUB_HDR the level pointers, then items of SUB_ITEM ints (fields SUB_K..; the front map is an int
-// offset in the record, -1 = no children; the destination of the contribution a double offset in the contribution area, -1 = C).
-// A front map holds four ints per front row: double offsets of the children's rows in the contribution area.
-constexpr int SUB_LEVELS = 0, SUB_ITEM0 = 1, SUB_CBUF = 2, SUB_TS = 3, SUB_ROOT_SLOT = 4 /* two ints */, SUB_HDR = 8;
-constexpr int SUB_K = 0, SUB_R = 1, SUB_FIRST = 2, SUB_TILE = 3, SUB_MAP = 4, SUB_CDST = 5, SUB_POFF = 6 /* two ints */, SUB_ITEM = SUB_POFF + 2;
-// 64-bit record fields as (low, high) int pairs
-__host__ __device__ inline void sub_split64(int64_t v, int *lohi) { lohi[0] = (int)(uint32_t)(v & 0xffffffff); lohi[1] = (int)(v >> 32); }
-__host__ __device__ inline int64_t sub_join64(int lo, int hi) { return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo); }
-constexpr int SUB_WAVES = 8;      // waves per subtree workgroup
+// The record's layout (SUB_*): fwd_record.hpp.
 __device__ __forceinline__ int sub_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __global__ __launch_bounds__(64 * SUB_WAVES) void solve_fwd_subtree_kernel(const int *__restrict__ recs, const int64_t *__restrict__ rec_off, const double *__restrict__ panels,
                                                                            const double *__restrict__ y, double *__restrict__ W, double *__restrict__ C) {
@@ -546,7 +537,7 @@ __global__ __launch_bounds__(64 * SUB_WAVES) void solve_fwd_subtree_kernel(const
 // Forward sweep, supernodes with k > 64: one block of NW waves = one
 // (supernode, 64-row tile); the waves split the columns, partial sums are
 // combined through LDS in wave order.  NW = 16 for the wide supernodes at the top of the tree; levels of narrower ones run
-// with 4 or 8 waves per tile (chosen per level from its widest supernode, upload.inc upload_factor): a CU holds the same
+// with 4 or 8 waves per tile (chosen per level from its widest supernode, sweep_plan.hpp plan_levels): a CU holds the same
 // number of waves either way, but four times as many tiles are resident at once and every wave has a full group of columns
 // to stream instead of a handful -- such levels are bound by the per-tile prologue latency, not by bytes.
 // DEPTH: panel columns per load group; 4 with 16 waves per tile (the top levels: few, long tiles).
@@ -790,7 +781,7 @@ __global__ __launch_bounds__(64 * NWB) void solve_bwd_kernel(const SweepItem *__
     ADMM_SWEEP_STAMP(2);
 }
 
-// Backward sweep over the bottom subtrees of the tree (upload.inc bwd_subtree_record; the record: bwd_record.hpp): one workgroup per
+// Backward sweep over the bottom subtrees of the tree (sweep_plan.hpp bwd_subtree_record; the record: bwd_record.hpp): one workgroup per
 // subtree walks its levels top-down, the mirror image of solve_fwd_subtree_kernel.  Per level the waves first stage [w_s; -x(R_s)] of
 // every member once (the rows of the level's stage table shared among all threads; w_s from global W, a row of a member higher up in
 // this subtree from the x area in LDS, a row above the subtree from global X, which earlier launches wrote), then the waves take

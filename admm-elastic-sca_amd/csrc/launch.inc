@@ -336,7 +336,7 @@ int launch_solve(admm_hip_ctx *ctx, hipEvent_t mid, hipEvent_t ex0 = nullptr, hi
             for (int l = (int)levels.size() - 1; l >= 0; --l) {
                 const LevelDev &L = levels[l];
                 if (!L.n_bwd) continue;
-                // the level's work items were cut for bwd_nw * bwd_cw columns per block (upload_factor): the kernel must be THAT pair
+                // the level's work items were cut for bwd_nw * bwd_cw columns per block (sweep_plan.hpp plan_levels): the kernel must be THAT pair
                 // (two waves per block: four columns per wave only)
                 bad_pair |= !with_int<4, 2, 1>(L.bwd_cw, [&](auto cw) { return with_int<2, 4, 8, 16>(L.bwd_nw, [&](auto nwb) {
                     constexpr int CW = decltype(cw)::value, NWB = decltype(nwb)::value;
@@ -381,7 +381,7 @@ int launch_solve(admm_hip_ctx *ctx, hipEvent_t mid, hipEvent_t ex0 = nullptr, hi
         backward(ctx->levels, ctx->stream);
         if (ctx->n_fuse_bwd)      // the bottom subtrees last, one workgroup each (bwd_small_nw: the block width of the per-level launches they replace)
             hipLaunchKernelGGL(solve_bwd_kernel_subtree, dim3(ctx->n_fuse_bwd), dim3(64 * SUB_WAVES), ctx->fuse_bwd_lds, ctx->stream, (const int *)ctx->d_fuse_bwd_rec,
-                               (const int64_t *)ctx->d_fuse_bwd_off, (const double *)ctx->d_panels, (const double *)ctx->d_w, ctx->d_xcur, 4 * ctx->bwd_small_nw - 1);
+                               (const int64_t *)ctx->d_fuse_bwd_off, (const double *)ctx->d_panels, (const double *)ctx->d_w, ctx->d_xcur, 4 * ctx->knobs.bwd_small_nw - 1);
         HIPCHK(hipGetLastError());
         if (bad_pair) return fail(ctx, ADMM_ERR_STATE, "backward sweep: no kernel for a level's (columns per wave, waves per block) pair");
         return ADMM_OK;

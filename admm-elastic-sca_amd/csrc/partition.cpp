@@ -1,4 +1,4 @@
-// partition.cpp -- subtree sharding (who owns which supernode / element) and the XCD-aware order of a level's work items.
+// partition.cpp -- subtree sharding: who owns which supernode / element.
 #include "ctx.hpp"
 
 using namespace admm_host;
@@ -255,36 +255,6 @@ int check_split_elements(admm_hip_ctx *ctx) {
         }
     }
     return ADMM_OK;
-}
-
-// XCD-aware order of a level's work items.  Workgroups are dealt round-robin to the 8 XCDs (workgroup i -> XCD i mod 8), each
-// with its own L2: in plain order the tiles of ONE supernode land on all eight, and every L2 fetches that supernode's staged
-// vector (y, contribution lists, the children's contributions / x of its rows) from HBM again.  Here every supernode of a level
-// is given to one XCD (longest first onto the least loaded) and the list is interleaved so that its items get workgroup ids of
-// that XCD; queues of unequal length are padded with empty items (k = r = 0: the kernels do nothing for them).  `group` = items
-// per workgroup (the wave-per-tile forward kernel packs several).  Levels with few supernodes keep the plain order: there every
-// XCD is needed for each of them.
-void xcd_order(std::vector<admm_dev::SweepItem> &items, int group, int min_supernodes) {
-    const int NX = 8;
-    std::vector<std::pair<int, int> > runs;      // (first item, count) per supernode; a supernode's items are consecutive
-    for (size_t i = 0; i < items.size();) { size_t j = i; while (j < items.size() && items[j].s == items[i].s) ++j; runs.push_back({(int)i, (int)(j - i)}); i = j; }
-    if ((int)runs.size() < min_supernodes) return;
-    std::vector<int> ord(runs.size());
-    std::iota(ord.begin(), ord.end(), 0);
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return runs[a].second > runs[b].second; });
-    std::vector<std::vector<admm_dev::SweepItem> > q(NX);
-    for (int r : ord) {
-        int best = 0;
-        for (int x = 1; x < NX; ++x) if (q[x].size() < q[best].size()) best = x;
-        q[best].insert(q[best].end(), items.begin() + runs[r].first, items.begin() + runs[r].first + runs[r].second);
-    }
-    size_t len = 0;
-    for (int x = 0; x < NX; ++x) len = std::max(len, (q[x].size() + group - 1) / group * group);
-    admm_dev::SweepItem none{};
-    std::vector<admm_dev::SweepItem> out;
-    out.reserve(len * NX);
-    for (size_t g0 = 0; g0 < len; g0 += group) for (int x = 0; x < NX; ++x) for (int t = 0; t < group; ++t) out.push_back(g0 + t < q[x].size() ? q[x][g0 + t] : none);
-    items.swap(out);
 }
 
 } // namespace admm_lib

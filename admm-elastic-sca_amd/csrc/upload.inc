@@ -1,4 +1,4 @@
-// upload.inc -- the factor and the batches on the device: sweep work items per level, SoA element arrays, RHS slot layout
+// upload.inc -- the factor and the batches on the device: the sweeps' plan (sweep_plan.hpp) printed and uploaded, SoA element arrays, RHS slot layout
 // (a part of the device translation unit admm_hip.hip: the kernels can live in one translation unit only)
 
 // ---- device upload ----------------------------------------------------------
@@ -13,221 +13,74 @@ template <class T> std::vector<T> permute_nodes(const std::vector<T> &h, const s
 // of the LAST iteration stay); meta: (tag, level, workgroups, KB, list, first slot) per launch
 unsigned long long *g_swp_base; size_t g_swp_wgs; std::vector<int> g_swp_meta;
 #endif
-// ---- the bottom subtrees of the forward sweep, one workgroup each (solve_fwd_subtree_kernel) ---------------------------------------
-// Cut level c: the highest level such that every supernode at or below it has at most 64 columns (the wave-per-tile forward and the
-// 4-column backward shape) and the subtrees below it -- supernodes up to level c whose parent lies above c -- still number at least two
-// per CU.  Each such subtree becomes one record, loaded into LDS once by its workgroup (admm_dev::SUB_* for the layout): the items of
-// every level, bottom-up; per supernode with children its front map (for every front row the LDS offsets of the children's
-// contribution rows landing on it, in the child order of Factor::cg4); the LDS offsets of the members' contributions.  Only the
-// subtree's root writes its contribution to C.  A subtree whose LDS does not leave two workgroups per CU, the subtree of a whole tree
-// (a root of the elimination tree at or below the cut) and trees whose front rows receive more than four contributions (no cg4) stay on
-// the per-level path.  fused[s] = 1 for the supernodes the fused launch sweeps.  ADMM_HIP_VERBOSE: one "plan fused" line per call, early returns
-// included (tests/test_sweep_subtree*.py assert the shapes they reach from it).
-// ... and of the backward sweep (solve_bwd_kernel_subtree; the record's layout: bwd_record.hpp).  The backward record of the subtree under
-// t, whose members bylv lists per level: the members top-down, per member its shape, where its staged vector [w_s; -x(R_s)] lies while
-// its level runs, where its x is kept for the members below it (none for a member without children), and for every front row beyond
-// its columns where x of that row is: in the x area (a column of a member higher up in this subtree) or in global X (above the subtree)
-// -- as one stage table per level, a row of it per row of the level's staged vectors, so that the workgroup's threads share them evenly.
-// One task per (member, four columns).  node_x: scratch, -1 for every node on entry and on return.  -> the workgroup's LDS bytes.
-int bwd_subtree_record(const admm_hip_ctx *ctx, const std::vector<std::vector<int> > &bylv, const std::vector<std::vector<int> > &children, std::vector<int> &node_x,
-                       std::vector<int> &v) {
-    using namespace admm_dev;
-    const Factor &F = ctx->F;
-    std::vector<int> lvm{0}, lvt{0}, lvs{0}, mem, tasks, stage;
-    int xd = 0, vmax = 0, nm = 0;
-    for (int l = (int)bylv.size() - 1; l >= 0; --l) {
-        if (bylv[l].empty()) continue;
-        int vd = 0;
-        for (int s : bylv[l]) {
-            const Supernode &S = F.sn[s];
-            int it[BS_MEM] = {};
-            it[BS_K] = S.ncols; it[BS_R] = S.nrows; it[BS_FIRST] = S.first; it[BS_XOFF] = -1; it[BS_VOFF] = vd; it[BS_ROW0] = (int)stage.size();
-            sub_split64(ctx->dev_panel_off[s], it + BS_POFF);
-            vd += 3 * (S.ncols + S.nrows);
-            for (int j = 0; j < S.ncols; ++j) stage.push_back(-1 - (2 * (S.first + j) + 1));
-            for (int q = 0; q < S.nrows; ++q) { const int node = F.rows[S.rows_off + q]; stage.push_back(node_x[node] >= 0 ? node_x[node] : -1 - 2 * node); }
-            if (!children[s].empty()) {
-                it[BS_XOFF] = xd;
-                for (int j = 0; j < S.ncols; ++j) node_x[S.first + j] = xd + 3 * j;
-                xd += 3 * S.ncols;
-            }
-            for (int g = 0; 4 * g < S.ncols; ++g) tasks.push_back(nm * 16 + g);
-            mem.insert(mem.end(), it, it + BS_MEM);
-            ++nm;
-        }
-        vmax = std::max(vmax, vd);
-        lvm.push_back(nm); lvt.push_back((int)tasks.size()); lvs.push_back((int)stage.size());
-    }
-    for (const std::vector<int> &lv : bylv) for (int s : lv) if (!children[s].empty()) for (int j = 0; j < F.sn[s].ncols; ++j) node_x[F.sn[s].first + j] = -1;
-    const int nl = (int)lvm.size() - 1;
-    const int mem0 = (BS_HDR + 3 * (nl + 1) + 3) & ~3, task0 = mem0 + BS_MEM * nm, stage0 = task0 + (int)tasks.size();
-    const int n_ints = (stage0 + (int)stage.size() + 3) & ~3;
-    v.assign(n_ints, 0);
-    const int xbuf = n_ints / 2, vbuf = xbuf + xd, end = vbuf + vmax;      // (doubles)
-    v[BS_LEVELS] = nl; v[BS_NMEM] = nm; v[BS_MEM0] = mem0; v[BS_NTASK] = (int)tasks.size(); v[BS_TASK0] = task0; v[BS_XBUF] = xbuf; v[BS_VBUF] = vbuf; v[BS_END] = end;
-    v[BS_NSTAGE] = (int)stage.size(); v[BS_STAGE0] = stage0;
-    for (int l = 0; l <= nl; ++l) { v[BS_HDR + l] = lvm[l]; v[BS_HDR + nl + 1 + l] = lvt[l]; v[BS_HDR + 2 * (nl + 1) + l] = lvs[l]; }
-    std::copy(mem.begin(), mem.end(), v.begin() + mem0);
-    std::copy(tasks.begin(), tasks.end(), v.begin() + task0);
-    std::copy(stage.begin(), stage.end(), v.begin() + stage0);
-    return 8 * end;
+// ---- the sweeps -------------------------------------------------------------------------------------------------------------------
+// The plan of both sweeps is a value that sweep_plan.hpp computes from the factor, the context's knobs and two numbers of the device:
+// nothing here decides anything about it.  upload_factor: the limits, the plan, its ADMM_HIP_VERBOSE lines, (the profile build's
+// slots,) the upload.
+
+// ADMM_HIP_VERBOSE, the fused launches: one "plan fused" and one "plan fused_bwd" line per call (tests/test_sweep_subtree*.py assert
+// the shapes they reach from them)
+void print_fuse_plan(const admm_lib::FusePlan &P, int lds_cap) {
+    if (P.why_off) fprintf(stderr, "admm_hip: plan fused off (%s)\n", P.why_off);
+    else fprintf(stderr, "admm_hip: plan fused cut %d subtrees %d left %d lds %d cap %d levels %d..%d maxin %d skip %d empty %d\n", P.cut, P.n_fuse(), P.left, P.lds, lds_cap,
+                 P.lv_min, P.lv_max, P.maxin, P.skip, P.empty);
+    if (P.why_bwd_off) fprintf(stderr, "admm_hip: plan fused_bwd off (%s)\n", P.why_bwd_off);
+    else fprintf(stderr, "admm_hip: plan fused_bwd cut %d subtrees %d left %d lds %d cap %d\n", P.cut, P.n_fuse_bwd(), P.candidates - P.n_fuse_bwd(), P.bwd_lds, lds_cap);
 }
 
-// fused_bwd[s] = 1 for the supernodes the fused backward launch sweeps: the members of those of the subtrees above whose backward record fits the
-// LDS cap too (a subset of fused: a subtree over the cap here keeps its per-level backward items only).  Every backward record passes
-// bwd_record_check before it is uploaded.  ADMM_HIP_VERBOSE: one "plan fused_bwd" line per call beside the "plan fused" one.
-int fuse_subtrees(admm_hip_ctx *ctx, const std::vector<int> *own, int want, std::vector<char> &fused, std::vector<char> &fused_bwd) {
+// ... and one pass over the levels, a line per level and one per root (tests/test_wide_supernodes.py asserts from them which kernel
+// paths a scene reaches): column chunks of the widest block item, row chunks of the tallest front in the backward kernel, and per root
+// its product's chunks
+void print_level_plans(const admm_hip_ctx *ctx, const char *pass, const std::vector<admm_lib::LevelPlan> &levels) {
     using namespace admm_dev;
-    const Factor &F = ctx->F;
-    const int ns = (int)F.sn.size();
-    fused.assign(ns, 0); fused_bwd.assign(ns, 0);
-    ctx->fuse_cut = -1; ctx->n_fuse = 0; ctx->fuse_lds = 0;
-    ctx->n_fuse_bwd = 0; ctx->fuse_bwd_lds = 0;
-    const bool verbose = getenv("ADMM_HIP_VERBOSE") != nullptr;
-    const char *why_bwd_off = !ctx->sweep_fuse ? "ADMM_HIP_SWEEP_FUSE=0" : (!ctx->sweep_fuse_bwd ? "ADMM_HIP_SWEEP_FUSE_BWD=0" : (F.n > BS_MAX_NODES ? "too many nodes" : nullptr));
-    auto bwd_off = [&](const char *why) { if (verbose) fprintf(stderr, "admm_hip: plan fused_bwd off (%s)\n", why); };
-    const char *why_off = !ctx->sweep_fuse ? "ADMM_HIP_SWEEP_FUSE=0" : (F.cg4.empty() ? "front rows with more than four contributions" : (F.levels.empty() ? "no cut level" : nullptr));
-    if (why_off) { if (verbose) fprintf(stderr, "admm_hip: plan fused off (%s)\n", why_off); bwd_off(why_bwd_off ? why_bwd_off : "no fused forward subtrees"); return ADMM_OK; }
-    auto mine = [&](int s) { return !own || (*own)[s] == want; };
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, ctx->device_id));
-    const int cus = std::max(prop.multiProcessorCount, 1);
-    const int lds_cap = (int)std::min<size_t>(prop.sharedMemPerBlock, prop.maxSharedMemoryPerMultiProcessor / 2);
-    const int kcap = std::min(std::min(ctx->fwd_small_k, ctx->bwd_small_k), FWD_SMALL_KMAX);
-    int cut = -1;
-    for (int l = 0; l < (int)F.levels.size(); ++l) {
-        bool narrow = true;
-        for (int s : F.levels[l]) if (mine(s) && F.sn[s].ncols > kcap) narrow = false;
-        if (!narrow) break;
-        int roots = 0;
-        for (int s = 0; s < ns; ++s) {
-            const int p = F.sn[s].parent;
-            if (mine(s) && F.sn[s].level <= l && p >= 0 && F.sn[p].level > l) ++roots;
-        }
-        if (roots >= 2 * cus) cut = l;
+    for (size_t l = 0; l < levels.size(); ++l) {
+        const admm_lib::LevelPlan &L = levels[l];
+        const int kchunk = L.big_nw == 16 ? FwdBig<16>::KCHUNK : (L.big_nw == 8 ? FwdBig<8>::KCHUNK : FwdBig<4>::KCHUNK);
+        int kmax = 0, fmax = 0;
+        for (const SweepItem &q : L.big) kmax = std::max(kmax, q.k);
+        for (const SweepItem &q : L.bwd) fmax = std::max(fmax, q.k + q.r);
+        fprintf(stderr, "admm_hip: plan %s level %zu: fwd wave %d block %d big_nw %d kmax %d chunks %d | bwd cw %d nw %d items %d fmax %d rchunks %d | cg4 %d\n",
+                pass, l, (int)L.small.size(), (int)L.big.size(), L.big_nw, kmax, (kmax + kchunk - 1) / kchunk, L.bwd_cw, L.bwd_nw, (int)L.bwd.size(), fmax,
+                (fmax + BWD_RCHUNK - 1) / BWD_RCHUNK, ctx->F.cg4.empty() ? 0 : 1);
+        for (const admm_lib::SweepRoot &R : L.roots)
+            fprintf(stderr, "admm_hip: plan %s level %zu: root k %d %s chunks %d\n", pass, l, R.k, R.k <= ctx->root_fuse_k ? "fused" : "gather", (R.k + ROOT_KCHUNK - 1) / ROOT_KCHUNK);
     }
-    if (cut < 0) { if (verbose) fprintf(stderr, "admm_hip: plan fused off (no cut level)\n"); bwd_off(why_bwd_off ? why_bwd_off : "no fused forward subtrees"); return ADMM_OK; }
-    std::vector<std::vector<int> > children(ns);
-    for (int s = 0; s < ns; ++s) if (F.sn[s].parent >= 0) children[F.sn[s].parent].push_back(s);
-    std::vector<int> local_slot(F.n_slots, -1);      // member's contribution slot -> LDS offset (doubles, from the contribution area)
-    struct Rec { std::vector<int> v; double bytes; std::vector<int> members; std::vector<int> bwd; };      // (bwd: empty = per-level backward items)
-    std::vector<Rec> recs;
-    int lds_max = 0, left = 0;      // (left: subtrees that stay on the per-level path)
-    std::vector<int> node_x(F.n, -1);      // (bwd_subtree_record's scratch)
-    int bwd_lds_max = 0, n_bwd = 0, candidates = 0;
-    // the shapes the fused records reach (ADMM_HIP_VERBOSE only): levels per record, the most child contributions into one front row,
-    // members whose parent lies two or more levels up, non-root members without contribution rows
-    int lv_min = 0, lv_max = 0, maxin = 0, skip = 0, empty = 0;
-    for (int t = 0; t < ns; ++t) {
-        const int p = F.sn[t].parent;
-        if (!mine(t) || F.sn[t].level > cut || p < 0 || F.sn[p].level <= cut) continue;
-        ++candidates;
-        std::vector<int> mem, stack{t};      // the subtree, then per level
-        while (!stack.empty()) { const int s = stack.back(); stack.pop_back(); mem.push_back(s); for (int c : children[s]) stack.push_back(c); }
-        const int nlv = F.sn[t].level + 1;
-        std::vector<std::vector<int> > bylv(nlv);
-        for (int s : mem) bylv[F.sn[s].level].push_back(s);
-        for (auto &v : bylv) std::sort(v.begin(), v.end());
-        bool ok = true;
-        for (int s : mem) if (!mine(s) || F.sn[s].root_inv_off >= 0) ok = false;
-        // layout: header, level pointers, items, front maps; then (in LDS) the members' contributions and the waves' staged vectors
-        int cdoubles = 0;
-        for (int s : mem) if (s != t) { for (int q = 0; q < F.sn[s].nrows; ++q) local_slot[F.sn[s].slot_off + q] = cdoubles + 3 * q; cdoubles += 3 * F.sn[s].nrows; }
-        std::vector<int> lvp{0}, items, maps;
-        int n_items = 0;
-        for (int l = 0; l < nlv; ++l) {
-            if (bylv[l].empty()) continue;
-            for (int s : bylv[l]) {
-                const Supernode &S = F.sn[s];
-                const int f = S.ncols + S.nrows;
-                int moff = -1;
-                if (!children[s].empty()) {
-                    moff = (int)maps.size();
-                    for (int fr = 0; fr < f; ++fr) for (int e = 0; e < 4; ++e) {
-                        const int g = F.cg4[4 * (size_t)(S.front_off + fr) + e];
-                        const int o = g < 0 ? -1 : local_slot[g];
-                        if (g >= 0 && o < 0) ok = false;
-                        maps.push_back(o);
-                    }
-                }
-                const int cdst = s == t ? -1 : (S.nrows ? local_slot[S.slot_off] : 0);      // (-1: the root, to C)
-                int it[SUB_ITEM] = {};
-                it[SUB_K] = S.ncols; it[SUB_R] = S.nrows; it[SUB_FIRST] = S.first; it[SUB_MAP] = moff; it[SUB_CDST] = cdst;
-                sub_split64(ctx->dev_panel_off[s], it + SUB_POFF);
-                for (int tile = 0; tile < (f + 63) / 64; ++tile) {
-                    it[SUB_TILE] = tile;
-                    items.insert(items.end(), it, it + SUB_ITEM);
-                    ++n_items;
-                }
-            }
-            lvp.push_back(n_items);
-        }
-        for (int s : mem) if (s != t) for (int q = 0; q < F.sn[s].nrows; ++q) local_slot[F.sn[s].slot_off + q] = -1;
-        if (!ok) { ++left; continue; }
-        const int nl = (int)lvp.size() - 1;
-        const int item0 = (SUB_HDR + nl + 1 + 3) & ~3, map0 = item0 + SUB_ITEM * n_items;
-        const int n_ints = (map0 + (int)maps.size() + 3) & ~3;
-        std::vector<int> v(n_ints, 0);
-        const int64_t rs = F.sn[t].slot_off;
-        const int cbuf = n_ints / 2;      // (doubles)
-        const int ts_off = cbuf + cdoubles;
-        v[SUB_LEVELS] = nl; v[SUB_ITEM0] = item0; v[SUB_CBUF] = cbuf; v[SUB_TS] = ts_off; sub_split64(rs, &v[SUB_ROOT_SLOT]);
-        for (int l = 0; l <= nl; ++l) v[SUB_HDR + l] = lvp[l];
-        for (size_t q = 0; q < items.size(); ++q) {
-            v[item0 + q] = items[q];
-            if (q % SUB_ITEM == SUB_MAP && items[q] >= 0) v[item0 + q] += map0;      // front map: offset in the record
-        }
-        std::copy(maps.begin(), maps.end(), v.begin() + map0);
-        const int lds = 8 * (ts_off + 3 * 64 * SUB_WAVES);
-        if (lds > lds_cap) { ++left; continue; }
-        double bytes = 0.0;
-        for (int s : mem) { const double k = F.sn[s].ncols, f = k + F.sn[s].nrows; bytes += 8.0 * (f * k - 0.5 * k * (k - 1)); }
-        lds_max = std::max(lds_max, lds);
-        if (verbose) {
-            lv_min = recs.empty() ? nl : std::min(lv_min, nl); lv_max = std::max(lv_max, nl);
-            for (size_t q = 0; q < maps.size(); q += 4) maxin = std::max(maxin, (maps[q] >= 0) + (maps[q + 1] >= 0) + (maps[q + 2] >= 0) + (maps[q + 3] >= 0));
-            for (int s : mem) if (s != t) { skip += F.sn[F.sn[s].parent].level - F.sn[s].level >= 2; empty += F.sn[s].nrows == 0; }
-        }
-        std::vector<int> bwd;
-        if (!why_bwd_off) {
-            const int bl = bwd_subtree_record(ctx, bylv, children, node_x, bwd);
-            if (bl > lds_cap) bwd.clear();
-            else {
-                char msg[256];
-                if (!bwd_record_check(bwd.data(), (int64_t)bwd.size(), F.n, ctx->dev_panels_size, msg, (int)sizeof msg)) return fail(ctx, ADMM_ERR_STATE, "%s", msg);
-                bwd_lds_max = std::max(bwd_lds_max, bl); ++n_bwd;
-            }
-        }
-        recs.push_back({std::move(v), bytes, std::move(mem), std::move(bwd)});
+}
+
+#ifdef ADMM_SWEEP_PROFILE
+// the profile build's slots: every workgroup of every launch of the pass gets one, written into its items before they are uploaded
+void profile_level_plans(std::vector<admm_lib::LevelPlan> &levels, int list) {
+    for (size_t l = 0; l < levels.size(); ++l) {
+        admm_lib::LevelPlan &L = levels[l];
+        auto reg = [&](std::vector<admm_dev::SweepItem> &v, int group, int tag) {
+            if (v.empty()) return;
+            const int n_wg = ((int)v.size() + group - 1) / group;
+            for (size_t i = 0; i < v.size(); ++i) v[i].pad2 = (v[i].k || v[i].r) ? (long long)(g_swp_wgs + i / group) : -1;
+            for (int q : {tag, (int)l, n_wg, (int)(L.mbytes * 1024), list, (int)g_swp_wgs}) g_swp_meta.push_back(q);
+            g_swp_wgs += n_wg;
+        };
+        reg(L.small, admm_dev::FWD_SMALL_WAVES, 0); reg(L.big, 1, L.big_nw); reg(L.bwd, 1, 100 + 10 * L.bwd_cw + (L.bwd_nw == 16 ? 6 : L.bwd_nw));
     }
-    if (verbose)
-        fprintf(stderr, "admm_hip: plan fused cut %d subtrees %d left %d lds %d cap %d levels %d..%d maxin %d skip %d empty %d\n", cut, (int)recs.size(), left, lds_max, lds_cap,
-                lv_min, lv_max, maxin, skip, empty);
-    if (why_bwd_off) bwd_off(why_bwd_off);
-    else if (!n_bwd) bwd_off(recs.empty() ? "no fused forward subtrees" : "every subtree over the LDS cap");
-    else if (verbose) fprintf(stderr, "admm_hip: plan fused_bwd cut %d subtrees %d left %d lds %d cap %d\n", cut, n_bwd, candidates - n_bwd, bwd_lds_max, lds_cap);
-    if (recs.empty()) return ADMM_OK;
-    // the largest subtrees start first
-    std::stable_sort(recs.begin(), recs.end(), [](const Rec &a, const Rec &b) { return a.bytes > b.bytes; });
-    std::vector<int> all; std::vector<int64_t> off{0};
-    for (const Rec &r : recs) { all.insert(all.end(), r.v.begin(), r.v.end()); off.push_back((int64_t)all.size()); for (int s : r.members) fused[s] = 1; }
-    TRY(upload(ctx, &ctx->d_fuse_rec, all)); TRY(upload(ctx, &ctx->d_fuse_off, off));
-    ctx->fuse_cut = cut; ctx->n_fuse = (int)recs.size(); ctx->fuse_lds = lds_max;
-    if (n_bwd) {      // (in the forward launch's order: the largest subtrees start first)
-        std::vector<int> ball; std::vector<int64_t> boff{0};
-        for (const Rec &r : recs) if (!r.bwd.empty()) { ball.insert(ball.end(), r.bwd.begin(), r.bwd.end()); boff.push_back((int64_t)ball.size()); for (int s : r.members) fused_bwd[s] = 1; }
-        TRY(upload(ctx, &ctx->d_fuse_bwd_rec, ball)); TRY(upload(ctx, &ctx->d_fuse_bwd_off, boff));
-        ctx->n_fuse_bwd = n_bwd; ctx->fuse_bwd_lds = bwd_lds_max;
+}
+#endif
+
+int upload_level_plans(admm_hip_ctx *ctx, const std::vector<admm_lib::LevelPlan> &plans, std::vector<LevelDev> &into) {
+    into.assign(plans.size(), LevelDev());
+    for (size_t l = 0; l < plans.size(); ++l) {
+        const admm_lib::LevelPlan &P = plans[l];
+        LevelDev &L = into[l];
+        L.level = (int)l; L.mbytes = P.mbytes; L.roots = P.roots;
+        L.n_small = (int)P.small.size(); L.n_big = (int)P.big.size(); L.n_bwd = (int)P.bwd.size();
+        L.big_nw = P.big_nw; L.bwd_cw = P.bwd_cw; L.bwd_nw = P.bwd_nw;
+        TRY(upload(ctx, &L.d_small, P.small)); TRY(upload(ctx, &L.d_big, P.big)); TRY(upload(ctx, &L.d_bwd, P.bwd));
     }
     return ADMM_OK;
 }
 
 int upload_factor(admm_hip_ctx *ctx) {
-#ifdef ADMM_SWEEP_PROFILE
-    g_swp_wgs = 0; g_swp_meta.clear();
-#endif
     Factor &F = ctx->F;
     const int ns = (int)F.sn.size();
+    const bool verbose = getenv("ADMM_HIP_VERBOSE") != nullptr;
     std::vector<int> first(ns), ncols(ns), nrows(ns);
     std::vector<int64_t> poff(ns), roff(ns), soff(ns), foff(ns);
     for (int s = 0; s < ns; ++s) { first[s] = F.sn[s].first; ncols[s] = F.sn[s].ncols; nrows[s] = F.sn[s].nrows; poff[s] = ctx->dev_panel_off[s]; roff[s] = F.sn[s].rows_off; soff[s] = F.sn[s].slot_off; foff[s] = F.sn[s].front_off; }
@@ -243,115 +96,46 @@ int upload_factor(admm_hip_ctx *ctx) {
     TRY(dalloc(ctx, &ctx->d_c, 3 * (size_t)std::max<int64_t>(F.n_slots, 1)));
     ctx->d_ainv = nullptr;
     if (ctx->dense) TRY(upload(ctx, &ctx->d_ainv, ctx->Ainv));
-    ctx->levels.assign(F.levels.size(), LevelDev());
-    // Per level, by its widest supernode: forward as wave items (one wave per 64-row tile, k <= fwd_small_k <= 64) or block
-    // items (NW waves split a tile's columns); backward with 4 columns per wave (k <= bwd_small_k), otherwise BWD_BIG_CW
-    // (2 on levels whose column count lies in (bwd_cw2_min_cols, bwd_cw2_max_cols]).
-    std::vector<int> level_kmax(F.levels.size(), 0);
-    for (size_t l = 0; l < F.levels.size(); ++l) for (int s : F.levels[l]) level_kmax[l] = std::max(level_kmax[l], F.sn[s].ncols);
-    const int fwd_small_k = std::min(ctx->fwd_small_k, admm_dev::FWD_SMALL_KMAX);
+
+    // (1) the limits: a fused subtree's workgroup may take the LDS that leaves room for a second one on its CU
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, ctx->device_id));
+    const admm_lib::DeviceLimits limits{std::max(prop.multiProcessorCount, 1), (int)std::min<size_t>(prop.sharedMemPerBlock, prop.maxSharedMemoryPerMultiProcessor / 2)};
+
+    // (2) the plan.  Plain: one pass over all supernodes.  Subtree sharding: this rank's own subtrees (the fused launches are among
+    // them), then the replicated top, whose backward sweep only has to reach the separators this rank needs (partition.cpp: top_needs)
     const bool subtree = ctx->shard_mode == 1 && ctx->world > 1;
-    ctx->levels_top.assign(subtree ? F.levels.size() : 0, LevelDev());
-    // passes: (which supernodes, into which list).  Plain: all -> levels.  Subtree sharding: this rank's -> levels, the replicated
-    // top -> levels_top.
-    struct Pass { int want; std::vector<LevelDev> *into; };
-    std::vector<Pass> passes;
-    if (subtree) { passes.push_back({ctx->rank, &ctx->levels}); passes.push_back({-1, &ctx->levels_top}); }
-    else passes.push_back({0, &ctx->levels});
     const std::vector<int> *own = subtree ? &ctx->sn_owner : nullptr;
-    std::vector<char> fused, fused_bwd;      // supernodes of the fused bottom subtrees (this rank's own ones under subtree sharding): no per-level items in the forward / the backward sweep
-    TRY(fuse_subtrees(ctx, own, subtree ? ctx->rank : 0, fused, fused_bwd));
-    // Subtree sharding: which top supernodes' x does a rank need?  The forward sweep over the top is complete on every rank (it sums
-    // towards the root), but the backward sweep only has to reach the separators a rank touches: those that appear among the front rows
-    // of its own subtrees, those its elements have a node in, and their ancestors.  Everybody evaluates the rule for EVERY rank (no
-    // communication): a top supernode's x goes into the per-frame assembly of the full vector from the lowest rank that computes it.
+    const int want = subtree ? ctx->rank : 0;
+    const admm_lib::FusePlan fuse = admm_lib::plan_fused_subtrees(F, ctx->dev_panel_off, ctx->dev_panels_size, own, want, ctx->knobs, limits);
+    if (!fuse.error.empty()) return fail(ctx, ADMM_ERR_STATE, "%s", fuse.error.c_str());
     std::vector<char> top_needed;                 // this rank's
     std::vector<int> top_provider;
     if (subtree) {
         std::vector<std::vector<char> > need;
-        top_needs(ctx, need, top_provider);      // (partition.cpp)
+        top_needs(ctx, need, top_provider);
         top_needed = need[ctx->rank];
-        if (getenv("ADMM_HIP_VERBOSE")) {
+    }
+    std::vector<admm_lib::LevelPlan> own_levels = admm_lib::plan_levels(F, ctx->dev_panel_off, ctx->dev_root_inv_off, own, want, top_needed, fuse.fused, fuse.fused_bwd, ctx->knobs), top_levels;
+    if (subtree) top_levels = admm_lib::plan_levels(F, ctx->dev_panel_off, ctx->dev_root_inv_off, own, -1, top_needed, fuse.fused, fuse.fused_bwd, ctx->knobs);
+
+    // (3) ADMM_HIP_VERBOSE
+    if (verbose) {
+        print_fuse_plan(fuse, limits.lds_cap);
+        if (subtree) {
             int nt = 0, nn = 0;
             for (int s2 = 0; s2 < ns; ++s2) if (ctx->sn_owner[s2] < 0) { ++nt; nn += top_needed[s2] ? 1 : 0; }
             fprintf(stderr, "admm_hip: rank %d: backward sweep over %d of the %d top supernodes\n", ctx->rank, nn, nt);
         }
+        print_level_plans(ctx, "own", own_levels); print_level_plans(ctx, "top", top_levels);
+        if (subtree && ctx->dist_top)      // (the top's per-level lines above are not run: the root's rows are this rank's product)
+            fprintf(stderr, "admm_hip: plan dist-top rank %d: root k %d rows %d..%d nrows %d chunks %d\n", ctx->rank, ctx->root_k, ctx->root_r0, ctx->root_r1,
+                    ctx->root_r1 - ctx->root_r0, (ctx->root_k + admm_dev::ROOT_KCHUNK - 1) / admm_dev::ROOT_KCHUNK);
     }
-    for (const Pass &ps : passes) {
-        for (size_t l = 0; l < F.levels.size(); ++l) {
-            LevelDev &L = (*ps.into)[l];
-            std::vector<admm_dev::SweepItem> sm, bg, bw;
-            L.level = (int)l; L.mbytes = 0.0;
-            const bool fwd_small = level_kmax[l] <= fwd_small_k, bwd_small = level_kmax[l] <= ctx->bwd_small_k;
-            L.bwd_cw = bwd_small ? 4 : BWD_BIG_CW;   // columns per wave in the backward kernel
-            // eight columns per block pay where a level has thousands of columns (one staging of the vector per 8 instead of 4
-            // columns); on levels with few columns the larger number of blocks matters more (50k-tet bar: 4 waves 222 us / 8: 228)
-            int level_cols = 0;
-            for (int s : F.levels[l]) if (!own || (*own)[s] == ps.want) level_cols += F.sn[s].ncols;
-            L.bwd_nw = bwd_small ? ctx->bwd_small_nw : (level_cols >= ctx->bwd_nw_min_cols ? ctx->bwd_nw : 4);
-            if (!bwd_small && ctx->bwd_cw2_min_cols > 0 && level_cols > ctx->bwd_cw2_min_cols && level_cols <= ctx->bwd_cw2_max_cols) L.bwd_cw = 2;
-            for (int s : F.levels[l]) {
-                if (own && (*own)[s] != ps.want) continue;
-                const Supernode &S = F.sn[s];
-                admm_dev::SweepItem it{};
-                it.s = s; it.k = S.ncols; it.r = S.nrows; it.first = S.first;
-                it.panel_off = ctx->dev_panel_off[s]; it.front_off = S.front_off; it.slot_off = S.slot_off; it.rows_off = S.rows_off;
-                const int f = S.ncols + S.nrows;
-                const int tiles = (f + 63) / 64;
-                L.mbytes += 8e-6 * ((double)f * S.ncols - 0.5 * (double)S.ncols * (S.ncols - 1));
-                if (S.root_inv_off >= 0 && ctx->root_inverse) {      // a root: x = (L L^T)^-1 t in the forward sweep, nothing in the backward sweep
-                    L.roots.push_back({S.ncols, S.first, S.front_off, ctx->dev_root_inv_off[s]});
-                    continue;
-                }
-                const bool in_fused = ps.want >= 0 && fused[s];
-                if (!in_fused) for (int t = 0; t < tiles; ++t) { it.part = t; if (fwd_small) sm.push_back(it); else bg.push_back(it); }
-                const int chunks = (S.ncols + L.bwd_nw * L.bwd_cw - 1) / (L.bwd_nw * L.bwd_cw);
-                if (subtree && ps.want < 0 && !top_needed[s]) continue;      // replicated top: no backward work for a separator this rank never reads
-                if (ps.want >= 0 && fused_bwd[s]) continue;
-                for (int c = 0; c < chunks; ++c) { it.part = c; bw.push_back(it); }
-            }
-            if (ctx->xcd_min_supernodes > 0) { xcd_order(sm, admm_dev::FWD_SMALL_WAVES, ctx->xcd_min_supernodes); xcd_order(bg, 1, ctx->xcd_min_supernodes); xcd_order(bw, 1, ctx->xcd_min_supernodes); }
-            L.n_small = (int)sm.size(); L.n_big = (int)bg.size(); L.n_bwd = (int)bw.size();
-            int kmax = 0;
-            for (const admm_dev::SweepItem &q : bg) kmax = std::max(kmax, q.k);
-            // few tiles (all resident at once even with 16 waves each): the more waves share a tile's columns the shorter its chain
-            L.big_nw = (int)bg.size() <= ctx->fwd_nw16_max_tiles ? 16 : (kmax <= ctx->fwd_nw4_kmax ? 4 : (kmax <= ctx->fwd_nw8_kmax ? 8 : 16));
-            if (getenv("ADMM_HIP_VERBOSE")) {
-                // the sweep plan of this level (tests/test_wide_supernodes.py asserts from it which kernel paths a scene reaches): column
-                // chunks of the widest block item, row chunks of the tallest front in the backward kernel, and per root its product's chunks
-                using namespace admm_dev;
-                const char *pass = ps.want < 0 ? "top" : "own";
-                const int kchunk = L.big_nw == 16 ? FwdBig<16>::KCHUNK : (L.big_nw == 8 ? FwdBig<8>::KCHUNK : FwdBig<4>::KCHUNK);
-                int fmax = 0;
-                for (const SweepItem &q : bw) fmax = std::max(fmax, q.k + q.r);
-                fprintf(stderr, "admm_hip: plan %s level %zu: fwd wave %d block %d big_nw %d kmax %d chunks %d | bwd cw %d nw %d items %d fmax %d rchunks %d | cg4 %d\n",
-                        pass, l, L.n_small, L.n_big, L.big_nw, kmax, (kmax + kchunk - 1) / kchunk, L.bwd_cw, L.bwd_nw, L.n_bwd, fmax, (fmax + BWD_RCHUNK - 1) / BWD_RCHUNK,
-                        F.cg4.empty() ? 0 : 1);
-                for (const LevelDev::Root &R : L.roots)
-                    fprintf(stderr, "admm_hip: plan %s level %zu: root k %d %s chunks %d\n", pass, l, R.k, R.k <= ctx->root_fuse_k ? "fused" : "gather",
-                            (R.k + ROOT_KCHUNK - 1) / ROOT_KCHUNK);
-            }
-#ifdef ADMM_SWEEP_PROFILE
-            {
-                const int list = ps.want < 0 ? 100 : (&ps - &passes[0]);
-                auto reg = [&](std::vector<admm_dev::SweepItem> &v, int group, int tag) {
-                    if (v.empty()) return;
-                    const int n_wg = ((int)v.size() + group - 1) / group;
-                    for (size_t i = 0; i < v.size(); ++i) v[i].pad2 = (v[i].k || v[i].r) ? (long long)(g_swp_wgs + i / group) : -1;
-                    for (int q : {tag, (int)l, n_wg, (int)(L.mbytes * 1024), list, (int)g_swp_wgs}) g_swp_meta.push_back(q);
-                    g_swp_wgs += n_wg;
-                };
-                reg(sm, admm_dev::FWD_SMALL_WAVES, 0); reg(bg, 1, L.big_nw); reg(bw, 1, 100 + 10 * L.bwd_cw + (L.bwd_nw == 16 ? 6 : L.bwd_nw));
-            }
-#endif
-            TRY(upload(ctx, &L.d_small, sm)); TRY(upload(ctx, &L.d_big, bg)); TRY(upload(ctx, &L.d_bwd, bw));
-        }
-    }
-    if (subtree && ctx->dist_top && getenv("ADMM_HIP_VERBOSE"))      // (the top's per-level lines above are not run: the root's rows are this rank's product)
-        fprintf(stderr, "admm_hip: plan dist-top rank %d: root k %d rows %d..%d nrows %d chunks %d\n", ctx->rank, ctx->root_k, ctx->root_r0, ctx->root_r1,
-                ctx->root_r1 - ctx->root_r0, (ctx->root_k + admm_dev::ROOT_KCHUNK - 1) / admm_dev::ROOT_KCHUNK);
 #ifdef ADMM_SWEEP_PROFILE
     {
+        g_swp_wgs = 0; g_swp_meta.clear();
+        profile_level_plans(own_levels, 0); profile_level_plans(top_levels, 100);
         unsigned long long *p = nullptr;
         TRY(dalloc(ctx, (double **)&p, 4 * g_swp_wgs + 4));
         HIPCHK(hipMemset(p, 0, sizeof(unsigned long long) * (4 * g_swp_wgs + 4)));
@@ -359,26 +143,20 @@ int upload_factor(admm_hip_ctx *ctx) {
         g_swp_base = p;
     }
 #endif
-    // subtree sharding: the exchange lists (see shard_pack_kernel) and the node masks
+
+    // (4) the upload
+    ctx->fuse_cut = fuse.n_fuse() ? fuse.cut : -1; ctx->n_fuse = fuse.n_fuse(); ctx->fuse_lds = fuse.lds;
+    ctx->n_fuse_bwd = fuse.n_fuse_bwd(); ctx->fuse_bwd_lds = fuse.bwd_lds;
+    if (fuse.n_fuse()) { TRY(upload(ctx, &ctx->d_fuse_rec, fuse.rec)); TRY(upload(ctx, &ctx->d_fuse_off, fuse.off)); }
+    if (fuse.n_fuse_bwd()) { TRY(upload(ctx, &ctx->d_fuse_bwd_rec, fuse.bwd_rec)); TRY(upload(ctx, &ctx->d_fuse_bwd_off, fuse.bwd_off)); }
+    TRY(upload_level_plans(ctx, own_levels, ctx->levels)); TRY(upload_level_plans(ctx, top_levels, ctx->levels_top));
     ctx->n_comm_top = ctx->n_comm_slots = 0;
     ctx->d_comm_top = ctx->d_comm_slots = nullptr; ctx->d_comm_mine = ctx->d_base_mask = ctx->d_keep_mask = nullptr; ctx->d_comm_buf = nullptr;
-    if (subtree) {
-        std::vector<int> top_nodes, slots; std::vector<unsigned char> mine, base(F.n), keep(F.n);
-        for (int i = 0; i < F.n; ++i) {
-            const int o = ctx->node_owner[i];
-            if (o < 0) top_nodes.push_back(i);
-            base[i] = keep[i] = (o == ctx->rank || (o < 0 && ctx->rank == 0)) ? 1 : 0;
-        }
-        for (int s2 = 0; s2 < ns; ++s2) if (ctx->sn_owner[s2] < 0)      // x of a top node comes from the lowest rank that computes it
-            for (int j = 0; j < F.sn[s2].ncols; ++j) keep[F.sn[s2].first + j] = top_provider[s2] == ctx->rank ? 1 : 0;
-        for (int s = 0; s < ns; ++s) {      // roots of the owned subtrees: their contribution rows feed the top
-            const int par = F.sn[s].parent;
-            if (ctx->sn_owner[s] < 0 || par < 0 || ctx->sn_owner[par] >= 0) continue;
-            for (int q = 0; q < F.sn[s].nrows; ++q) { slots.push_back((int)(F.sn[s].slot_off + q)); mine.push_back(ctx->sn_owner[s] == ctx->rank ? 1 : 0); }
-        }
-        ctx->n_comm_top = (int)top_nodes.size(); ctx->n_comm_slots = (int)slots.size();
-        TRY(upload(ctx, &ctx->d_comm_top, top_nodes)); TRY(upload(ctx, &ctx->d_comm_slots, slots)); TRY(upload(ctx, &ctx->d_comm_mine, mine));
-        TRY(upload(ctx, &ctx->d_base_mask, base)); TRY(upload(ctx, &ctx->d_keep_mask, keep));
+    if (subtree) {      // the exchange lists (see shard_pack_kernel) and the node masks
+        const admm_lib::ShardExchange E = admm_lib::plan_shard_exchange(F, ctx->sn_owner, ctx->node_owner, top_provider, ctx->rank);
+        ctx->n_comm_top = (int)E.top_nodes.size(); ctx->n_comm_slots = (int)E.slots.size();
+        TRY(upload(ctx, &ctx->d_comm_top, E.top_nodes)); TRY(upload(ctx, &ctx->d_comm_slots, E.slots)); TRY(upload(ctx, &ctx->d_comm_mine, E.mine));
+        TRY(upload(ctx, &ctx->d_base_mask, E.base)); TRY(upload(ctx, &ctx->d_keep_mask, E.keep));
         TRY(dalloc(ctx, &ctx->d_comm_buf, 3 * (size_t)std::max(1, ctx->n_comm_top + ctx->n_comm_slots)));
     }
     return ADMM_OK;

@@ -1,6 +1,6 @@
 // The host check of a fused backward subtree record (csrc/bwd_record.hpp bwd_record_check), compiled for the host so that
-// tests/test_sweep_subtree_bwd.py can hand it records without a GPU: the very same header is what upload.inc calls before it
-// uploads a record.
+// tests/test_sweep_subtree_bwd.py can hand it records without a GPU: the very same header is what sweep_plan.hpp calls on every
+// record it builds.
 #include "../admm-elastic-sca_amd/csrc/bwd_record.hpp"
 
 extern "C" {

@@ -1,4 +1,4 @@
-"""The bottom subtrees of the elimination tree swept by one launch per sweep, one workgroup per subtree (upload.inc fuse_subtrees,
+"""The bottom subtrees of the elimination tree swept by one launch per sweep, one workgroup per subtree (sweep_plan.hpp plan_fused_subtrees,
 solve_fwd_subtree_kernel): the same x, BIT FOR BIT, as the per-level launches (ADMM_HIP_SWEEP_FUSE=0) -- after one solve and after
 whole frames -- on the headline bar, the mixed scene and a two-rank subtree-sharded run on one GPU.  Every case also asserts from the
 sweep plan (ADMM_HIP_VERBOSE) that subtrees were fused at all, so that a comparison of the per-level path with itself cannot pass.

@@ -1,15 +1,15 @@
-"""The fused backward sweep over the bottom subtrees (upload.inc bwd_subtree_record, solve_bwd_kernel_subtree): the same x, BIT FOR
+"""The fused backward sweep over the bottom subtrees (sweep_plan.hpp bwd_subtree_record, solve_bwd_kernel_subtree): the same x, BIT FOR
 BIT, as the per-level backward launches under the same knobs (ADMM_HIP_SWEEP_FUSE_BWD=0: the forward sweep stays fused), on the scenes
 of tests/test_sweep_subtree_trees.py.
 
-Every GPU case first asserts from the sweep plan (ADMM_HIP_VERBOSE: one "plan fused_bwd" line per call of fuse_subtrees) that backward
+Every GPU case first asserts from the sweep plan (ADMM_HIP_VERBOSE: one "plan fused_bwd" line per call of upload_factor) that backward
 subtrees were fused at all and that the reference run fused none, so that a comparison of the per-level path with itself cannot
 pass; then three right-hand sides of checkers.solve_rhs solve to the same x bit for bit, and m_x / m_v are bitwise equal after two
 frames of ten iterations.
 
 The CPU test covers the host check of a record (csrc/bwd_record.hpp bwd_record_check, through tests/bwd_record_shim.cpp) only: a
 hand-written record passes; one out-of-range offset and, separately, one column written twice are refused.  The builder of the records is
-exercised by the GPU cases: upload.inc runs the same check on every record it builds and refuses to launch on a violation.
+exercised by the GPU cases: sweep_plan.hpp runs the same check on every record it builds and refuses to launch on a violation.
 """
 import ctypes as C
 import os

@@ -1,9 +1,9 @@
-"""The fused forward sweep over the bottom subtrees (upload.inc fuse_subtrees, solve_fwd_subtree_kernel) on elimination-tree shapes
+"""The fused forward sweep over the bottom subtrees (sweep_plan.hpp plan_fused_subtrees, solve_fwd_subtree_kernel) on elimination-tree shapes
 the structured bars of tests/test_sweep_subtree.py never give it: front rows fed by three or four children, children several levels
 below their parent, subtrees of different depths in one launch, members without contribution rows (a forest of disconnected
 bodies), eight-way trees, a narrow kernel cap, and irregular subtree shards.
 
-Every case first asserts from the sweep plan (ADMM_HIP_VERBOSE: one "plan fused" line per call of fuse_subtrees, its fields below)
+Every case first asserts from the sweep plan (ADMM_HIP_VERBOSE: one "plan fused" line per call of upload_factor, its fields below)
 that it reached the shape it exists for -- a case that fuses nothing fails -- and then checks
 
   * bitwise: the three right-hand sides of checkers.solve_rhs solve to the same x, bit for bit, as the per-level path
