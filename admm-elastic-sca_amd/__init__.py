@@ -87,6 +87,9 @@ class ReactionInfo(C.Structure):
 # admm_hip_contact: 64 bytes, the four bytes behind `node` are padding
 CONTACT_DTYPE = np.dtype(dict(names=["node", "f", "point", "depth"], formats=[np.int32, (np.float64, 3), (np.float64, 3), np.float64],
                               offsets=[0, 8, 32, 56], itemsize=64))
+# admm_hip_contact_owner: 64 bytes
+CONTACT_OWNER_DTYPE = np.dtype(dict(names=["node", "entry", "normal", "f_normal", "f_tangent"], formats=[np.int32, np.int32, (np.float64, 3), np.float64, (np.float64, 3)],
+                                    offsets=[0, 4, 8, 32, 40], itemsize=64))
 
 
 class GroupMoments(C.Structure):
@@ -166,6 +169,11 @@ def lib():
         L.admm_hip_get_contacts.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.admm_hip_contact_resultant.argtypes = [C.c_void_p, C.c_double, _dp, _dp, C.POINTER(C.c_int64)]
         L.admm_hip_reaction_query.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _ip, _dp]
+        L.admm_hip_enable_contact_attribution.argtypes = [C.c_void_p, C.c_int]
+        L.admm_hip_batch_contact_owner.argtypes = [C.c_void_p, C.c_int, _ip, _dp]
+        L.admm_hip_get_contact_owners.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.admm_hip_entry_resultants.argtypes = [C.c_void_p, C.c_double, _dp, C.c_int, _dp, C.POINTER(C.c_int64)]
+        L.admm_hip_attribution_query.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp]
         L.admm_hip_add_damping_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int)]
         L.admm_hip_set_damping.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
         L.admm_hip_get_group_moments.argtypes = [C.c_void_p, C.c_int, C.POINTER(GroupMoments)]
@@ -589,6 +597,24 @@ def reaction_query(w2, u, z, x, depth_min=1e-10, pivot=(0.0, 0.0, 0.0)):
     return dict(f=f, depth=depth, flag=flag.astype(bool), force=r6[:3].copy(), torque=r6[3:].copy())
 
 
+def attribution_query(before=None, after=None, f=None, normal=None):
+    """the contact attribution rule on the host (admm_hip_attribution_query; csrc/attribution.hpp, the device's bits; needs no GPU):
+    before, after [n][3]: a candidate before an entry's rule and behind it (before friction), f [n][3]: reactions (default: zeros) ->
+    dict(moved [n]: a coordinate's bits differ, normal [n][3]: (after - before) / its length, 0 where not moved, fn [n], ft [n][3]: f's
+    part along the normal and the rest).  normal [n][3] given: the split is about these normals, and before / after may be left out."""
+    first = before if before is not None else normal
+    n = np.ascontiguousarray(first, dtype=np.float64).reshape(-1, 3).shape[0]
+    arr = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(n, 3)
+    b, a, nin = arr(before), arr(after), arr(normal)
+    ff = np.zeros((n, 3)) if f is None else arr(f)
+    moved = np.zeros(n, np.int32); nr = np.zeros((n, 3)); fn = np.zeros(n); ft = np.zeros((n, 3))
+    ptr = lambda v: None if v is None else _d(v)
+    rc = lib().admm_hip_attribution_query(n, ptr(b), ptr(a), _d(ff), ptr(nin), _i(moved), _d(nr), _d(fn), _d(ft))
+    if rc:
+        raise AdmmHipError("admm_hip_attribution_query error %d" % rc)
+    return dict(moved=moved.astype(bool), normal=nr, fn=fn, ft=ft)
+
+
 def damping_query(m, x, v, dt, drag, internal):
     """the velocity filter of one damping group on the host (admm_hip_damping_query; csrc/damping.hpp, the device's bits; needs no GPU):
     m [n] (or a scalar): the nodes' masses, x, v [n][3], dt, the rates drag and internal in 1/s -> (v_out [n][3], moments: the dict of
@@ -796,7 +822,7 @@ class System:
 
     def collision_form(self):
         """which kernels the collision batches launch for the current list (admm_hip_debug_collision_form): 0 frictionless, 1 friction,
-        2 moving friction, 3 framed, 4 shell, 5 sheet self-collision, 6 side memory, 7 body self-collision"""
+        2 moving friction, 3 framed, 4 shell, 5 sheet self-collision, 6 side memory, 7 body self-collision, 8 contact attribution (0-8)"""
         f = C.c_int()
         self._chk(self.L.admm_hip_debug_collision_form(self.h, C.byref(f)))
         return f.value
@@ -1041,6 +1067,40 @@ class System:
         out = np.zeros(6); cnt = C.c_int64(0)
         self._chk(self.L.admm_hip_contact_resultant(self.h, float(depth_min), _d(pv), _d(out), C.byref(cnt)))
         return out[:3].copy(), out[3:].copy(), cnt.value
+
+    # ---- contact attribution: what a node touches (extension; include/admm_hip.h) ----
+    def enable_contact_attribution(self, on=True):
+        """every collision batch records, in every local step, the list entry that last moved each element's candidate and the direction
+        of that push (admm_hip_enable_contact_attribution; collision_form() reads 8 while on).  Before or after initialize(), between frames."""
+        self._chk(self.L.admm_hip_enable_contact_attribution(self.h, 1 if on else 0))
+
+    def batch_contact_owner(self, batch):
+        """-> (entry [n_local] int32, normal [n_local][3]) of one COLLISION batch, in read_local's order: the last entry of the list that
+        moved the element's candidate in the last local step (-1: none) and the unit direction of its push (0 where none)"""
+        n = self.local_elements(batch).size
+        entry = np.zeros(n, np.int32); normal = np.zeros((n, 3))
+        self._chk(self.L.admm_hip_batch_contact_owner(self.h, batch, _i(entry), _d(normal)))
+        return entry, normal
+
+    def contact_owners(self, depth_min=1e-10, capacity=None):
+        """-> the nodes of contacts(depth_min), in its order, as a structured array with the fields node, entry, normal, f_normal,
+        f_tangent: the owner entry and normal of the collision element that gives the node its depth, and the node's f_contact split
+        about that normal.  capacity as in contacts()."""
+        cap = self.n_nodes if capacity is None else int(capacity)
+        rec = np.zeros(max(cap, 0), CONTACT_OWNER_DTYPE); cnt = C.c_int64(0)
+        self._chk(self.L.admm_hip_get_contact_owners(self.h, float(depth_min), rec.ctypes.data_as(C.c_void_p) if cap > 0 else None, cap, C.byref(cnt)))
+        self.last_contact_count = cnt.value
+        return rec[:min(cnt.value, max(cap, 0))]
+
+    def entry_resultants(self, pivot=(0.0, 0.0, 0.0), depth_min=1e-10, n_entries=None):
+        """-> (force [n_entries + 1][3], torque [n_entries + 1][3] about `pivot`, count [n_entries + 1]): row q over the contacts whose
+        owner is entry q of the current shape list, the last row over those that nothing moved in the last local step (entry -1).
+        n_entries (default: the current list's length) must be that length."""
+        ne = self.n_collision_shapes() if n_entries is None else int(n_entries)
+        pv = np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
+        out = np.zeros((max(ne, 0) + 1, 6)); cnt = np.zeros(max(ne, 0) + 1, np.int64)
+        self._chk(self.L.admm_hip_entry_resultants(self.h, float(depth_min), _d(pv), ne, _d(out), cnt.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out[:, :3].copy(), out[:, 3:].copy(), cnt
 
     # ---- velocity damping per node group, applied after every frame (extension; include/admm_hip.h) ----
     def add_damping_group(self, node_first=0, node_count=None, drag=0.0, internal=0.0):

@@ -1,5 +1,6 @@
 // abi_reaction.inc -- C ABI: the reactions of the one-node constraints (COLLISION, ANCHOR) in the last frame, per element and per node,
-// the compact list of the nodes in contact and their resultant (kernels_reaction.hpp, reaction.hpp)
+// the compact list of the nodes in contact and their resultant (kernels_reaction.hpp, reaction.hpp); contact attribution (attribution.hpp):
+// the switch, the owner entry and normal per element and per contact, the per-entry resultants
 // (a part of the device translation unit admm_hip.hip: the kernels can live in one translation unit only)
 // Extension, no reference counterpart.  Nothing here writes x, v, u, z, the warm starts, the cost counters or the sides, and nothing
 // drops a captured graph: the kernels read the state and write buffers of their own.  Every launch and copy is asynchronous on the
@@ -164,5 +165,127 @@ int admm_hip_contact_resultant(admm_hip_ctx *ctx, double depth_min, const double
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (out6) for (int q = 0; q < 6; ++q) out6[q] = h[q];
     if (count) *count = c;
+    return ADMM_OK;
+}
+
+// ---- contact attribution (attribution.hpp; include/admm_hip.h "contact attribution") ---------------------------------------------------
+// The switch changes which kernel the collision batches launch (collision_plan.hpp: form 8), so it drops the captured graphs like a setter
+// that changes the form (abi_setup.inc: push_shapes); the reports below read the record form 8 writes and change nothing a frame reads.
+int admm_hip_enable_contact_attribution(admm_hip_ctx *ctx, int on) {
+    if (!ctx) return ADMM_ERR_ARG;
+    const bool want = on != 0;
+    if (want && ctx->finalized && ctx->device_id >= 0) { TRY(attribution_allocate(ctx)); TRY(attribution_fill(ctx)); }      // (before finalize: finalize does both)
+    if (want != ctx->attribution) drop_iteration_graphs(ctx);
+    ctx->attribution = want;
+    return ADMM_OK;
+}
+
+static int require_attribution(admm_hip_ctx *ctx, const char *who) {
+    TRY(require_reactions(ctx, who));
+    if (!ctx->attribution) return fail(ctx, ADMM_ERR_STATE, "%s: contact attribution is off (admm_hip_enable_contact_attribution)", who);
+    return ADMM_OK;
+}
+
+// the reports' buffers and, parallel to the gather's collision CSR, where every entry's element sits in the record; created by the first report
+static int ensure_attribution_buffers(admm_hip_ctx *ctx) {
+    using namespace admm_dev;
+    TRY(ensure_reaction_buffers(ctx));
+    if (ctx->at_ready) return ADMM_OK;
+    const int n = ctx->n_nodes, nblk = std::max(energy_blocks(n), 1), rows = ADMM_MAX_SHAPES + 1;
+    if (!ctx->d_at_rec) { OwnerRecord *r = nullptr; TRY(dalloc(ctx, &r, (size_t)std::max(n, 1))); ctx->d_at_rec = r; }
+    if (!ctx->d_at_blk) TRY(dalloc(ctx, &ctx->d_at_blk, 2 * (size_t)rows * nblk));
+    if (!ctx->d_at_tot) TRY(dalloc(ctx, &ctx->d_at_tot, (size_t)rows));
+    if (!ctx->d_at_perm) TRY(dalloc(ctx, &ctx->d_at_perm, (size_t)std::max(n, 1)));
+    if (!ctx->d_at_part) TRY(dalloc(ctx, &ctx->d_at_part, 6 * (size_t)(nblk + rows)));
+    if (!ctx->d_at_out) TRY(dalloc(ctx, &ctx->d_at_out, 6 * (size_t)rows));
+    if (!ctx->d_at_csr) {
+        std::vector<NodeCsrEntry> entries;      // (the order of ensure_reaction_buffers' collision entries: the two CSRs share ptr)
+        for (const Batch &b : ctx->batches) if (b.kind == ADMM_KIND_COLLISION)
+            for (int el = 0; el < b.n_local; ++el) entries.push_back({b.idx[b.local[el]], b.at_off + el, 1});
+        TRY(upload(ctx, &ctx->d_at_csr, build_node_csr(n, entries).off));
+    }
+    ctx->at_ready = true;
+    return ADMM_OK;
+}
+
+// behind launch_node_reactions and launch_compaction(depth_min, *): the owner records of the same contacts, in the same places
+static int launch_owner_records(admm_hip_ctx *ctx, double depth_min) {
+    using namespace admm_dev;
+    const int n = ctx->n_nodes, nblk = reaction_blocks(n);
+    const int *off = ctx->d_rx_blk + std::max(nblk, 1);
+    const NodeCsr &cc = ctx->rx_csr[0];
+    if (nblk) hipLaunchKernelGGL(contact_owner_scatter_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, (const double *)ctx->d_rx_node, depth_min, off, (long long)n,
+                                 (const int *)cc.ptr, (const long long *)cc.off, (const int *)cc.stride, (const long long *)ctx->d_at_csr, (const double *)ctx->d_rx_el,
+                                 (const int *)ctx->d_at_owner, (const double *)ctx->d_at_normal, ctx->at_total, (OwnerRecord *)ctx->d_at_rec);
+    HIPCHK(hipGetLastError());
+    return ADMM_OK;
+}
+
+int admm_hip_batch_contact_owner(admm_hip_ctx *ctx, int batch, int32_t *entry, double *normal) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (batch < 0 || batch >= (int)ctx->batches.size()) return ADMM_ERR_ARG;
+    const Batch &b = ctx->batches[batch];
+    if (b.kind != ADMM_KIND_COLLISION) return fail(ctx, ADMM_ERR_UNSUPPORTED, "batch_contact_owner: batch %d (kind %d) is not a collision batch", batch, b.kind);
+    TRY(require_attribution(ctx, "batch_contact_owner"));
+    HIPCHK(hipSetDevice(ctx->device_id));
+    const int n = b.n_local;
+    std::vector<double> t(3 * (size_t)std::max(n, 1), 0.0);
+    if (n && entry) HIPCHK(hipMemcpyAsync(entry, ctx->d_at_owner + b.at_off, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (n && normal) for (int j = 0; j < 3; ++j)
+        HIPCHK(hipMemcpyAsync(t.data() + (size_t)j * n, ctx->d_at_normal + (size_t)j * (size_t)ctx->at_total + b.at_off, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (normal) to_element_major(t, 3, n, normal);
+    return ADMM_OK;
+}
+
+int admm_hip_get_contact_owners(admm_hip_ctx *ctx, double depth_min, admm_hip_contact_owner *records, int64_t capacity, int64_t *count) {
+    if (!ctx) return ADMM_ERR_ARG;
+    if (!(depth_min >= 0.0) || capacity < 0 || (capacity && !records)) return fail(ctx, ADMM_ERR_ARG, "get_contact_owners: depth_min must be >= 0 (got %g), capacity >= 0 and records given with it", depth_min);
+    TRY(require_attribution(ctx, "get_contact_owners"));
+    TRY(ensure_attribution_buffers(ctx));
+    TRY(launch_node_reactions(ctx, nullptr));
+    TRY(launch_compaction(ctx, depth_min, false));
+    TRY(launch_owner_records(ctx, depth_min));
+    static_assert(sizeof(admm_hip_contact_owner) == sizeof(admm_dev::OwnerRecord), "admm_hip_contact_owner is the device's record");
+    const size_t want = (size_t)std::min<int64_t>(capacity, ctx->n_nodes);      // (as admm_hip_get_contacts: the count is not known before the synchronisation)
+    std::vector<admm_hip_contact_owner> tmp(want);
+    long long c = 0;
+    if (want) HIPCHK(hipMemcpyAsync(tmp.data(), ctx->d_at_rec, sizeof(admm_hip_contact_owner) * want, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&c, ctx->d_rx_count, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const size_t k = (size_t)std::min<long long>(c, (long long)want);
+    if (k) std::memcpy(records, tmp.data(), sizeof(admm_hip_contact_owner) * k);
+    if (count) *count = c;
+    return ADMM_OK;
+}
+
+int admm_hip_entry_resultants(admm_hip_ctx *ctx, double depth_min, const double pivot[3], int n_entries, double *out, int64_t *count) {
+    using namespace admm_dev;
+    if (!ctx) return ADMM_ERR_ARG;
+    if (!(depth_min >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "entry_resultants: depth_min must be >= 0, got %g", depth_min);
+    if (n_entries != ctx->shapes.n || n_entries > ADMM_MAX_SHAPES) return fail(ctx, ADMM_ERR_ARG, "entry_resultants: %d entries given, the shape list has %d", n_entries, ctx->shapes.n);
+    TRY(require_attribution(ctx, "entry_resultants"));
+    TRY(ensure_attribution_buffers(ctx));
+    TRY(launch_node_reactions(ctx, nullptr));
+    TRY(launch_compaction(ctx, depth_min, true));
+    TRY(launch_owner_records(ctx, depth_min));
+    const int rows = n_entries + 1, nblk = std::max(energy_blocks(ctx->n_nodes), 1), n_part = nblk + ADMM_MAX_SHAPES + 1;
+    int *cnt = ctx->d_at_blk, *off = ctx->d_at_blk + (size_t)(ADMM_MAX_SHAPES + 1) * nblk;
+    const long long *total = ctx->d_at_tot;
+    const OwnerRecord *orec = (const OwnerRecord *)ctx->d_at_rec;
+    const double p0 = pivot ? pivot[0] : 0.0, p1 = pivot ? pivot[1] : 0.0, p2 = pivot ? pivot[2] : 0.0;
+    hipLaunchKernelGGL(entry_count_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, orec, rows, nblk, cnt);
+    hipLaunchKernelGGL(entry_scan_kernel, dim3(rows), dim3(RX_SCAN), 0, ctx->stream, nblk, (const int *)cnt, off, ctx->d_at_tot);
+    hipLaunchKernelGGL(entry_place_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, orec, rows, nblk, (const int *)off, total, ctx->d_at_perm);
+    hipLaunchKernelGGL(entry_partial_kernel, dim3(nblk + rows), dim3(ENERGY_BLOCK), 0, ctx->stream, (const ContactRecord *)ctx->d_rx_rec, (const int *)ctx->d_at_perm, rows, total, p0, p1, p2,
+                       n_part, ctx->d_at_part);
+    hipLaunchKernelGGL(entry_reduce_kernel, dim3(6 * rows), dim3(ENERGY_REDUCE), 0, ctx->stream, rows, total, n_part, (const double *)ctx->d_at_part, ctx->d_at_out);
+    HIPCHK(hipGetLastError());
+    std::vector<double> h(6 * (size_t)rows); std::vector<long long> c((size_t)rows);
+    HIPCHK(hipMemcpyAsync(h.data(), ctx->d_at_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(c.data(), ctx->d_at_tot, sizeof(long long) * c.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (out) std::copy(h.begin(), h.end(), out);
+    if (count) for (int q = 0; q < rows; ++q) count[q] = c[q];
     return ADMM_OK;
 }

@@ -770,6 +770,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     for (size_t i = 0; i < ctx->meshes.size(); ++i) ctx->meshes[i].side_row = plan.side_row[i];
     if (ctx->device_id < 0) ctx->h_side.assign((size_t)ctx->n_side_slots * (size_t)ctx->n_nodes, 0);
     if (ctx->device_id >= 0) TRY(upload_all(ctx, plan));
+    if (ctx->device_id >= 0 && ctx->attribution) { TRY(attribution_allocate(ctx)); TRY(attribution_fill(ctx)); }      // (switched on before finalize)
     ctx->finalized = true;
     return ADMM_OK;
 }

@@ -246,7 +246,7 @@ int admm_hip_debug_graph_state(admm_hip_ctx *ctx, int *iter_graph, int *frame_gr
     return ADMM_OK;
 }
 
-// which kernels the collision batches launch for the current list (launch.inc: collision_form)
+// which kernels the collision batches launch for the current list (launch.inc: collision_form); 8 while contact attribution is on
 int admm_hip_debug_collision_form(admm_hip_ctx *ctx, int *form) {
     if (!ctx || !form) return ADMM_ERR_ARG;
     *form = collision_form(ctx).form;

@@ -18,7 +18,8 @@ namespace admm_lib {
 struct MeshFacts { bool body; double thickness; bool self_collision; double side_reach, body_self_r, body_mu; bool has_vel; };
 
 // form: 0 the frictionless kernels, 1 the friction form, 2 its moving form, 3 the framed form, 4 the shell form, 5 the self-collision
-// form, 6 the side-memory form, 7 the body self-collision form -- the highest whose trigger an entry of the list sets off:
+// form, 6 the side-memory form, 7 the body self-collision form -- the highest whose trigger an entry of the list sets off (8, the
+// attributed form, is set off by the context's switch, below):
 //   1  an entry carries a friction coefficient
 //   2  an entry with a coefficient has a rigid motion that is not all zero or names a mesh with vertex velocities; or an entry, whatever
 //      its own coefficient, names a body surface that has one
@@ -28,11 +29,13 @@ struct MeshFacts { bool body; double thickness; bool self_collision; double side
 // own_launch: the collision batches go out in a launch of their own (launch.inc: launch_collision_mesh) instead of as a segment of
 // project_multi_kernel or through project_collision_kernel: any mesh registered, named or not, or friction, or a framed entry or a box.
 // A mesh that no entry names triggers nothing; neither do the entries from S.n on.
+// attribution (admm_hip_enable_contact_attribution; the context's switch, not a property of the list): form 8 whatever the list holds,
+// always in a launch of its own; sided keeps its meaning, so the latch still runs by its own trigger.
 struct CollisionForm { int form; bool own_launch, sided; };
 
 // facts(id) -> the MeshFacts of mesh id, asked for the meshes the list names only (0 <= id < n_meshes): a caller with records of its
 // own builds no table per launch
-template <class FactsOf> CollisionForm collision_form_of(const admm_dev::ShapeTable &S, int n_meshes, FactsOf &&facts) {
+template <class FactsOf> CollisionForm collision_form_of(const admm_dev::ShapeTable &S, int n_meshes, FactsOf &&facts, bool attribution = false) {
     bool friction = false, moving = false, framed = false, shell = false, self = false, sided = false, bodyself = false;
     for (int q = 0; q < S.n; ++q) {
         const bool mu = S.mu[q] > 0.0;
@@ -49,6 +52,7 @@ template <class FactsOf> CollisionForm collision_form_of(const admm_dev::ShapeTa
         bodyself |= m.body_self_r > 0.0;
     }
     const int form = bodyself ? 7 : sided ? 6 : self ? 5 : shell ? 4 : framed ? 3 : moving ? 2 : friction ? 1 : 0;
+    if (attribution) return CollisionForm{8, true, sided};
     return CollisionForm{form, n_meshes > 0 || friction || framed, sided};
 }
 

@@ -66,6 +66,7 @@ struct Batch {
     double *d_gg = nullptr, *d_gstress = nullptr, *d_gvol = nullptr; int *d_gcnt = nullptr; long long gr_cf_off = 0;
     std::vector<double> G;                // [12][n_local] selector block per element, corners in device order
     long long rx_off = 0;                 // reactions (abi_reaction.inc): where a collision / anchor batch's rows sit in the context's d_rx_el
+    long long at_off = 0;                 // contact attribution (abi_reaction.inc): where a collision batch's elements sit in the context's d_at_owner / d_at_normal
     long long aa_off_z = 0, aa_off_u = 0; // Anderson acceleration (abi_anderson.inc): where the batch's z and u sit in every state-sized buffer
     // ---- ADMM_KIND_GENERIC (user-defined forces): selector rows as CSR over the batch's rows
     std::vector<int64_t> g_elem_row;      // [n_total + 1] first batch row of every element
@@ -285,6 +286,14 @@ struct admm_hip_ctx {
     // the compaction's block counts, then their offsets; d_rx_count: the contacts' count; d_rx_rec [n_nodes] records; d_rx_part: the
     // resultant's partials [6][blocks], then its six totals
     bool rx_ready = false; double *d_rx_el = nullptr, *d_rx_node = nullptr, *d_rx_part = nullptr; int *d_rx_blk = nullptr; long long *d_rx_count = nullptr; void *d_rx_rec = nullptr; admm_lib::NodeCsr rx_csr[2];
+    // contact attribution (admm_hip_enable_contact_attribution; abi_reaction.inc, attribution.hpp; off by default).  attribution: the
+    // switch, which makes every collision batch launch form 8 (collision_plan.hpp).  The record, allocated by the switch once finalized or
+    // by finalize, never by admm_hip_step: at_total elements over the collision batches (a batch's slice at Batch::at_off), d_at_owner
+    // [at_total] the last mover of every element (-1: none), d_at_normal SoA [3][at_total] its normal.  The reports' buffers, created by the
+    // first report: d_at_rec [n_nodes] owner records, d_at_blk the per-entry block counts, then their offsets, d_at_tot the entries'
+    // counts, d_at_perm the contacts sorted by entry, d_at_part the per-entry partials [6][blocks], d_at_out the rows
+    bool attribution = false, at_ready = false; long long at_total = 0; int *d_at_owner = nullptr; double *d_at_normal = nullptr;
+    void *d_at_rec = nullptr; int *d_at_blk = nullptr, *d_at_perm = nullptr; long long *d_at_tot = nullptr, *d_at_csr = nullptr; double *d_at_part = nullptr, *d_at_out = nullptr;
     // velocity damping per node group (abi_damping.inc, kernels_damping.hpp, damping.hpp; no group = off, the default).  damp_groups: the
     // caller's groups in the order they were added; rate_dirty: the device's rate entry is older than drag / internal.  Device side, created
     // by upload_all when there is a group: the block -> (group, first node) table, the groups' ranges, their rates (written by

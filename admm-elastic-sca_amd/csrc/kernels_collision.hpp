@@ -3,8 +3,8 @@
 //
 // One element per node, D = I, one lane per element: the point p = Dx + u is pushed out of every entry of the shape list that it
 // penetrates, in list order (CollisionFloor.hpp:51-58, CollisionSphere.hpp:50-66, CollisionCylinder.hpp:48-66), then u += Dx - p, z = p
-// and the element's share of the right-hand side.  The list's composition selects one of eight forms (launch.inc collision_form); each
-// form knows everything the forms below it know and gives their bits on their lists (tests/test_collision_form_ladder.py holds every
+// and the element's share of the right-hand side.  The list's composition selects one of eight forms, the context's attribution switch
+// a ninth (launch.inc collision_form); each form knows everything the forms below it know and gives their bits on their lists (tests/test_collision_form_ladder.py holds every
 // form to the bits of every form below it, on lists that a far trigger entry moves up).  A form is a kernel of its own, not a flag inside
 // one: a list launches exactly the kernel of its form, and the lower forms keep their smaller register footprint.
 //
@@ -52,11 +52,17 @@
 //      bounded by R that passes over what is near the node in the rest shape, the unsigned rule outside, the mirror push for a node that
 //      has crossed the skin (no translation, no frame: refused on a body surface) --, an interior node skips the entry.  reach,
 //      side_slot, bnd, side: null where no mesh has memory.
+//   8  project_collision_attributed_kernel<MESH>: contact attribution (admm_hip_enable_contact_attribution; collision_plan.hpp: the context's
+//      switch, whatever the list holds).  Everything form 7 does, and per element the last entry that moved the candidate -- the bits of
+//      the point behind the entry's rule and before friction differ from `before` -- with the unit direction of that push (attribution.hpp),
+//      stored beside u and z in every local step, owner -1 with a zero normal included.  Entries that `continue` record nothing.  z, u
+//      and the slot keep the bits of the form the list would otherwise select.  It runs in contexts without the features of forms 4 to 7:
+//      which table may be null is listed at project_collision_form.
 //
 // In every form the loads of an element (idx, dst, w2h2, x, x0, u) are issued together at the top, and every load of an entry before
 // its rule: behind the u / z stores a load would wait for them.  Forms 0 to 2 are short kernels of their own built from the pieces
 // below (they push through collide_analytic, and form 1 applies the rule at rest to every analytic entry without a mu > 0 early-out);
-// forms 3 to 7 are strictly nested and are instantiations of one body, project_collision_form<FORM, MESH>.  Resources and timings of
+// forms 3 to 8 are strictly nested and are instantiations of one body, project_collision_form<FORM, MESH>.  Resources and timings of
 // this layout beside the one with a written-out kernel per form: profiles/collision_forms/.
 
 // the device tables of a collision launch, filled once on the host (launch.inc collision_tables); null means what the forms above say
@@ -71,6 +77,9 @@ struct CollisionTables {
     const double *reach; const int *side_slot; const int *const *bnd; int *side; int side_stride;      // side_stride = n_nodes
     const double *bself; const double *const *rest;
     double dt;
+    // form 8 only (launch.inc launch_collision_mesh fills them per batch; null in every other launch): the batch's slice of the contact
+    // attribution record, one owner per element and its normal, SoA [3][at_stride]
+    int *owner; double *normal; long long at_stride;
 };
 
 // the traversal stack of mesh_query.hpp's searches: the lane's column of an LDS array int[MAX_DEPTH][LOCAL_BLOCK]
@@ -271,12 +280,24 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_friction_moving
     collision_store(b, e, c);
 }
 
-// ---- forms 3 to 7 -----------------------------------------------------------------------------------------------------------------
+// ---- forms 3 to 8 -----------------------------------------------------------------------------------------------------------------
 // what a form adds to the one below it stands under if constexpr (FORM >= ...); the tests of a table for null and of what is uniform
 // across the wave are run-time tests
+//
+// Form 8 (contact attribution) is launched on lists of EVERY lower form, in contexts that lack the features of forms 4 to 7, so it meets
+// device tables that are null.  Per table read under FORM >= 4, in form 8:
+//   thick, mm   read in the mesh branch only (MESH: the context has meshes), and upload.inc upload_meshes fills both for every context
+//               with a mesh: reached only where filled
+//   self        tested for null (as in forms 6 and 7)
+//   vid         tested for null (as in forms 6 and 7); mm[mesh].cid is read by closest_within_excluding only for a node of a sheet that
+//               collides with itself, whose vid upload_meshes filled, and cid is uploaded for every mesh
+//   reach       tested for null in remembered_side (as in form 7); side_slot, side: read only behind reach[mesh] > 0, and upload_meshes
+//               fills reach, side_slot, bnd and side together; bnd: read only behind a side != 0, which implies the same
+//   bself       tested for null (form 7 does not: it implies a self-colliding body); rest: read only behind bself[3 mesh] > 0, and
+//               upload_meshes fills bself and rest together, rest[mesh] for exactly the meshes with bself[3 mesh] > 0
 template <int FORM, bool MESH>
 __device__ __forceinline__ void project_collision_form(const BatchDev &b, const double *__restrict__ x, const CollisionTables &T, int *stack_col) {
-    static_assert(FORM >= 3 && FORM <= 7 && (MESH || FORM == 3), "forms 4 and up imply meshes");
+    static_assert(FORM >= 3 && FORM <= 8 && (MESH || FORM == 3 || FORM == 8), "forms 4 to 7 imply meshes");
     const int e = b.e0 + (int)blockIdx.x * LOCAL_BLOCK + threadIdx.x;
     if (e >= b.e1) return;
     CollisionElem c;
@@ -287,6 +308,8 @@ __device__ __forceinline__ void project_collision_form(const BatchDev &b, const 
     int vi_own = -1;      // the node's vertex id on the self-colliding surface that owns it (-1: none)
     if constexpr (FORM == 5) vi_own = T.vid[c.id];
     if constexpr (FORM >= 6) vi_own = T.vid ? T.vid[c.id] : -1;
+    int at_q = -1;                                // form 8: the last entry that moved the candidate and how far (attribution.hpp)
+    double at_d[3] = {0.0, 0.0, 0.0};
     const int ns = shapes->n;
     for (int q = 0; q < ns; ++q) {
         const double before[3] = {c.p[0], c.p[1], c.p[2]};
@@ -303,7 +326,8 @@ __device__ __forceinline__ void project_collision_form(const BatchDev &b, const 
             const admm_mesh::MeshDev m = T.meshes[mi];
             const bool mine = own >= 0 && m.owner == own;
             bool bs = false;      // the node's body owns the mesh and its surface collides with itself
-            if constexpr (FORM >= 7) bs = mine && T.bself[3 * mi] > 0.0;
+            if constexpr (FORM == 7) bs = mine && T.bself[3 * mi] > 0.0;
+            if constexpr (FORM >= 8) bs = mine && T.bself && T.bself[3 * mi] > 0.0;
             if constexpr (FORM <= 4) { if (mine) continue; }
             else if constexpr (FORM == 5) { if (mine && !T.self[mi]) continue; }
             else { if (mine && !bs && !(T.self && T.self[mi])) continue; }
@@ -343,9 +367,18 @@ __device__ __forceinline__ void project_collision_form(const BatchDev &b, const 
             if (framed) admm_frame::to_world(f, l, c.p); else { c.p[0] = l[0]; c.p[1] = l[1]; c.p[2] = l[2]; }
             vhit = mesh_contact_velocity(m, T.mm[mi], qq, h, f, framed, mu, vi);
         }
+        if constexpr (FORM >= 8) {      // the point behind the rule, before friction
+            if (admm_attribution::moved(before, c.p)) { at_q = q; at_d[0] = c.p[0] - before[0]; at_d[1] = c.p[1] - before[1]; at_d[2] = c.p[2] - before[2]; }
+        }
         friction_moving(shapes->motion[q], T.dt, before, c.p, c.x0, vhit, vi, mu);
     }
     collision_store(b, e, c);
+    if constexpr (FORM >= 8) {          // every local step writes the record, owner -1 with a zero normal included
+        double nr[3] = {0.0, 0.0, 0.0};
+        if (at_q >= 0) admm_attribution::normal_of(at_d, nr);
+        T.owner[e] = at_q;
+        T.normal[e] = nr[0]; T.normal[(size_t)T.at_stride + e] = nr[1]; T.normal[2 * (size_t)T.at_stride + e] = nr[2];
+    }
 }
 
 template <bool MESH>
@@ -368,6 +401,13 @@ __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_sided_kernel(Ba
 __global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_bodyself_kernel(BatchDev b, const double *__restrict__ x, const CollisionTables T) {
     __shared__ int stack[admm_mesh::MAX_DEPTH][LOCAL_BLOCK];
     project_collision_form<7, true>(b, x, T, &stack[0][threadIdx.x]);
+}
+
+// form 8: everything form 7 knows, and the record of the last mover (attribution.hpp) beside the u / z stores
+template <bool MESH>
+__global__ __launch_bounds__(LOCAL_BLOCK) void project_collision_attributed_kernel(BatchDev b, const double *__restrict__ x, const CollisionTables T) {
+    __shared__ int stack[MESH ? admm_mesh::MAX_DEPTH : 1][LOCAL_BLOCK];
+    project_collision_form<8, MESH>(b, x, T, &stack[0][threadIdx.x]);
 }
 
 // the latch of side memory (mesh_query.hpp side_latch), once per frame from the frame-start x, eager at the start of admm_hip_step

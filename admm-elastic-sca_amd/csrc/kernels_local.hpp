@@ -33,6 +33,7 @@
 #include "mesh_query.hpp"
 #include "friction.hpp"
 #include "frame.hpp"
+#include "attribution.hpp"
 #include "../../include/admm_kinds.h"
 
 namespace admm_dev {

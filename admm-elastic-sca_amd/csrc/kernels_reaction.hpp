@@ -29,9 +29,26 @@
 // Cost: not measured, no timing claimed.  Expected to be bound by memory: an element reads 84 B (idx, w2, u, z, its node's x) and writes
 // 56 B; a node's gather reads its CSR bounds, a 12 B entry and 56 B per incident element and writes 80 B; the count reads 8 B per node,
 // the scatter 64 B per node in contact and writes as much.
+//
+// Contact attribution (attribution.hpp; admm_hip_get_contact_owners, admm_hip_entry_resultants; only while the switch is on).  None of the
+// kernels above changes or is launched differently; these run behind them, no atomics, fixed orders:
+//   contact_owner_scatter_kernel  contact_scatter_kernel's flags and places again; a node in contact walks its collision entries by the
+//                           gather's rule (the largest depth, the first on ties) and takes the winning element's owner and normal from the
+//                           record form 8 wrote, then splits the node's f_contact about that normal: one 64-byte OwnerRecord per contact
+//   entry_count_kernel      one wave per ENERGY_BLOCK = 64 contacts k < count: per row q (an entry of the list, the last row: owner -1) the
+//                           number of the block's contacts with that entry, by __popcll(__ballot)
+//   entry_scan_kernel       one wave per row: contact_scan_kernel's scan of the row's block counts -> block offsets and the row's total
+//   entry_place_kernel      the count kernel's flags again: perm[(the totals of the rows before) + block offset + rank in the wave] = k, the
+//                           contacts sorted by row, ascending k inside a row
+//   entry_partial_kernel    one wave per 64 consecutive contacts OF ONE ROW (a block finds its row from the totals; the blocks of row q start
+//                           at sum over q' < q of ceil(total[q'] / 64)): contact_resultant_kernel's six terms and block sums, the row's last
+//                           block padded with +0.0
+//   entry_reduce_kernel     one workgroup per (row, component): the row's partials in energy_reduce_kernel's order -- so a row is exactly the
+//                           two-stage sum of reaction.hpp over the contacts with that entry
 #pragma once
 #include "kernels_energy.hpp"
 #include "reaction.hpp"
+#include "attribution.hpp"
 
 namespace admm_dev {
 
@@ -148,6 +165,139 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void contact_resultant_kernel(const l
     }
 #pragma unroll
     for (int q = 0; q < 6; ++q) track_block_sum(t[q], &partial[(size_t)q * n_blocks + blockIdx.x]);
+}
+
+// ---- contact attribution ------------------------------------------------------------------------------------------------------------
+struct OwnerRecord { int node; int entry; double normal[3], f_normal, f_tangent[3]; };      // = admm_hip_contact_owner
+static_assert(sizeof(OwnerRecord) == 64, "the record is 64 bytes");
+
+// el, ptr_c / off_c / stride_c: the gather's element buffer and its collision CSR; at_idx[k]: where entry k's element sits in owner and in
+// every row of normal (SoA [3][at_stride])
+__global__ __launch_bounds__(RX_BLOCK) void contact_owner_scatter_kernel(const int n_nodes, const double *__restrict__ nodes, const double depth_min, const int *__restrict__ blk_off,
+                                                                         const long long capacity, const int *__restrict__ ptr_c, const long long *__restrict__ off_c,
+                                                                         const int *__restrict__ stride_c, const long long *__restrict__ at_idx, const double *__restrict__ el,
+                                                                         const int *__restrict__ owner, const double *__restrict__ normal, const long long at_stride,
+                                                                         OwnerRecord *__restrict__ rec) {
+    __shared__ int wave_count[RX_WAVES];
+    const int i = (int)blockIdx.x * RX_BLOCK + threadIdx.x;
+    const size_t n = (size_t)n_nodes;
+    const double d = i < n_nodes ? nodes[6 * n + i] : 0.0;
+    const bool c = i < n_nodes && admm_reaction::in_contact(d, depth_min);
+    const unsigned long long m = __ballot(c);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_count[wave] = __popcll(m);
+    __syncthreads();
+    if (!c) return;
+    long long place = blk_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) place += wave_count[w];
+    if (place >= capacity) return;
+    double depth = 0.0;
+    int win = -1;      // (a node in contact has an entry with d > 0)
+    for (int k = ptr_c[i], k1 = ptr_c[i + 1]; k < k1; ++k) {
+        const double dk = el[off_c[k] + 3 * (size_t)stride_c[k]];
+        if (dk > depth) { depth = dk; win = k; }
+    }
+    OwnerRecord r;
+    r.node = i; r.entry = -1; r.normal[0] = r.normal[1] = r.normal[2] = 0.0;
+    if (win >= 0) {
+        const long long a = at_idx[win];
+        r.entry = owner[a];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) r.normal[j] = normal[(size_t)j * (size_t)at_stride + a];
+    }
+    const double f[3] = {nodes[3 * (size_t)i], nodes[3 * (size_t)i + 1], nodes[3 * (size_t)i + 2]};
+    admm_attribution::split(f, r.normal, r.f_normal, r.f_tangent);
+    rec[place] = r;
+}
+
+// the row of contact k: its entry, the last row n_rows - 1 for owner -1 (and for an entry beyond the list, which the record cannot hold)
+__device__ __forceinline__ int entry_row(const OwnerRecord *__restrict__ rec, const long long k, const int n_rows) {
+    const int q = rec[k].entry;
+    return (q >= 0 && q < n_rows - 1) ? q : n_rows - 1;
+}
+
+// blk_count [n_rows][n_blocks]
+__global__ __launch_bounds__(ENERGY_BLOCK) void entry_count_kernel(const long long *__restrict__ count, const OwnerRecord *__restrict__ rec, const int n_rows, const int n_blocks,
+                                                                   int *__restrict__ blk_count) {
+    const long long k = (long long)blockIdx.x * ENERGY_BLOCK + threadIdx.x;
+    const int row = k < *count ? entry_row(rec, k, n_rows) : -1;
+    for (int q = 0; q < n_rows; ++q) {      // (uniform: every lane runs every row)
+        const unsigned long long m = __ballot(row == q);
+        if (threadIdx.x == 0) blk_count[(size_t)q * n_blocks + blockIdx.x] = __popcll(m);
+    }
+}
+
+// row blockIdx.x: exclusive scan of its n_blocks counts -> blk_off, total[row]; one wave
+__global__ __launch_bounds__(RX_SCAN) void entry_scan_kernel(const int n_blocks, const int *__restrict__ blk_count, int *__restrict__ blk_off, long long *__restrict__ total) {
+    const int lane = threadIdx.x;
+    const int *cnt = blk_count + (size_t)blockIdx.x * n_blocks;
+    int *off = blk_off + (size_t)blockIdx.x * n_blocks;
+    int carry = 0;
+    for (int base = 0; base < n_blocks; base += RX_SCAN) {
+        const int i = base + lane;
+        const int v = i < n_blocks ? cnt[i] : 0;
+        int incl = v;
+#pragma unroll
+        for (int d = 1; d < RX_SCAN; d <<= 1) { const int o = __shfl_up(incl, d, RX_SCAN); if (lane >= d) incl += o; }
+        if (i < n_blocks) off[i] = carry + incl - v;
+        carry += __shfl(incl, RX_SCAN - 1, RX_SCAN);
+    }
+    if (lane == 0) total[blockIdx.x] = carry;
+}
+
+// perm [count]: the contacts sorted by row
+__global__ __launch_bounds__(ENERGY_BLOCK) void entry_place_kernel(const long long *__restrict__ count, const OwnerRecord *__restrict__ rec, const int n_rows, const int n_blocks,
+                                                                   const int *__restrict__ blk_off, const long long *__restrict__ total, int *__restrict__ perm) {
+    const long long k = (long long)blockIdx.x * ENERGY_BLOCK + threadIdx.x;
+    const int row = k < *count ? entry_row(rec, k, n_rows) : -1;
+    long long base = 0;
+    for (int q = 0; q < n_rows; ++q) {
+        const unsigned long long m = __ballot(row == q);
+        if (row == q) perm[base + blk_off[(size_t)q * n_blocks + blockIdx.x] + __popcll(m & ((1ull << threadIdx.x) - 1ull))] = (int)k;
+        base += total[q];
+    }
+}
+
+// partial [6][n_part]: block B is block B - (the blocks of the rows before) of its row
+__global__ __launch_bounds__(ENERGY_BLOCK) void entry_partial_kernel(const ContactRecord *__restrict__ rec, const int *__restrict__ perm, const int n_rows, const long long *__restrict__ total,
+                                                                     const double p0, const double p1, const double p2, const int n_part, double *__restrict__ partial) {
+    long long base = 0, blk0 = 0;
+    int row = -1;
+    for (int q = 0; q < n_rows; ++q) {      // (uniform across the block)
+        const long long nb = (total[q] + ENERGY_BLOCK - 1) / ENERGY_BLOCK;
+        if ((long long)blockIdx.x < blk0 + nb) { row = q; break; }
+        blk0 += nb; base += total[q];
+    }
+    if (row < 0) return;                    // beyond the last row's blocks: nobody reads this partial
+    const long long r = ((long long)blockIdx.x - blk0) * ENERGY_BLOCK + threadIdx.x;
+    double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (r < total[row]) {
+        const double pivot[3] = {p0, p1, p2};
+        const ContactRecord c = rec[perm[base + r]];
+        admm_reaction::resultant_terms(c.f, c.point, pivot, t);
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) track_block_sum(t[q], &partial[(size_t)q * n_part + blockIdx.x]);
+}
+
+// workgroup (row, component) = (blockIdx.x / 6, blockIdx.x % 6): out[row][component], energy_reduce_kernel's order over the row's partials
+__global__ __launch_bounds__(ENERGY_REDUCE) void entry_reduce_kernel(const int n_rows, const long long *__restrict__ total, const int n_part, const double *__restrict__ partial,
+                                                                     double *__restrict__ out) {
+    __shared__ double acc[ENERGY_REDUCE];
+    const int row = (int)blockIdx.x / 6, comp = (int)blockIdx.x % 6, t = threadIdx.x;
+    long long blk0 = 0;
+    for (int q = 0; q < row; ++q) blk0 += (total[q] + ENERGY_BLOCK - 1) / ENERGY_BLOCK;
+    const int n = (int)((total[row] + ENERGY_BLOCK - 1) / ENERGY_BLOCK);
+    const double *p = partial + (size_t)comp * n_part + blk0;
+    double a = 0.0;
+    for (int i = t; i < n; i += ENERGY_REDUCE) a += p[i];
+    acc[t] = a;
+    __syncthreads();
+    for (int h = ENERGY_REDUCE / 2; h >= 1; h >>= 1) {
+        if (t < h) acc[t] += acc[t + h];
+        __syncthreads();
+    }
+    if (t == 0) out[(size_t)row * 6 + comp] = acc[0];
 }
 
 } // namespace admm_dev

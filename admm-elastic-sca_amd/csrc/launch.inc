@@ -14,7 +14,8 @@ void tet_trace_next(hipStream_t st) {
 }
 #endif
 // which kernels the collision batches launch for the current list, and whether in a launch of their own (collision_plan.hpp: the forms 0
-// to 7, their triggers, own_launch and sided): one pass over the list, from the current coefficients, motions, frames and mesh records.
+// to 7, their triggers, own_launch and sided; form 8 while contact attribution is on): one pass over the list, from the current
+// coefficients, motions, frames and mesh records.
 // Evaluated at every launch or capture, never kept: a setter changes it between frames, and the one that does drops the captured graphs
 // (abi_setup.inc: push_shapes).  A form's kernel is an instantiation beside the others, not a flag inside them: a list that sets off no
 // higher trigger launches exactly the kernels it launched before that form existed.
@@ -22,7 +23,7 @@ admm_lib::CollisionForm collision_form(const admm_hip_ctx *ctx) {
     return admm_lib::collision_form_of(ctx->shapes, (int)ctx->meshes.size(), [ctx](int id) {
         const admm_hip_ctx::CollisionMesh &m = ctx->meshes[id];
         return admm_lib::MeshFacts{m.body(), m.mesh.thickness, m.self_collision, m.side_reach, m.body_self[0], m.body_mu, m.has_vel};
-    });
+    }, ctx->attribution);
 }
 
 // The scene's batches as segments of ONE project_multi_kernel launch (false: launch batch after batch -- a kind without a segment
@@ -171,17 +172,20 @@ int latch_sides(admm_hip_ctx *ctx) {
     return ADMM_OK;
 }
 
-// a collision batch of a context with mesh obstacles, friction, framed entries or boxes: the kernel of the list's form.  (Forms 4 and up
-// imply meshes; a body surface with a coefficient implies meshes and an entry's motion counts only beside its coefficient, so form 2 is reached.)
+// a collision batch of a context with mesh obstacles, friction, framed entries or boxes, or with contact attribution on: the kernel of
+// the list's form.  (Forms 4 to 7 imply meshes; form 8 runs with and without; a body surface with a coefficient implies meshes and an
+// entry's motion counts only beside its coefficient, so form 2 is reached.)
 void launch_collision_mesh(admm_hip_ctx *ctx, const Batch &b, int form) {
     using namespace admm_dev;
     const BatchDev d = batch_dev(ctx, b);
     const dim3 grid((d.e1 - d.e0 + LOCAL_BLOCK - 1) / LOCAL_BLOCK), block(LOCAL_BLOCK);
     const double *x = ctx->d_xcur;
-    const CollisionTables T = collision_tables(ctx);
+    CollisionTables T = collision_tables(ctx);
     const bool mesh = !ctx->meshes.empty();
+    if (form == 8) { T.owner = ctx->d_at_owner + b.at_off; T.normal = ctx->d_at_normal + b.at_off; T.at_stride = ctx->at_total; }      // (allocated by the switch or by finalize)
 #define ADMM_COLLIDE(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, 0, ctx->stream, d, x, T)
     switch (form) {
+    case 8: if (mesh) ADMM_COLLIDE(project_collision_attributed_kernel<true>); else ADMM_COLLIDE(project_collision_attributed_kernel<false>); break;
     case 7: ADMM_COLLIDE(project_collision_bodyself_kernel); break;
     case 6: ADMM_COLLIDE(project_collision_sided_kernel); break;
     case 5: ADMM_COLLIDE(project_collision_self_kernel); break;

@@ -561,6 +561,26 @@ int upload_all(admm_hip_ctx *ctx, const admm_lib::MeshTables &plan) {
     return ADMM_OK;
 }
 
+// contact attribution (admm_hip_enable_contact_attribution): the record of every collision element of this rank, allocated once -- by the
+// switch in a finalized context, else by finalize --, and its fill: owner -1, normal 0.0
+int attribution_allocate(admm_hip_ctx *ctx) {
+    if (ctx->d_at_owner) return ADMM_OK;
+    HIPCHK(hipSetDevice(ctx->device_id));
+    long long total = 0;
+    for (Batch &b : ctx->batches) if (b.kind == ADMM_KIND_COLLISION) { b.at_off = total; total += std::max(b.n_local, 1); }
+    ctx->at_total = std::max(total, 1ll);
+    TRY(dalloc(ctx, &ctx->d_at_normal, 3 * (size_t)ctx->at_total));
+    TRY(dalloc(ctx, &ctx->d_at_owner, (size_t)ctx->at_total));
+    return ADMM_OK;
+}
+int attribution_fill(admm_hip_ctx *ctx) {
+    HIPCHK(hipSetDevice(ctx->device_id));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ctx->d_at_owner, -1, (size_t)ctx->at_total, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_at_normal, 0, sizeof(double) * 3 * (size_t)ctx->at_total, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ADMM_OK;
+}
+
 BatchDev batch_dev(const admm_hip_ctx *ctx, const Batch &b) {
     BatchDev d{};
     d.n = b.n_local; d.e0 = 0; d.e1 = b.n_local; d.keep_z = ctx->keep_z ? 1 : 0; d.idx = b.d_idx; d.rest = b.d_rest; d.par = b.d_par; d.w2h2 = b.d_w2h2; d.kblend = b.d_kblend; d.w2 = b.d_w2;

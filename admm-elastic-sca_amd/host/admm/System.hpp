@@ -71,7 +71,12 @@ public:
         // (0 .. 8; admm_hip_set_acceleration, System::acceleration_log()).  0 (default) = the reference's iteration.  Not available on
         // a sharded system or with user-defined forces.
         int anderson_window;
-        Settings() : timestep_s(0.04), verbose(1), admm_iters(10), residual_tol_primal(0.0), residual_tol_dual(0.0), residual_check_every(1), track_objective(false), anderson_window(0) {}
+        // extension, no reference counterpart: every collision element records, in every local step, the entry of its CollisionForce's
+        // shape list that last moved it and the direction of that push (admm_hip_enable_contact_attribution; System::contact_owners(),
+        // System::entry_resultants()).  false (default): nothing is recorded and nothing else is launched.
+        bool contact_attribution;
+        Settings() : timestep_s(0.04), verbose(1), admm_iters(10), residual_tol_primal(0.0), residual_tol_dual(0.0), residual_check_every(1), track_objective(false), anderson_window(0),
+                     contact_attribution(false) {}
     } settings;
 
     double elapsed_s;
@@ -337,6 +342,10 @@ public:
         if (!check(admm_hip_set_tolerance(gpu, settings.residual_tol_primal, settings.residual_tol_dual, settings.residual_check_every < 1 ? 1 : settings.residual_check_every))) return false;
         if (!check(admm_hip_enable_objective(gpu, settings.track_objective ? 1 : 0))) return false;
         if (!check(admm_hip_set_acceleration(gpu, settings.anderson_window))) return false;
+        if ((int)settings.contact_attribution != attribution_sent) {      // (on a change only: switching it on clears the record)
+            if (!check(admm_hip_enable_contact_attribution(gpu, settings.contact_attribution ? 1 : 0))) return false;
+            attribution_sent = (int)settings.contact_attribution;
+        }
         if (!check(admm_hip_step(gpu, settings.admm_iters))) return false;
         if (!check(admm_hip_download_state(gpu, m_x.data(), m_v.data()))) return false;
         // released MovingAnchors follow their node: point->pos = Dx (AnchorForce.cpp:80-83)
@@ -456,6 +465,33 @@ public:
         r.count = (long)n;
         return r;
     }
+    // what the contacts touch, under settings.contact_attribution (admm_hip_get_contact_owners): the nodes of contacts(depth_min) in its
+    // order, each with the entry of the shape list that last moved it (-1: none in the last local step), the direction of that push and
+    // the node's contact force split into its part along that normal and the rest; empty when none or when the call failed
+    std::vector<admm_hip_contact_owner> contact_owners(double depth_min = 1e-10) {
+        std::vector<admm_hip_contact_owner> c;
+        if (!initialized) return c;
+        c.resize((size_t)m_x.size() / 3);
+        int64_t n = 0;
+        if (!check(admm_hip_get_contact_owners(gpu, depth_min, c.data(), (int64_t)c.size(), &n))) n = 0;
+        c.resize((size_t)(n < (int64_t)c.size() ? n : (int64_t)c.size()));
+        return c;
+    }
+    // the contacts' resultant per entry of the shape list (admm_hip_entry_resultants): rows [n_entries + 1], the last one for the contacts
+    // that nothing moved in the last local step; n_entries: the length of the CollisionForce's shape list.  Empty: the call failed.
+    std::vector<ContactResultant> entry_resultants(int n_entries, double px = 0.0, double py = 0.0, double pz = 0.0, double depth_min = 1e-10) {
+        std::vector<ContactResultant> rows;
+        if (!initialized || n_entries < 0) return rows;
+        const double pivot[3] = {px, py, pz};
+        std::vector<double> out(6 * ((size_t)n_entries + 1)); std::vector<int64_t> n((size_t)n_entries + 1);
+        if (!check(admm_hip_entry_resultants(gpu, depth_min, pivot, n_entries, out.data(), n.data()))) return rows;
+        rows.resize((size_t)n_entries + 1);
+        for (size_t q = 0; q < rows.size(); ++q) {
+            for (int j = 0; j < 3; ++j) { rows[q].force[j] = out[6 * q + j]; rows[q].torque[j] = out[6 * q + 3 + j]; }
+            rows[q].count = (long)n[q];
+        }
+        return rows;
+    }
     // the Cauchy stress of the tets of device batch `batch` (admm_hip_batch_stress): seven doubles per tet, xx, yy, zz, xy, xz, yz, von
     // Mises, in the order of admm_hip_read_local; empty when the call failed (not a tet batch, not initialized, no GPU)
     std::vector<double> batch_stress(int batch) {
@@ -523,6 +559,7 @@ public:
 
 protected:
     bool initialized;
+    int attribution_sent = -1;      // settings.contact_attribution as the library last got it (-1: never)
     admm_hip_ctx *gpu;
     std::vector<std::pair<const admm_hip_mesh *, int> > mesh_ids;      // CollisionMesh obstacles registered with the context -> their mesh_id
     std::vector<long> mesh_versions;                                  // ... and the CollisionMesh::version the context last received
@@ -604,7 +641,7 @@ protected:
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
         mesh_ids.clear(); mesh_versions.clear(); body_ids.clear(); friction_pushed = false;
         motion_pushed = false; frames_pushed = false; mesh_vel_versions.clear(); mesh_thick.clear(); body_mu.clear();
-        initialized = false;
+        initialized = false; attribution_sent = -1;
     }
 
     bool push_shapes(const CollisionForce *cf) {

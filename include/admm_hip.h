@@ -919,8 +919,8 @@ int admm_hip_acceleration_query(int m_k, const double *gram, const double *rhs, 
  *                              point = z.  ADMM_ERR_ARG: n < 0, depth_min not >= 0, a NULL input with n > 0.
  * Any output pointer may be NULL.
  * What it holds under the solver's options:
- *   every collision form (admm_hip_debug_collision_form 0-7): the report reads only u, z and x, which every form leaves by the same
- *     epilogue.  Friction's tangential part is inside f; normal and tangential parts are not told apart.
+ *   every collision form (admm_hip_debug_collision_form 0-8): the report reads only u, z and x, which every form leaves by the same
+ *     epilogue.  Friction's tangential part is inside f; contact attribution (below) tells normal and tangential parts apart.
  *   admm_hip_keep_z(ctx, 0): only the tet kernels honour it; the collision and anchor kernels store z in every iteration.
  *   an early exit by tolerance: the identity holds for the last iteration that ran.
  *   Anderson acceleration: every iteration writes its s_out to the batches' z and u and rebuilds the right-hand-side shares from them
@@ -928,8 +928,8 @@ int admm_hip_acceleration_query(int m_k, const double *gram, const double *rhs, 
  *   a released anchor (active = 0) goes through the same formula, no special case: its z is x_prev + u with x_prev the iterate the last
  *     local step saw, so f = w^2 (x_prev - x) up to rounding residue -- the last iteration's increment, zero at convergence.  The same holds
  *     for a collision element that touches nothing: its depth is residue (no contact), its f that increment.
- * Not covered: which list entry a contact belongs to and per-obstacle resultants (the last mover is not stored), reactions on the triangles
- * of a body or sheet surface (the push is one-sided), user-defined (GENERIC) batches, a per-iteration history.
+ * Not covered: reactions on the triangles of a body or sheet surface (the push is one-sided), user-defined (GENERIC) batches, a
+ * per-iteration history, a normal from more than the last mover (contact attribution, below, records the last one).
  * Sharded contexts: every call covers THIS rank's local elements; the ranks' node vectors add up to the one-rank vector (they are not
  * gathered into one), and a node's contact is reported by the rank that owns its collision element.                                    */
 typedef struct admm_hip_reaction_info {
@@ -945,6 +945,52 @@ int admm_hip_get_contacts(admm_hip_ctx *ctx, double depth_min, admm_hip_contact 
 int admm_hip_contact_resultant(admm_hip_ctx *ctx, double depth_min, const double pivot[3], double out6[6], int64_t *count);
 int admm_hip_reaction_query(int64_t n, const double *w2, const double *u, const double *z, const double *x, double depth_min, const double *pivot,
                             double *f, double *depth, int32_t *flag, double *resultant6);
+
+/* ---- contact attribution: WHAT a node touches -- owner entry, normal, normal / tangential parts, per-obstacle resultants -------------------
+ * Extension, no reference counterpart; off unless asked for: a context that never enables it uploads and launches exactly what it did and
+ * produces the same bits.  One definition, csrc/attribution.hpp, compiled without fused multiply-adds for the host and the device.
+ * An entry q of the collision list MOVED an element's candidate when a coordinate's BITS differ between the point before the entry's
+ * rule and the point behind the rule and before friction; an entry that is skipped or whose rule does not fire moved nothing.
+ *     owner    the index of the last entry in list order that moved the candidate in that local step; -1: none did
+ *     normal   of that last mover: d = after - before, len = sqrt((d0 d0 + d1 d1) + d2 d2), n = d / len; owner -1: exactly 0.  The
+ *              direction of the push: a floor's normal, a sphere's radial, a closed mesh's outward direction at the closest point, for a
+ *              node mirrored back by side memory or body self-collision the remembered / outer side
+ *     split    of a reaction f about n: fn = (f0 n0 + f1 n1) + f2 n2, ft_j = f_j - fn n_j
+ *   admm_hip_enable_contact_attribution  on != 0: every collision batch launches form 8 of the collision kernel (admm_hip_debug_collision_form
+ *                              reads 8), whatever the list holds: everything form 7 knows -- z, u and the right-hand side keep the bits of
+ *                              the form the list would otherwise select -- and one int32 owner and three doubles of normal stored per
+ *                              collision element in EVERY local step, owner -1 with a zero normal included: what the record holds after a
+ *                              frame is that of the last local step that ran, extrapolated by Anderson acceleration or not.  Callable
+ *                              before or after finalize and between frames; the record is allocated by this call in a finalized context,
+ *                              else by finalize, never by admm_hip_step; switching on fills it with owner -1, normal 0.  A change drops the
+ *                              captured iteration and frame graphs, like a setter that changes the form; on = 0 returns the context to the
+ *                              list's own form.  Allowed under sharding: each rank records its local elements.
+ * The reports read the record; they check and behave like the reaction calls above (same order of checks, one synchronisation, buffers
+ * created by the first call, no atomics, fixed orders, nothing written that a frame reads) and return ADMM_ERR_STATE while the switch is off.
+ *   admm_hip_batch_contact_owner  one COLLISION batch (another kind: ADMM_ERR_UNSUPPORTED): entry [n_local] and normal [n_local][3] in the
+ *                              order of admm_hip_read_local.
+ *   admm_hip_get_contact_owners  the nodes and the order of admm_hip_get_contacts for that depth_min, as 64-byte records {node, entry,
+ *                              normal, f_normal, f_tangent}: entry and normal are those of the collision element that gives the node its
+ *                              depth and point (the largest depth, the first on ties), the split is of the node's f_contact.
+ *   admm_hip_entry_resultants  out [(n_entries + 1)][6], count [n_entries + 1]: row q = {sum f, sum (point - pivot) x f} over the contacts
+ *                              whose entry is q, in ascending node index, through exactly the two-stage sum of csrc/reaction.hpp; the
+ *                              last row takes the contacts with entry -1 (deeper than depth_min from earlier iterations, moved by nothing
+ *                              in the last local step).  n_entries must be the current list's length (ADMM_ERR_ARG otherwise).  The rows
+ *                              add up to admm_hip_contact_resultant's up to the order of the additions.
+ *   admm_hip_attribution_query  context-free host evaluation, the device's bits; needs no GPU: before, after, f [n][3] -> moved [n],
+ *                              normal [n][3] (not moved: 0), fn [n], ft [n][3].  normal_in [n][3] (may be NULL): the split is about these
+ *                              normals instead, and before / after may then both be NULL (moved 0, normal 0).  Outputs may be NULL.
+ * Not covered: a normal from more than the last mover, a per-iteration history of owners.                                                   */
+typedef struct admm_hip_contact_owner {
+    int32_t node, entry;
+    double normal[3], f_normal, f_tangent[3];
+} admm_hip_contact_owner;
+int admm_hip_enable_contact_attribution(admm_hip_ctx *ctx, int on);
+int admm_hip_batch_contact_owner(admm_hip_ctx *ctx, int batch, int32_t *entry, double *normal);
+int admm_hip_get_contact_owners(admm_hip_ctx *ctx, double depth_min, admm_hip_contact_owner *records, int64_t capacity, int64_t *count);
+int admm_hip_entry_resultants(admm_hip_ctx *ctx, double depth_min, const double pivot[3], int n_entries, double *out, int64_t *count);
+int admm_hip_attribution_query(int64_t n, const double *before, const double *after, const double *f, const double *normal_in, int32_t *moved, double *normal,
+                               double *fn, double *ft);
 
 /* ---- velocity damping per node group, applied after every frame ---------------------------------------------------------------------------
  * Extension, no reference counterpart.  A damping group is a range [node_first, node_first + node_count) of nodes in the caller's node
