@@ -31,6 +31,7 @@ KIND_STATE = [0, 0, 0, 0, 4, 4, 0, 0, 0, 0, 4]
 SHAPE = dict(FLOOR=0, SPHERE=1, CYLINDER=2, MESH=3, BOX=4)
 SHAPE_BOX = SHAPE["BOX"]
 EXPLICIT = dict(CONST=0, WIND=1)
+PRESSURE = {"CONSTANT": 0, "GAS": 1}      # ADMM_PRESSURE_* (include/admm_hip.h)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -101,6 +102,24 @@ class GroupMoments(C.Structure):
         d = {n: getattr(self, n) for n in ("mass", "t_total", "t_rigid", "n_nodes", "degenerate")}
         d.update({n: np.array(getattr(self, n)[:]) for n in ("com", "p", "l", "inertia", "omega")})
         return d
+
+
+class ChamberState(C.Structure):
+    """admm_hip_chamber_state: a pressure chamber's volume, area, area vector, pressure, resultant = pressure * area vector"""
+    _fields_ = [("volume", C.c_double), ("area", C.c_double), ("area_vector", C.c_double * 3), ("pressure", C.c_double), ("resultant", C.c_double * 3),
+                ("n_tris", C.c_int64), ("collapsed", C.c_int64)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n in ("volume", "area", "pressure", "n_tris", "collapsed")}
+        d.update({n: np.array(getattr(self, n)[:]) for n in ("area_vector", "resultant")})
+        return d
+
+
+def _pressure_law(mode, p, amount, ambient):
+    """-> (mode id, params [2]) of a pressure law given by name or id: "constant" takes p, "gas" takes amount and ambient"""
+    mid = PRESSURE[mode.upper()] if isinstance(mode, str) else int(mode)
+    par = np.array([amount, ambient] if mid == PRESSURE["GAS"] else [p, 0.0], dtype=np.float64)
+    return mid, par
 
 
 class AccelerationRecord(C.Structure):
@@ -178,6 +197,10 @@ def lib():
         L.admm_hip_set_damping.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
         L.admm_hip_get_group_moments.argtypes = [C.c_void_p, C.c_int, C.POINTER(GroupMoments)]
         L.admm_hip_damping_query.argtypes = [C.c_int64, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, C.POINTER(GroupMoments)]
+        L.admm_hip_add_pressure_chamber.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, _dp, C.POINTER(C.c_int)]
+        L.admm_hip_set_pressure.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        L.admm_hip_get_chamber_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(ChamberState)]
+        L.admm_hip_pressure_query.argtypes = [C.c_int64, _dp, _dp, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp, C.c_double, _dp, C.POINTER(ChamberState)]
         L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
         L.admm_hip_add_nodes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
@@ -629,6 +652,29 @@ def damping_query(m, x, v, dt, drag, internal):
     if rc:
         raise AdmmHipError("admm_hip_damping_query error %d" % rc)
     return out, rec.as_dict()
+
+
+def pressure_query(x, m, chambers, dt):
+    """the pressure chambers' load on the host (admm_hip_pressure_query; csrc/pressure.hpp, the device's bits; needs no GPU): x [nv][3],
+    m [nv] (or a scalar): the nodes' masses, chambers: one dict or a list of dicts(tris=[nt][3], mode="constant" | "gas", p=, amount=,
+    ambient=) as System.add_pressure_chamber takes them, dt -> (dv [nv][3], the list of the chambers' records as System.chamber_state
+    returns them; `collapsed` is 1 where this evaluation found a gas chamber's volume not positive)"""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+    nv = x.shape[0]
+    mm = np.ascontiguousarray(np.broadcast_to(np.asarray(m, dtype=np.float64), (nv,)))
+    if isinstance(chambers, dict):
+        chambers = [chambers]
+    tl = [np.ascontiguousarray(c["tris"], dtype=np.int32).reshape(-1, 3) for c in chambers]
+    laws = [_pressure_law(c.get("mode", "constant"), c.get("p", 0.0), c.get("amount", 0.0), c.get("ambient", 0.0)) for c in chambers]
+    ptr = np.concatenate([[0], np.cumsum([len(t) for t in tl])]).astype(np.int64)
+    tris = np.ascontiguousarray(np.concatenate(tl) if tl else np.zeros((0, 3), np.int32))
+    mode = np.array([l[0] for l in laws], dtype=np.int32)
+    par = np.ascontiguousarray(np.array([l[1] for l in laws], dtype=np.float64).reshape(-1, 2))
+    dv = np.zeros((nv, 3)); recs = (ChamberState * max(len(tl), 1))()
+    rc = lib().admm_hip_pressure_query(nv, _d(x), _d(mm), len(tl), ptr.ctypes.data_as(C.POINTER(C.c_int64)), _i(tris), _i(mode), _d(par), float(dt), _d(dv), recs)
+    if rc:
+        raise AdmmHipError("admm_hip_pressure_query error %d" % rc)
+    return dv, [recs[c].as_dict() for c in range(len(tl))]
 
 
 def stress_query(kind, dx, params, volume):
@@ -1120,6 +1166,27 @@ class System:
         degenerate) of one damping group from the device's current x, v"""
         rec = GroupMoments()
         self._chk(self.L.admm_hip_get_group_moments(self.h, int(group), C.byref(rec)))
+        return rec.as_dict()
+
+    # ---- pressure chambers: constant and gas-law surface loads, added before every frame (extension; include/admm_hip.h) ----
+    def add_pressure_chamber(self, tris, mode="constant", p=0.0, amount=0.0, ambient=0.0):
+        """-> chamber id.  tris [nt][3]: oriented triangles over the caller's node ids (outward normals and p > 0 inflate); mode "constant"
+        (gauge pressure p) or "gas" (p = amount / V - ambient; the chamber must be closed).  Before initialize() only."""
+        t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        mid, par = _pressure_law(mode, p, amount, ambient)
+        c = C.c_int()
+        self._chk(self.L.admm_hip_add_pressure_chamber(self.h, t.shape[0], _i(t), mid, _d(par), C.byref(c)))
+        return c.value
+
+    def set_pressure(self, chamber, mode="constant", p=0.0, amount=0.0, ambient=0.0):
+        """a new law for one chamber, in effect from the next step() on"""
+        mid, par = _pressure_law(mode, p, amount, ambient)
+        self._chk(self.L.admm_hip_set_pressure(self.h, int(chamber), mid, _d(par)))
+
+    def chamber_state(self, chamber):
+        """-> dict(volume, area, area_vector [3], pressure, resultant [3], n_tris, collapsed) of one chamber from the device's current x"""
+        rec = ChamberState()
+        self._chk(self.L.admm_hip_get_chamber_state(self.h, int(chamber), C.byref(rec)))
         return rec.as_dict()
 
     def enable_objective(self, on=True):

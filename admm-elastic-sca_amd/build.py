@@ -10,6 +10,7 @@
   anderson_host.cpp                      : the host twin of Anderson acceleration's small solve (anderson.hpp), likewise
   reaction_host.cpp                      : the host twin of the contact and anchor reactions and their resultant (reaction.hpp), likewise
   damping_host.cpp                       : the host twin of the velocity damping per node group and its moments (damping.hpp), likewise
+  pressure_host.cpp                      : the host twin of the pressure chambers and their records (pressure.hpp), likewise
   attribution_host.cpp                   : the host twin of the contact attribution rule and the normal / tangential split (attribution.hpp), likewise
   admm_hip.hip                           : the device translation unit: kernels (kernels_*.hpp, factor_dev.hpp), device factorization,
                                            upload, launches, step loop, C ABI; hipcc --offload-arch=gfx950, -ffp-contract=off
@@ -86,6 +87,7 @@ def _jobs(extra_hip_flags, tag):
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "anderson_host.cpp", "anderson_host.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "reaction_host.cpp", "reaction_host.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "damping_host.cpp", "damping_host.o"),
+        (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "pressure_host.cpp", "pressure_host.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "attribution_host.cpp", "attribution_host.o"),
         ([hipcc] + HIP_FLAGS + list(extra_hip_flags), "admm_hip.hip", "admm_hip%s.o" % tag),
     ]

@@ -737,6 +737,8 @@ extern "C" int admm_hip_debug_tet_profile(unsigned long long *out) {
 #endif
 
 
+static int check_pressure_chambers(admm_hip_ctx *ctx);      // (abi_pressure.inc)
+
 int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (!ctx) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "already finalized");
@@ -752,6 +754,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     TRY(check_sheet_self_collision(ctx));
     TRY(check_body_self_collision(ctx));
     TRY(check_side_entries(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
+    TRY(check_pressure_chambers(ctx));
     TRY(host_assemble(ctx, false));
     TRY(host_factor(ctx, false));
     ctx->info.rank = ctx->rank; ctx->info.world = ctx->world;

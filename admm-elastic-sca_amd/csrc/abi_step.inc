@@ -98,6 +98,7 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     TRY(mark(ctx));
     if (ctx->d_body_tag) TRY(update_bodies(ctx));      // body surfaces from the frame-start x, before the explicit forces (eager, outside the graphs)
     if (ctx->d_side) TRY(latch_sides(ctx));            // side memory: every node's side from the frame-start x (eager, outside the graphs)
+    if (!ctx->chambers.empty()) TRY(launch_pressure(ctx));      // pressure chambers (abi_pressure.inc): eager, from the frame-start x, into v before gravity and the wind
     if (ctx->frames++ > 0)      // the blocks of the large tet batches by what they cost in the frame before
         for (const Batch &b : ctx->batches) if (b.n_blocks_ordered)
             hipLaunchKernelGGL(order_by_cost_kernel, dim3(1), dim3(1024), 0, ctx->stream, b.n_blocks_ordered, b.d_cost, b.d_order);

@@ -28,6 +28,7 @@
 #include "kernels_anderson.hpp"
 #include "kernels_reaction.hpp"
 #include "kernels_damping.hpp"
+#include "kernels_pressure.hpp"
 
 extern "C" int omp_get_max_threads(void);
 
@@ -78,6 +79,7 @@ extern "C" {
 #include "abi_anderson.inc"
 #include "abi_reaction.inc"
 #include "abi_damping.inc"
+#include "abi_pressure.inc"
 #include "abi_step.inc"
 #include "abi_parity.inc"
 

@@ -302,6 +302,17 @@ struct admm_hip_ctx {
     struct DampGroupHost { int node_first = 0, node_count = 0; double drag = 0.0, internal = 0.0; bool rate_dirty = true; };
     std::vector<DampGroupHost> damp_groups;
     int damp_blocks = 0; void *d_damp_blk = nullptr, *d_damp_grp = nullptr, *d_damp_rate = nullptr, *d_damp_mom = nullptr; double *d_damp_vc = nullptr, *d_damp_part = nullptr;
+    // pressure chambers (abi_pressure.inc, kernels_pressure.hpp, pressure.hpp; no chamber = off, the default).  chambers: the caller's
+    // chambers in the order they were added, tris in the caller's node ids; law_dirty: the device's law entry is older than mode / par.
+    // Device side, created by upload_all when there is a chamber: the block -> (chamber, first triangle) table, the chambers' ranges,
+    // their laws (written by pressure_set_law_kernel from kernel arguments, at the start of the first frame that runs after a change),
+    // the records, the collapse counters, the triangles' corners as device positions, their chamber, their normals [3][pres_tris], the
+    // partials [5][pres_blocks] and the node CSR of the gather over the pres_nodes distinct chamber nodes
+    struct PressureChamberHost { std::vector<int32_t> tris; int mode = 0; double par[2] = {0.0, 0.0}; bool law_dirty = true; };
+    std::vector<PressureChamberHost> chambers;
+    int pres_blocks = 0, pres_tris = 0, pres_nodes = 0;
+    void *d_pres_blk = nullptr, *d_pres_chm = nullptr, *d_pres_law = nullptr, *d_pres_rec = nullptr; long long *d_pres_collapsed = nullptr, *d_pres_off = nullptr;
+    int *d_pres_tri = nullptr, *d_pres_trichm = nullptr, *d_pres_node = nullptr, *d_pres_ptr = nullptr, *d_pres_stride = nullptr; double *d_pres_nrm = nullptr, *d_pres_part = nullptr;
     // Anderson acceleration (abi_anderson.inc, kernels_anderson.hpp; window 0 = off, the default; every buffer created by the first step
     // that needs it, again when the window grows).  aa_T: doubles per state-sized vector (all batches' z and u, each segment at an even
     // offset), aa_nblk: blocks of the elementwise launches; d_aa_ring, allocated for the window aa_cap_m, used as [2][aa_m + 1][aa_T]: the history's g, then its f;

@@ -556,6 +556,44 @@ int upload_all(admm_hip_ctx *ctx, const admm_lib::MeshTables &plan) {
         HIPCHK(hipMemset(dr, 0, sizeof(DampRate) * ng)); HIPCHK(hipMemset(dm, 0, sizeof(admm_damping::Moments) * ng)); HIPCHK(hipMemset(ctx->d_damp_vc, 0, sizeof(double) * 3 * ng));
         ctx->d_damp_blk = db; ctx->d_damp_grp = dg; ctx->d_damp_rate = dr; ctx->d_damp_mom = dm;
     }
+    // pressure chambers (kernels_pressure.hpp): one block per 64 consecutive triangles of a chamber, counted from its first; the corners as
+    // device positions; the gather's node CSR over the distinct chamber nodes in the caller's order, a node's corners ordered by chamber,
+    // then triangle, then corner; a context with no chamber uploads nothing
+    ctx->pres_blocks = ctx->pres_tris = ctx->pres_nodes = 0;
+    ctx->d_pres_blk = ctx->d_pres_chm = ctx->d_pres_law = ctx->d_pres_rec = nullptr; ctx->d_pres_collapsed = ctx->d_pres_off = nullptr;
+    ctx->d_pres_tri = ctx->d_pres_trichm = ctx->d_pres_node = ctx->d_pres_ptr = ctx->d_pres_stride = nullptr; ctx->d_pres_nrm = ctx->d_pres_part = nullptr;
+    if (!ctx->chambers.empty()) {
+        using namespace admm_dev;
+        const size_t nc = ctx->chambers.size();
+        size_t nt_all = 0;
+        for (const admm_hip_ctx::PressureChamberHost &H : ctx->chambers) nt_all += H.tris.size() / 3;
+        if (nt_all > (size_t)0x7fffffff / 3) return fail(ctx, ADMM_ERR_ARG, "pressure chambers: %zu triangles in all are more than the tables index", nt_all);
+        std::vector<PresChamber> chm(nc); std::vector<PresBlock> blk; std::vector<int> tri, trichm; std::vector<NodeCsrEntry> entries;
+        tri.reserve(3 * nt_all); trichm.reserve(nt_all); entries.reserve(3 * nt_all);
+        for (size_t c = 0; c < nc; ++c) {
+            admm_hip_ctx::PressureChamberHost &H = ctx->chambers[c];
+            const int nt = (int)(H.tris.size() / 3), first = (int)trichm.size(), nb = (nt + PRES_BLOCK - 1) / PRES_BLOCK;
+            chm[c] = PresChamber{first, nt, (int)blk.size(), nb, F.iperm[H.tris[0]], 0};
+            for (int b = 0; b < nb; ++b) blk.push_back(PresBlock{(int)c, first + b * PRES_BLOCK});
+            for (int t = 0; t < nt; ++t) {
+                for (int j = 0; j < 3; ++j) { tri.push_back(F.iperm[H.tris[3 * (size_t)t + j]]); entries.push_back(NodeCsrEntry{H.tris[3 * (size_t)t + j], (long long)(first + t), (int)nt_all}); }
+                trichm.push_back((int)c);
+            }
+            H.law_dirty = true;
+        }
+        const NodeCsrHost full = build_node_csr(n, entries);
+        std::vector<int> node, ptr(1, 0);      // the distinct chamber nodes, compacted: device position and the run of corners
+        for (int i = 0; i < n; ++i) if (full.ptr[i + 1] > full.ptr[i]) { node.push_back(F.iperm[i]); ptr.push_back(full.ptr[i + 1]); }
+        ctx->pres_blocks = (int)blk.size(); ctx->pres_tris = (int)nt_all; ctx->pres_nodes = (int)node.size();
+        PresBlock *db = nullptr; PresChamber *dc = nullptr; PresLaw *dl = nullptr; admm_pressure::Record *dr = nullptr;
+        TRY(upload(ctx, &db, blk)); TRY(upload(ctx, &dc, chm)); TRY(dalloc(ctx, &dl, nc)); TRY(dalloc(ctx, &dr, nc)); TRY(dalloc(ctx, &ctx->d_pres_collapsed, nc));
+        TRY(upload(ctx, &ctx->d_pres_tri, tri)); TRY(upload(ctx, &ctx->d_pres_trichm, trichm)); TRY(upload(ctx, &ctx->d_pres_node, node)); TRY(upload(ctx, &ctx->d_pres_ptr, ptr));
+        TRY(upload(ctx, &ctx->d_pres_off, full.off)); TRY(upload(ctx, &ctx->d_pres_stride, full.stride));
+        TRY(dalloc(ctx, &ctx->d_pres_nrm, 3 * nt_all)); TRY(dalloc(ctx, &ctx->d_pres_part, (size_t)admm_pressure::N_SUMS * blk.size()));
+        HIPCHK(hipMemset(dl, 0, sizeof(PresLaw) * nc)); HIPCHK(hipMemset(dr, 0, sizeof(admm_pressure::Record) * nc)); HIPCHK(hipMemset(ctx->d_pres_collapsed, 0, sizeof(long long) * nc));
+        HIPCHK(hipMemset(ctx->d_pres_nrm, 0, sizeof(double) * 3 * nt_all));
+        ctx->d_pres_blk = db; ctx->d_pres_chm = dc; ctx->d_pres_law = dl; ctx->d_pres_rec = dr;
+    }
     HIPCHK(hipDeviceSynchronize());
     ctx->info.t_upload_s = now_s() - t0;
     return ADMM_OK;

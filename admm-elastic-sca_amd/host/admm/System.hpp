@@ -288,6 +288,10 @@ public:
             const DampingGroup &d = damping_groups[g];
             if (!check(admm_hip_add_damping_group(gpu, d.node_first, d.node_count < 0 ? dof / 3 - d.node_first : d.node_count, d.drag, d.internal, nullptr))) return false;
         }
+        for (size_t c = 0; c < pressure_chambers.size(); ++c) {      // (a bad triangle, an open gas chamber or a bad parameter fails here, with the library's message)
+            const PressureChamber &p = pressure_chambers[c];
+            if (!check(admm_hip_add_pressure_chamber(gpu, (int)(p.tris.size() / 3), p.tris.data(), p.mode, p.params, nullptr))) return false;
+        }
         if (!check(admm_hip_finalize(gpu))) return false;
         // write back what Force::initialize / get_selector compute in the reference
         user_local.clear();
@@ -555,6 +559,37 @@ public:
         return r;
     }
 
+    // extension, no reference counterpart (admm_hip_add_pressure_chamber): a pressure chamber, oriented triangles tris [nt][3] over m_x's
+    // node order with a law -- ADMM_PRESSURE_CONSTANT {p}: the gauge pressure p; ADMM_PRESSURE_GAS {amount, ambient}: p = amount / V -
+    // ambient, the chamber must be closed and enclose a positive volume.  Every step() adds dt f / m to the velocities on the device, from
+    // the frame-start positions, before gravity and the wind.  Before initialize() only, which hands the chambers to the library and fails
+    // on a bad one; returns the chamber's id (-1: refused because the system is initialized already).
+    struct PressureChamber { std::vector<int32_t> tris; int mode; double params[2]; };
+    int add_pressure_chamber(const std::vector<int> &tris, int mode = ADMM_PRESSURE_CONSTANT, double param0 = 0.0, double param1 = 0.0) {
+        if (initialized) { std::cerr << "\n**Solver Error: add_pressure_chamber after initialize()" << std::endl; return -1; }
+        PressureChamber p;
+        p.tris.assign(tris.begin(), tris.end()); p.mode = mode; p.params[0] = param0; p.params[1] = param1;
+        pressure_chambers.push_back(p);
+        return (int)pressure_chambers.size() - 1;
+    }
+    // a new law for one chamber (admm_hip_set_pressure), in effect from the next step() on; before or after initialize()
+    bool set_pressure(int chamber, int mode, double param0, double param1 = 0.0) {
+        if (chamber < 0 || chamber >= (int)pressure_chambers.size()) { std::cerr << "\n**Solver Error: set_pressure: chamber " << chamber << " does not exist" << std::endl; return false; }
+        const double params[2] = {param0, param1};
+        if (initialized && !check(admm_hip_set_pressure(gpu, chamber, mode, params))) return false;
+        pressure_chambers[chamber].mode = mode; pressure_chambers[chamber].params[0] = param0; pressure_chambers[chamber].params[1] = param1;
+        return true;
+    }
+    // a chamber's volume, area, area vector, pressure and resultant from the device state as the last step() left it
+    // (admm_hip_get_chamber_state); ok = false: the call failed (not initialized, no such chamber)
+    struct ChamberState { admm_hip_chamber_state s; bool ok; };
+    ChamberState chamber_state(int chamber) {
+        ChamberState r; std::memset(&r.s, 0, sizeof r.s); r.ok = false;
+        if (!initialized) return r;
+        r.ok = check(admm_hip_get_chamber_state(gpu, chamber, &r.s));
+        return r;
+    }
+
     admm_hip_ctx *context() { return gpu; }
 
 protected:
@@ -581,6 +616,7 @@ protected:
     void *pinned_x, *pinned_v, *seen_x, *seen_v; size_t pinned_bytes;
     std::vector<double> anchor_tgt, anchor_loc; std::vector<int32_t> anchor_act, anchor_ids;     // step(): this frame's control points
     std::vector<DampingGroup> damping_groups;      // add_damping_group's records, handed to the library by initialize()
+    std::vector<PressureChamber> pressure_chambers;      // add_pressure_chamber's records, handed to the library by initialize()
     int init_count;                        // initialize() calls so far (every rank counts alike: part of the rendezvous file's name)
 
     // world > 1: hand rank / world / mode to the library and install the all-reduce -- a caller's hook, or (default) an RCCL

@@ -1034,6 +1034,59 @@ int admm_hip_get_group_moments(admm_hip_ctx *ctx, int group, admm_hip_group_mome
 int admm_hip_damping_query(int64_t n, const double *m, const double *x, const double *v, double dt, double drag, double internal,
                            double *v_out, admm_hip_group_moments *moments);
 
+/* ---- pressure chambers: constant and gas-law surface loads, added before every frame -------------------------------------------------------
+ * Extension, no reference counterpart.  A pressure chamber is an ordered list of oriented triangles tris [nt][3] over simulated nodes (the
+ * caller's node ids) with a pressure law.  Once per frame, from the frame-start x, admm_hip_step works out the chamber's volume, area and
+ * area vector with fixed-order sums, derives the pressure p and adds dt f_i / m_i to v:
+ *     n_t = (x1 - x0) x (x2 - x0),   V = sum (r0 . (r1 x r2)) / 6,   A = sum |n_t| / 2,   N = sum n_t / 2       (r_k = x_k - o, o the
+ *     f_i = p sum_{t with i} n_t / 6                                                        first triangle's first node: V loses no digits
+ *                                                                                           to the chamber's distance from the origin)
+ * For a closed chamber f_i is exactly p dV/dx_i and the forces add up to no net force and no net torque.  The normal of a triangle
+ * follows its orientation: outward normals and p > 0 inflate.  Laws (params[2]):
+ *   ADMM_PRESSURE_CONSTANT {p, unused}         p as given (gauge; negative: suction, or ambient pressure on a body with outward normals)
+ *   ADMM_PRESSURE_GAS      {amount, ambient}   p = amount / V - ambient (isothermal).  A frame whose V is not > 0 or not finite gets
+ *                                              p = 0 and adds one to the chamber's `collapsed` counter.
+ * A constant chamber with p == 0, or a gas chamber with amount == 0 and ambient == 0, is inactive: it is passed over, and a node in no
+ * active chamber is not written.  A node in two chambers (a septum) receives both.
+ * Order in the frame: after the body surfaces' update and the side latch, before gravity, the constant accelerations and the wind --
+ * pressure reads the frame-start surface the collision kernels see, and its increment is in v before gravity is added and before the
+ * wind reads v.  One definition, csrc/pressure.hpp, compiled without fused multiply-adds for the host and the device, with the sums'
+ * order written out (64-triangle blocks from the chamber's first triangle, then the energies' two-stage reduction; the per-node sum over
+ * a node CSR ordered by chamber, triangle, corner; no atomics): both give the same bits, which depend neither on the elimination order
+ * nor on sharding.  Every rank of a sharded context applies the load to its own whole copy of v.
+ * Launches (csrc/kernels_pressure.hpp), on the context's stream, eager, outside the captured graphs, inside the prologue interval of the
+ * timing events: three per frame when any chamber is active, none otherwise -- a context without chambers launches and uploads what it
+ * did before and produces bitwise the same frames.
+ *   admm_hip_add_pressure_chamber  extension, no reference counterpart.  Before finalize only (ADMM_ERR_STATE after).  ADMM_ERR_ARG, with
+ *                                  admm_hip_last_error naming the value: nt < 1, a node id outside the nodes added so far, a triangle
+ *                                  naming a node twice, an unknown mode, a non-finite parameter; in gas mode an edge that is not shared
+ *                                  by exactly two oppositely oriented triangles (the edge is named).  *chamber: 0, 1, ... in call order.
+ *                                  admm_hip_finalize refuses a gas chamber whose rest volume is not positive (chamber and volume named).
+ *   admm_hip_set_pressure          extension, no reference counterpart.  Before or after finalize: a new law for one chamber, in effect from
+ *                                  the next admm_hip_step on; no synchronisation, legal between steps on a caller's stream.  A change to
+ *                                  gas mode checks closedness again.
+ *   admm_hip_get_chamber_state     extension, no reference counterpart.  The record from the context's current x, computed on demand (two
+ *                                  launches, one synchronisation), also for an inactive chamber; changes nothing.  `collapsed` is the
+ *                                  frames counted so far.  Needs a device and a finalized context (ADMM_ERR_STATE otherwise).
+ *   admm_hip_pressure_query        extension, no reference counterpart.  Context-free host evaluation, the device's bits; needs no GPU:
+ *                                  x [nv][3], m [nv] (scalar masses), n_chambers chambers whose triangles are tris[tri_ptr[c] ..
+ *                                  tri_ptr[c + 1]) (tri_ptr [n_chambers + 1], tris [..][3]), mode [n_chambers], params [n_chambers][2], dt
+ *                                  -> dv [nv][3] (0 for a node in no active chamber), records [n_chambers] (collapsed: 1 if this
+ *                                  evaluation collapsed).  Either output may be NULL.  ADMM_ERR_ARG: nv < 1, a NULL input, dt not > 0, an
+ *                                  empty chamber, a node id out of range, an unknown mode, a non-finite parameter.
+ * Not covered: no pressure term in admm_hip_energy or the objective, none in admm_hip_node_forces, no adiabatic exponent, no flow
+ * between chambers; the load is explicit (frame-start geometry, one evaluation per frame).                                              */
+enum { ADMM_PRESSURE_CONSTANT = 0, ADMM_PRESSURE_GAS = 1 };
+typedef struct admm_hip_chamber_state {
+    double volume, area, area_vector[3], pressure, resultant[3];      /* resultant = pressure * area_vector */
+    int64_t n_tris, collapsed;
+} admm_hip_chamber_state;
+int admm_hip_add_pressure_chamber(admm_hip_ctx *ctx, int nt, const int32_t *tris, int mode, const double *params, int *chamber);
+int admm_hip_set_pressure(admm_hip_ctx *ctx, int chamber, int mode, const double *params);
+int admm_hip_get_chamber_state(admm_hip_ctx *ctx, int chamber, admm_hip_chamber_state *out);
+int admm_hip_pressure_query(int64_t nv, const double *x, const double *m, int n_chambers, const int64_t *tri_ptr, const int32_t *tris,
+                            const int32_t *mode, const double *params, double dt, double *dv, admm_hip_chamber_state *records);
+
 #ifdef __cplusplus
 }
 #endif
