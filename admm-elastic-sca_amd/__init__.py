@@ -91,6 +91,18 @@ CONTACT_DTYPE = np.dtype(dict(names=["node", "f", "point", "depth"], formats=[np
 # admm_hip_contact_owner: 64 bytes
 CONTACT_OWNER_DTYPE = np.dtype(dict(names=["node", "entry", "normal", "f_normal", "f_tangent"], formats=[np.int32, np.int32, (np.float64, 3), np.float64, (np.float64, 3)],
                                     offsets=[0, 4, 8, 32, 40], itemsize=64))
+# admm_hip_surface_contact (two-way contact): status as in SURFACE_STATUS
+SURFACE_CONTACT_DTYPE = np.dtype(dict(names=["node", "mesh", "tri", "corner", "status", "weight", "share"],
+                                      formats=[np.int32, np.int32, np.int32, (np.int32, 3), np.int32, (np.float64, 3), np.float64],
+                                      offsets=[0, 4, 8, 12, 24, 32, 56], itemsize=64))
+SURFACE_STATUS = dict(reacting=0, unowned=1, other=2, self=3)
+
+
+class SurfaceReactionInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_contacts", "n_reacting", "n_unowned", "n_other", "n_self")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class GroupMoments(C.Structure):
@@ -201,6 +213,11 @@ def lib():
         L.admm_hip_set_pressure.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
         L.admm_hip_get_chamber_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(ChamberState)]
         L.admm_hip_pressure_query.argtypes = [C.c_int64, _dp, _dp, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp, C.c_double, _dp, C.POINTER(ChamberState)]
+        L.admm_hip_set_surface_reaction.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.admm_hip_set_surface_reaction_depth.argtypes = [C.c_void_p, C.c_double]
+        L.admm_hip_get_surface_reaction.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(SurfaceReactionInfo)]
+        L.admm_hip_surface_reaction_query.argtypes = [C.c_int64, _dp, C.c_int64, _dp, _ip, _dp, _dp, C.c_double, _dp]
+        L.admm_hip_debug_stable_sort.argtypes = [C.c_void_p, C.c_int64, _ip, C.c_int64, _ip]
         L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
         L.admm_hip_add_nodes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
@@ -675,6 +692,29 @@ def pressure_query(x, m, chambers, dt):
     if rc:
         raise AdmmHipError("admm_hip_pressure_query error %d" % rc)
     return dv, [recs[c].as_dict() for c in range(len(tl))]
+
+
+def surface_reaction_query(m3, f, corner, weight, share, dt):
+    """two-way contact's shares and ordered sums on the host (admm_hip_surface_reaction_query; csrc/surface_reaction.hpp, the device's
+    bits; needs no GPU): m3 [n_nodes][3] the nodes' mass per component (or [n_nodes]: one mass per node), and per contact f [K][3],
+    corner [K][3] (node ids), weight [K][3], share [K] (or a scalar), dt -> dv [n_nodes][3]: v <- v - dv.  A row with share 0 adds
+    nothing."""
+    mm = np.asarray(m3, dtype=np.float64)
+    if mm.ndim == 1:
+        mm = np.repeat(mm[:, None], 3, axis=1)
+    mm = np.ascontiguousarray(mm.reshape(-1, 3))
+    n = mm.shape[0]
+    f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 3)
+    K = f.shape[0]
+    cn = np.ascontiguousarray(corner, dtype=np.int32).reshape(-1, 3)
+    w = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1, 3)
+    sh = np.ascontiguousarray(np.broadcast_to(np.asarray(share, dtype=np.float64), (K,)))
+    assert cn.shape[0] == K and w.shape[0] == K
+    dv = np.zeros((n, 3))
+    rc = lib().admm_hip_surface_reaction_query(n, _d(mm), K, _d(f), _i(cn), _d(w), _d(sh), float(dt), _d(dv))
+    if rc:
+        raise AdmmHipError("admm_hip_surface_reaction_query error %d" % rc)
+    return dv
 
 
 def stress_query(kind, dx, params, volume):
@@ -1188,6 +1228,32 @@ class System:
         rec = ChamberState()
         self._chk(self.L.admm_hip_get_chamber_state(self.h, int(chamber), C.byref(rec)))
         return rec.as_dict()
+
+    # ---- two-way contact: a contact's reaction on the nodes of the surface it landed on (extension; include/admm_hip.h) ----
+    def set_surface_reaction(self, mesh_id, share):
+        """the share in [0, 1] of a contact's reaction that the corners of the triangle it landed on receive, for one body or sheet
+        surface (0: none, the default); needs contact attribution on.  Before or after initialize(), between frames."""
+        self._chk(self.L.admm_hip_set_surface_reaction(self.h, int(mesh_id), float(share)))
+
+    def set_surface_reaction_depth(self, depth_min):
+        """the depth above which a node counts as in contact for the reaction (default 0), as in contacts(depth_min)"""
+        self._chk(self.L.admm_hip_set_surface_reaction_depth(self.h, float(depth_min)))
+
+    def surface_reaction(self, capacity=None):
+        """-> (dv [n_nodes][3], records, info) of the last frame: dv what the reaction took off v (0 where nothing landed); one record
+        per contact in contacts()' order with the fields node, mesh, tri, corner [3], status (SURFACE_STATUS), weight [3], share; info:
+        dict(n_contacts, n_reacting, n_unowned, n_other, n_self)"""
+        cap = self.n_nodes if capacity is None else int(capacity)
+        dv = np.zeros((self.n_nodes, 3)); rec = np.zeros(max(cap, 0), SURFACE_CONTACT_DTYPE); cnt = C.c_int64(0); info = SurfaceReactionInfo()
+        self._chk(self.L.admm_hip_get_surface_reaction(self.h, _d(dv), rec.ctypes.data_as(C.c_void_p) if cap > 0 else None, cap, C.byref(cnt), C.byref(info)))
+        return dv, rec[:min(cnt.value, max(cap, 0))], info.as_dict()
+
+    def debug_stable_sort(self, keys, key_bound):
+        """-> perm [n] int32: the stable ascending order of keys [n] (each in [0, key_bound)) by the reaction's sort kernels alone"""
+        k = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+        perm = np.zeros(k.size, np.int32)
+        self._chk(self.L.admm_hip_debug_stable_sort(self.h, k.size, _i(k), int(key_bound), _i(perm)))
+        return perm
 
     def enable_objective(self, on=True):
         self._chk(self.L.admm_hip_enable_objective(self.h, 1 if on else 0))

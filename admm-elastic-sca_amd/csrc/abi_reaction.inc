@@ -174,6 +174,8 @@ int admm_hip_contact_resultant(admm_hip_ctx *ctx, double depth_min, const double
 int admm_hip_enable_contact_attribution(admm_hip_ctx *ctx, int on) {
     if (!ctx) return ADMM_ERR_ARG;
     const bool want = on != 0;
+    if (!want) for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) if (ctx->meshes[mi].reaction_share > 0.0)      // (abi_surface_reaction.inc)
+        return fail(ctx, ADMM_ERR_STATE, "enable_contact_attribution: surface %d has a reaction share of %g, which needs every contact's owner entry: set it to 0 first", (int)mi, ctx->meshes[mi].reaction_share);
     if (want && ctx->finalized && ctx->device_id >= 0) { TRY(attribution_allocate(ctx)); TRY(attribution_fill(ctx)); }      // (before finalize: finalize does both)
     if (want != ctx->attribution) drop_iteration_graphs(ctx);
     ctx->attribution = want;

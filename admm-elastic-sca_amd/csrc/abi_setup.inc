@@ -652,6 +652,8 @@ int admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, const
 int admm_hip_set_shard(admm_hip_ctx *ctx, int rank, int world) {
     if (!ctx || world < 1 || rank < 0 || rank >= world) return ADMM_ERR_ARG;
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "shard must be set before finalize");
+    if (world > 1) for (const admm_hip_ctx::CollisionMesh &m : ctx->meshes) if (m.reaction_share > 0.0)      // (abi_surface_reaction.inc)
+        return fail(ctx, ADMM_ERR_UNSUPPORTED, "set_shard: a surface reaction share is set, which is not available in a sharded context (world = %d)", world);
     ctx->rank = rank; ctx->world = world;
     return ADMM_OK;
 }
@@ -738,6 +740,8 @@ extern "C" int admm_hip_debug_tet_profile(unsigned long long *out) {
 
 
 static int check_pressure_chambers(admm_hip_ctx *ctx);      // (abi_pressure.inc)
+static bool surface_reaction_any(const admm_hip_ctx *ctx);  // (abi_surface_reaction.inc)
+static int surface_reaction_allocate(admm_hip_ctx *ctx);
 
 int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (!ctx) return ADMM_ERR_ARG;
@@ -755,6 +759,10 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     TRY(check_body_self_collision(ctx));
     TRY(check_side_entries(ctx, ctx->shapes.n, ctx->shapes.type, &ctx->shapes.par[0][0]));
     TRY(check_pressure_chambers(ctx));
+    // (belt and braces: admm_hip_set_shard refuses world > 1 above a share and admm_hip_set_surface_reaction refuses a share in a sharded
+    //  context, so no sequence of calls reaches this today; it guards the step's launches against a later setter that forgets)
+    if (ctx->world > 1 && surface_reaction_any(ctx))
+        return fail(ctx, ADMM_ERR_UNSUPPORTED, "a surface reaction share is set in a sharded context (world = %d): a destination node may live on another rank", ctx->world);
     TRY(host_assemble(ctx, false));
     TRY(host_factor(ctx, false));
     ctx->info.rank = ctx->rank; ctx->info.world = ctx->world;
@@ -774,6 +782,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (ctx->device_id < 0) ctx->h_side.assign((size_t)ctx->n_side_slots * (size_t)ctx->n_nodes, 0);
     if (ctx->device_id >= 0) TRY(upload_all(ctx, plan));
     if (ctx->device_id >= 0 && ctx->attribution) { TRY(attribution_allocate(ctx)); TRY(attribution_fill(ctx)); }      // (switched on before finalize)
+    if (ctx->device_id >= 0 && surface_reaction_any(ctx)) TRY(surface_reaction_allocate(ctx));      // (a share set before finalize)
     ctx->finalized = true;
     return ADMM_OK;
 }

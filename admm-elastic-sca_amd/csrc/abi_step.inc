@@ -233,6 +233,7 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     TRY(shard_sync_x(ctx));
     hipLaunchKernelGGL(epilogue_kernel, dim3((n3 + 255) / 256), dim3(256), 0, ctx->stream, n3, ctx->dt, ctx->d_x, ctx->d_v, ctx->d_xcur);
     HIPCHK(hipGetLastError());
+    if (surface_reaction_any(ctx)) TRY(launch_surface_reaction(ctx));      // two-way contact (abi_surface_reaction.inc): eager, on the v the epilogue left, before the damping filter
     if (!ctx->damp_groups.empty()) TRY(launch_damping(ctx));      // velocity damping per node group (abi_damping.inc): eager, on the v the epilogue left
     TRY(mark(ctx));
     if (ctx->rccl_comm) TRY(comm_poll(ctx, nullptr));      // once per frame: a dead peer becomes a failed step, not a hang in the caller's next sync

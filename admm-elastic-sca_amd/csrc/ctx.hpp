@@ -165,6 +165,9 @@ struct admm_hip_ctx {
         // body_mu: a body surface's coefficient.
         double *d_vel = nullptr; bool has_vel = false; double body_mu = 0.0; std::vector<double> vel;
         MeshUpdate upd{};             // the device buffers (finalize; all null in a host-only context)
+        // two-way contact (admm_hip_set_surface_reaction; a surface of simulated nodes only): the share of a contact's reaction its
+        // triangle's corners receive, 0: none; share_dirty: the device's table entry is older
+        double reaction_share = 0.0; bool share_dirty = false;
         int side_row = -1;            // its row of d_side / h_side (finalize; -1: no side memory)
         bool body() const { return !body_nodes.empty(); }         // a surface of simulated nodes, not an obstacle
         bool open() const { return mesh.thickness > 0.0; }        // a thick shell, not a closed mesh
@@ -313,6 +316,17 @@ struct admm_hip_ctx {
     int pres_blocks = 0, pres_tris = 0, pres_nodes = 0;
     void *d_pres_blk = nullptr, *d_pres_chm = nullptr, *d_pres_law = nullptr, *d_pres_rec = nullptr; long long *d_pres_collapsed = nullptr, *d_pres_off = nullptr;
     int *d_pres_tri = nullptr, *d_pres_trichm = nullptr, *d_pres_node = nullptr, *d_pres_ptr = nullptr, *d_pres_stride = nullptr; double *d_pres_nrm = nullptr, *d_pres_part = nullptr;
+    // two-way contact (abi_surface_reaction.inc, kernels_surface_reaction.hpp, surface_reaction.hpp; every share 0 = off, the default).
+    // sr_depth_min: the depth above which a node counts as in contact (admm_hip_set_surface_reaction_depth); sr_frame: the value of
+    // `frames` after the last step that ran the reaction (-1: none).  Device side, allocated by the first share set in a finalized
+    // context or by finalize, never by admm_hip_step: sr_cap contacts at most (the nodes that carry a collision element), sr_nb blocks of
+    // 64 shares, sr_passes sort passes; d_sr_mesh the per-mesh table (vertex -> caller's node, share), d_sr_rec [sr_cap] records,
+    // d_sr_key / d_sr_idx [2][3 sr_cap] the keys and the shares' indices (ping-pong), d_sr_val [3 sr_cap][3] the contributions, d_sr_blk
+    // the sort's block counts, then their offsets ([256][sr_nb] each), d_sr_tot its 256 totals, d_sr_n [6] the shares of the last reacting
+    // frame and, behind them, the report's five counts, d_sr_dv [n_nodes][3] in the caller's node order
+    double sr_depth_min = 0.0; long long sr_frame = -1; bool sr_ready = false; int sr_cap = 0, sr_nb = 0, sr_passes = 1;
+    void *d_sr_mesh = nullptr, *d_sr_rec = nullptr; int *d_sr_key = nullptr, *d_sr_idx = nullptr, *d_sr_blk = nullptr, *d_sr_tot = nullptr;
+    double *d_sr_val = nullptr, *d_sr_dv = nullptr; long long *d_sr_n = nullptr;
     // Anderson acceleration (abi_anderson.inc, kernels_anderson.hpp; window 0 = off, the default; every buffer created by the first step
     // that needs it, again when the window grows).  aa_T: doubles per state-sized vector (all batches' z and u, each segment at an even
     // offset), aa_nblk: blocks of the elementwise launches; d_aa_ring, allocated for the window aa_cap_m, used as [2][aa_m + 1][aa_T]: the history's g, then its f;

@@ -375,6 +375,9 @@ public:
     // (admm_hip_set_body_self_collision); read at System::initialize, where a force that projects on the host refuses it.  (A
     // CollisionSheet has a flag of the same name instead: admm_hip_set_sheet_self_collision.)
     double self_collision[3] = {0.0, 0.0, 0.0};
+    // two-way contact (admm_hip_set_surface_reaction): the share in [0, 1] of a contact's reaction that the corners of the triangle it
+    // landed on receive; 0: none.  Needs System::settings.contact_attribution; read at every step(), so it may change between frames.
+    double reaction_share = 0.0;
 };
 
 // Extension, no reference counterpart: CollisionBody for an open surface of simulated nodes such as a cloth (admm_hip_add_sheet_surface):

@@ -346,10 +346,12 @@ public:
         if (!check(admm_hip_set_tolerance(gpu, settings.residual_tol_primal, settings.residual_tol_dual, settings.residual_check_every < 1 ? 1 : settings.residual_check_every))) return false;
         if (!check(admm_hip_enable_objective(gpu, settings.track_objective ? 1 : 0))) return false;
         if (!check(admm_hip_set_acceleration(gpu, settings.anderson_window))) return false;
+        if (!push_reaction_shares(true)) return false;      // (shares that went to zero: before the switch, which cannot go off above them)
         if ((int)settings.contact_attribution != attribution_sent) {      // (on a change only: switching it on clears the record)
             if (!check(admm_hip_enable_contact_attribution(gpu, settings.contact_attribution ? 1 : 0))) return false;
             attribution_sent = (int)settings.contact_attribution;
         }
+        if (!push_reaction_shares(false)) return false;     // (shares above zero: behind the switch they need)
         if (!check(admm_hip_step(gpu, settings.admm_iters))) return false;
         if (!check(admm_hip_download_state(gpu, m_x.data(), m_v.data()))) return false;
         // released MovingAnchors follow their node: point->pos = Dx (AnchorForce.cpp:80-83)
@@ -481,6 +483,22 @@ public:
         c.resize((size_t)(n < (int64_t)c.size() ? n : (int64_t)c.size()));
         return c;
     }
+    // two-way contact (CollisionBody::reaction_share; admm_hip_get_surface_reaction): what the last step() took off the velocities of the
+    // surfaces' nodes, dv [3 n] (0 where nothing landed), one record per contact in contacts()' order, and the counts; ok = false: the
+    // call failed
+    struct SurfaceReaction { std::vector<double> dv; std::vector<admm_hip_surface_contact> records; admm_hip_surface_reaction_info info; bool ok; };
+    SurfaceReaction surface_reaction() {
+        SurfaceReaction r;
+        r.info = admm_hip_surface_reaction_info(); r.ok = false;
+        if (!initialized) return r;
+        r.dv.assign((size_t)m_x.size(), 0.0);
+        r.records.resize((size_t)m_x.size() / 3);
+        int64_t n = 0;
+        r.ok = check(admm_hip_get_surface_reaction(gpu, r.dv.data(), r.records.data(), (int64_t)r.records.size(), &n, &r.info));
+        if (!r.ok) n = 0;
+        r.records.resize((size_t)(n < (int64_t)r.records.size() ? n : (int64_t)r.records.size()));
+        return r;
+    }
     // the contacts' resultant per entry of the shape list (admm_hip_entry_resultants): rows [n_entries + 1], the last one for the contacts
     // that nothing moved in the last local step; n_entries: the length of the CollisionForce's shape list.  Empty: the call failed.
     std::vector<ContactResultant> entry_resultants(int n_entries, double px = 0.0, double py = 0.0, double pz = 0.0, double depth_min = 1e-10) {
@@ -605,6 +623,7 @@ protected:
     std::vector<long> mesh_vel_versions;                               // the CollisionMesh::vel_version the context last received
     std::vector<double> body_mu;                                       // the CollisionBody::surface_friction the context last received
     std::vector<std::pair<const CollisionBody *, int> > body_ids;     // CollisionBody surfaces registered with the context -> their mesh_id
+    std::vector<double> body_share;                                    // the CollisionBody::reaction_share the context last received
     std::vector<int> batch_first, batch_count, batch_kind;
     std::vector<char> batch_moving;
     std::vector<long> batch_urow0;         // generic batches: first of their rows among the user rows (-1 otherwise)
@@ -676,7 +695,7 @@ protected:
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
         mesh_ids.clear(); mesh_versions.clear(); body_ids.clear(); friction_pushed = false;
-        motion_pushed = false; frames_pushed = false; mesh_vel_versions.clear(); mesh_thick.clear(); body_mu.clear();
+        motion_pushed = false; frames_pushed = false; mesh_vel_versions.clear(); mesh_thick.clear(); body_mu.clear(); body_share.clear();
         initialized = false; attribution_sent = -1;
     }
 
@@ -777,6 +796,19 @@ protected:
         if (!moving && !motion_pushed) return true;
         motion_pushed = true;
         return check(admm_hip_set_collision_motion(gpu, (int)cf->collisionShapes.size(), mo.data()));
+    }
+
+    // CollisionBody::reaction_share of every registered surface, on a change only (admm_hip_set_surface_reaction); zeros: the shares that
+    // are now zero, else the others
+    bool push_reaction_shares(bool zeros) {
+        body_share.resize(body_ids.size(), 0.0);
+        for (size_t k = 0; k < body_ids.size(); ++k) {
+            const double s = body_ids[k].first->reaction_share;
+            if (s == body_share[k] || (s == 0.0) != zeros) continue;
+            if (!check(admm_hip_set_surface_reaction(gpu, body_ids[k].second, s))) return false;
+            body_share[k] = s;
+        }
+        return true;
     }
 
     bool check(int rc) {

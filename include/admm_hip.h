@@ -166,7 +166,8 @@ int  admm_hip_update_collision_mesh(admm_hip_ctx *ctx, int mesh_id, int nv, cons
  *     non-positive volume) keeps the last good surface, is counted, and the step returns ADMM_OK;
  *   - has an owner, its node range: the collision elements of those nodes skip the mesh (every interior node is inside its own body).
  * Edge-edge contact is out of scope (open surfaces: the thick-shell section below; self-collision within one body: admm_hip_set_body_self_collision, further below).  Friction against a body surface:
- * admm_hip_set_body_surface_friction below; it acts on the node in contact only, the surface's own nodes feel no reaction from it.
+ * admm_hip_set_body_surface_friction below; it acts on the node in contact, and the surface's own nodes feel its reaction only with a
+ * share set by admm_hip_set_surface_reaction (two-way contact, at the end of this file).
  *   admm_hip_add_body_surface  before finalize; tris [n_tris][3] are global node ids, all inside [node_first, node_first + node_count).
  *                           Vertices: the distinct referenced nodes in ascending id order, at their current positions (admm_hip_add_nodes
  *                           / admm_hip_set_x); triangles in the given order, renumbered.  Validated like admm_hip_mesh_create, with the
@@ -928,7 +929,8 @@ int admm_hip_acceleration_query(int m_k, const double *gram, const double *rhs, 
  *   a released anchor (active = 0) goes through the same formula, no special case: its z is x_prev + u with x_prev the iterate the last
  *     local step saw, so f = w^2 (x_prev - x) up to rounding residue -- the last iteration's increment, zero at convergence.  The same holds
  *     for a collision element that touches nothing: its depth is residue (no contact), its f that increment.
- * Not covered: reactions on the triangles of a body or sheet surface (the push is one-sided), user-defined (GENERIC) batches, a
+ * Reactions on the triangles of a body or sheet surface: two-way contact, further below (admm_hip_set_surface_reaction), for the nodes
+ * of other bodies; a self-contact's push stays one-sided.  Not covered: user-defined (GENERIC) batches, a
  * per-iteration history, a normal from more than the last mover (contact attribution, below, records the last one).
  * Sharded contexts: every call covers THIS rank's local elements; the ranks' node vectors add up to the one-rank vector (they are not
  * gathered into one), and a node's contact is reported by the rank that owns its collision element.                                    */
@@ -1086,6 +1088,74 @@ int admm_hip_set_pressure(admm_hip_ctx *ctx, int chamber, int mode, const double
 int admm_hip_get_chamber_state(admm_hip_ctx *ctx, int chamber, admm_hip_chamber_state *out);
 int admm_hip_pressure_query(int64_t nv, const double *x, const double *m, int n_chambers, const int64_t *tri_ptr, const int32_t *tris,
                             const int32_t *mode, const double *params, double dt, double *dv, admm_hip_chamber_state *records);
+
+/* ---- two-way contact: the reaction of a contact on the nodes of the body or sheet surface it landed on ------------------------------------
+ * Extension, no reference counterpart; off unless asked for.  A node that lands on a body or sheet surface is pushed out; with a share
+ * s_M > 0 on that surface M, the corners of the triangle it landed on receive -s_M times the node's reaction, as an impulse on v.
+ * Once per frame, after admm_hip_step's epilogue and before the velocity damping, on the v the epilogue left:
+ *   contacts   exactly the list of admm_hip_get_contacts(depth_min) (depth_min: admm_hip_set_surface_reaction_depth, default 0): K nodes,
+ *              ascending caller's node index, f = the node's f_contact, point; entry = admm_hip_get_contact_owners' owner entry.
+ *   status     the first that holds: ADMM_SURFACE_UNOWNED entry < 0; ADMM_SURFACE_OTHER the entry is no ADMM_SHAPE_MESH, or its mesh M is
+ *              an obstacle, or s_M is 0; ADMM_SURFACE_SELF the node is one of M's own nodes (M's owner range: self-contacts of a
+ *              self-colliding sheet or body do not react, the unbounded query would find the node's own 1-ring); else ADMM_SURFACE_REACTING.
+ *   hit        point in the entry's coordinates as the collision rule takes it there (frame, then translation); M's closest point to it on
+ *              the surface as this frame's start rebuilt it (the unbounded search, ties to the lowest triangle); lambda = the barycentric
+ *              weights there; corners = the triangle's three vertices as nodes: what admm_hip_mesh_velocity_query returns as `weights`
+ *              and `corner_ids` on a copy of the surface at the frame-start positions.
+ *   shares     p = dt f once per contact; corner c of the hit adds (s_M lambda_c) p to its node.  Per destination node t, over its shares
+ *              in ascending (contact index, corner): a = 0.0; a = a + share;  dv = a / m_t;  v_t = v_t - dv  (per component; every product
+ *              rounded).  A node with no share is not touched.
+ * One definition, csrc/surface_reaction.hpp, compiled without fused multiply-adds for the host and the device: both give the same bits.
+ * Linear momentum: sum_t m_t dv_t = dt sum_k s_k f_k up to rounding (the weights add up to one).  Friction's tangential part is inside f
+ * and reacts too.  The load is explicit: it has no term in admm_hip_energy or the objective, and it lags the push by one frame.  Angular
+ * momentum is not exact: the force acts at the node, the reaction at the surface.
+ * Launches (csrc/kernels_surface_reaction.hpp): the reaction and attribution reports' kernels, one kernel per contact for the hits, a
+ * stable radix sort of the 3 K shares by destination (three launches per 8 bits of the node range) and one kernel that sums each node's
+ * run in order -- no float atomics, no host synchronisation, K stays on the device; eager on the context's stream, outside the captured
+ * graphs, inside the epilogue interval of the timing events.  Every buffer is allocated by the first admm_hip_set_surface_reaction with
+ * share > 0 in a finalized context, or by finalize, never by admm_hip_step.  With all shares zero admm_hip_step launches and uploads
+ * exactly what it did and produces bitwise the same frames.  The frame's launches overwrite the buffers of the reaction and attribution
+ * reports (as a report for depth_min would).
+ *   admm_hip_set_surface_reaction        share in [0, 1] for one body or sheet surface, in effect from the next admm_hip_step on; before or
+ *                                        after finalize and between frames, no synchronisation.  Order of the checks: ADMM_ERR_ARG an
+ *                                        unknown mesh, a mesh that is not a body or sheet surface, a share outside [0, 1] or NaN; then
+ *                                        ADMM_ERR_STATE share > 0 while contact attribution is off; then ADMM_ERR_UNSUPPORTED share > 0 in a
+ *                                        sharded context (a destination may live on another rank).  The other way round,
+ *                                        admm_hip_enable_contact_attribution(ctx, 0) returns ADMM_ERR_STATE and admm_hip_set_shard with
+ *                                        world > 1 ADMM_ERR_UNSUPPORTED while any share is above 0 (admm_hip_finalize checks
+ *                                        the same once more; no sequence of calls reaches that check today).
+ *   admm_hip_set_surface_reaction_depth  depth_min >= 0 (ADMM_ERR_ARG otherwise, NaN included).
+ *   admm_hip_get_surface_reaction        the last frame's: dv [n_nodes][3] in the caller's node order, exactly 0.0 where nothing landed;
+ *                                        one 64-byte record per contact in admm_hip_get_contacts' order {node, mesh (-1: the entry names
+ *                                        none), tri (original index), corner[3] (caller's node ids), status, weight[3], share}, -1 and 0.0
+ *                                        where the contact does not react; *count = K, records [capacity] receives the first
+ *                                        min(K, capacity); info over all K.  Checks and behaves like the reaction reports: its own
+ *                                        arguments, a host-only context, ADMM_ERR_STATE before the first step.  The counts are summed
+ *                                        on the device (one one-wave launch); dv, K and the counts arrive behind one wait, the
+ *                                        min(K, capacity) records behind a second: nothing beyond them is copied.  After
+ *                                        a frame that ran with all shares zero: dv 0, no records.  Any output may be NULL.
+ *   admm_hip_surface_reaction_query      context-free host evaluation of the shares and the ordered sums, the device's bits; needs no GPU:
+ *                                        m3 [n_nodes][3] (a node's mass per component), f [K][3], corner [K][3], weight [K][3], share [K]
+ *                                        -> dv [n_nodes][3].  A row with share 0 adds nothing (its corners are not read).  ADMM_ERR_ARG:
+ *                                        n_nodes < 1, K < 0, a NULL pointer, dt not > 0, a share outside [0, 1], a corner of a row with
+ *                                        share > 0 outside the nodes.
+ *   admm_hip_debug_stable_sort           the feature's sort kernels alone: perm [n] = the stable ascending order of keys [n], every key in
+ *                                        [0, key_bound), key_bound <= 2^31 - 1; one pass per 8 bits of key_bound - 1.  For tests.
+ * Not covered: reactions of self-contacts, edge-edge contact, continuous detection, sharded contexts.                                      */
+enum { ADMM_SURFACE_REACTING = 0, ADMM_SURFACE_UNOWNED = 1, ADMM_SURFACE_OTHER = 2, ADMM_SURFACE_SELF = 3 };
+typedef struct admm_hip_surface_contact {
+    int32_t node, mesh, tri, corner[3], status, pad_;
+    double weight[3], share;
+} admm_hip_surface_contact;
+typedef struct admm_hip_surface_reaction_info {
+    int64_t n_contacts, n_reacting, n_unowned, n_other, n_self;
+} admm_hip_surface_reaction_info;
+int admm_hip_set_surface_reaction(admm_hip_ctx *ctx, int mesh_id, double share);
+int admm_hip_set_surface_reaction_depth(admm_hip_ctx *ctx, double depth_min);
+int admm_hip_get_surface_reaction(admm_hip_ctx *ctx, double *dv, admm_hip_surface_contact *records, int64_t capacity, int64_t *count, admm_hip_surface_reaction_info *info);
+int admm_hip_surface_reaction_query(int64_t n_nodes, const double *m3, int64_t K, const double *f, const int32_t *corner, const double *weight, const double *share,
+                                    double dt, double *dv);
+int admm_hip_debug_stable_sort(admm_hip_ctx *ctx, int64_t n, const int32_t *keys, int64_t key_bound, int32_t *perm);
 
 #ifdef __cplusplus
 }
