@@ -105,6 +105,46 @@ class SurfaceReactionInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RigidStateRecord(C.Structure):
+    """admm_hip_rigid_state: a rigid body's state c, q = (w, x, y, z), v, L; derived omega, R (row-major), the entry's par; the last
+    frame's applied F, tau and number of contacts"""
+    _fields_ = [("c", C.c_double * 3), ("q", C.c_double * 4), ("v", C.c_double * 3), ("L", C.c_double * 3), ("omega", C.c_double * 3), ("R", C.c_double * 9),
+                ("par", C.c_double * 4), ("F", C.c_double * 3), ("tau", C.c_double * 3), ("count", C.c_int64), ("entry", C.c_int32), ("pad_", C.c_int32)]
+
+
+RIGID_FIELDS = ("c", "q", "v", "L", "omega", "R", "par", "F", "tau")
+
+
+class RigidState:
+    """one body's record as numpy arrays (c, q, v, L, omega, R [3][3], par, F, tau), count, entry; `body`: the constants rigid_query takes
+    (type, mass, inertia, accel, c0, par0), None when built by hand.  frame / motion: the entry's rows of the shape table."""
+
+    def __init__(self, rec, body=None):
+        for n in RIGID_FIELDS:
+            setattr(self, n, np.array(getattr(rec, n)[:], dtype=np.float64))
+        self.R = self.R.reshape(3, 3)
+        self.count, self.entry, self.body = int(rec.count), int(rec.entry), body
+
+    def record(self):
+        r = RigidStateRecord()
+        for n in RIGID_FIELDS:
+            a = np.asarray(getattr(self, n), dtype=np.float64).ravel()
+            getattr(r, n)[:] = a.tolist()
+        r.count, r.entry = int(self.count), int(self.entry)
+        return r
+
+    @property
+    def frame(self):
+        return np.concatenate([self.R.ravel(), self.c])
+
+    @property
+    def motion(self):
+        return np.concatenate([self.v, self.omega, self.c])
+
+    def same_bits(self, o):
+        return self.count == o.count and self.entry == o.entry and all(getattr(self, n).tobytes() == getattr(o, n).tobytes() for n in RIGID_FIELDS)
+
+
 class GroupMoments(C.Structure):
     """admm_hip_group_moments: a damping group's mass, centre of mass, momentum, angular momentum and inertia about it, angular velocity"""
     _fields_ = [("mass", C.c_double), ("com", C.c_double * 3), ("p", C.c_double * 3), ("l", C.c_double * 3), ("inertia", C.c_double * 6), ("omega", C.c_double * 3),
@@ -218,6 +258,13 @@ def lib():
         L.admm_hip_get_surface_reaction.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(SurfaceReactionInfo)]
         L.admm_hip_surface_reaction_query.argtypes = [C.c_int64, _dp, C.c_int64, _dp, _ip, _dp, _dp, C.c_double, _dp]
         L.admm_hip_debug_stable_sort.argtypes = [C.c_void_p, C.c_int64, _ip, C.c_int64, _ip]
+        L.admm_hip_add_rigid_body.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, C.POINTER(C.c_int)]
+        L.admm_hip_set_rigid_depth.argtypes = [C.c_void_p, C.c_double]
+        L.admm_hip_get_rigid_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(RigidStateRecord)]
+        L.admm_hip_set_rigid_state.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+        L.admm_hip_set_rigid_accel.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.admm_hip_get_rigid_body.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp, _dp, _dp, _dp]
+        L.admm_hip_rigid_query.argtypes = [C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.POINTER(RigidStateRecord), _dp, _dp, C.c_int64, C.c_double, C.POINTER(RigidStateRecord)]
         L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
         L.admm_hip_add_nodes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
@@ -715,6 +762,23 @@ def surface_reaction_query(m3, f, corner, weight, share, dt):
     if rc:
         raise AdmmHipError("admm_hip_surface_reaction_query error %d" % rc)
     return dv
+
+
+def rigid_query(state, row, dt, count=0, body=None):
+    """one frame of a rigid body on the host (admm_hip_rigid_query; csrc/rigid.hpp, the device's bits; needs no GPU): state a
+    RigidState, row [6] = the body's {sum f, sum (point - c) x f} of entry_resultants(pivot = state.c), dt, count the row's number of
+    contacts; body (default state.body): dict(type, mass, inertia [6] = xx xy xz yy yz zz, accel [3], c0 [3], par0 [4]) -> RigidState"""
+    K = state.body if body is None else body
+    a = {n: np.ascontiguousarray(K[n], dtype=np.float64) for n in ("inertia", "accel", "c0", "par0")}
+    assert a["inertia"].size == 6 and a["accel"].size == 3 and a["c0"].size == 3 and a["par0"].size == 4
+    r = np.ascontiguousarray(row, dtype=np.float64).reshape(6)
+    fe, te = r[:3].copy(), r[3:].copy()
+    rin, out = state.record(), RigidStateRecord()
+    ty = SHAPE[K["type"]] if isinstance(K["type"], str) else int(K["type"])
+    rc = lib().admm_hip_rigid_query(ty, float(K["mass"]), _d(a["inertia"]), _d(a["accel"]), _d(a["c0"]), _d(a["par0"]), C.byref(rin), _d(fe), _d(te), int(count), float(dt), C.byref(out))
+    if rc:
+        raise AdmmHipError("admm_hip_rigid_query error %d" % rc)
+    return RigidState(out, K)
 
 
 def stress_query(kind, dx, params, volume):
@@ -1247,6 +1311,47 @@ class System:
         dv = np.zeros((self.n_nodes, 3)); rec = np.zeros(max(cap, 0), SURFACE_CONTACT_DTYPE); cnt = C.c_int64(0); info = SurfaceReactionInfo()
         self._chk(self.L.admm_hip_get_surface_reaction(self.h, _d(dv), rec.ctypes.data_as(C.c_void_p) if cap > 0 else None, cap, C.byref(cnt), C.byref(info)))
         return dv, rec[:min(cnt.value, max(cap, 0))], info.as_dict()
+
+    # ---- rigid bodies in the collision list, moved by their contacts (extension; include/admm_hip.h) ----
+    def add_rigid_body(self, entry, mass, inertia, com, accel=(0.0, 0.0, 0.0)):
+        """-> body id.  Entry `entry` of the current shape list (a sphere, a box or a closed obstacle mesh) becomes a rigid body: mass,
+        inertia [6] = xx xy xz yy yz zz about com in the entry's own unrotated coordinates, com [3] in world coordinates, accel [3] a
+        constant acceleration (gravity).  Needs contact attribution on.  Before or after initialize()."""
+        J = np.ascontiguousarray(inertia, dtype=np.float64).reshape(6)
+        c = np.ascontiguousarray(com, dtype=np.float64).reshape(3)
+        a = np.ascontiguousarray(accel, dtype=np.float64).reshape(3)
+        b = C.c_int()
+        self._chk(self.L.admm_hip_add_rigid_body(self.h, int(entry), float(mass), _d(J), _d(c), _d(a), C.byref(b)))
+        self.n_rigid = getattr(self, "n_rigid", 0) + 1
+        return b.value
+
+    def rigid_body(self, body):
+        """-> dict(entry, type, mass, inertia [6], accel [3], c0 [3], par0 [4]): a body's constants, what rigid_query takes"""
+        e, t, m = C.c_int(), C.c_int(), C.c_double()
+        J, a, c0, p0 = np.zeros(6), np.zeros(3), np.zeros(3), np.zeros(4)
+        self._chk(self.L.admm_hip_get_rigid_body(self.h, int(body), C.byref(e), C.byref(t), C.byref(m), _d(J), _d(a), _d(c0), _d(p0)))
+        return dict(entry=e.value, type=t.value, mass=m.value, inertia=J, accel=a, c0=c0, par0=p0)
+
+    def rigid_state(self):
+        """-> [RigidState] of every body, in the order they were added (admm_hip_get_rigid_state: one synchronisation)"""
+        n = getattr(self, "n_rigid", 0)
+        recs = (RigidStateRecord * max(n, 1))()
+        self._chk(self.L.admm_hip_get_rigid_state(self.h, n, recs))
+        return [RigidState(recs[b], self.rigid_body(b)) for b in range(n)]
+
+    def set_rigid_state(self, body, c, q, v, L):
+        """c [3], q [4] = (w, x, y, z), v [3], L [3] of one body: a checkpoint, or a kick between frames"""
+        a = [np.ascontiguousarray(x, dtype=np.float64).reshape(k) for x, k in ((c, 3), (q, 4), (v, 3), (L, 3))]
+        self._chk(self.L.admm_hip_set_rigid_state(self.h, int(body), _d(a[0]), _d(a[1]), _d(a[2]), _d(a[3])))
+
+    def set_rigid_accel(self, body, accel):
+        """a body's constant acceleration, in effect from the next step() on"""
+        a = np.ascontiguousarray(accel, dtype=np.float64).reshape(3)
+        self._chk(self.L.admm_hip_set_rigid_accel(self.h, int(body), _d(a)))
+
+    def set_rigid_depth(self, depth_min):
+        """the depth above which a node's contact loads a rigid body (default 0), as in entry_resultants(depth_min)"""
+        self._chk(self.L.admm_hip_set_rigid_depth(self.h, float(depth_min)))
 
     def debug_stable_sort(self, keys, key_bound):
         """-> perm [n] int32: the stable ascending order of keys [n] (each in [0, key_bound)) by the reaction's sort kernels alone"""

@@ -176,6 +176,8 @@ int admm_hip_enable_contact_attribution(admm_hip_ctx *ctx, int on) {
     const bool want = on != 0;
     if (!want) for (size_t mi = 0; mi < ctx->meshes.size(); ++mi) if (ctx->meshes[mi].reaction_share > 0.0)      // (abi_surface_reaction.inc)
         return fail(ctx, ADMM_ERR_STATE, "enable_contact_attribution: surface %d has a reaction share of %g, which needs every contact's owner entry: set it to 0 first", (int)mi, ctx->meshes[mi].reaction_share);
+    if (!want && !ctx->rigid.empty())      // (abi_rigid.inc)
+        return fail(ctx, ADMM_ERR_STATE, "enable_contact_attribution: entry %d is a rigid body, whose load needs every contact's owner entry", ctx->rigid[0].K.entry);
     if (want && ctx->finalized && ctx->device_id >= 0) { TRY(attribution_allocate(ctx)); TRY(attribution_fill(ctx)); }      // (before finalize: finalize does both)
     if (want != ctx->attribution) drop_iteration_graphs(ctx);
     ctx->attribution = want;

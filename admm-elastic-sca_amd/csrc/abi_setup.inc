@@ -286,6 +286,14 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
     }
     TRY(check_body_entries(ctx, n_shapes, types, params, true, nullptr, nullptr, nullptr));
     TRY(check_side_entries(ctx, n_shapes, types, params));
+    // rigid bodies (abi_rigid.inc) are entries of THIS list: its length stands while one exists, a body's entry keeps its type, and its
+    // params are the body's own (the device rewrites them at every step), not the caller's
+    if (!ctx->rigid.empty() && n_shapes != ctx->shapes.n)
+        return fail(ctx, ADMM_ERR_STATE, "collision shapes: a list of %d entries while entry %d of the current %d is a rigid body: the list keeps its length while bodies exist", n_shapes,
+                    ctx->rigid[0].K.entry, ctx->shapes.n);
+    for (const admm_hip_ctx::RigidBodyHost &B : ctx->rigid)
+        if (types[B.K.entry] != B.K.type)
+            return fail(ctx, ADMM_ERR_ARG, "collision shape %d is a rigid body of type %d: its type cannot change to %d", B.K.entry, B.K.type, types[B.K.entry]);
     // (a list of the same length keeps its coefficients, motions and frames: one that now names a body surface where one of them is set is
     //  refused here -- a coefficient once finalized, by finalize before)
     if (n_shapes == ctx->shapes.n)
@@ -299,7 +307,9 @@ int admm_hip_set_collision_shapes(admm_hip_ctx *ctx, int n_shapes, const int32_t
     ctx->shapes.n = n_shapes;
     for (int j = 0; j < n_shapes; ++j) {
         ctx->shapes.type[j] = types[j];
-        for (int q = 0; q < 4; ++q) ctx->shapes.par[j][q] = params[4 * (size_t)j + q];
+        bool rigid = false;
+        for (const admm_hip_ctx::RigidBodyHost &B : ctx->rigid) rigid |= B.K.entry == j;
+        if (!rigid) for (int q = 0; q < 4; ++q) ctx->shapes.par[j][q] = params[4 * (size_t)j + q];
     }
     return push_shapes(ctx, form);
 }
@@ -654,6 +664,8 @@ int admm_hip_set_shard(admm_hip_ctx *ctx, int rank, int world) {
     if (ctx->finalized) return fail(ctx, ADMM_ERR_STATE, "shard must be set before finalize");
     if (world > 1) for (const admm_hip_ctx::CollisionMesh &m : ctx->meshes) if (m.reaction_share > 0.0)      // (abi_surface_reaction.inc)
         return fail(ctx, ADMM_ERR_UNSUPPORTED, "set_shard: a surface reaction share is set, which is not available in a sharded context (world = %d)", world);
+    if (world > 1 && !ctx->rigid.empty())      // (abi_rigid.inc)
+        return fail(ctx, ADMM_ERR_UNSUPPORTED, "set_shard: entry %d is a rigid body, which is not available in a sharded context (world = %d)", ctx->rigid[0].K.entry, world);
     ctx->rank = rank; ctx->world = world;
     return ADMM_OK;
 }
@@ -742,6 +754,7 @@ extern "C" int admm_hip_debug_tet_profile(unsigned long long *out) {
 static int check_pressure_chambers(admm_hip_ctx *ctx);      // (abi_pressure.inc)
 static bool surface_reaction_any(const admm_hip_ctx *ctx);  // (abi_surface_reaction.inc)
 static int surface_reaction_allocate(admm_hip_ctx *ctx);
+static int rigid_allocate(admm_hip_ctx *ctx, int first_new);  // (abi_rigid.inc)
 
 int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (!ctx) return ADMM_ERR_ARG;
@@ -783,6 +796,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (ctx->device_id >= 0) TRY(upload_all(ctx, plan));
     if (ctx->device_id >= 0 && ctx->attribution) { TRY(attribution_allocate(ctx)); TRY(attribution_fill(ctx)); }      // (switched on before finalize)
     if (ctx->device_id >= 0 && surface_reaction_any(ctx)) TRY(surface_reaction_allocate(ctx));      // (a share set before finalize)
+    if (ctx->device_id >= 0 && !ctx->rigid.empty()) TRY(rigid_allocate(ctx, 0));      // (bodies registered before finalize)
     ctx->finalized = true;
     return ADMM_OK;
 }

@@ -96,6 +96,7 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     } else ctx->ev_pending_prev = false;      // an untimed step: there is no timed "step before the last one" any more
     ctx->ev_used = 0; ctx->ev_iters = admm_iters; ctx->ev_timed = 0; ctx->ev_pending = ctx->timing;
     TRY(mark(ctx));
+    if (!ctx->rigid.empty()) TRY(launch_rigid_pose(ctx));      // rigid bodies (abi_rigid.inc): their pose into the shape table, before anything reads it (eager, outside the graphs)
     if (ctx->d_body_tag) TRY(update_bodies(ctx));      // body surfaces from the frame-start x, before the explicit forces (eager, outside the graphs)
     if (ctx->d_side) TRY(latch_sides(ctx));            // side memory: every node's side from the frame-start x (eager, outside the graphs)
     if (!ctx->chambers.empty()) TRY(launch_pressure(ctx));      // pressure chambers (abi_pressure.inc): eager, from the frame-start x, into v before gravity and the wind
@@ -234,6 +235,7 @@ int admm_hip_step(admm_hip_ctx *ctx, int admm_iters) {
     hipLaunchKernelGGL(epilogue_kernel, dim3((n3 + 255) / 256), dim3(256), 0, ctx->stream, n3, ctx->dt, ctx->d_x, ctx->d_v, ctx->d_xcur);
     HIPCHK(hipGetLastError());
     if (surface_reaction_any(ctx)) TRY(launch_surface_reaction(ctx));      // two-way contact (abi_surface_reaction.inc): eager, on the v the epilogue left, before the damping filter
+    if (!ctx->rigid.empty()) TRY(launch_rigid_integrate(ctx));      // rigid bodies (abi_rigid.inc): eager, their contacts' reaction from the u, z, x the frame left, then one step of the rule
     if (!ctx->damp_groups.empty()) TRY(launch_damping(ctx));      // velocity damping per node group (abi_damping.inc): eager, on the v the epilogue left
     TRY(mark(ctx));
     if (ctx->rccl_comm) TRY(comm_poll(ctx, nullptr));      // once per frame: a dead peer becomes a failed step, not a hang in the caller's next sync
@@ -299,6 +301,7 @@ int admm_hip_set_collision_sides(admm_hip_ctx *ctx, int mesh_id, const int32_t *
 int admm_hip_latch_collision_sides(admm_hip_ctx *ctx) {
     TRY(require_device(ctx));
     HIPCHK(hipSetDevice(ctx->device_id));
+    if (!ctx->rigid.empty()) TRY(launch_rigid_pose(ctx));
     if (ctx->d_body_tag) TRY(update_bodies(ctx));
     if (ctx->d_side) TRY(latch_sides(ctx));
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -30,6 +30,7 @@
 #include "kernels_damping.hpp"
 #include "kernels_pressure.hpp"
 #include "kernels_surface_reaction.hpp"
+#include "kernels_rigid.hpp"
 
 extern "C" int omp_get_max_threads(void);
 
@@ -82,6 +83,7 @@ extern "C" {
 #include "abi_damping.inc"
 #include "abi_pressure.inc"
 #include "abi_surface_reaction.inc"
+#include "abi_rigid.inc"
 #include "abi_step.inc"
 #include "abi_parity.inc"
 

@@ -24,6 +24,7 @@
 #include "node_csr.hpp"
 #include "collision_plan.hpp"
 #include "sweep_plan.hpp"
+#include "rigid.hpp"
 
 namespace admm_lib {
 
@@ -327,6 +328,16 @@ struct admm_hip_ctx {
     double sr_depth_min = 0.0; long long sr_frame = -1; bool sr_ready = false; int sr_cap = 0, sr_nb = 0, sr_passes = 1;
     void *d_sr_mesh = nullptr, *d_sr_rec = nullptr; int *d_sr_key = nullptr, *d_sr_idx = nullptr, *d_sr_blk = nullptr, *d_sr_tot = nullptr;
     double *d_sr_val = nullptr, *d_sr_dv = nullptr; long long *d_sr_n = nullptr;
+    // rigid bodies in the collision list (abi_rigid.inc, kernels_rigid.hpp, rigid.hpp; no body = off, the default).  rigid: the bodies in
+    // the order they were added -- their constants, the inertia as given, the host's copy of the record (as registered, as last set or
+    // as admm_hip_get_rigid_state last read it) and accel_dirty: the device's constants hold an older accel.  rg_depth_min: the depth
+    // above which a node's contact loads a body.  Device side, allocated by finalize or by the first admm_hip_add_rigid_body of a
+    // finalized context, never by admm_hip_step: d_rg_table the RigidTable (row -> body, the constants), d_rg_rec [ADMM_MAX_SHAPES] the
+    // records, d_rg_out [ADMM_MAX_SHAPES][6] the bodies' rows of the entry sums
+    struct RigidBodyHost { admm_rigid::Const K; double inertia[6]; admm_rigid::Record rec; bool accel_dirty = false; };
+    std::vector<RigidBodyHost> rigid;
+    double rg_depth_min = 0.0; bool rg_ready = false;
+    void *d_rg_table = nullptr, *d_rg_rec = nullptr; double *d_rg_out = nullptr;
     // Anderson acceleration (abi_anderson.inc, kernels_anderson.hpp; window 0 = off, the default; every buffer created by the first step
     // that needs it, again when the window grows).  aa_T: doubles per state-sized vector (all batches' z and u, each segment at an even
     // offset), aa_nblk: blocks of the elementwise launches; d_aa_ring, allocated for the window aa_cap_m, used as [2][aa_m + 1][aa_T]: the history's g, then its f;

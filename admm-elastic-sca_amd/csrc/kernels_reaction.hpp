@@ -258,21 +258,24 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void entry_place_kernel(const long lo
     }
 }
 
-// partial [6][n_part]: block B is block B - (the blocks of the rows before) of its row
-__global__ __launch_bounds__(ENERGY_BLOCK) void entry_partial_kernel(const ContactRecord *__restrict__ rec, const int *__restrict__ perm, const int n_rows, const long long *__restrict__ total,
-                                                                     const double p0, const double p1, const double p2, const int n_part, double *__restrict__ partial) {
-    long long base = 0, blk0 = 0;
-    int row = -1;
-    for (int q = 0; q < n_rows; ++q) {      // (uniform across the block)
+// the row of block B = blockIdx.x: the blocks of row q start at sum over q' < q of ceil(total[q'] / 64); -> the row (-1: beyond the last
+// row's blocks), the contacts and the blocks of the rows before it.  Uniform across the block.
+__device__ __forceinline__ int entry_block_row(const int n_rows, const long long *__restrict__ total, long long &base, long long &blk0) {
+    base = 0; blk0 = 0;
+    for (int q = 0; q < n_rows; ++q) {
         const long long nb = (total[q] + ENERGY_BLOCK - 1) / ENERGY_BLOCK;
-        if ((long long)blockIdx.x < blk0 + nb) { row = q; break; }
+        if ((long long)blockIdx.x < blk0 + nb) return q;
         blk0 += nb; base += total[q];
     }
-    if (row < 0) return;                    // beyond the last row's blocks: nobody reads this partial
+    return -1;
+}
+// block blockIdx.x of `row`: contact_resultant_kernel's six terms about `pivot` and block sums -> partial [6][n_part] at blockIdx.x
+// (shared by entry_partial_kernel and kernels_rigid.hpp's rigid_partial_kernel)
+__device__ __forceinline__ void entry_partial_block(const ContactRecord *__restrict__ rec, const int *__restrict__ perm, const long long row_total, const long long base, const long long blk0,
+                                                    const double *pivot, const int n_part, double *__restrict__ partial) {
     const long long r = ((long long)blockIdx.x - blk0) * ENERGY_BLOCK + threadIdx.x;
     double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (r < total[row]) {
-        const double pivot[3] = {p0, p1, p2};
+    if (r < row_total) {
         const ContactRecord c = rec[perm[base + r]];
         admm_reaction::resultant_terms(c.f, c.point, pivot, t);
     }
@@ -280,11 +283,21 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void entry_partial_kernel(const Conta
     for (int q = 0; q < 6; ++q) track_block_sum(t[q], &partial[(size_t)q * n_part + blockIdx.x]);
 }
 
-// workgroup (row, component) = (blockIdx.x / 6, blockIdx.x % 6): out[row][component], energy_reduce_kernel's order over the row's partials
-__global__ __launch_bounds__(ENERGY_REDUCE) void entry_reduce_kernel(const int n_rows, const long long *__restrict__ total, const int n_part, const double *__restrict__ partial,
-                                                                     double *__restrict__ out) {
+// partial [6][n_part]: block B is block B - (the blocks of the rows before) of its row
+__global__ __launch_bounds__(ENERGY_BLOCK) void entry_partial_kernel(const ContactRecord *__restrict__ rec, const int *__restrict__ perm, const int n_rows, const long long *__restrict__ total,
+                                                                     const double p0, const double p1, const double p2, const int n_part, double *__restrict__ partial) {
+    long long base, blk0;
+    const int row = entry_block_row(n_rows, total, base, blk0);
+    if (row < 0) return;                    // beyond the last row's blocks: nobody reads this partial
+    const double pivot[3] = {p0, p1, p2};
+    entry_partial_block(rec, perm, total[row], base, blk0, pivot, n_part, partial);
+}
+
+// one (row, component) by the whole workgroup: the row's partials in energy_reduce_kernel's order -> *out
+// (shared by entry_reduce_kernel and kernels_rigid.hpp's rigid_reduce_kernel)
+__device__ __forceinline__ void entry_reduce_row(const int row, const int comp, const long long *__restrict__ total, const int n_part, const double *__restrict__ partial, double *__restrict__ out) {
     __shared__ double acc[ENERGY_REDUCE];
-    const int row = (int)blockIdx.x / 6, comp = (int)blockIdx.x % 6, t = threadIdx.x;
+    const int t = threadIdx.x;
     long long blk0 = 0;
     for (int q = 0; q < row; ++q) blk0 += (total[q] + ENERGY_BLOCK - 1) / ENERGY_BLOCK;
     const int n = (int)((total[row] + ENERGY_BLOCK - 1) / ENERGY_BLOCK);
@@ -297,7 +310,14 @@ __global__ __launch_bounds__(ENERGY_REDUCE) void entry_reduce_kernel(const int n
         if (t < h) acc[t] += acc[t + h];
         __syncthreads();
     }
-    if (t == 0) out[(size_t)row * 6 + comp] = acc[0];
+    if (t == 0) *out = acc[0];
+}
+
+// workgroup (row, component) = (blockIdx.x / 6, blockIdx.x % 6): out[row][component], energy_reduce_kernel's order over the row's partials
+__global__ __launch_bounds__(ENERGY_REDUCE) void entry_reduce_kernel(const int n_rows, const long long *__restrict__ total, const int n_part, const double *__restrict__ partial,
+                                                                     double *__restrict__ out) {
+    const int row = (int)blockIdx.x / 6, comp = (int)blockIdx.x % 6;
+    entry_reduce_row(row, comp, total, n_part, partial, &out[(size_t)row * 6 + comp]);
 }
 
 } // namespace admm_dev

@@ -237,6 +237,15 @@ public:
         for (int j = 0; j < 3; ++j) f[9 + j] = about[j];
     }
     virtual Vector3d frame_pivot() const { return orientation_pivot; }
+    // ... and a rigid body (admm_hip_add_rigid_body; a sphere, a box or a closed obstacle mesh): rigid_mass > 0 makes the shape one, moved
+    // on the device by the reaction of its contacts.  rigid_inertia = (xx, xy, xz, yy, yz, zz) about the centre of mass in the shape's own
+    // unrotated coordinates, rigid_accel a constant acceleration (gravity).  The centre of mass is `center` for a sphere and the frame's
+    // pivot otherwise, unless rigid_com_set names rigid_com.  Read once, by System::initialize, behind the frames; needs
+    // System::settings.contact_attribution.  From then on the device owns the shape's pose: System::rigid_state() reports it, and
+    // `center`, `orientation` and the motion members are no longer read for it.
+    double rigid_mass = 0.0, rigid_inertia[6] = {0, 0, 0, 0, 0, 0};
+    Vector3d rigid_accel = Vector3d(0, 0, 0), rigid_com = Vector3d(0, 0, 0);
+    bool rigid_com_set = false;
 };
 class CollisionFloor : public CollisionShape {
 public:

@@ -17,6 +17,7 @@
 // host (System.cpp:57-58) and z - u returns to the device-side right-hand side.
 // A user-written ExplicitForce::project runs here at the start of step().
 #pragma once
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -499,6 +500,14 @@ public:
         r.records.resize((size_t)(n < (int64_t)r.records.size() ? n : (int64_t)r.records.size()));
         return r;
     }
+    // rigid bodies (CollisionShape::rigid_mass; admm_hip_get_rigid_state): one record per body in the order of the shape list -- the state
+    // c, q, v, L, the derived omega, R and the entry's par, the last frame's applied F, tau and number of contacts.  Empty: none, or the
+    // call failed.
+    std::vector<admm_hip_rigid_state> rigid_state() {
+        std::vector<admm_hip_rigid_state> r(rigid_shapes.size());
+        if (!initialized || r.empty() || !check(admm_hip_get_rigid_state(gpu, (int)r.size(), r.data()))) r.clear();
+        return r;
+    }
     // the contacts' resultant per entry of the shape list (admm_hip_entry_resultants): rows [n_entries + 1], the last one for the contacts
     // that nothing moved in the last local step; n_entries: the length of the CollisionForce's shape list.  Empty: the call failed.
     std::vector<ContactResultant> entry_resultants(int n_entries, double px = 0.0, double py = 0.0, double pz = 0.0, double depth_min = 1e-10) {
@@ -623,6 +632,7 @@ protected:
     std::vector<long> mesh_vel_versions;                               // the CollisionMesh::vel_version the context last received
     std::vector<double> body_mu;                                       // the CollisionBody::surface_friction the context last received
     std::vector<std::pair<const CollisionBody *, int> > body_ids;     // CollisionBody surfaces registered with the context -> their mesh_id
+    std::vector<const CollisionShape *> rigid_shapes;                  // the shapes registered as rigid bodies, in body order
     std::vector<double> body_share;                                    // the CollisionBody::reaction_share the context last received
     std::vector<int> batch_first, batch_count, batch_kind;
     std::vector<char> batch_moving;
@@ -695,7 +705,7 @@ protected:
         unpin_state();
         if (gpu) { admm_hip_destroy(gpu); gpu = nullptr; }
         mesh_ids.clear(); mesh_versions.clear(); body_ids.clear(); friction_pushed = false;
-        motion_pushed = false; frames_pushed = false; mesh_vel_versions.clear(); mesh_thick.clear(); body_mu.clear(); body_share.clear();
+        motion_pushed = false; frames_pushed = false; mesh_vel_versions.clear(); mesh_thick.clear(); body_mu.clear(); body_share.clear(); rigid_shapes.clear();
         initialized = false; attribution_sent = -1;
     }
 
@@ -774,6 +784,20 @@ protected:
         if (oriented || frames_pushed) {
             frames_pushed = true;
             if (!check(admm_hip_set_collision_frames(gpu, (int)cf->collisionShapes.size(), fr.data()))) return false;
+        }
+        // rigid bodies (CollisionShape::rigid_mass > 0; admm_hip_add_rigid_body): registered once, behind the frames; they need the
+        // attribution switch, which otherwise travels with the first step()
+        for (size_t q = 0; q < cf->collisionShapes.size(); ++q) {
+            const CollisionShape &sh = *cf->collisionShapes[q];
+            if (!(sh.rigid_mass > 0.0) || std::find(rigid_shapes.begin(), rigid_shapes.end(), &sh) != rigid_shapes.end()) continue;
+            if (settings.contact_attribution && attribution_sent != 1) {
+                if (!check(admm_hip_enable_contact_attribution(gpu, 1))) return false;
+                attribution_sent = 1;
+            }
+            const Vector3d c = sh.rigid_com_set ? sh.rigid_com : (sh.shape_type() == ADMM_SHAPE_SPHERE ? sh.center : sh.frame_pivot());
+            const double com[3] = {c[0], c[1], c[2]}, acc[3] = {sh.rigid_accel[0], sh.rigid_accel[1], sh.rigid_accel[2]};
+            if (!check(admm_hip_add_rigid_body(gpu, (int)q, sh.rigid_mass, sh.rigid_inertia, com, acc, nullptr))) return false;
+            rigid_shapes.push_back(&sh);
         }
         // the shapes' friction coefficients (contexts that never saw one above 0 skip the call: they run the frictionless kernels anyway)
         std::vector<double> mu;

@@ -1157,6 +1157,63 @@ int admm_hip_surface_reaction_query(int64_t n_nodes, const double *m3, int64_t K
                                     double dt, double *dv);
 int admm_hip_debug_stable_sort(admm_hip_ctx *ctx, int64_t n, const int32_t *keys, int64_t key_bound, int32_t *perm);
 
+/* ---- rigid bodies in the collision list, moved by their contacts ---------------------------------------------------------------------------
+ * Extension, no reference counterpart; off unless asked for.  An entry of the collision list (a sphere, a box or a closed obstacle mesh)
+ * becomes a rigid body with a mass and an inertia tensor.  Once per frame, after admm_hip_step's epilogue and the two-way contact and
+ * before the velocity damping, the device takes the body's row {sum f, sum (point - c) x f} of admm_hip_entry_resultants(depth_min,
+ * pivot = the body's own centre c) -- what its contacts exerted on the nodes -- applies the opposite to the body, integrates it and
+ * keeps the new state; at the very start of the next admm_hip_step, before the body surfaces and the side latch, it writes the pose
+ * into the entry's rows of the shape table (par, frame, framed, motion).  No host synchronisation, no atomics, fixed orders: two runs
+ * give the same bits.  One definition, csrc/rigid.hpp, compiled without fused multiply-adds for the host and the device:
+ *   state      c[3] centre of mass, q[4] = (w, x, y, z) unit quaternion, v[3], L[3] angular momentum about c in world axes
+ *   one frame  F = -Fe, tau = -Te;  v' = v + dt (F / m + accel);  L' = L + dt tau;  R = R(q);  omega' = R (Jinv (R^T L'));
+ *              c' = c + dt v';  h = (dt / 2) omega';  q' = normalise((1, h) / sqrt(1 + |h|^2) (x) q)  -- the Cayley transform, an exact
+ *              rotation by 2 atan|h|, within (dt |omega|)^3 / 12 of dt |omega| per frame
+ *   pose       frame = {R(q'), c'}, framed = R(q') is not exactly I, motion = {v', omega', c'}; a sphere's or a mesh's par[0..2] =
+ *              par0 + (c' - c0), a box's par unchanged (its centre is the frame's pivot)
+ * Launches per frame (csrc/kernels_rigid.hpp): rigid_pose_kernel at the start; behind the epilogue the reaction and attribution reports'
+ * kernels, entry_count / scan / place, rigid_partial_kernel, rigid_reduce_kernel, rigid_integrate_kernel -- eager on the context's stream,
+ * outside the captured graphs.  Every buffer is allocated by finalize or by the first admm_hip_add_rigid_body of a finalized context,
+ * never by admm_hip_step.  A context without a body launches and uploads exactly what it did.  Because the pose is rewritten at every
+ * step, a setter that uploads the host's (older) shape table between frames does not undo a body's motion.
+ *   admm_hip_add_rigid_body   entry of the current list; inertia[6] = (xx, xy, xz, yy, yz, zz) about com in the entry's own unrotated
+ *                             coordinates; com[3] in world coordinates; accel[3] a constant acceleration (gravity).  Before or after
+ *                             finalize.  Order of the checks: ADMM_ERR_ARG the entry is out of range or a body already; its type is
+ *                             FLOOR or CYLINDER (infinite shapes); it is a mesh that is a body or sheet surface; mass, inertia, com or
+ *                             accel not finite, mass not > 0, inertia not positive definite; then ADMM_ERR_STATE contact attribution is
+ *                             off; then ADMM_ERR_UNSUPPORTED world > 1 (a rank sees its share of the contacts only); then ADMM_ERR_ARG
+ *                             the entry's frame is neither the identity (its pivot then becomes com) nor pivoted at com (a box: com
+ *                             must be its pivot, the box's centre).  The orientation starts from the entry's R.  While a body exists,
+ *                             admm_hip_enable_contact_attribution(ctx, 0) returns ADMM_ERR_STATE, admm_hip_set_shard with world > 1
+ *                             ADMM_ERR_UNSUPPORTED, admm_hip_set_collision_shapes with a list of another length ADMM_ERR_STATE; with
+ *                             the same length a body entry keeps its type (ADMM_ERR_ARG otherwise) and its params are ignored.
+ *   admm_hip_set_rigid_depth  depth_min >= 0 of the contacts that load the bodies (default 0).
+ *   admm_hip_get_rigid_state  one record per body, in the order they were added: the state, the derived omega, R (row-major) and the
+ *                             entry's par, the last frame's applied F, tau and number of contacts.  One synchronisation; it also brings
+ *                             the host's shape table up to date for the bodies' entries.  n_bodies must be the number of bodies.
+ *   admm_hip_set_rigid_state  c, q, v, L of one body (a checkpoint, or a kick between frames); q is normalised unless |q|^2 is within
+ *                             8 ulp of 1 (a q read back keeps its bits); omega is derived from the q given, which may differ in the
+ *                             last bits from what the frame before left; F, tau and the count return to 0.  ADMM_ERR_ARG: not finite.
+ *   admm_hip_set_rigid_accel  between any two frames; travels as a kernel argument with the next step.
+ *   admm_hip_rigid_query      context-free host evaluation of one frame for one body, the device's bits; needs no GPU.
+ * Not covered: bodies do not collide with each other or with static entries; no compound bodies of several entries; a node's whole
+ * f_contact goes to the owner of its winning element (the last mover); the load is explicit and one frame behind -- the staggered
+ * coupling is stable only while the body's mass is well above that of the nodes it touches; where it breaks is not measured.          */
+typedef struct admm_hip_rigid_state {
+    double c[3], q[4], v[3], L[3], omega[3], R[9], par[4], F[3], tau[3];
+    int64_t count;
+    int32_t entry, pad_;
+} admm_hip_rigid_state;
+int admm_hip_add_rigid_body(admm_hip_ctx *ctx, int entry, double mass, const double inertia[6], const double com[3], const double accel[3], int *body_id);
+int admm_hip_set_rigid_depth(admm_hip_ctx *ctx, double depth_min);
+int admm_hip_get_rigid_state(admm_hip_ctx *ctx, int n_bodies, admm_hip_rigid_state *out);
+int admm_hip_set_rigid_state(admm_hip_ctx *ctx, int body, const double c[3], const double q[4], const double v[3], const double L[3]);
+int admm_hip_set_rigid_accel(admm_hip_ctx *ctx, int body, const double accel[3]);
+/* a body's constants as registered (accel: as last set), what admm_hip_rigid_query takes; any output may be NULL */
+int admm_hip_get_rigid_body(admm_hip_ctx *ctx, int body, int *entry, int *type, double *mass, double inertia[6], double accel[3], double c0[3], double par0[4]);
+int admm_hip_rigid_query(int type, double mass, const double inertia[6], const double accel[3], const double c0[3], const double par0[4],
+                         const admm_hip_rigid_state *in, const double Fe[3], const double Te[3], int64_t count, double dt, admm_hip_rigid_state *out);
+
 #ifdef __cplusplus
 }
 #endif
