@@ -265,6 +265,11 @@ def lib():
         L.admm_hip_set_rigid_accel.argtypes = [C.c_void_p, C.c_int, _dp]
         L.admm_hip_get_rigid_body.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp, _dp, _dp, _dp]
         L.admm_hip_rigid_query.argtypes = [C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.POINTER(RigidStateRecord), _dp, _dp, C.c_int64, C.c_double, C.POINTER(RigidStateRecord)]
+        L.admm_hip_attach_anchors.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        L.admm_hip_detach_anchors.argtypes = [C.c_void_p, C.c_int]
+        L.admm_hip_get_attachment.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, _dp]
+        L.admm_hip_get_attachment_load.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]
+        L.admm_hip_attachment_query.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, C.POINTER(C.c_int64)]
         L.admm_hip_get_objective.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int)]
         L.admm_hip_set_timestep.argtypes = [C.c_void_p, C.c_double]
         L.admm_hip_add_nodes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
@@ -779,6 +784,33 @@ def rigid_query(state, row, dt, count=0, body=None):
     if rc:
         raise AdmmHipError("admm_hip_rigid_query error %d" % rc)
     return RigidState(out, K)
+
+
+def attachment_query(c=None, R=None, local=None, f=None, point=None, active=None, pivot=None):
+    """rigid attachments on the host (admm_hip_attachment_query; csrc/attach.hpp, the device's bits; needs no GPU).  Target half, when
+    `local` [n][3] is given: targets [n][3] = c + R local from a body's c [3] and R [3][3].  Sum half, when `f` [n][3] is given: the row
+    {sum f, sum (point - pivot) x f} over the elements in the device's order from f and point [n][3] (batch_reaction's f, read_local's
+    z), active [n] (None: all active; a released element adds zeros) and pivot [3].  -> dict with targets and / or row [6], n_active"""
+    out = {}
+    if local is not None:
+        loc = np.ascontiguousarray(local, dtype=np.float64).reshape(-1, 3)
+        cc = np.ascontiguousarray(c, dtype=np.float64).reshape(3); rr = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+        tg = np.zeros_like(loc)
+        rc = lib().admm_hip_attachment_query(len(loc), _d(cc), _d(rr), _d(loc), _d(tg), None, None, None, None, None, None)
+        if rc:
+            raise AdmmHipError("admm_hip_attachment_query error %d" % rc)
+        out["targets"] = tg
+    if f is not None:
+        ff = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 3); pt = np.ascontiguousarray(point, dtype=np.float64).reshape(-1, 3)
+        assert ff.shape == pt.shape
+        ac = None if active is None else np.ascontiguousarray(active, dtype=np.int32).reshape(len(ff))
+        pv = None if pivot is None else np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
+        row = np.zeros(6); na = C.c_int64(0)
+        rc = lib().admm_hip_attachment_query(len(ff), None, None, None, None, _d(ff), _d(pt), _i(ac), _d(pv), _d(row), C.byref(na))
+        if rc:
+            raise AdmmHipError("admm_hip_attachment_query error %d" % rc)
+        out["row"] = row; out["n_active"] = int(na.value)
+    return out
 
 
 def stress_query(kind, dx, params, volume):
@@ -1352,6 +1384,37 @@ class System:
     def set_rigid_depth(self, depth_min):
         """the depth above which a node's contact loads a rigid body (default 0), as in entry_resultants(depth_min)"""
         self._chk(self.L.admm_hip_set_rigid_depth(self.h, float(depth_min)))
+
+    # ---- rigid attachments: anchor batches fastened to rigid bodies (extension; include/admm_hip.h) ----
+    def attach_anchors(self, batch, body, local=None):
+        """The whole ANCHOR batch `batch` is fastened to rigid body `body`: from the next step on the device rewrites its targets from the
+        body's pose at the start of every frame and adds the reaction of its active elements to the body's load.  local [n][3]: the
+        elements' offsets in the body's own coordinates; None: derived from the batch's current targets and the body's current pose.
+        Before or after initialize()."""
+        batch = int(batch)
+        n = self.batches[batch][1] if 0 <= batch < len(self.batches) else 0
+        loc = None if local is None else np.ascontiguousarray(local, dtype=np.float64).reshape(n, 3)
+        self._chk(self.L.admm_hip_attach_anchors(self.h, batch, int(body), _d(loc)))
+
+    def detach_anchors(self, batch):
+        """the batch's targets stay where the last frame put them; it is a plain moving-anchor batch again"""
+        self._chk(self.L.admm_hip_detach_anchors(self.h, int(batch)))
+
+    def attachment(self, batch):
+        """-> dict(body (-1: not attached), local [n][3], targets [n][3] as the device holds them now: one synchronisation)"""
+        batch = int(batch)
+        n = self.batches[batch][1] if 0 <= batch < len(self.batches) else 0
+        body = C.c_int(-1); loc = np.zeros((n, 3)); tg = np.zeros((n, 3))
+        self._chk(self.L.admm_hip_get_attachment(self.h, batch, C.byref(body), _d(loc), _d(tg)))
+        return dict(body=int(body.value), local=loc, targets=tg)
+
+    def attachment_load(self):
+        """-> (Fa [n_bodies][3], Ta [n_bodies][3], n_active [n_bodies]): the last frame's attachment row per body, about its centre before
+        that frame's integration, as the nodes felt it (the body received the opposite)"""
+        n = getattr(self, "n_rigid", 0)
+        Fa = np.zeros((max(n, 1), 3)); Ta = np.zeros((max(n, 1), 3)); na = np.zeros(max(n, 1), np.int64)
+        self._chk(self.L.admm_hip_get_attachment_load(self.h, n, _d(Fa), _d(Ta), na.ctypes.data_as(C.POINTER(C.c_int64))))
+        return Fa[:n], Ta[:n], na[:n]
 
     def debug_stable_sort(self, keys, key_bound):
         """-> perm [n] int32: the stable ascending order of keys [n] (each in [0, key_bound)) by the reaction's sort kernels alone"""

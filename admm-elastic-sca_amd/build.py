@@ -14,6 +14,7 @@
   attribution_host.cpp                   : the host twin of the contact attribution rule and the normal / tangential split (attribution.hpp), likewise
   surface_reaction_host.cpp              : the host twin of two-way contact's shares and ordered sums (surface_reaction.hpp), likewise
   rigid_host.cpp                         : the host twin of a rigid body's frame (rigid.hpp), likewise
+  attach_host.cpp                        : the host twin of the rigid attachments' targets and load sums (attach.hpp), likewise
   admm_hip.hip                           : the device translation unit: kernels (kernels_*.hpp, factor_dev.hpp), device factorization,
                                            upload, launches, step loop, C ABI; hipcc --offload-arch=gfx950, -ffp-contract=off
                                            (operation order = reference's)
@@ -93,6 +94,7 @@ def _jobs(extra_hip_flags, tag):
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "attribution_host.cpp", "attribution_host.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "surface_reaction_host.cpp", "surface_reaction_host.o"),
         (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "rigid_host.cpp", "rigid_host.o"),
+        (["g++"] + HOST_FLAGS + ["-ffp-contract=off"], "attach_host.cpp", "attach_host.o"),
         ([hipcc] + HIP_FLAGS + list(extra_hip_flags), "admm_hip.hip", "admm_hip%s.o" % tag),
     ]
 

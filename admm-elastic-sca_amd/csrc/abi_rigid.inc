@@ -6,6 +6,9 @@
 // the reaction and attribution reports (abi_reaction.inc), nothing else of the solver's state; they run eagerly on the context's stream,
 // outside the captured iteration and frame graphs, and drop none of them.  A context without a body launches and uploads nothing here.
 
+static int launch_attach_targets(admm_hip_ctx *ctx);      // (abi_attach.inc)
+static int launch_attach_load(admm_hip_ctx *ctx);
+
 static int body_of_entry(const admm_hip_ctx *ctx, int entry) {
     for (size_t b = 0; b < ctx->rigid.size(); ++b) if (ctx->rigid[b].K.entry == entry) return (int)b;
     return -1;
@@ -61,6 +64,7 @@ static int launch_rigid_pose(admm_hip_ctx *ctx) {
     }
     hipLaunchKernelGGL(rigid_pose_kernel, dim3(1), dim3(RIGID_BLOCK), 0, ctx->stream, (const RigidTable *)T, (const admm_rigid::Record *)ctx->d_rg_rec, ctx->d_shapes);
     HIPCHK(hipGetLastError());
+    if (ctx->att_slots) TRY(launch_attach_targets(ctx));      // rigid attachments (abi_attach.inc): the attached batches' targets from the same records
     return ADMM_OK;
 }
 
@@ -85,6 +89,7 @@ static int launch_rigid_integrate(admm_hip_ctx *ctx) {
     hipLaunchKernelGGL(rigid_partial_kernel, dim3(nblk + rows), dim3(ENERGY_BLOCK), 0, ctx->stream, (const ContactRecord *)ctx->d_rx_rec, (const int *)ctx->d_at_perm, rows, total, T,
                        (const admm_rigid::Record *)rec, n_part, ctx->d_at_part);
     hipLaunchKernelGGL(rigid_reduce_kernel, dim3(6 * nb), dim3(ENERGY_REDUCE), 0, ctx->stream, T, total, n_part, (const double *)ctx->d_at_part, ctx->d_rg_out);
+    if (ctx->att_slots) TRY(launch_attach_load(ctx));      // rigid attachments (abi_attach.inc): what the bodies carry, added to their rows
     hipLaunchKernelGGL(rigid_integrate_kernel, dim3(1), dim3(RIGID_BLOCK), 0, ctx->stream, T, total, (const double *)ctx->d_rg_out, ctx->dt, rec);
     HIPCHK(hipGetLastError());
     return ADMM_OK;

@@ -755,6 +755,8 @@ static int check_pressure_chambers(admm_hip_ctx *ctx);      // (abi_pressure.inc
 static bool surface_reaction_any(const admm_hip_ctx *ctx);  // (abi_surface_reaction.inc)
 static int surface_reaction_allocate(admm_hip_ctx *ctx);
 static int rigid_allocate(admm_hip_ctx *ctx, int first_new);  // (abi_rigid.inc)
+static bool attach_any(const admm_hip_ctx *ctx);              // (abi_attach.inc)
+static int attach_upload(admm_hip_ctx *ctx);
 
 int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (!ctx) return ADMM_ERR_ARG;
@@ -797,6 +799,7 @@ int admm_hip_finalize(admm_hip_ctx *ctx) {
     if (ctx->device_id >= 0 && ctx->attribution) { TRY(attribution_allocate(ctx)); TRY(attribution_fill(ctx)); }      // (switched on before finalize)
     if (ctx->device_id >= 0 && surface_reaction_any(ctx)) TRY(surface_reaction_allocate(ctx));      // (a share set before finalize)
     if (ctx->device_id >= 0 && !ctx->rigid.empty()) TRY(rigid_allocate(ctx, 0));      // (bodies registered before finalize)
+    if (ctx->device_id >= 0 && attach_any(ctx)) TRY(attach_upload(ctx));      // (anchor batches attached before finalize)
     ctx->finalized = true;
     return ADMM_OK;
 }

@@ -52,6 +52,8 @@ int admm_hip_update_anchors(admm_hip_ctx *ctx, int batch, const double *targets,
     if (!ctx || batch < 0 || batch >= (int)ctx->batches.size()) return ADMM_ERR_ARG;
     Batch &b = ctx->batches[batch];
     if (b.kind != ADMM_KIND_ANCHOR) return fail(ctx, ADMM_ERR_ARG, "batch %d is not an anchor batch", batch);
+    if (targets && b.attach_body >= 0)      // (abi_attach.inc)
+        return fail(ctx, ADMM_ERR_STATE, "update_anchors: batch %d is attached to rigid body %d, which rewrites its targets at every step: detach it first, or pass the flags alone", batch, b.attach_body);
     if (targets) std::copy(targets, targets + (size_t)3 * b.n_total, b.targets.begin());
     if (active) std::copy(active, active + b.n_total, b.active.begin());
     if (ctx->finalized && ctx->device_id >= 0 && b.n_local) {

@@ -31,6 +31,7 @@
 #include "kernels_pressure.hpp"
 #include "kernels_surface_reaction.hpp"
 #include "kernels_rigid.hpp"
+#include "kernels_attach.hpp"
 
 extern "C" int omp_get_max_threads(void);
 
@@ -84,6 +85,7 @@ extern "C" {
 #include "abi_pressure.inc"
 #include "abi_surface_reaction.inc"
 #include "abi_rigid.inc"
+#include "abi_attach.inc"
 #include "abi_step.inc"
 #include "abi_parity.inc"
 

@@ -69,6 +69,9 @@ struct Batch {
     long long rx_off = 0;                 // reactions (abi_reaction.inc): where a collision / anchor batch's rows sit in the context's d_rx_el
     long long at_off = 0;                 // contact attribution (abi_reaction.inc): where a collision batch's elements sit in the context's d_at_owner / d_at_normal
     long long aa_off_z = 0, aa_off_u = 0; // Anderson acceleration (abi_anderson.inc): where the batch's z and u sit in every state-sized buffer
+    // rigid attachments (abi_attach.inc; anchors only): the body the whole batch is fastened to (-1: none), its elements' offsets in the
+    // body's own coordinates [n_total][3], and the device's copy of this rank's [n_local][3] (allocated by the first attachment, kept)
+    int attach_body = -1; std::vector<double> attach_local; double *d_attach_local = nullptr;
     // ---- ADMM_KIND_GENERIC (user-defined forces): selector rows as CSR over the batch's rows
     std::vector<int64_t> g_elem_row;      // [n_total + 1] first batch row of every element
     std::vector<int64_t> g_rowptr;        // [rows + 1]
@@ -338,6 +341,16 @@ struct admm_hip_ctx {
     std::vector<RigidBodyHost> rigid;
     double rg_depth_min = 0.0; bool rg_ready = false;
     void *d_rg_table = nullptr, *d_rg_rec = nullptr; double *d_rg_out = nullptr;
+    // rigid attachments (abi_attach.inc, kernels_attach.hpp, attach.hpp; no attached batch = off, the default; a batch's own record is
+    // Batch::attach_body / attach_local).  Device side, allocated by finalize or by the first admm_hip_attach_anchors of a finalized
+    // context, never by admm_hip_step, for every anchor batch the context has: d_att_bat the attached batches' descriptors, d_att_blk the
+    // targets' block -> (batch, first element) table, d_att_slot / d_att_elem the attached elements sorted by (body, batch, element),
+    // d_att_total / d_att_carry [ADMM_MAX_SHAPES] the elements per body and whether it carries a batch, d_att_part [6][att_pcap] and
+    // d_att_cnt [att_pcap] the load's block partials and active counts, d_att_out [ADMM_MAX_SHAPES][6] the bodies' attachment rows,
+    // d_att_nact their active elements.  att_slots / att_tblk / att_pblk: attached batches, blocks of the targets and of the load now.
+    bool att_ready = false; int att_slots = 0, att_tblk = 0, att_pblk = 0, att_pcap = 0;
+    void *d_att_bat = nullptr, *d_att_blk = nullptr; int *d_att_slot = nullptr, *d_att_elem = nullptr, *d_att_carry = nullptr, *d_att_cnt = nullptr;
+    long long *d_att_total = nullptr, *d_att_nact = nullptr; double *d_att_part = nullptr, *d_att_out = nullptr;
     // Anderson acceleration (abi_anderson.inc, kernels_anderson.hpp; window 0 = off, the default; every buffer created by the first step
     // that needs it, again when the window grows).  aa_T: doubles per state-sized vector (all batches' z and u, each segment at an even
     // offset), aa_nblk: blocks of the elementwise launches; d_aa_ring, allocated for the window aa_cap_m, used as [2][aa_m + 1][aa_T]: the history's g, then its f;

@@ -166,6 +166,7 @@ public:
 };
 
 class MovingAnchor;
+class CollisionShape;
 class ControlPoint {
 public:
     ControlPoint() : active(true), anchorForce(0) { pos.setZero(); }
@@ -185,6 +186,12 @@ public:
     void describe(int *id, double *p) const { id[0] = idx; p[0] = weight; p[1] = point->active ? 1.0 : 0.0; }
     int idx;
     std::shared_ptr<ControlPoint> point;
+    // Extension, no reference counterpart (admm_hip_attach_anchors): a CollisionShape that is a rigid body (rigid_mass > 0) -- the anchor
+    // is fastened to it.  The device then moves the control point with the body's pose at the start of every step and loads the body
+    // with the anchor's reaction; point->pos gives the offset once, at System::initialize, is not uploaded while attached and is
+    // refreshed from the device only by System::attachment_targets().  point->active still releases the anchor.  Null (default): a
+    // plain moving anchor.  Consecutive moving anchors with the same body form one device batch.
+    std::shared_ptr<CollisionShape> body;
 };
 
 namespace helper {

@@ -216,7 +216,7 @@ public:
             }
         }
         // consecutive forces of one kind (and one anchor flavour) -> one batch, order preserved
-        batch_first.clear(); batch_count.clear(); batch_kind.clear(); batch_moving.clear(); batch_urow0.clear();
+        batch_first.clear(); batch_count.clear(); batch_kind.clear(); batch_moving.clear(); batch_urow0.clear(); batch_body.clear();
         user_rows = 0;
         std::vector<double> user_weights;
         for (size_t i = 0; i < forces.size();) {
@@ -239,7 +239,7 @@ public:
                 for (size_t t = 0; t < trips.size(); ++t) { tr[t] = (int32_t)(trips[t].row() - (long)row0); tc[t] = (int32_t)trips[t].col(); tv[t] = trips[t].value(); }
                 int b = -1;
                 if (!check(admm_hip_add_generic_batch(gpu, (int)(j - i), erp.data(), (int64_t)trips.size(), tr.data(), tc.data(), tv.data(), user_weights.data() + row0, &b))) return false;
-                batch_first.push_back((int)i); batch_count.push_back((int)(j - i)); batch_kind.push_back(ADMM_KIND_GENERIC); batch_moving.push_back(false); batch_urow0.push_back((long)row0);
+                batch_first.push_back((int)i); batch_count.push_back((int)(j - i)); batch_kind.push_back(ADMM_KIND_GENERIC); batch_moving.push_back(false); batch_urow0.push_back((long)row0); batch_body.push_back(nullptr);
                 i = j;
                 continue;
             }
@@ -252,15 +252,18 @@ public:
                 if (!check(admm_hip_add_batch(gpu, kind, nn_, idx.data(), par.data(), nullptr, &b))) return false;
                 cf->n_nodes = nn_; cf->Di_rows = dof;
                 if (!push_shapes(cf)) return false;
-                batch_first.push_back((int)i); batch_count.push_back(1); batch_kind.push_back(kind); batch_moving.push_back(false); batch_urow0.push_back(-1);
+                batch_first.push_back((int)i); batch_count.push_back(1); batch_kind.push_back(kind); batch_moving.push_back(false); batch_urow0.push_back(-1); batch_body.push_back(nullptr);
                 ++i;
                 continue;
             }
             const bool moving = dynamic_cast<MovingAnchor *>(forces[i].get()) != nullptr;
+            // (a run of moving anchors also ends where the body they are fastened to changes; all null: the grouping by kind and flavour alone)
+            const CollisionShape *const body = moving ? static_cast<const MovingAnchor *>(forces[i].get())->body.get() : nullptr;
             size_t j = i;
             std::vector<int32_t> idx; std::vector<double> par, tgt;
             const int nn = ADMM_KIND_NODES[kind], np = ADMM_KIND_PARAMS[kind];
-            for (; j < forces.size() && forces[j]->kind() == kind && (dynamic_cast<MovingAnchor *>(forces[j].get()) != nullptr) == moving; ++j) {
+            for (; j < forces.size() && forces[j]->kind() == kind && (dynamic_cast<MovingAnchor *>(forces[j].get()) != nullptr) == moving &&
+                   (!moving || static_cast<const MovingAnchor *>(forces[j].get())->body.get() == body); ++j) {
                 int id[4] = {0, 0, 0, 0}; double p[4] = {0, 0, 0, 0};
                 forces[j]->describe(id, p);
                 idx.insert(idx.end(), id, id + nn); par.insert(par.end(), p, p + np);
@@ -268,8 +271,18 @@ public:
             }
             int b = -1;
             if (!check(admm_hip_add_batch(gpu, kind, (int)(j - i), idx.data(), par.data(), moving ? tgt.data() : nullptr, &b))) return false;
-            batch_first.push_back((int)i); batch_count.push_back((int)(j - i)); batch_kind.push_back(kind); batch_moving.push_back(moving); batch_urow0.push_back(-1);
+            batch_first.push_back((int)i); batch_count.push_back((int)(j - i)); batch_kind.push_back(kind); batch_moving.push_back(moving); batch_urow0.push_back(-1); batch_body.push_back(body);
             i = j;
+        }
+        // rigid attachments (MovingAnchor::body; admm_hip_attach_anchors): behind the loop, where every CollisionForce has registered its
+        // rigid bodies; the offsets come from the control points and the body's pose as they stand
+        for (size_t b = 0; b < batch_body.size(); ++b) if (batch_body[b]) {
+            const size_t k = std::find(rigid_shapes.begin(), rigid_shapes.end(), batch_body[b]) - rigid_shapes.begin();
+            if (k == rigid_shapes.size()) {
+                std::cerr << "\n**Solver Error: force " << batch_first[b] << ": MovingAnchor::body is not a rigid body of a CollisionForce's shape list (rigid_mass > 0, settings.contact_attribution)" << std::endl;
+                return false;
+            }
+            if (!check(admm_hip_attach_anchors(gpu, (int)b, (int)k, nullptr))) return false;
         }
         user_rows = (long)user_weights.size();
         if (user_rows && !check(admm_hip_set_project_hook(gpu, &System::project_hook, this))) return false;
@@ -330,7 +343,8 @@ public:
                 for (int c = 0; c < 3; ++c) tgt[3 * (size_t)e + c] = ma->point->pos[c];
                 act[e] = ma->point->active ? 1 : 0;
             }
-            if (!check(admm_hip_update_anchors(gpu, (int)b, tgt.data(), act.data()))) return false;
+            // (an attached batch's control points are the device's: only the flags travel)
+            if (!check(admm_hip_update_anchors(gpu, (int)b, batch_body[b] ? nullptr : tgt.data(), act.data()))) return false;
         }
         // user-written explicit forces act on the host copy before it is uploaded (System.cpp:37-39; they run before the
         // device-side ones, in their own relative order)
@@ -508,6 +522,38 @@ public:
         if (!initialized || r.empty() || !check(admm_hip_get_rigid_state(gpu, (int)r.size(), r.data()))) r.clear();
         return r;
     }
+    // rigid attachments (MovingAnchor::body; admm_hip_get_attachment): the control points of every attached anchor, as the device moved
+    // them at the start of the last step(), into point->pos (a released one: its node's position).  false: the call failed.
+    bool attachment_targets() {
+        if (!initialized) return false;
+        for (size_t b = 0; b < batch_body.size(); ++b) if (batch_body[b]) {
+            std::vector<double> &tgt = anchor_tgt;
+            tgt.resize((size_t)batch_count[b] * 3);
+            if (!check(admm_hip_get_attachment(gpu, (int)b, nullptr, nullptr, tgt.data()))) return false;
+            for (int e = 0; e < batch_count[b]; ++e) {
+                MovingAnchor *ma = static_cast<MovingAnchor *>(forces[batch_first[b] + e].get());
+                for (int c = 0; c < 3; ++c) ma->point->pos[c] = tgt[3 * (size_t)e + c];
+            }
+        }
+        return true;
+    }
+    // ... and what the bodies carried in the last step() (admm_hip_get_attachment_load): per body, in rigid_state()'s order, the force
+    // and the torque about its centre before that step's integration as the nodes felt them (the body received the opposite) and the
+    // number of active attached anchors.  Empty: no body, or the call failed.
+    struct AttachmentLoad { double force[3], torque[3]; long n_active; };
+    std::vector<AttachmentLoad> attachment_load() {
+        std::vector<AttachmentLoad> rows;
+        const size_t n = rigid_shapes.size();
+        if (!initialized || !n) return rows;
+        std::vector<double> F(3 * n), T(3 * n); std::vector<int64_t> na(n);
+        if (!check(admm_hip_get_attachment_load(gpu, (int)n, F.data(), T.data(), na.data()))) return rows;
+        rows.resize(n);
+        for (size_t q = 0; q < n; ++q) {
+            for (int j = 0; j < 3; ++j) { rows[q].force[j] = F[3 * q + j]; rows[q].torque[j] = T[3 * q + j]; }
+            rows[q].n_active = (long)na[q];
+        }
+        return rows;
+    }
     // the contacts' resultant per entry of the shape list (admm_hip_entry_resultants): rows [n_entries + 1], the last one for the contacts
     // that nothing moved in the last local step; n_entries: the length of the CollisionForce's shape list.  Empty: the call failed.
     std::vector<ContactResultant> entry_resultants(int n_entries, double px = 0.0, double py = 0.0, double pz = 0.0, double depth_min = 1e-10) {
@@ -636,6 +682,7 @@ protected:
     std::vector<double> body_share;                                    // the CollisionBody::reaction_share the context last received
     std::vector<int> batch_first, batch_count, batch_kind;
     std::vector<char> batch_moving;
+    std::vector<const CollisionShape *> batch_body;      // moving-anchor batches: the rigid body they are fastened to (MovingAnchor::body), else null
     std::vector<long> batch_urow0;         // generic batches: first of their rows among the user rows (-1 otherwise)
     std::vector<int> explicit_slot;        // explicit_forces[i] -> index among the device-side explicit forces, -1 = host
     // user-written forces: their rows of Dx / u / z (the vectors Force::project receives) and this rank's forces

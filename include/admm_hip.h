@@ -1214,6 +1214,61 @@ int admm_hip_get_rigid_body(admm_hip_ctx *ctx, int body, int *entry, int *type, 
 int admm_hip_rigid_query(int type, double mass, const double inertia[6], const double accel[3], const double c0[3], const double par0[4],
                          const admm_hip_rigid_state *in, const double Fe[3], const double Te[3], int64_t count, double dt, admm_hip_rigid_state *out);
 
+/* ---- rigid attachments: anchor batches fastened to rigid bodies -----------------------------------------------------------------------------
+ * Extension, no reference counterpart; off unless asked for.  A whole ANCHOR batch is attached to one rigid body of the section above.
+ * At the very start of every admm_hip_step, behind the bodies' pose and before anything reads a target, the device rewrites the batch's
+ * targets from the body's record as the frame before left it; behind the epilogue, before the bodies are integrated, it adds the
+ * reaction of the batch's active elements to the body's row, so a body is moved by what it carries as well as by what it touches.  No
+ * host synchronisation, no atomics, fixed orders: two runs give the same bits.  One definition, csrc/attach.hpp, compiled without
+ * fused multiply-adds for the host and the device:
+ *   offset     r = R^T (t - c), on the host at attachment, from an element's target t and the body's c, R of that moment
+ *   target     t = c + R r; recomputed from a derived offset it may differ from the target the offset came from in the last bits
+ *   load       an element with active != 0: f = w^2 ((z - u) - x) (csrc/reaction.hpp) applied at z, its torque about the body's centre
+ *              before this frame's integration; a released element (active == 0): six +0.0
+ *   sum        per body over its attached elements in ascending (batch index, element in admm_hip_read_local's order), in reaction.hpp's
+ *              two-stage order (64-element blocks, then 256 lanes)
+ *   combined   only a body that carries a batch: Fe = Fc + Fa, Te = Tc + Ta, one rounded add each, then the rule of the section above
+ *              unchanged; a body without a batch keeps the bits it had.  admm_hip_rigid_state.count stays the number of contacts, F and
+ *              tau are the total applied.
+ * Launches per frame (csrc/kernels_attach.hpp): attach_targets_kernel behind rigid_pose_kernel; attach_partial_kernel and
+ * attach_reduce_kernel before rigid_integrate_kernel -- eager on the context's stream, outside the captured graphs, which keep working
+ * because a batch's targets keep their address.  Every buffer is allocated by finalize or by the attaching call on a finalized context,
+ * never by admm_hip_step.  A context without an attached batch launches and uploads exactly what it did.
+ *   admm_hip_attach_anchors      before or after finalize.  local [n_total][3]: the elements' offsets in the body's own coordinates, in
+ *                                the order the batch was added; NULL: derived from the batch's current targets (a batch added without
+ *                                targets: its nodes' positions) and the body's current pose (one synchronisation after finalize).
+ *                                Order of the checks: ADMM_ERR_ARG the batch is not an anchor batch; the body is not a rigid body; the
+ *                                batch is attached already; an offset is not finite; then ADMM_ERR_UNSUPPORTED world > 1 (which
+ *                                admm_hip_add_rigid_body refuses too; the message names the batch).  A body that carries a batch still
+ *                                needs what admm_hip_add_rigid_body needs: contact attribution on and world == 1.  A context with a body,
+ *                                attachments and no collision batch at all steps: the body is then loaded by its attachments alone.
+ *   admm_hip_detach_anchors      the targets stay where the last frame put them; the batch is a plain moving-anchor batch again.
+ *                                ADMM_ERR_ARG: not an anchor batch, or not attached.
+ *   admm_hip_get_attachment      body (-1: not attached), local [n_total][3] (zeros when not attached), targets [n_total][3] as the
+ *                                device holds them now (one synchronisation); any output may be NULL.  A released element's target is
+ *                                its node's position, which the anchor kernel stores there in every local step.
+ *   admm_hip_get_attachment_load the last frame's attachment row per body, Fa [n][3] and Ta [n][3] about the centre before that frame's
+ *                                integration, and the number of active attached elements; as the nodes felt it, the body received the
+ *                                opposite.  n_bodies must be the number of bodies.  Zeros before the first frame and for a body without
+ *                                a batch.
+ *   admm_hip_attachment_query    context-free host evaluation, the device's bits; needs no GPU.  Target half (targets != NULL):
+ *                                targets [n][3] from c[3], R[9] (row-major) and local [n][3].  Sum half (row6 or n_active != NULL): the
+ *                                six sums {sum f, sum (point - pivot) x f} over the n elements in the device's order, from f [n][3] and
+ *                                point [n][3] -- what admm_hip_batch_reaction and admm_hip_read_local's z return -- active [n] (NULL: all
+ *                                active; a released element adds six +0.0) and pivot[3] (NULL: the origin).
+ * While a batch is attached, admm_hip_update_anchors with targets != NULL returns ADMM_ERR_STATE (the next step would overwrite them);
+ * the flags alone stay allowed and take effect as before.  admm_hip_set_rigid_state simply moves the attached targets at the next step.
+ * Limits: whole batches only; one body per batch; no joints between bodies; not available under sharding.  The coupling is explicit and
+ * staggered like the contact load -- the body feels this frame's reaction in the next -- and is stable only while the body is well
+ * heavier than the nodes fastened to it; where it breaks is not measured.  Linear momentum balances up to the solve's residual; angular
+ * momentum is not exact, because the reaction is applied at the target z, not at the node.                                              */
+int admm_hip_attach_anchors(admm_hip_ctx *ctx, int batch, int body, const double *local);
+int admm_hip_detach_anchors(admm_hip_ctx *ctx, int batch);
+int admm_hip_get_attachment(admm_hip_ctx *ctx, int batch, int *body, double *local, double *targets);
+int admm_hip_get_attachment_load(admm_hip_ctx *ctx, int n_bodies, double *Fa, double *Ta, int64_t *n_active);
+int admm_hip_attachment_query(int64_t n, const double c[3], const double R[9], const double *local, double *targets, const double *f, const double *point,
+                              const int32_t *active, const double pivot[3], double *row6, int64_t *n_active);
+
 #ifdef __cplusplus
 }
 #endif
