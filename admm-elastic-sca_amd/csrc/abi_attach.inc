@@ -50,12 +50,11 @@ static int attach_upload(admm_hip_ctx *ctx) {
         carry[b.attach_body] = 1; total[b.attach_body] += nl;
     }
     std::vector<int> el_slot, el_elem;      // sorted by (body, batch index, element)
-    int pblk = 0;
     for (int body = 0; body < (int)ctx->rigid.size(); ++body) {
         for (size_t k = 0; k < ctx->batches.size(); ++k) if (ctx->batches[k].attach_body == body)
             for (int el = 0; el < ctx->batches[k].n_local; ++el) { el_slot.push_back(slot_of[k]); el_elem.push_back(el); }
-        pblk += (int)((total[body] + ENERGY_BLOCK - 1) / ENERGY_BLOCK);
     }
+    const int pblk = (int)admm_layout::blocks_before(total.data(), (int)ctx->rigid.size());      // the blocks of all bodies
     if (pblk > ctx->att_pcap) return fail(ctx, ADMM_ERR_STATE, "attachments: %d blocks of attached elements, room for %d", pblk, ctx->att_pcap);
     if (!bat.empty()) HIPCHK(hipMemcpy(ctx->d_att_bat, bat.data(), sizeof(AttachBatchDev) * bat.size(), hipMemcpyHostToDevice));
     if (!blk.empty()) HIPCHK(hipMemcpy(ctx->d_att_blk, blk.data(), sizeof(AttachBlock) * blk.size(), hipMemcpyHostToDevice));

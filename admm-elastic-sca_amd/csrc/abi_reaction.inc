@@ -16,6 +16,18 @@ static int require_reactions(admm_hip_ctx *ctx, const char *who) {
     return ADMM_OK;
 }
 
+// the buffers of the two-stage row sums behind the chain (kernels_reaction.hpp: entry_partial_kernel / entry_reduce_kernel and their
+// rigid twins): rows rows, row q's contacts perm[sum of totals before q ...) (null: the records in order), counts / offsets
+// [rows_max][nblk] for the sort, partials [6][n_part], out [rows][6].  sorted: the entries' rows + one for the contacts without an owner,
+// on the attribution reports' buffers; else one row, all contacts, on buffers that exist without attribution
+struct EntryWork { int *counts, *offsets; long long *totals; int *perm; double *partials, *out; int nblk, n_part, rows; };
+static EntryWork entry_work(const admm_hip_ctx *ctx, bool sorted) {
+    const long long items = std::max(ctx->n_nodes, 1);
+    const int rows_max = sorted ? ADMM_MAX_SHAPES + 1 : 1, nblk = (int)admm_layout::row_blocks(items), n_part = (int)admm_layout::partial_blocks_bound(items, rows_max);
+    if (!sorted) return EntryWork{nullptr, nullptr, ctx->d_rx_count, nullptr, ctx->d_rx_part, ctx->d_rx_part + 6 * (size_t)n_part, nblk, n_part, 1};
+    return EntryWork{ctx->d_at_blk, ctx->d_at_blk + (size_t)rows_max * nblk, ctx->d_at_tot, ctx->d_at_perm, ctx->d_at_part, ctx->d_at_out, nblk, n_part, ctx->shapes.n + 1};
+}
+
 // every buffer the kernels write and the gather's two CSRs (0: the collision batches, 1: the anchor batches; batch order, then local
 // element order), created by the first call
 static int ensure_reaction_buffers(admm_hip_ctx *ctx) {
@@ -34,7 +46,7 @@ static int ensure_reaction_buffers(admm_hip_ctx *ctx) {
     if (!ctx->d_rx_blk) TRY(dalloc(ctx, &ctx->d_rx_blk, 2 * (size_t)std::max(reaction_blocks(n), 1)));
     if (!ctx->d_rx_count) TRY(dalloc(ctx, &ctx->d_rx_count, 1));
     if (!ctx->d_rx_rec) { ContactRecord *r = nullptr; TRY(dalloc(ctx, &r, (size_t)std::max(n, 1))); ctx->d_rx_rec = r; }
-    if (!ctx->d_rx_part) TRY(dalloc(ctx, &ctx->d_rx_part, 6 * (size_t)std::max(energy_blocks(n), 1) + 6));
+    if (!ctx->d_rx_part) TRY(dalloc(ctx, &ctx->d_rx_part, 6 * (size_t)entry_work(ctx, false).n_part + 6));
     for (int which = 0; which < 2; ++which) {
         const int kind = which ? ADMM_KIND_ANCHOR : ADMM_KIND_COLLISION;
         std::vector<NodeCsrEntry> entries;
@@ -56,32 +68,54 @@ static int launch_batch_reaction(admm_hip_ctx *ctx, const Batch &b) {
     return ADMM_OK;
 }
 
-// every reported batch's elements, then the nodes' sums, depths and points -> d_rx_node
-static int launch_node_reactions(admm_hip_ctx *ctx, admm_hip_reaction_info *info) {
+// The contact chain, the one launch sequence behind every report and feature that reads the contacts of the last frame.  Always: every
+// reported batch's elements, the nodes' sums, depths and points -> d_rx_node, and the count and scan of the nodes with depth > depth_min
+// (the count stays on the device, at d_rx_count).  Then what `what` asks for, in this order: CHAIN_RECORDS the contact records -> d_rx_rec;
+// CHAIN_OWNERS the owner records of the same contacts in the same places -> d_at_rec; CHAIN_SORTED (with CHAIN_OWNERS) the contacts
+// sorted by entry: entry_count / row_scan / entry_place -> entry_work(ctx, true).  The last two need ensure_attribution_buffers.
+// Every caller runs the whole chain with its own depth_min; nothing is kept from one call to the next.
+enum { CHAIN_NODES = 0, CHAIN_RECORDS = 1, CHAIN_OWNERS = 2, CHAIN_SORTED = 4 };
+
+static int launch_contact_chain(admm_hip_ctx *ctx, double depth_min, int what, admm_hip_reaction_info *info = nullptr) {
     using namespace admm_dev;
     for (const Batch &b : ctx->batches) {
         if (!reaction_reported(b)) { if (info) ++info->batches_skipped; continue; }
         if (info) ++(b.kind == ADMM_KIND_ANCHOR ? info->batches_anchor : info->batches_collision);
         TRY(launch_batch_reaction(ctx, b));
     }
-    const int n = ctx->n_nodes, nblk = energy_blocks(n);
+    const int n = ctx->n_nodes, gblk = energy_blocks(n), nblk = reaction_blocks(n);
     const NodeCsr &cc = ctx->rx_csr[0], &ca = ctx->rx_csr[1];
-    if (nblk) hipLaunchKernelGGL(reaction_gather_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, n, (const int *)cc.ptr, (const long long *)cc.off, (const int *)cc.stride,
+    if (gblk) hipLaunchKernelGGL(reaction_gather_kernel, dim3(gblk), dim3(ENERGY_BLOCK), 0, ctx->stream, n, (const int *)cc.ptr, (const long long *)cc.off, (const int *)cc.stride,
                                  (const int *)ca.ptr, (const long long *)ca.off, (const int *)ca.stride, (const double *)ctx->d_rx_el, ctx->d_rx_node);
+    int *cnt = ctx->d_rx_blk, *off = ctx->d_rx_blk + std::max(nblk, 1);
+    const double *nodes = ctx->d_rx_node;
+    if (nblk) hipLaunchKernelGGL(contact_count_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, nodes + 6 * (size_t)n, depth_min, cnt);
+    hipLaunchKernelGGL(row_scan_kernel, dim3(1), dim3(RX_SCAN), 0, ctx->stream, nblk, (const int *)cnt, off, ctx->d_rx_count);
+    if ((what & CHAIN_RECORDS) && nblk)
+        hipLaunchKernelGGL(contact_scatter_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, nodes, depth_min, (const int *)off, (long long)n, (ContactRecord *)ctx->d_rx_rec);
+    if ((what & CHAIN_OWNERS) && nblk)
+        hipLaunchKernelGGL(contact_owner_scatter_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, nodes, depth_min, (const int *)off, (long long)n, (const int *)cc.ptr,
+                           (const long long *)cc.off, (const int *)cc.stride, (const long long *)ctx->d_at_csr, (const double *)ctx->d_rx_el, (const int *)ctx->d_at_owner,
+                           (const double *)ctx->d_at_normal, ctx->at_total, (OwnerRecord *)ctx->d_at_rec);
+    if (what & CHAIN_SORTED) {
+        const EntryWork W = entry_work(ctx, true);
+        const long long *count = ctx->d_rx_count;
+        const OwnerRecord *orec = (const OwnerRecord *)ctx->d_at_rec;
+        hipLaunchKernelGGL(entry_count_kernel, dim3(W.nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, count, orec, W.rows, W.nblk, W.counts);
+        hipLaunchKernelGGL(row_scan_kernel, dim3(W.rows), dim3(RX_SCAN), 0, ctx->stream, W.nblk, (const int *)W.counts, W.offsets, W.totals);
+        hipLaunchKernelGGL(entry_place_kernel, dim3(W.nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, count, orec, W.rows, W.nblk, (const int *)W.offsets, (const long long *)W.totals, W.perm);
+    }
     HIPCHK(hipGetLastError());
     return ADMM_OK;
 }
 
-// count, scan and -- with `records` -- scatter of the nodes with depth > depth_min into d_rx_rec; the count stays on the device, at d_rx_count
-static int launch_compaction(admm_hip_ctx *ctx, double depth_min, bool records) {
+// behind the chain: W's rows about one pivot (null: the origin), entry_partial_kernel then entry_reduce_kernel -> W.out [rows][6]
+static int launch_row_sums(admm_hip_ctx *ctx, const EntryWork &W, const double *pivot) {
     using namespace admm_dev;
-    const int n = ctx->n_nodes, nblk = reaction_blocks(n);
-    int *cnt = ctx->d_rx_blk, *off = ctx->d_rx_blk + std::max(nblk, 1);
-    const double *depth = ctx->d_rx_node + 6 * (size_t)n;
-    if (nblk) hipLaunchKernelGGL(contact_count_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, depth, depth_min, cnt);
-    hipLaunchKernelGGL(contact_scan_kernel, dim3(1), dim3(RX_SCAN), 0, ctx->stream, nblk, (const int *)cnt, off, ctx->d_rx_count);
-    if (records && nblk) hipLaunchKernelGGL(contact_scatter_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, (const double *)ctx->d_rx_node, depth_min, (const int *)off, (long long)n,
-                                            (ContactRecord *)ctx->d_rx_rec);
+    const double p0 = pivot ? pivot[0] : 0.0, p1 = pivot ? pivot[1] : 0.0, p2 = pivot ? pivot[2] : 0.0;
+    hipLaunchKernelGGL(entry_partial_kernel, dim3(W.nblk + W.rows), dim3(ENERGY_BLOCK), 0, ctx->stream, (const ContactRecord *)ctx->d_rx_rec, (const int *)W.perm, W.rows, (const long long *)W.totals, p0, p1, p2,
+                       W.n_part, W.partials);
+    hipLaunchKernelGGL(entry_reduce_kernel, dim3(6 * W.rows), dim3(ENERGY_REDUCE), 0, ctx->stream, W.rows, (const long long *)W.totals, W.n_part, (const double *)W.partials, W.out);
     HIPCHK(hipGetLastError());
     return ADMM_OK;
 }
@@ -110,8 +144,7 @@ int admm_hip_node_reactions(admm_hip_ctx *ctx, double *f_contact, double *f_anch
     TRY(require_reactions(ctx, "node_reactions"));
     TRY(ensure_reaction_buffers(ctx));
     admm_hip_reaction_info I{};
-    TRY(launch_node_reactions(ctx, &I));
-    TRY(launch_compaction(ctx, 0.0, false));
+    TRY(launch_contact_chain(ctx, 0.0, CHAIN_NODES, &I));
     const size_t n = (size_t)ctx->n_nodes;
     long long count = 0;
     if (f_contact && n) HIPCHK(hipMemcpyAsync(f_contact, ctx->d_rx_node, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -128,8 +161,7 @@ int admm_hip_get_contacts(admm_hip_ctx *ctx, double depth_min, admm_hip_contact 
     if (!(depth_min >= 0.0) || capacity < 0 || (capacity && !records)) return fail(ctx, ADMM_ERR_ARG, "get_contacts: depth_min must be >= 0 (got %g), capacity >= 0 and records given with it", depth_min);
     TRY(require_reactions(ctx, "get_contacts"));
     TRY(ensure_reaction_buffers(ctx));
-    TRY(launch_node_reactions(ctx, nullptr));
-    TRY(launch_compaction(ctx, depth_min, true));
+    TRY(launch_contact_chain(ctx, depth_min, CHAIN_RECORDS));
     // (the count is not known before the synchronisation: the copy covers what the capacity could hold, the caller gets the filled part)
     static_assert(sizeof(admm_hip_contact) == sizeof(admm_dev::ContactRecord), "admm_hip_contact is the device's record");
     const size_t want = (size_t)std::min<int64_t>(capacity, ctx->n_nodes);
@@ -150,17 +182,11 @@ int admm_hip_contact_resultant(admm_hip_ctx *ctx, double depth_min, const double
     if (!(depth_min >= 0.0)) return fail(ctx, ADMM_ERR_ARG, "contact_resultant: depth_min must be >= 0, got %g", depth_min);
     TRY(require_reactions(ctx, "contact_resultant"));
     TRY(ensure_reaction_buffers(ctx));
-    TRY(launch_node_reactions(ctx, nullptr));
-    TRY(launch_compaction(ctx, depth_min, true));
-    const int nblk = energy_blocks(ctx->n_nodes);
-    double *part = ctx->d_rx_part, *tot = ctx->d_rx_part + 6 * (size_t)std::max(nblk, 1);
-    const double p0 = pivot ? pivot[0] : 0.0, p1 = pivot ? pivot[1] : 0.0, p2 = pivot ? pivot[2] : 0.0;
-    if (nblk) hipLaunchKernelGGL(contact_resultant_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, (const ContactRecord *)ctx->d_rx_rec, p0, p1, p2, nblk, part);
-    for (int q = 0; q < 6; ++q)
-        hipLaunchKernelGGL(energy_reduce_kernel, dim3(1), dim3(ENERGY_REDUCE), 0, ctx->stream, nblk, (const double *)(part + (size_t)q * nblk), (const int *)nullptr, tot + q, (long long *)nullptr);
-    HIPCHK(hipGetLastError());
+    TRY(launch_contact_chain(ctx, depth_min, CHAIN_RECORDS));
+    const EntryWork W = entry_work(ctx, false);      // one row: all contacts, in the records' order
+    TRY(launch_row_sums(ctx, W, pivot));
     double h[6]; long long c = 0;
-    HIPCHK(hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h, W.out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(&c, ctx->d_rx_count, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (out6) for (int q = 0; q < 6; ++q) out6[q] = h[q];
@@ -195,12 +221,13 @@ static int ensure_attribution_buffers(admm_hip_ctx *ctx) {
     using namespace admm_dev;
     TRY(ensure_reaction_buffers(ctx));
     if (ctx->at_ready) return ADMM_OK;
-    const int n = ctx->n_nodes, nblk = std::max(energy_blocks(n), 1), rows = ADMM_MAX_SHAPES + 1;
+    const int n = ctx->n_nodes, rows = ADMM_MAX_SHAPES + 1;
+    const EntryWork W = entry_work(ctx, true);      // (the sizes alone: the pointers are being created)
     if (!ctx->d_at_rec) { OwnerRecord *r = nullptr; TRY(dalloc(ctx, &r, (size_t)std::max(n, 1))); ctx->d_at_rec = r; }
-    if (!ctx->d_at_blk) TRY(dalloc(ctx, &ctx->d_at_blk, 2 * (size_t)rows * nblk));
+    if (!ctx->d_at_blk) TRY(dalloc(ctx, &ctx->d_at_blk, 2 * (size_t)rows * W.nblk));
     if (!ctx->d_at_tot) TRY(dalloc(ctx, &ctx->d_at_tot, (size_t)rows));
     if (!ctx->d_at_perm) TRY(dalloc(ctx, &ctx->d_at_perm, (size_t)std::max(n, 1)));
-    if (!ctx->d_at_part) TRY(dalloc(ctx, &ctx->d_at_part, 6 * (size_t)(nblk + rows)));
+    if (!ctx->d_at_part) TRY(dalloc(ctx, &ctx->d_at_part, 6 * (size_t)W.n_part));
     if (!ctx->d_at_out) TRY(dalloc(ctx, &ctx->d_at_out, 6 * (size_t)rows));
     if (!ctx->d_at_csr) {
         std::vector<NodeCsrEntry> entries;      // (the order of ensure_reaction_buffers' collision entries: the two CSRs share ptr)
@@ -209,19 +236,6 @@ static int ensure_attribution_buffers(admm_hip_ctx *ctx) {
         TRY(upload(ctx, &ctx->d_at_csr, build_node_csr(n, entries).off));
     }
     ctx->at_ready = true;
-    return ADMM_OK;
-}
-
-// behind launch_node_reactions and launch_compaction(depth_min, *): the owner records of the same contacts, in the same places
-static int launch_owner_records(admm_hip_ctx *ctx, double depth_min) {
-    using namespace admm_dev;
-    const int n = ctx->n_nodes, nblk = reaction_blocks(n);
-    const int *off = ctx->d_rx_blk + std::max(nblk, 1);
-    const NodeCsr &cc = ctx->rx_csr[0];
-    if (nblk) hipLaunchKernelGGL(contact_owner_scatter_kernel, dim3(nblk), dim3(RX_BLOCK), 0, ctx->stream, n, (const double *)ctx->d_rx_node, depth_min, off, (long long)n,
-                                 (const int *)cc.ptr, (const long long *)cc.off, (const int *)cc.stride, (const long long *)ctx->d_at_csr, (const double *)ctx->d_rx_el,
-                                 (const int *)ctx->d_at_owner, (const double *)ctx->d_at_normal, ctx->at_total, (OwnerRecord *)ctx->d_at_rec);
-    HIPCHK(hipGetLastError());
     return ADMM_OK;
 }
 
@@ -247,9 +261,7 @@ int admm_hip_get_contact_owners(admm_hip_ctx *ctx, double depth_min, admm_hip_co
     if (!(depth_min >= 0.0) || capacity < 0 || (capacity && !records)) return fail(ctx, ADMM_ERR_ARG, "get_contact_owners: depth_min must be >= 0 (got %g), capacity >= 0 and records given with it", depth_min);
     TRY(require_attribution(ctx, "get_contact_owners"));
     TRY(ensure_attribution_buffers(ctx));
-    TRY(launch_node_reactions(ctx, nullptr));
-    TRY(launch_compaction(ctx, depth_min, false));
-    TRY(launch_owner_records(ctx, depth_min));
+    TRY(launch_contact_chain(ctx, depth_min, CHAIN_OWNERS));
     static_assert(sizeof(admm_hip_contact_owner) == sizeof(admm_dev::OwnerRecord), "admm_hip_contact_owner is the device's record");
     const size_t want = (size_t)std::min<int64_t>(capacity, ctx->n_nodes);      // (as admm_hip_get_contacts: the count is not known before the synchronisation)
     std::vector<admm_hip_contact_owner> tmp(want);
@@ -270,24 +282,13 @@ int admm_hip_entry_resultants(admm_hip_ctx *ctx, double depth_min, const double 
     if (n_entries != ctx->shapes.n || n_entries > ADMM_MAX_SHAPES) return fail(ctx, ADMM_ERR_ARG, "entry_resultants: %d entries given, the shape list has %d", n_entries, ctx->shapes.n);
     TRY(require_attribution(ctx, "entry_resultants"));
     TRY(ensure_attribution_buffers(ctx));
-    TRY(launch_node_reactions(ctx, nullptr));
-    TRY(launch_compaction(ctx, depth_min, true));
-    TRY(launch_owner_records(ctx, depth_min));
-    const int rows = n_entries + 1, nblk = std::max(energy_blocks(ctx->n_nodes), 1), n_part = nblk + ADMM_MAX_SHAPES + 1;
-    int *cnt = ctx->d_at_blk, *off = ctx->d_at_blk + (size_t)(ADMM_MAX_SHAPES + 1) * nblk;
-    const long long *total = ctx->d_at_tot;
-    const OwnerRecord *orec = (const OwnerRecord *)ctx->d_at_rec;
-    const double p0 = pivot ? pivot[0] : 0.0, p1 = pivot ? pivot[1] : 0.0, p2 = pivot ? pivot[2] : 0.0;
-    hipLaunchKernelGGL(entry_count_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, orec, rows, nblk, cnt);
-    hipLaunchKernelGGL(entry_scan_kernel, dim3(rows), dim3(RX_SCAN), 0, ctx->stream, nblk, (const int *)cnt, off, ctx->d_at_tot);
-    hipLaunchKernelGGL(entry_place_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, orec, rows, nblk, (const int *)off, total, ctx->d_at_perm);
-    hipLaunchKernelGGL(entry_partial_kernel, dim3(nblk + rows), dim3(ENERGY_BLOCK), 0, ctx->stream, (const ContactRecord *)ctx->d_rx_rec, (const int *)ctx->d_at_perm, rows, total, p0, p1, p2,
-                       n_part, ctx->d_at_part);
-    hipLaunchKernelGGL(entry_reduce_kernel, dim3(6 * rows), dim3(ENERGY_REDUCE), 0, ctx->stream, rows, total, n_part, (const double *)ctx->d_at_part, ctx->d_at_out);
-    HIPCHK(hipGetLastError());
+    TRY(launch_contact_chain(ctx, depth_min, CHAIN_RECORDS | CHAIN_OWNERS | CHAIN_SORTED));
+    const EntryWork W = entry_work(ctx, true);
+    TRY(launch_row_sums(ctx, W, pivot));
+    const int rows = W.rows;
     std::vector<double> h(6 * (size_t)rows); std::vector<long long> c((size_t)rows);
-    HIPCHK(hipMemcpyAsync(h.data(), ctx->d_at_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(c.data(), ctx->d_at_tot, sizeof(long long) * c.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h.data(), W.out, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(c.data(), W.totals, sizeof(long long) * c.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (out) std::copy(h.begin(), h.end(), out);
     if (count) for (int q = 0; q < rows; ++q) count[q] = c[q];

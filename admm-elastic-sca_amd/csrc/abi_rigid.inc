@@ -74,21 +74,15 @@ static int launch_rigid_integrate(admm_hip_ctx *ctx) {
     if (!ctx->rg_ready) return fail(ctx, ADMM_ERR_STATE, "rigid bodies: a body is registered but the buffers were never allocated");
     const double depth_min = ctx->rg_depth_min;
     // the contacts of admm_hip_entry_resultants(depth_min) and their owners, sorted by entry, by the reports' own launches
-    TRY(launch_node_reactions(ctx, nullptr));
-    TRY(launch_compaction(ctx, depth_min, true));
-    TRY(launch_owner_records(ctx, depth_min));
-    const int rows = ctx->shapes.n + 1, nblk = std::max(energy_blocks(ctx->n_nodes), 1), n_part = nblk + ADMM_MAX_SHAPES + 1, nb = (int)ctx->rigid.size();
-    int *cnt = ctx->d_at_blk, *off = ctx->d_at_blk + (size_t)(ADMM_MAX_SHAPES + 1) * nblk;
-    const long long *total = ctx->d_at_tot;
-    const OwnerRecord *orec = (const OwnerRecord *)ctx->d_at_rec;
+    TRY(launch_contact_chain(ctx, depth_min, CHAIN_RECORDS | CHAIN_OWNERS | CHAIN_SORTED));
+    const EntryWork W = entry_work(ctx, true);
+    const int nb = (int)ctx->rigid.size();
+    const long long *total = W.totals;
     const RigidTable *T = (const RigidTable *)ctx->d_rg_table;
     admm_rigid::Record *rec = (admm_rigid::Record *)ctx->d_rg_rec;
-    hipLaunchKernelGGL(entry_count_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, orec, rows, nblk, cnt);
-    hipLaunchKernelGGL(entry_scan_kernel, dim3(rows), dim3(RX_SCAN), 0, ctx->stream, nblk, (const int *)cnt, off, ctx->d_at_tot);
-    hipLaunchKernelGGL(entry_place_kernel, dim3(nblk), dim3(ENERGY_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, orec, rows, nblk, (const int *)off, total, ctx->d_at_perm);
-    hipLaunchKernelGGL(rigid_partial_kernel, dim3(nblk + rows), dim3(ENERGY_BLOCK), 0, ctx->stream, (const ContactRecord *)ctx->d_rx_rec, (const int *)ctx->d_at_perm, rows, total, T,
-                       (const admm_rigid::Record *)rec, n_part, ctx->d_at_part);
-    hipLaunchKernelGGL(rigid_reduce_kernel, dim3(6 * nb), dim3(ENERGY_REDUCE), 0, ctx->stream, T, total, n_part, (const double *)ctx->d_at_part, ctx->d_rg_out);
+    hipLaunchKernelGGL(rigid_partial_kernel, dim3(W.nblk + W.rows), dim3(ENERGY_BLOCK), 0, ctx->stream, (const ContactRecord *)ctx->d_rx_rec, (const int *)W.perm, W.rows, total, T,
+                       (const admm_rigid::Record *)rec, W.n_part, W.partials);
+    hipLaunchKernelGGL(rigid_reduce_kernel, dim3(6 * nb), dim3(ENERGY_REDUCE), 0, ctx->stream, T, total, W.n_part, (const double *)W.partials, ctx->d_rg_out);
     if (ctx->att_slots) TRY(launch_attach_load(ctx));      // rigid attachments (abi_attach.inc): what the bodies carry, added to their rows
     hipLaunchKernelGGL(rigid_integrate_kernel, dim3(1), dim3(RIGID_BLOCK), 0, ctx->stream, T, total, (const double *)ctx->d_rg_out, ctx->dt, rec);
     HIPCHK(hipGetLastError());

@@ -94,9 +94,7 @@ static int launch_surface_reaction(admm_hip_ctx *ctx) {
     hipLaunchKernelGGL(surface_clear_kernel, dim3(nb), dim3(SR_BLOCK), 0, ctx->stream, (const long long *)ctx->d_sr_n, (const int *)skey, n, ctx->d_sr_dv);
     HIPCHK(hipGetLastError());
     // the contacts of admm_hip_get_contacts(depth_min) and their owners, by the reports' own launches
-    TRY(launch_node_reactions(ctx, nullptr));
-    TRY(launch_compaction(ctx, depth_min, true));
-    TRY(launch_owner_records(ctx, depth_min));
+    TRY(launch_contact_chain(ctx, depth_min, CHAIN_RECORDS | CHAIN_OWNERS));
     hipLaunchKernelGGL(surface_hit_kernel, dim3((cap + SR_BLOCK - 1) / SR_BLOCK), dim3(SR_BLOCK), 0, ctx->stream, (const long long *)ctx->d_rx_count, (const ContactRecord *)ctx->d_rx_rec,
                        (const OwnerRecord *)ctx->d_at_rec, (const ShapeTable *)ctx->d_shapes, (const admm_mesh::MeshDev *)ctx->d_meshes,
                        (const admm_mesh::MeshMotion *)ctx->d_mesh_motion, (const SrMesh *)sm, (const int *)ctx->d_body_tag, (const int *)ctx->d_iperm, ctx->dt, n, (long long)cap,

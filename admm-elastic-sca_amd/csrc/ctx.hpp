@@ -291,14 +291,14 @@ struct admm_hip_ctx {
     // batch's elements, SoA [7][n_local] per batch at Batch::rx_off (f, depth, z); d_rx_node: f_contact [n][3], f_anchor [n][3], depth [n],
     // point [n][3] in the caller's node order; the two CSRs of reaction_gather_kernel (0: collision batches, 1: anchor batches); d_rx_blk:
     // the compaction's block counts, then their offsets; d_rx_count: the contacts' count; d_rx_rec [n_nodes] records; d_rx_part: the
-    // resultant's partials [6][blocks], then its six totals
+    // resultant's partials [6][n_part] (one row of the per-entry sums; abi_reaction.inc entry_work), then its six totals
     bool rx_ready = false; double *d_rx_el = nullptr, *d_rx_node = nullptr, *d_rx_part = nullptr; int *d_rx_blk = nullptr; long long *d_rx_count = nullptr; void *d_rx_rec = nullptr; admm_lib::NodeCsr rx_csr[2];
     // contact attribution (admm_hip_enable_contact_attribution; abi_reaction.inc, attribution.hpp; off by default).  attribution: the
     // switch, which makes every collision batch launch form 8 (collision_plan.hpp).  The record, allocated by the switch once finalized or
     // by finalize, never by admm_hip_step: at_total elements over the collision batches (a batch's slice at Batch::at_off), d_at_owner
     // [at_total] the last mover of every element (-1: none), d_at_normal SoA [3][at_total] its normal.  The reports' buffers, created by the
     // first report: d_at_rec [n_nodes] owner records, d_at_blk the per-entry block counts, then their offsets, d_at_tot the entries'
-    // counts, d_at_perm the contacts sorted by entry, d_at_part the per-entry partials [6][blocks], d_at_out the rows
+    // counts, d_at_perm the contacts sorted by entry, d_at_part the per-entry partials [6][n_part], d_at_out the rows (carved by abi_reaction.inc entry_work)
     bool attribution = false, at_ready = false; long long at_total = 0; int *d_at_owner = nullptr; double *d_at_normal = nullptr;
     void *d_at_rec = nullptr; int *d_at_blk = nullptr, *d_at_perm = nullptr; long long *d_at_tot = nullptr, *d_at_csr = nullptr; double *d_at_part = nullptr, *d_at_out = nullptr;
     // velocity damping per node group (abi_damping.inc, kernels_damping.hpp, damping.hpp; no group = off, the default).  damp_groups: the

@@ -14,14 +14,15 @@
 //                           t = c + R r from rec[body] (one uniform read per block) and the element's offset; three doubles into the
 //                           batch's targets [n][3] (lane i at 24 i bytes: the wave's stores cover 1.5 KiB without a gap), nothing else
 // Behind the frame's epilogue, before rigid_integrate_kernel:
-//   attach_partial_kernel   one wave per 64 consecutive attached elements OF ONE BODY (entry_block_row over total: a body's blocks start
-//                           at the sum of ceil(total / 64) of the bodies before it).  Every load first (idx, w2, active, u, z, then the
+//   attach_partial_kernel   one wave per 64 consecutive attached elements OF ONE BODY (row_layout.hpp's block_row over total, a body being
+//                           a row).  Every load first (idx, w2, active, u, z, then the
 //                           node's x), then attach.hpp's six terms about rec[body].c, folded by track_block_sum -- the butterfly of
 //                           entry_partial_block and the energies -- into partial [6][n_part]; the block's number of active elements by
 //                           __popcll(__ballot) into cnt [n_part].  Every lane stays: one beyond the body's elements adds six +0.0.
 //   attach_reduce_kernel    one workgroup per (body, component): entry_reduce_row over the body's partials (energy_reduce_kernel's
 //                           order) -> out [bodies][6]; then lane 0 adds that into the body's row of the contacts' sums rows [bodies][6]
-//                           -- only where carry[body] != 0 -- and, for component 0, sums the blocks' active counts into n_active [bodies]
+//                           -- only where carry[body] != 0 -- and, for component 0, sums the blocks' active counts (the body's blocks by
+//                           row_layout.hpp, ascending) into n_active [bodies]
 // Every index is bounded: a block's slot < n_slots and a slot's body < n_bodies <= ADMM_MAX_SHAPES are checked before use; first + lane
 // < n of the batch; a body's elements k < sum of total, the length of el_slot / el_elem; idx[e] is the batch's own device node id, as
 // every local kernel reads it; blockIdx.x < n_part by the launch (the host counts the blocks from the same totals it uploads).
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void attach_partial_kernel(const int 
                                                                       const int n_bodies, const long long *__restrict__ total, const admm_rigid::Record *__restrict__ rec,
                                                                       const double *__restrict__ x, const int n_part, double *__restrict__ partial, int *__restrict__ cnt) {
     long long base, blk0;
-    const int body = entry_block_row(n_bodies, total, base, blk0);
+    const int body = admm_layout::block_row(total, n_bodies, blockIdx.x, base, blk0);
     if (body < 0) return;                   // beyond the last body's blocks: nobody reads this partial
     const long long r = ((long long)blockIdx.x - blk0) * ENERGY_BLOCK + threadIdx.x;
     double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -97,10 +98,9 @@ __global__ __launch_bounds__(ENERGY_REDUCE) void attach_reduce_kernel(const long
     if (threadIdx.x != 0) return;
     if (carry[b] != 0) rows[(size_t)b * 6 + comp] = admm_attach::combine(rows[(size_t)b * 6 + comp], out[(size_t)b * 6 + comp]);
     if (comp == 0) {
-        long long blk0 = 0, na = 0;
-        for (int q = 0; q < b; ++q) blk0 += (total[q] + ENERGY_BLOCK - 1) / ENERGY_BLOCK;
-        const long long nb = (total[b] + ENERGY_BLOCK - 1) / ENERGY_BLOCK;
-        for (long long i = 0; i < nb; ++i) na += cnt[blk0 + i];
+        const long long blk0 = admm_layout::blocks_before(total, b), nb = admm_layout::row_blocks(total[b]);
+        long long na = 0;
+        for (long long i = 0; i < nb; ++i) na += cnt[blk0 + i];      // ascending block
         n_active[b] = na;
     }
 }

@@ -5,9 +5,9 @@
 // The table: RigidTable { n, body_of_row[rows], K[bodies] } (the constants; uploaded by the host, accel rewritten by
 // rigid_set_accel_kernel from kernel arguments) and rec [ADMM_MAX_SHAPES] admm_rigid::Record, the bodies' state and derived fields.
 //
-// Behind the frame's epilogue, after the reaction and attribution reports' launches and entry_count / scan / place
+// Behind the frame's epilogue, after the reaction and attribution reports' launches and entry_count / row_scan / entry_place
 // (kernels_reaction.hpp) have sorted the contacts by entry:
-//   rigid_partial_kernel    entry_partial_kernel's block layout and entry_partial_block, the pivot of a row being its body's own centre
+//   rigid_partial_kernel    entry_partial_kernel's block layout (row_layout.hpp's block_row) and entry_partial_block, the pivot of a row being its body's own centre
 //                           rec[body].c (one read per block, uniform); a row that is no body returns before it writes
 //   rigid_reduce_kernel     one workgroup per (body, component): entry_reduce_row over the body's row -> out [bodies][6]; a body's six
 //                           sums are bit for bit the row admm_hip_entry_resultants(pivot = c) returns
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void rigid_partial_kernel(const Conta
                                                                      const RigidTable *__restrict__ T, const admm_rigid::Record *__restrict__ body, const int n_part,
                                                                      double *__restrict__ partial) {
     long long base, blk0;
-    const int row = entry_block_row(n_rows, total, base, blk0);
+    const int row = admm_layout::block_row(total, n_rows, blockIdx.x, base, blk0);
     if (row < 0) return;
     const int b = T->body_of_row[row];
     if (b < 0) return;                      // not a rigid body: nobody reads this row's partials

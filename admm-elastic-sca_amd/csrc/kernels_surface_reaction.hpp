@@ -1,5 +1,5 @@
 // kernels_surface_reaction.hpp -- two-way contact on the device (surface_reaction.hpp): per frame, behind the reaction and attribution
-// chain of kernels_reaction.hpp (reaction_elem_kernel, reaction_gather_kernel, contact_count / scan / scatter_kernel,
+// chain of kernels_reaction.hpp (reaction_elem_kernel, reaction_gather_kernel, contact_count / row_scan / contact_scatter_kernel,
 // contact_owner_scatter_kernel, all launched unchanged), the contacts that landed on a body or sheet surface with a share hand
 // -f to the corners of the triangle they landed on.  Extension, no reference counterpart; launched by admm_hip_step only while some
 // surface has a share above zero (abi_surface_reaction.inc).  No float atomics and no integer atomics anywhere: every contribution is
@@ -25,9 +25,9 @@
 // (surface_reaction.hpp sort_passes), three launches per pass, no spinning across workgroups:
 //   sort_count_kernel    one wave per 64 keys: the lanes with the same digit find each other with eight ballots (one per bit of the
 //                        digit), the lowest of them writes their number to an LDS histogram of 256 digits; counts [256][blocks]
-//   sort_scan_kernel     one wave per digit: contact_scan_kernel's shuffle scan over that digit's block counts -> block offsets, total
-//   sort_place_kernel    the count kernel's ballots again; a key's place = (the totals of the lower digits: a one-wave scan of the 256
-//                        totals in LDS) + its block's offset + its rank among the lanes with the same digit; moves the key and the index
+//   sort_scan_kernel     one wave per digit: kernels_reaction.hpp's wave_scan_row over that digit's block counts -> block offsets, total
+//   sort_place_kernel    the count kernel's ballots again; a key's place = (the totals of the lower digits: wave_scan_inclusive over the
+//                        256 totals, four per lane, into LDS) + its block's offset + its rank among the lanes with the same digit; moves the key and the index
 //                        it carries.  Equal keys keep their order: ascending block, then ascending lane.
 // After the last pass a node's shares are adjacent, in ascending (contact k, corner c): the order surface_reaction.hpp demands.
 // surface_apply_kernel   one lane per sorted share: the lane at the start of a run (the key before differs) walks its run in sorted order,
@@ -181,24 +181,11 @@ __global__ __launch_bounds__(SR_BLOCK) void sort_count_kernel(const long long *_
     for (int q = 0; q < 4; ++q) blk_count[(size_t)(4 * lane + q) * nb_stride + blockIdx.x] = hist[4 * lane + q];
 }
 
-// digit blockIdx.x: exclusive scan of its counts over the ceil(N / 64) blocks in use -> blk_off, total[digit]; one wave
+// digit blockIdx.x: wave_scan_row over its counts of the ceil(N / 64) blocks in use -> blk_off, total[digit]; one wave
 __global__ __launch_bounds__(RX_SCAN) void sort_scan_kernel(const long long *__restrict__ n, const int nb_stride, const int *__restrict__ blk_count, int *__restrict__ blk_off,
                                                             int *__restrict__ total) {
-    const int lane = threadIdx.x;
-    const int n_blocks = (int)((*n + SR_BLOCK - 1) / SR_BLOCK);
-    const int *cnt = blk_count + (size_t)blockIdx.x * nb_stride;
-    int *off = blk_off + (size_t)blockIdx.x * nb_stride;
-    int carry = 0;
-    for (int base = 0; base < n_blocks; base += RX_SCAN) {      // (uniform: every lane runs every chunk)
-        const int i = base + lane;
-        const int v = i < n_blocks ? cnt[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < RX_SCAN; d <<= 1) { const int o = __shfl_up(incl, d, RX_SCAN); if (lane >= d) incl += o; }
-        if (i < n_blocks) off[i] = carry + incl - v;
-        carry += __shfl(incl, RX_SCAN - 1, RX_SCAN);
-    }
-    if (lane == 0) total[blockIdx.x] = carry;
+    const int t = wave_scan_row((int)((*n + SR_BLOCK - 1) / SR_BLOCK), blk_count + (size_t)blockIdx.x * nb_stride, blk_off + (size_t)blockIdx.x * nb_stride);
+    if (threadIdx.x == 0) total[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(SR_BLOCK) void sort_place_kernel(const long long *__restrict__ n, const int *__restrict__ key_in, const int *__restrict__ idx_in, const int shift,
@@ -208,14 +195,11 @@ __global__ __launch_bounds__(SR_BLOCK) void sort_place_kernel(const long long *_
     const long long N = *n, base = (long long)blockIdx.x * SR_BLOCK;
     if (base >= N) return;      // (uniform across the block)
     const int lane = threadIdx.x;
-    {   // exclusive scan of the 256 totals: four per lane, then a shuffle scan of the lanes' sums
+    {   // exclusive scan of the 256 totals: four per lane, then wave_scan_inclusive of the lanes' sums
         int t[4], s = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) { t[q] = total[4 * lane + q]; s += t[q]; }
-        int incl = s;
-#pragma unroll
-        for (int d = 1; d < SR_BLOCK; d <<= 1) { const int o = __shfl_up(incl, d, SR_BLOCK); if (lane >= d) incl += o; }
-        int run = incl - s;
+        int run = wave_scan_inclusive(s, lane) - s;
 #pragma unroll
         for (int q = 0; q < 4; ++q) { digit_base[4 * lane + q] = run; run += t[q]; }
     }

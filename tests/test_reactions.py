@@ -26,7 +26,7 @@ FLOOR_Y = 2.0
 SPH = [1.5, 2.0, 1.5, 0.25]
 W_COLL = 8.0
 ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = 1, 2, 3, 4
-# contact_count_kernel counts RX_BLOCK = 128 nodes per block and contact_scan_kernel scans RX_SCAN = 64 block counts per pass of its one
+# contact_count_kernel counts RX_BLOCK = 128 nodes per block and row_scan_kernel scans RX_SCAN = 64 block counts per pass of its one
 # wave: 64 * 128 + 1 collision nodes are one block more than one pass covers (csrc/kernels_reaction.hpp)
 RX_BLOCK, RX_SCAN = 128, 64
 N_BIG = RX_BLOCK * RX_SCAN + 1
@@ -187,8 +187,8 @@ def test_argument_and_state_errors_on_the_host(pkg):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # GPU 1: what the numbers mean, on free particles
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _particles(pkg, N, mode="mixed", n_anchor=3):
-    """N massed nodes, no elastic force, one COLLISION batch over all of them, a floor at y = 2 and a sphere half sunk in it, gravity;
+def _particles(pkg, N, mode="mixed", n_anchor=3, sphere=True):
+    """N massed nodes, no elastic force, one COLLISION batch over all of them, a floor at y = 2 and (`sphere`) a sphere half sunk in it, gravity;
     odd nodes (mode "all": all, "none": none) start 0.02 .. 0.1 above the floor at 5 m/s downwards and hit it within the frame, the
     others hang 0.6 above it; n_anchor more nodes of their own carry one ANCHOR element each, the target 0.05 above the node"""
     rng = np.random.default_rng(1000 + N)
@@ -204,7 +204,7 @@ def _particles(pkg, N, mode="mixed", n_anchor=3):
     s.coll = s.add_forces(KIND["COLLISION"], np.arange(N, dtype=np.int32), [W_COLL])
     s.anch = s.add_forces(KIND["ANCHOR"], np.arange(N, N + n_anchor, dtype=np.int32), [-1.0, 1.0], targets=xa + [0.0, 0.05, 0.0])
     s.add_gravity(G)
-    s.set_collision_shapes([FLOOR, SPHERE], [[0.0, FLOOR_Y, 0.0, 0.0], SPH])
+    s.set_collision_shapes([FLOOR, SPHERE][:2 if sphere else 1], [[0.0, FLOOR_Y, 0.0, 0.0], SPH][:2 if sphere else 1])
     s.initialize()
     s.m_v = v0.ravel()
     s.N, s.x0, s.v0, s.m = N, x0, v0, m
@@ -303,6 +303,34 @@ def test_all_or_no_node_in_contact_and_capacities(pkg, mode):
         assert not force.any() and not torque.any()
     else:
         assert force[1] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("count", [0, 1, 64, 65, 64 * 256 + 1])
+def test_contact_resultant_on_the_one_row_path(pkg, count):
+    """contact_resultant sums all contacts as ONE row of the per-entry sums (entry_partial_kernel without a permutation, then
+    entry_reduce_kernel over the ceil(count / 64) partials that are filled).  Contact counts (asserted) of no block, one contact, one full
+    block, a block and one, and 64 * 256 + 1: 257 partials, so thread 0 of the second stage adds two.  `count` nodes that all hit the
+    floor (three that do not at count 0), one frame, on two fresh systems.  Attribution off -- the call needs none of its buffers: bit for
+    bit the host twin reaction_query.  Attribution on: the twin again, and entry_resultants summed over its rows.  The list is the floor
+    alone, so every contact is owned by entry 0 (asserted) and row 0 goes through the permutation, which is then the identity; the row
+    of the contacts nobody owns is empty, +0.0 six times, so the rows' sum is row 0 + 0.0 and must be contact_resultant's bits."""
+    pivot = (1.5, 2.0, 1.5)
+    for attribution in (False, True):
+        s = _particles(pkg, count if count else 3, "all" if count else "none", sphere=False)
+        if attribution:
+            s.enable_contact_attribution()
+        s.step(10)
+        r = s.read_local(s.coll)
+        q = pkg.reaction_query(s.read_rest(s.coll)["weight"] ** 2, r["u"], r["z"], s.m_x.reshape(-1, 3)[:s.N], pivot=pivot)
+        force, torque, n = s.contact_resultant(pivot=pivot)
+        assert n == count == int(q["flag"].sum())
+        assert np.array_equal(force, q["force"]) and np.array_equal(torque, q["torque"]), (count, attribution)
+        assert force[1] > 0 if count else not (force.any() or torque.any())
+        if attribution:
+            ef, et, ec = s.entry_resultants(pivot=pivot)
+            assert ec.tolist() == [count, 0]
+            assert np.array_equal(ef[0] + ef[1], force) and np.array_equal(et[0] + et[1], torque), (count, ef, et)
 
 
 @pytest.mark.gpu

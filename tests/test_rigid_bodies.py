@@ -623,6 +623,54 @@ def test_options_device_against_the_rule_from_outside(pkg, option):
 
 
 @pytest.mark.gpu
+def test_the_two_consumers_of_one_frame_keep_their_own_depths(pkg):
+    """two-way contact and the rigid bodies run the same contact chain in one frame, each with its own depth_min: neither may read the
+    other's compaction.  Scene 1 with a share of 0.5 on bar A's surface; six frames bring the ball and bar B onto bar A, then one frame
+    (a) as it is, both depths 0, (b) with set_rigid_depth(d_r), (c) with set_surface_reaction_depth(d_s).  The runs are the same bits up
+    to that frame, so d_r and d_s come from (a)'s contacts of that frame: the middle between the shallowest and the deepest contact of
+    the ball, and of bar A's surface.  At least one contact lies between 0 and either depth (asserted through contacts(depth_min)
+    counts), and each setting does change its own consumer (asserted).  (a) against (b): the surface report's dv and the nodes' v,
+    bitwise.  (a) against (c): the body's record, bitwise."""
+    def run(rigid_depth=None, surface_depth=None):
+        s = _ball_on_bars(pkg, True)
+        s.set_surface_reaction(s.bodies[0], 0.5)
+        s.initialize()
+        for _ in range(6):
+            s.step(10)
+        if rigid_depth is not None:
+            s.set_rigid_depth(rigid_depth)
+        if surface_depth is not None:
+            s.set_surface_reaction_depth(surface_depth)
+        s.step(10)
+        return s
+
+    def body(s):
+        r = s.rigid_state()[0]
+        return b"".join(getattr(r, n).tobytes() for n in pkg.RIGID_FIELDS), r.count
+
+    a = run()
+    c, o = a.contacts(depth_min=0.0), a.contact_owners(depth_min=0.0)
+    assert np.array_equal(c["node"], o["node"])
+    ball, surf = np.sort(c["depth"][o["entry"] == 3]), np.sort(c["depth"][o["entry"] == 1])
+    assert len(ball) >= 2 and len(surf) >= 2 and ball[0] < ball[-1] and surf[0] < surf[-1], (ball, surf)
+    d_r, d_s = 0.5 * (ball[0] + ball[-1]), 0.5 * (surf[0] + surf[-1])
+    n0 = len(c)
+    print("cross-talk: %d contacts, the ball's depths %s, the surface's %s, d_r %.3g (%d contacts above), d_s %.3g (%d above)" %
+          (n0, ball, surf, d_r, len(a.contacts(depth_min=d_r)), d_s, len(a.contacts(depth_min=d_s))))
+    assert len(a.contacts(depth_min=d_r)) < n0 and len(a.contacts(depth_min=d_s)) < n0      # a contact between 0 and either depth
+    dv_a, _, info_a = a.surface_reaction()
+    assert info_a["n_reacting"] >= 2 and body(a)[1] == len(ball)
+    b = run(rigid_depth=d_r)
+    dv_b, _, info_b = b.surface_reaction()
+    assert dv_b.tobytes() == dv_a.tobytes() and info_b == info_a and b.m_v.tobytes() == a.m_v.tobytes() and b.m_x.tobytes() == a.m_x.tobytes()
+    assert body(b)[1] < body(a)[1] and body(b)[0] != body(a)[0]          # the setting reached its own consumer
+    k = run(surface_depth=d_s)
+    assert body(k) == body(a)
+    dv_k, _, info_k = k.surface_reaction()
+    assert info_k["n_contacts"] < info_a["n_contacts"] and dv_k.tobytes() != dv_a.tobytes()      # the setting reached its own consumer
+
+
+@pytest.mark.gpu
 def test_off_is_off(pkg):
     """no body registered: the frames of the scene built without touching the new calls, bit for bit -- with attribution on and the
     feature's depth set and its (empty) state read, and against the plain scene with attribution off"""

@@ -1,7 +1,7 @@
 """What a rigid body costs a frame: a bar of nx x ny x nz cells (default 8 x 8 x 40: 15 360 Neo-Hookean tets, 3 321 nodes) anchored at one
 end, one collision element per node, contact attribution on, a sphere resting 1 mm above its top -- the same frames with the sphere left
 kinematic and with it registered as a rigid body under gravity (admm_hip_add_rigid_body: per frame the pose launch, the reaction and
-attribution reports' launches, entry_count / scan / place, rigid_partial / reduce / integrate).  Prints the wall time per frame of both,
+attribution reports' launches, entry_count / row_scan / entry_place, rigid_partial / reduce / integrate).  Prints the wall time per frame of both,
 synchronised once at the end; the first frames (graph capture) are left out.
 
     timeout -k 10 300 python tools/probe_rigid.py [nx ny nz]
